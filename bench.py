@@ -12,6 +12,10 @@ the path shards over independent polynomials, one per GPU, no data-path collecti
 RCCL is used only for the barrier and the max-over-ranks of the timed region.
 
 Prints ONE JSON line on rank 0.
+
+A plain run does only what the headline needs: set-up, warm-up, the --steps timed steps, the outputs of the last step when
+--dump-outputs DIR is given, and the line.  Everything else (round-trip checks, the per-kernel HIP-event pass and its roofline,
+batched throughput, the latency regime, the CPU baselines, with --gpus N > 1 the split EXTEND) runs with --full.
 """
 import argparse
 import json
@@ -57,6 +61,27 @@ def synth(field, n, seed):
     bad = (a[:, 3] == 0xFFFFFFFFFFFFFFFF) & (a[:, 2] == 0xFFFFFFFFFFFFFFFF) & (a[:, 1] == 0xFFFFFFFFFFFFFFFF) & (a[:, 0] >= 0xFFFFFFFEFFFFFC2F)
     a[bad, 0] = 0
     return a   # any canonical 256-bit pattern < p is a valid Montgomery-form element
+
+
+HEADLINE_SEED = 0x5EED0002     # synth seed of the timed input (+ rank)
+DUMP_MAX_ELEMS = 1 << 18    # --dump-outputs: elements kept per array (secp256k1: 16 MiB per array as float64 words)
+DUMP_SEED = 0xD0D0
+
+
+def dump_outputs(outdir, arrays, n):
+    """--dump-outputs: each array of n elements (a caller's view: uint64[n, 4] Montgomery limbs for secp256k1, uint32[n] for M31)
+    as <outdir>/<name>.npy in float64, exactly: an element becomes its little-endian 32-bit words, which float64 holds without
+    rounding.  Above DUMP_MAX_ELEMS elements every array keeps the same fixed, seeded sample of positions, written as
+    sample_index.npy, so that two builds can be compared element for element."""
+    if n <= DUMP_MAX_ELEMS:
+        idx = np.arange(n)
+    else:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n, DUMP_MAX_ELEMS, replace=False))
+    os.makedirs(outdir, exist_ok=True)
+    np.save(os.path.join(outdir, "sample_index.npy"), idx.astype(np.float64))
+    for name, a in arrays.items():
+        words = np.ascontiguousarray(a).view(np.uint32)
+        np.save(os.path.join(outdir, f"{name}.npy"), words[idx].astype(np.float64))
 
 
 def cpu_baseline(field, log_n):
@@ -154,19 +179,29 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--log-n", type=int, default=20)
     ap.add_argument("--field", default="secp256k1", choices=["secp256k1", "m31"])
-    ap.add_argument("--cpu-log-n", type=int, default=15, help="size of the bounded CPU-baseline sample (0 = skip)")
-    ap.add_argument("--no-profile", action="store_true", help="skip the per-launch HIP-event pass")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline does not need: round-trip checks, per-launch HIP-event pass + roofline, batched "
+                         "throughput, latency regime, CPU baselines, and with --gpus N > 1 the split EXTEND")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step as DIR/<name>.npy (float64; see dump_outputs)")
+    ap.add_argument("--cpu-log-n", type=int, default=15, help="--full: size of the bounded CPU-baseline sample (0 = skip)")
+    ap.add_argument("--no-profile", action="store_true", help="--full: skip the per-launch HIP-event pass")
     ap.add_argument("--mode", default="enter-exit", choices=["enter-exit", "extend-split", "enter-exit-split"],
                     help="extend-split: BASELINE configs[3] — ONE EXTEND of 2^log-n evaluations split over the ranks with RCCL all-to-all; "
                          "enter-exit-split: ONE ENTER+EXIT of 2^log-n coefficients split over the ranks (strong scaling)")
-    ap.add_argument("--batch", type=int, default=8, help="also report throughput with this many polynomials per launch (0 = skip)")
+    ap.add_argument("--batch", type=int, default=8, help="--full: also report throughput with this many polynomials per launch (0 = skip)")
     ap.add_argument("--split-log-n", type=int, default=20, help="--gpus N > 1: size of the ONE ENTER+EXIT split over the ranks reported under `split` (0 = skip)")
-    ap.add_argument("--split-log-e", type=int, default=22, help="--gpus N > 1: size of the ONE EXTEND split over the ranks reported under `split` (0 = skip)")
+    ap.add_argument("--split-log-e", type=int, default=22, help="--gpus N > 1 with --full: size of the ONE EXTEND split over the ranks reported under `split` (0 = skip)")
     ap.add_argument("--stripe-min-gain", type=int, default=None, help="--gpus N > 1: ecfft_comm_set_link_striping threshold in bytes for the split part (default: the library's — striping OFF since round 6; 4194304 = the projection's threshold; 0 = always when it helps; -1 = never)")
     ap.add_argument("--split-exit", default="auto", choices=["auto", "gather", "shard"],
                     help="--gpus N > 1: form of the split EXIT — gather: full (replicated) context, ONE all-gather, top levels redundant; shard: "
                          "EXIT-shard context, split top levels; auto: gather up to n = 2^21, shard above")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    world = int(os.environ.get("WORLD_SIZE", "1"))
+    if args.dump_outputs and (world > 1 or args.mode != "enter-exit"):
+        ap.error("--dump-outputs: only the single-GPU ENTER+EXIT path (--gpus 1, --mode enter-exit)")
 
     import torch
     import ecfft_amd
@@ -175,7 +210,6 @@ def main():
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
-    world = int(os.environ.get("WORLD_SIZE", "1"))
     if args.gpus > 1 and world != args.gpus:
         raise SystemExit(f"--gpus {args.gpus} needs torch.distributed.run with {args.gpus} processes (WORLD_SIZE={world})")
     ndev = torch.cuda.device_count()
@@ -207,7 +241,7 @@ def main():
     F = ecfft_amd.FIELDS[args.field]
     # host-side input first, so that nothing but the upload separates the device's first work (context, tree build) from the warm-up steps:
     # an idle gap of tens of ms lets the chip drop its clocks, and the first 3 - 4 steps after one run 5 - 30 % slow (tools/ramp_check.py)
-    host = synth(args.field, n, 0x5EED0000 + 2 + rank)
+    host = synth(args.field, n, HEADLINE_SEED + rank)
     view = host.view(np.int64) if args.field == "secp256k1" else host.view(np.int32)
     # the process's first device work (HIP context, queues, module load: 0.1 - 0.2 s on this stack) is not tree construction:
     # it is timed on its own so that tree_build_s is what ecfft_build_fftree costs a process that already uses its GPU
@@ -236,7 +270,7 @@ def main():
     for _ in range(args.warmup):
         ev, back = step()
     barrier()
-    if args.warmup:
+    if args.full and args.warmup:
         assert torch.equal(back, coeffs), "EXIT(ENTER(c)) != c"
 
     # ---- timed region: exactly K steps --------------------------------------------------------
@@ -250,12 +284,15 @@ def main():
         tt = torch.tensor([elapsed], dtype=torch.float64, device=red_dev)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
-    assert torch.equal(back, coeffs), "EXIT(ENTER(c)) != c"
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"evaluations": ev.cpu().numpy(), "coefficients": back.cpu().numpy()}, n)
+    if args.full:
+        assert torch.equal(back, coeffs), "EXIT(ENTER(c)) != c"
 
     # ---- per-kernel HIP-event pass over the same K steps (events on the launch stream) -----------
     roofline = None
     split = {}
-    if not args.no_profile and args.steps > 0:
+    if args.full and not args.no_profile:
         tree.profile(True)
         te0 = time.perf_counter()
         for _ in range(args.steps):
@@ -272,7 +309,7 @@ def main():
 
     # ---- extra: batched throughput (B independent polynomials share every launch; not the headline value) -----
     batched = None
-    if args.batch > 1 and args.steps > 0:
+    if args.full and args.batch > 1:
         B = args.batch
         big = torch.from_numpy(np.concatenate([view] * B)).cuda() if args.field == "m31" else torch.from_numpy(np.concatenate([view] * B, axis=0)).cuda()
         evb = tree.enter(big, count=B); backb = tree.exit(evb, count=B)        # warm-up (also grows the scratch)
@@ -291,7 +328,7 @@ def main():
     # ---- extra: the latency regime (BASELINE.json configs[1], n = 2^16, and 2^17 = the rank-local chunk of an 8-GPU split at 2^20):
     # one transform, device buffers, median of 15 — reported beside the headline, never part of `value` ----
     latency = None
-    if world == 1 and args.field == "secp256k1" and args.log_n == 20 and args.steps > 0 and not os.environ.get("ECFFT_BENCH_NO_LATENCY"):
+    if args.full and world == 1 and args.field == "secp256k1" and args.log_n == 20 and not os.environ.get("ECFFT_BENCH_NO_LATENCY"):
         latency = {}
         for ln in (16, 17):
             ts = F.build_fftree(1 << ln, device=local_rank)
@@ -320,7 +357,7 @@ def main():
             "metric": f"{args.field} Fp field-mul/s, ENTER+EXIT at n=2^{args.log_n}",
             "value": value, "unit": "field-mul/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": elapsed * 1e3 / args.steps, "higher_is_better": True, "scaling": "weak",
-            "vs_baseline": None, "dtype": "u256" if args.field == "secp256k1" else "u32", "data": "synthetic",
+            "vs_baseline": None, "dtype": "u256" if args.field == "secp256k1" else "u32", "data": "synthetic", "full": args.full,
             "value_note": "reference-equivalent throughput: the ALGORITHMIC multiply count of the reference's recursion (SURVEY 8(d)) per second; "
                           "the kernels execute about half as many multiplies (normalised butterflies) — see executed_field_mul_per_s",
             "executed_field_mul_per_s": sum(executed_mul(n)) * args.steps * world / elapsed,
@@ -340,7 +377,7 @@ def main():
     # split over the ranks (grouped ncclSend/ncclRecv at the top log2 N levels, sharded tables), same process group.  The replica
     # measurement above is complete at this point: a watchdog makes sure a fault in the split part (this is the only code of the
     # repository that a one-GPU lease cannot run over real multi-rank RCCL) costs the `split` object and not the whole line. -----
-    if world > 1 and (args.split_log_n or args.split_log_e):
+    if world > 1 and (args.split_log_n or (args.full and args.split_log_e)):
         import threading
         del tree, coeffs, ev, back
         torch.cuda.empty_cache()
@@ -391,7 +428,7 @@ def main():
         try:
             if args.split_log_n:
                 split_obj["enter_exit"] = enter_exit_split(args, torch, dist, ecfft_amd, rank, local_rank, world, red_dev, args.split_log_n)
-            if args.split_log_e:
+            if args.full and args.split_log_e:
                 split_obj["extend"] = extend_split(args, torch, dist, ecfft_amd, rank, local_rank, world, red_dev, args.split_log_e)
         except Exception as ex:  # a rank that fails here leaves its peers in an exchange: their watchdogs abort those
             split_obj.setdefault("error", f"{type(ex).__name__}: {ex}")
@@ -427,7 +464,7 @@ def main():
                 out["headline"] = "replicas"
 
     if rank == 0:
-        if world == 1 and args.cpu_log_n > 0:
+        if args.full and world == 1 and args.cpu_log_n > 0:
             out["cpu_baseline"] = cpu_baseline(args.field, args.cpu_log_n)
             out["gpu_over_cpu"] = value / out["cpu_baseline"]["value"]
             out["cpu_baseline_socket"] = cpu_baseline_socket(args.field, args.cpu_log_n)
@@ -513,21 +550,24 @@ def extend_split(args, torch, dist, ecfft_amd, rank, local_rank, world, red_dev=
         y = run(x, ecfft_amd.Moiety.S1)
     barrier()
     elapsed = time.perf_counter() - t0
-    back = run(y, ecfft_amd.Moiety.S0)
-    ok = bool(torch.equal(back, x))
-    # second pass with per-exchange events: communication vs compute per step
-    comm.stats(True)
-    barrier(); t1 = time.perf_counter()
-    for _ in range(args.steps):
-        y = run(x, ecfft_amd.Moiety.S1)
-    barrier(); inst = time.perf_counter() - t1
-    phases = _split_report(comm, args.steps)
-    phases["instrumented_ms_per_step"] = inst * 1e3 / max(args.steps, 1)
-    phases["compute_ms_per_step"] = phases["instrumented_ms_per_step"] - phases["comm_ms_per_step"] - phases.get("self_copy_ms_per_step", 0.0)
-    comm.stats(False)
+    ok = phases = None
+    if args.full:
+        back = run(y, ecfft_amd.Moiety.S0)
+        ok = bool(torch.equal(back, x))
+        # second pass with per-exchange events: communication vs compute per step
+        comm.stats(True)
+        barrier(); t1 = time.perf_counter()
+        for _ in range(args.steps):
+            y = run(x, ecfft_amd.Moiety.S1)
+        barrier(); inst = time.perf_counter() - t1
+        phases = _split_report(comm, args.steps)
+        phases["instrumented_ms_per_step"] = inst * 1e3 / max(args.steps, 1)
+        phases["compute_ms_per_step"] = phases["instrumented_ms_per_step"] - phases["comm_ms_per_step"] - phases.get("self_copy_ms_per_step", 0.0)
+        comm.stats(False)
     if dist is not None:
         tt = torch.tensor([elapsed], dtype=torch.float64, device=red_dev); dist.all_reduce(tt, op=dist.ReduceOp.MAX); elapsed = float(tt.item())
-        fl = torch.tensor([1 if ok else 0], device=red_dev); dist.all_reduce(fl, op=dist.ReduceOp.MIN); ok = bool(fl.item())
+        if ok is not None:
+            fl = torch.tensor([1 if ok else 0], device=red_dev); dist.all_reduce(fl, op=dist.ReduceOp.MIN); ok = bool(fl.item())
     L = log_e
     return {"metric": f"{args.field} Fp field-mul/s, one EXTEND of 2^{L} evaluations split over {world} GPU(s)",
             "value": 4 * e * L * args.steps / elapsed, "unit": "field-mul/s", "n_gpus": world, "steps": args.steps,
@@ -593,16 +633,19 @@ def enter_exit_split(args, torch, dist, ecfft_amd, rank, local_rank, world, red_
         back = step()
     barrier()
     elapsed = time.perf_counter() - t0
+    # the round trip decides whether a --gpus N > 1 line promotes this transform to its headline, so it runs in a plain run too
     ok = bool(torch.equal(back.reshape(x.shape), x))
-    comm.stats(True)
-    barrier(); t1 = time.perf_counter()
-    for _ in range(args.steps):
-        back = step()
-    barrier(); inst = time.perf_counter() - t1
-    phases = _split_report(comm, args.steps)
-    phases["instrumented_ms_per_step"] = inst * 1e3 / max(args.steps, 1)
-    phases["compute_ms_per_step"] = phases["instrumented_ms_per_step"] - phases["comm_ms_per_step"] - phases.get("self_copy_ms_per_step", 0.0)
-    comm.stats(False)
+    phases = None
+    if args.full:
+        comm.stats(True)
+        barrier(); t1 = time.perf_counter()
+        for _ in range(args.steps):
+            back = step()
+        barrier(); inst = time.perf_counter() - t1
+        phases = _split_report(comm, args.steps)
+        phases["instrumented_ms_per_step"] = inst * 1e3 / max(args.steps, 1)
+        phases["compute_ms_per_step"] = phases["instrumented_ms_per_step"] - phases["comm_ms_per_step"] - phases.get("self_copy_ms_per_step", 0.0)
+        comm.stats(False)
     if dist is not None:
         tt = torch.tensor([elapsed], dtype=torch.float64, device=red_dev); dist.all_reduce(tt, op=dist.ReduceOp.MAX); elapsed = float(tt.item())
         fl = torch.tensor([1 if ok else 0], device=red_dev); dist.all_reduce(fl, op=dist.ReduceOp.MIN); ok = bool(fl.item())

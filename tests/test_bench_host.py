@@ -108,7 +108,7 @@ def test_gpus2_headline_is_the_split_transform(transport):
         env.update(ECFFT_BENCH_TRANSPORT="rccl", ECFFT_BENCH_RCCL_LIB=stub)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--log-n", "12",
-           "--split-log-n", "12", "--split-log-e", "12", "--cpu-log-n", "0", "--batch", "0"]
+           "--split-log-n", "12", "--split-log-e", "12", "--cpu-log-n", "0", "--batch", "0", "--full"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -132,8 +132,8 @@ def test_gpus2_headline_is_the_split_transform(transport):
 @pytest.mark.gpu
 def test_the_drivers_scale_command_with_8_ranks_dry_run():
     """the command the driver launches on an 8-GPU node — `python -m torch.distributed.run --nproc-per-node 8 bench.py
-    --gpus 8 --steps K --warmup W`, nothing else on the line: n = 2^20 split ENTER+EXIT (9 exchanges per step), e = 2^22 split EXTEND
-    (4), three kinds of contexts per rank — run END TO END with 8 ranks sharing this box's one GPU: gloo process group, the library's
+    --gpus 8 --steps K --warmup W`, nothing else on the line but --full (the split EXTEND and the per-exchange pass): n = 2^20 split
+    ENTER+EXIT (9 exchanges per step), e = 2^22 split EXTEND (4), three kinds of contexts per rank — run END TO END with 8 ranks sharing this box's one GPU: gloo process group, the library's
     RCCL transport bound to the stand-in library.  Functional only (times mean nothing).  The first real 8-GPU run must not be the
     first 8-rank run.  Needs ~25 GB of HBM for the eight ranks' contexts: skipped on a busy / small device."""
     import socket
@@ -148,7 +148,7 @@ def test_the_drivers_scale_command_with_8_ranks_dry_run():
         subprocess.run(["/opt/rocm/bin/hipcc", "-O2", "-fPIC", "-shared", "-o", stub, os.path.join(ROOT, "tests", "stub_rccl", "stub_rccl.cpp"), "-lrt"], check=True)
     env = dict(os.environ, ECFFT_BENCH_BACKEND="gloo", MASTER_ADDR="127.0.0.1", ECFFT_BENCH_TRANSPORT="rccl", ECFFT_BENCH_RCCL_LIB=stub)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "8", "--master-addr", "127.0.0.1",
-           "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "2", "--warmup", "1"]
+           "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "2", "--warmup", "1", "--full"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -174,7 +174,7 @@ def test_a_stuck_split_part_costs_the_split_object_not_the_line():
     env = dict(os.environ, ECFFT_BENCH_BACKEND="gloo", MASTER_ADDR="127.0.0.1", ECFFT_SPLIT_TIMEOUT_S="0.01")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--log-n", "12",
-           "--split-log-n", "16", "--split-log-e", "0", "--cpu-log-n", "0", "--batch", "0"]
+           "--split-log-n", "16", "--split-log-e", "0", "--cpu-log-n", "0", "--batch", "0", "--full"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -188,8 +188,55 @@ def test_a_stuck_split_part_costs_the_split_object_not_the_line():
 @pytest.mark.gpu
 def test_single_gpu_line_is_unchanged_by_the_split_option():
     import subprocess
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--log-n", "12", "--cpu-log-n", "0", "--batch", "0"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--log-n", "12", "--cpu-log-n", "0", "--batch", "0",
+                        "--full"],
                        capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     d = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][0])
     assert "split" not in d and d["n_gpus"] == 1 and d["roofline"]["frac_alg"] > 0
+
+
+def test_dump_outputs_is_exact_seeded_and_bounded(tmp_path, monkeypatch):
+    """--dump-outputs: float64 words that give back the caller's elements bit for bit, the same seeded sample of positions in every
+    array and every run above DUMP_MAX_ELEMS, every position below it, and at most 64 MB for the largest dump (two secp256k1
+    arrays + the index)"""
+    import numpy as np
+    assert (2 * 8 + 1) * 8 * bench.DUMP_MAX_ELEMS <= 64 << 20
+    monkeypatch.setattr(bench, "DUMP_MAX_ELEMS", 64)
+    secp = bench.synth("secp256k1", 1000, 1).view(np.int64)
+    m31 = bench.synth("m31", 1000, 2).view(np.int32)
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), {"s": secp, "m": m31}, 1000)
+    a = {f: np.load(tmp_path / "a" / f"{f}.npy") for f in ("sample_index", "s", "m")}
+    for f, arr in a.items():
+        assert arr.dtype == np.float64 and np.array_equal(arr, np.load(tmp_path / "b" / f"{f}.npy"))
+    idx = a["sample_index"].astype(np.int64)
+    assert len(idx) == 64 and np.all(np.diff(idx) > 0) and idx[-1] < 1000
+    assert np.array_equal(a["s"].astype(np.uint32).view(np.uint64), secp.view(np.uint64)[idx])
+    assert np.array_equal(a["m"].astype(np.uint32), m31.view(np.uint32)[idx])
+    bench.dump_outputs(str(tmp_path / "c"), {"m": m31[:64]}, 64)
+    assert np.array_equal(np.load(tmp_path / "c" / "sample_index.npy"), np.arange(64))
+    assert np.array_equal(np.load(tmp_path / "c" / "m.npy"), m31[:64].astype(np.float64))
+
+
+@pytest.mark.gpu
+def test_plain_line_is_lean_and_dumps_what_the_timed_path_computed(tmp_path, oracle_mod):
+    """A plain run (no --full) times exactly --steps steps, runs none of the extras, and --dump-outputs writes the last step's ENTER
+    output (the oracle's ENTER of the same seeded input) and EXIT output (that input again)."""
+    import subprocess
+    import numpy as np
+    out = tmp_path / "dump"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--log-n", "12",
+                        "--dump-outputs", str(out)], capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-3000:]
+    d = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][0])
+    assert d["steps"] == 3 and d["ms_per_step"] > 0 and d["value"] > 0 and d["full"] is False
+    assert d["roofline"] is None and d["batched"] is None and d["latency_regime"] is None and d["cpu_baseline"] is None
+    n = 1 << 12
+    c = bench.synth("secp256k1", n, bench.HEADLINE_SEED)
+    ev = oracle_mod.field("secp256k1").build_fftree(n).enter(c)
+
+    def words(name):
+        return np.load(out / f"{name}.npy").astype(np.uint32).view(np.uint64)
+    assert np.array_equal(np.load(out / "sample_index.npy"), np.arange(n))
+    assert np.array_equal(words("evaluations"), ev) and np.array_equal(words("coefficients"), c)
