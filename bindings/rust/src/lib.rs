@@ -51,6 +51,7 @@ pub mod ffi {
         pub fn ecfft_enter_many(ctx: *mut EcfftCtx, coeffs: *const c_void, evals: *mut c_void, n: usize, count: usize, mem: i32, stream: *mut c_void) -> i32;
         pub fn ecfft_exit_many(ctx: *mut EcfftCtx, evals: *const c_void, coeffs: *mut c_void, n: usize, count: usize, mem: i32, stream: *mut c_void) -> i32;
         pub fn ecfft_extend(ctx: *mut EcfftCtx, inp: *const c_void, out: *mut c_void, e: usize, moiety: i32, count: usize, mem: i32, stream: *mut c_void) -> i32;
+        pub fn ecfft_poly_mul(ctx: *mut EcfftCtx, a: *const c_void, na: usize, b: *const c_void, nb: usize, out: *mut c_void, count: usize, mem: i32, stream: *mut c_void) -> i32;
         pub fn ecfft_mextend(ctx: *mut EcfftCtx, inp: *const c_void, out: *mut c_void, e: usize, moiety: i32, count: usize, mem: i32, stream: *mut c_void) -> i32;
         pub fn ecfft_redc(ctx: *mut EcfftCtx, evals: *const c_void, a: *const c_void, out: *mut c_void, n: usize, moiety: i32, mem: i32, stream: *mut c_void) -> i32;
         pub fn ecfft_modular_reduce(ctx: *mut EcfftCtx, evals: *const c_void, a: *const c_void, c: *const c_void, out: *mut c_void, n: usize, mem: i32, stream: *mut c_void) -> i32;
@@ -213,6 +214,17 @@ impl<F: HipField> HipFFTree<F> {
         let mut out = Self::out_vec(evals.len());
         check(unsafe { ffi::ecfft_extend(self.ctx, evals.as_ptr().cast(), out.as_mut_ptr().cast(), evals.len(), moiety_id(moiety), 1, ffi::MEM_HOST, core::ptr::null_mut()) });
         unsafe { out.set_len(evals.len()) };
+        out
+    }
+
+    /// `a * b` in coefficient form (ecfft_poly_mul; no reference counterpart): `a.len() + b.len() - 1` coefficients; the tree must hold
+    /// `next_pow2(a.len() + b.len() - 1)` leaves.  `mul(a, a)` is a squaring.
+    pub fn mul(&self, a: &[F], b: &[F]) -> Vec<F> {
+        assert!(!a.is_empty() && !b.is_empty());
+        let n = a.len() + b.len() - 1;
+        let mut out = Self::out_vec(n);
+        check(unsafe { ffi::ecfft_poly_mul(self.ctx, a.as_ptr().cast(), a.len(), b.as_ptr().cast(), b.len(), out.as_mut_ptr().cast(), 1, ffi::MEM_HOST, core::ptr::null_mut()) });
+        unsafe { out.set_len(n) };
         out
     }
 

@@ -1606,6 +1606,87 @@ public:
         if (cur != out) (void)hipMemcpyAsync(out, cur, n * sizeof(E), hipMemcpyDeviceToDevice, s);
     }
 
+    // ecfft_poly_mul (no reference counterpart): out_b = a_b * b_b for `count` pairs laid end to end (a: count x na, b: count x nb,
+    // out: count x (na + nb - 1) coefficients) on T_N, N = next_pow2(na + nb - 1) <= size().  Device pointers, asynchronous on `s`;
+    // caller holds lock().  An operand of at most N/2 coefficients is entered at its own size m = next_pow2(len) and LIFTED: with the
+    // high half zero, enter_impl (src/fftree.rs:143-161) is ENTER_2m(p | 0) = interleave(E, EXTEND_S1(E)), E = ENTER_m(p) — v0 = v1 = 0
+    // drop the xnn_s term — so every doubling costs one EXTEND of the current size.  The two operands (and all pairs) share the launches
+    // from the size at which they meet, the last lift's interleave is the load of k_poly_pointwise, and one batched EXIT_N returns the
+    // coefficients.  An operand longer than N/2 is zero-padded and entered at N.  a == b with na == nb (squaring) enters one operand.
+    bool poly_mul(const E* a, size_t na, const E* b, size_t nb, E* out, size_t count, hipStream_t s) {
+        const size_t nc = na + nb - 1;
+        size_t N = 1; while (N < nc) N <<= 1;
+        const size_t h = N / 2;
+        auto pow2_ceil = [](size_t n) { size_t m = 1; while (m < n) m <<= 1; return m; };
+        const int nops = (a == b && na == nb) ? 1 : 2;
+        const E* src[2] = {a, b};
+        const size_t len[2] = {na, nb}, m[2] = {pow2_ceil(na), pow2_ceil(nb)};
+        // count rows of n coefficients -> count rows of mm, zero-padded
+        auto pad = [&](E* dst, const E* p, size_t n, size_t mm) {
+            const size_t mask = mm - 1; const unsigned lm = ilog2(mm);
+            foreach_n(s, count * mm, [=] __device__(size_t i) { const size_t j = i & mask; dst[i] = j < n ? p[(i >> lm) * n + j] : F::zero(); });
+        };
+        // cnt vectors of mm evaluations on T_mm (cur) -> 2mm evaluations on T_2mm (dst): interleave(cur, EXTEND_S1(cur)); ext: work
+        auto lift = [&](const E* cur, E* dst, E* ext, size_t mm, size_t cnt) -> bool {
+            if (!extend_api(cur, ext, mm, cnt, 1, s)) return false;
+            foreach_n(s, 2 * mm * cnt, [=] __device__(size_t i) { dst[i] = (i & 1) ? ext[i >> 1] : cur[i >> 1]; });
+            return true;
+        };
+        bool ok = true;
+        PolyEvals<F> ev[2];
+        int slot[2] = {-1, -1}, nl = 0;                           // lifted operands: slot q of the joint buffer
+        for (int i = 0; i < nops; ++i) {
+            if (m[i] < N) { slot[i] = nl++; continue; }
+            E* P = temp(count * N);                               // longer than N/2: ENTER_N of the zero-padded vector
+            if (len[i] == N) ok = enter(src[i], P, N, count, s) && ok;
+            else { pad(P, src[i], len[i], N); ok = enter(P, P, N, count, s) && ok; }
+            ev[i] = PolyEvals<F>{P, P + 1, N, 2u};
+        }
+        E *U = nullptr, *V = nullptr;
+        const E* cur = nullptr;
+        if (nl) {
+            // joint layout at size mm: slot q holds its operand's count vectors at [q*count*mm, (q+1)*count*mm)
+            U = temp(count * N); V = temp(count * N);
+            E* X = temp(nl * count * h);
+            size_t hi = 0;
+            for (int i = 0; i < nops; ++i) if (slot[i] >= 0 && m[i] > hi) hi = m[i];
+            int nbig = 0, q0 = -1;
+            for (int i = 0; i < nops; ++i)
+                if (slot[i] >= 0 && m[i] == hi) { pad(U + slot[i] * count * hi, src[i], len[i], hi); ++nbig; if (q0 < 0) q0 = slot[i]; }
+            ok = enter(U + q0 * count * hi, U + q0 * count * hi, hi, nbig * count, s) && ok;   // the slots at `hi` are adjacent
+            for (int i = 0; i < nops; ++i) {
+                if (slot[i] < 0 || m[i] == hi) continue;
+                // the shorter operand alone up to `hi`: ping-pong in V (each half holds count*h >= count*hi/2), last lift into its slot
+                E* c = V;
+                pad(V, src[i], len[i], m[i]);
+                ok = enter(V, V, m[i], count, s) && ok;
+                for (size_t mm = m[i]; mm < hi; mm *= 2) {
+                    E* dst = 2 * mm == hi ? U + slot[i] * count * hi : (c == V ? V + count * h : V);
+                    ok = lift(c, dst, X, mm, count) && ok;
+                    c = dst;
+                }
+            }
+            E* c = U;
+            for (size_t mm = hi; mm < h; mm *= 2) { E* dst = c == U ? V : U; ok = lift(c, dst, X, mm, nl * count) && ok; c = dst; }
+            ok = extend_api(c, X, h, nl * count, 1, s) && ok;      // the last lift's EXTEND; its interleave is k_poly_pointwise's load
+            cur = c;
+            for (int i = 0; i < nops; ++i)
+                if (slot[i] >= 0) ev[i] = PolyEvals<F>{cur + slot[i] * count * h, X + slot[i] * count * h, h, 1u};
+        }
+        if (nops == 1) ev[1] = ev[0];
+        E* Y = nl ? (cur == U ? V : U) : temp(count * N);
+        const size_t total = count * N;
+        ECFFT_LAUNCH(KC_POINTWISE, sizeof(E) * (nops + 1.0) * (double)total, k_poly_pointwise<F>, dim3(nblocks(total)), dim3(kBlock), 0, s,
+                     Y, ev[0], ev[1], F::to_table(rinv_), ilog2(N), total);
+        if (nc == N) ok = exit(Y, out, N, count, s) && ok;
+        else {
+            ok = exit(Y, Y, N, count, s) && ok;                  // coefficients nc .. N-1 are zero: keep the first nc of each row
+            ok = ok && hipMemcpy2DAsync(out, nc * sizeof(E), Y, N * sizeof(E), nc * sizeof(E), count, hipMemcpyDeviceToDevice, s) == hipSuccess;
+        }
+        temps_done();
+        return ok && hipGetLastError() == hipSuccess;
+    }
+
     // ------------------------------------------------------------------------------------------
     // Public wrappers of the remaining FFTree algorithms on USER data (crate representation),
     // composed from the same EXTEND kernels.  Device pointers; synchronous (they drain `s` before returning

@@ -141,6 +141,42 @@ int run_op(ecfft_ctx* c, DeviceChain<F>& ch, Op op, const void* in, void* out, s
     return ECFFT_OK;
 }
 
+// ecfft_poly_mul: like run_op (staging, lock, cross-stream event), inputs of na and nb and an output of na + nb - 1 elements per pair
+template <class F>
+int run_poly_mul(ecfft_ctx* c, DeviceChain<F>& ch, const void* a, size_t na, const void* b, size_t nb, void* out, size_t count,
+                 int mem, void* stream) {
+    using E = typename F::elem;
+    if (!a || !b || !out) return ECFFT_ERR_BAD_ARG;
+    if (na > ch.size() || nb > ch.size()) return ECFFT_ERR_TREE_TOO_SMALL;
+    const size_t nc = na + nb - 1;
+    size_t N = 1; while (N < nc) N <<= 1;
+    if (N > ch.size()) return ECFFT_ERR_TREE_TOO_SMALL;                   // "FFTree is too small"
+    if (count > SIZE_MAX / (8 * N * sizeof(E))) return ECFFT_ERR_BAD_ARG;  // byte counts of the temporaries must not wrap
+    if (mem != ECFFT_MEM_HOST && mem != ECFFT_MEM_DEVICE) return ECFFT_ERR_BAD_ARG;
+    hipStream_t s = (hipStream_t)stream;
+    DeviceGuard dev(c->device);
+    if (!dev.ok) return ECFFT_ERR_HIP;
+    std::lock_guard<std::mutex> guard(ch.lock());
+    OpScope scope(c, s);
+    if (!scope.ok) return ECFFT_ERR_HIP;
+    const bool sq = a == b && na == nb;
+    const size_t ba = na * count * sizeof(E), bb = sq ? 0 : nb * count * sizeof(E), bc = nc * count * sizeof(E);
+    const E *da = (const E*)a, *db = (const E*)b; E* dout = (E*)out;
+    if (mem == ECFFT_MEM_HOST) {
+        if (!ensure_stage(c, ba + bb + bc)) return ECFFT_ERR_HIP;
+        char* st = (char*)c->stage;
+        da = (const E*)st; db = sq ? da : (const E*)(st + ba); dout = (E*)(st + ba + bb);
+        if (hipMemcpyAsync((void*)da, a, ba, hipMemcpyHostToDevice, s) != hipSuccess) return ECFFT_ERR_HIP;
+        if (!sq && hipMemcpyAsync((void*)db, b, bb, hipMemcpyHostToDevice, s) != hipSuccess) return ECFFT_ERR_HIP;
+    }
+    if (!ch.poly_mul(da, na, db, nb, dout, count, s)) return ECFFT_ERR_HIP;
+    if (mem == ECFFT_MEM_HOST) {
+        if (hipMemcpyAsync(out, dout, bc, hipMemcpyDeviceToHost, s) != hipSuccess) return ECFFT_ERR_HIP;
+        if (hipStreamSynchronize(s) != hipSuccess) return ECFFT_ERR_HIP;
+    }
+    return ECFFT_OK;
+}
+
 // standard = true: plain standard-form residues (the FFTree wire format) instead of the crate's in-memory representation
 template <class F>
 int table_of(DeviceChain<F>& ch, size_t m, int which, void* host_out, size_t cap, size_t* count, bool standard = false) {
@@ -844,6 +880,12 @@ int ecfft_extend(ecfft_ctx* ctx, const void* in, void* out, size_t e, int moiety
     if (!ctx || shard_only(ctx)) return ECFFT_ERR_BAD_ARG;
     return guarded([&] { return ctx->field == ECFFT_FIELD_SECP256K1 ? run_op(ctx, *ctx->secp, OP_EXTEND, in, out, e, count, moiety, mem, stream)
                                                : run_op(ctx, *ctx->m31, OP_EXTEND, in, out, e, count, moiety, mem, stream); });
+}
+
+int ecfft_poly_mul(ecfft_ctx* ctx, const void* a, size_t na, const void* b, size_t nb, void* out, size_t count, int mem, void* stream) {
+    if (!ctx || shard_only(ctx) || na == 0 || nb == 0 || count == 0) return ECFFT_ERR_BAD_ARG;
+    return guarded([&] { return ctx->field == ECFFT_FIELD_SECP256K1 ? run_poly_mul(ctx, *ctx->secp, a, na, b, nb, out, count, mem, stream)
+                                               : run_poly_mul(ctx, *ctx->m31, a, na, b, nb, out, count, mem, stream); });
 }
 
 int ecfft_extend_top_cyclic(ecfft_ctx* ctx, void* buf, size_t e, int moiety, unsigned log_p, unsigned rank, int recombine, int mem, void* stream) {

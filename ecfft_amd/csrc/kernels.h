@@ -2074,6 +2074,35 @@ __global__ __launch_bounds__(kBlock) void k_scale_by_table(typename F::elem* dst
 }
 
 // ---------------------------------------------------------------------------------------------
+// pointwise product of ecfft_poly_mul (no reference counterpart): out[b*N + j] = A_b(x_j) * B_b(x_j) * R^-1 on the N leaves of T_N,
+// in the natural leaf order EXIT reads.  An operand's evaluations at the even leaves j = 2k and the odd leaves j = 2k+1 are read
+// through two pointers, so the last lift of a zero-padded operand (ENTER_N(p | 0) = interleave(E, EXTEND_S1(E)), src/fftree.rs:
+// 155-159 with v0 = v1 = 0) needs no interleave pass of its own: even = E, odd = EXTEND_S1(E), stride 1; an operand entered at the
+// full size N is even = P, odd = P + 1, stride 2.  User data is x*R (secp256k1, R = 2^256; field_secp256k1.h), so the plain product
+// of two operands carries R^2: the table multiply by R^-1 (rinv) puts it back in the crate's form.  M31 has R = 1.
+// ---------------------------------------------------------------------------------------------
+template <class F>
+struct PolyEvals {
+    const typename F::elem* even;   // evaluations at the leaves 2k of polynomial b: even[b*batch + k*stride]
+    const typename F::elem* odd;    // ... at the leaves 2k + 1: odd[b*batch + k*stride]
+    size_t batch;
+    uint32_t stride;
+};
+template <class F>
+__global__ __launch_bounds__(kBlock) void k_poly_pointwise(typename F::elem* __restrict__ out, PolyEvals<F> a, PolyEvals<F> b,
+                                                           typename F::telem rinv, uint32_t log_n, size_t total) {
+    using E = typename F::elem;
+    const size_t g = (size_t)blockIdx.x * kBlock + threadIdx.x;
+    if (g >= total) return;
+    const size_t bi = g >> log_n, j = g & (((size_t)1 << log_n) - 1), k = j >> 1;
+    const E* pa = (j & 1) ? a.odd : a.even;
+    const E* pb = (j & 1) ? b.odd : b.even;
+    E r = F::mul(pa[bi * a.batch + k * a.stride], pb[bi * b.batch + k * b.stride]);
+    if constexpr (sizeof(E) == 32) r = F::tmul(rinv, r);
+    out[g] = F::canon(r);
+}
+
+// ---------------------------------------------------------------------------------------------
 // generic element-wise helper for tree construction: functor(i) for i < n
 // ---------------------------------------------------------------------------------------------
 template <class Fn>

@@ -31,7 +31,8 @@ EXPORTS = ["ecfft_elem_size", "ecfft_build_fftree", "ecfft_fftree_new", "ecfft_c
            "ecfft_mul_ceiling", "ecfft_elems_to_standard", "ecfft_elems_from_standard", "ecfft_table_fma", "ecfft_enter_many", "ecfft_exit_many", "ecfft_mextend", "ecfft_redc", "ecfft_modular_reduce", "ecfft_vanish", "ecfft_degree",
            "ecfft_comm_get_unique_id", "ecfft_comm_init_rank", "ecfft_comm_init_callback", "ecfft_comm_destroy", "ecfft_comm_rank", "ecfft_comm_world",
            "ecfft_comm_stats_enable", "ecfft_comm_stats_read", "ecfft_extend_sharded", "ecfft_enter_sharded", "ecfft_exit_sharded", "ecfft_device_copy", "ecfft_shader_clock", "ecfft_device_alloc", "ecfft_device_free", "ecfft_device_sync", "ecfft_build_extend_shard", "ecfft_ctx_device_bytes", "ecfft_extend_sharded_layout", "ecfft_build_enter_shard", "ecfft_build_exit_shard", "ecfft_build_exit_shard_opts",
-           "ecfft_fftree_serialize", "ecfft_fftree_deserialize", "ecfft_tree_rational_maps", "ecfft_ctx_trim", "ecfft_comm_abort", "ecfft_comm_set_rccl_library", "ecfft_comm_set_link_striping"]
+           "ecfft_fftree_serialize", "ecfft_fftree_deserialize", "ecfft_tree_rational_maps", "ecfft_ctx_trim", "ecfft_comm_abort", "ecfft_comm_set_rccl_library", "ecfft_comm_set_link_striping",
+           "ecfft_poly_mul"]
 
 # include/ecfft_hip_hooks.h: only in a build with -DECFFT_TEST_HOOKS (tests/hooks/libecfft_hip_hooks.so), never in the shipped library
 HOOK_EXPORTS = ['ecfft_selftest_field', 'ecfft_selfcheck_pointwise_z', 'ecfft_test_fail_next_collective', 'ecfft_selftest_blk16', 'ecfft_selftest_blk16_small', 'ecfft_test_fail_build_rank', 'ecfft_comm_init_projection', 'ecfft_selftest_blk32', 'ecfft_ctx_low_map']
@@ -65,6 +66,7 @@ def _bind(L):
     L.ecfft_enter.restype, L.ecfft_enter.argtypes = ci, [vp, vp, vp, sz, ci, vp]
     L.ecfft_exit.restype, L.ecfft_exit.argtypes = ci, [vp, vp, vp, sz, ci, vp]
     L.ecfft_extend.restype, L.ecfft_extend.argtypes = ci, [vp, vp, vp, sz, ci, sz, ci, vp]
+    L.ecfft_poly_mul.restype, L.ecfft_poly_mul.argtypes = ci, [vp, vp, sz, vp, sz, vp, sz, ci, vp]
     L.ecfft_tree_table.restype, L.ecfft_tree_table.argtypes = ci, [vp, sz, ci, vp, sz, ctypes.POINTER(sz)]
     L.ecfft_build_points.restype, L.ecfft_build_points.argtypes = ci, [ci, sz, vp, vp, vp]
     L.ecfft_device_info.restype, L.ecfft_device_info.argtypes = ci, [ci, ctypes.c_char_p, sz]
@@ -383,6 +385,33 @@ class FFTree:
         pin, out, pout, mem, stream, total = self._io(evals)
         assert total % count == 0
         _check(self._L.ecfft_extend(self._h, pin, pout, total // count, int(moiety), count, mem, stream))
+        return out
+
+    def poly_mul(self, a, b, count=1):
+        """c = a * b in coefficient form (ecfft_poly_mul; no reference counterpart): `count` pairs laid end to end, a of
+        count * na and b of count * nb coefficients, any lengths; returns count * (na + nb - 1) coefficients.  Needs a tree of
+        next_pow2(na + nb - 1) leaves.  Passing the same object as a and b is a squaring (one forward transform).  numpy arrays
+        (host) or contiguous CUDA tensors (device, on the tensor's current stream), both of the same kind."""
+        if _is_torch(a) or _is_torch(b):
+            import torch
+            assert _is_torch(a) and _is_torch(b), "a and b must both be numpy arrays or both CUDA tensors"
+            for x in (a, b):
+                assert x.is_cuda and x.is_contiguous(), "device tensors must be contiguous CUDA tensors"
+            na, nb = a.shape[0], b.shape[0]
+            out = torch.empty((count * max(na // count + nb // count - 1, 0),) + tuple(a.shape[1:]), dtype=a.dtype, device=a.device)
+            pa, pb, pout, mem, stream = a.data_ptr(), b.data_ptr(), out.data_ptr(), MEM_DEVICE, torch.cuda.current_stream(a.device).cuda_stream
+        else:
+            sq = a is b
+            a = np.ascontiguousarray(a, self.field.dtype)
+            b = a if sq else np.ascontiguousarray(b, self.field.dtype)
+            na, nb = a.shape[0], b.shape[0]
+            out = np.empty(self.field.shape(count * max(na // count + nb // count - 1, 0)), self.field.dtype)
+            pa, pb, pout, mem, stream = a.ctypes.data, b.ctypes.data, out.ctypes.data, MEM_HOST, None
+        assert count > 0 and na % count == 0 and nb % count == 0
+        rc = self._L.ecfft_poly_mul(self._h, pa, na // count, pb, nb // count, pout, count, mem, stream)
+        if rc == ERR_BAD_ARG:
+            raise ValueError("poly_mul: empty operand, count = 0 or a context that holds no full tree")
+        _check(rc)
         return out
 
     # ---- the remaining FFTree algorithms (host numpy arrays; synchronous) ---------------------

@@ -154,11 +154,23 @@ public:
         check(ecfft_degree(ctx_, evals.data(), evals.size(), ECFFT_MEM_HOST, nullptr, &d));
         return d;
     }
+    // c = a * b in coefficient form (ecfft_poly_mul; no reference counterpart): any lengths, na + nb - 1 coefficients; the tree
+    // must hold next_pow2(na + nb - 1) leaves.  mul(a, a) on the same vector is a squaring.
+    std::vector<Elem> mul(const std::vector<Elem>& a, const std::vector<Elem>& b) const {
+        require(!a.empty() && !b.empty(), "mul: operands must not be empty");
+        std::vector<Elem> out(a.size() + b.size() - 1);
+        check(ecfft_poly_mul(ctx_, a.data(), a.size(), b.data(), b.size(), out.data(), 1, ECFFT_MEM_HOST, nullptr));
+        return out;
+    }
     size_t device_bytes() const { return ecfft_ctx_device_bytes(ctx_); }     // HBM held between calls: tables + scratch
     // device-resident variants (pointers into HBM, caller's stream)
     void enter_device(const Elem* coeffs, Elem* evals, size_t n, void* stream) const { check(ecfft_enter(ctx_, coeffs, evals, n, ECFFT_MEM_DEVICE, stream)); }
     void exit_device(const Elem* evals, Elem* coeffs, size_t n, void* stream) const { check(ecfft_exit(ctx_, evals, coeffs, n, ECFFT_MEM_DEVICE, stream)); }
     void extend_device(const Elem* in, Elem* out, size_t e, Moiety m, size_t count, void* stream) const { check(ecfft_extend(ctx_, in, out, e, (int)m, count, ECFFT_MEM_DEVICE, stream)); }
+    // count pairs: a count x na, b count x nb, out count x (na + nb - 1)
+    void mul_device(const Elem* a, size_t na, const Elem* b, size_t nb, Elem* out, size_t count, void* stream) const {
+        check(ecfft_poly_mul(ctx_, a, na, b, nb, out, count, ECFFT_MEM_DEVICE, stream));
+    }
 
     // ONE transform split over the ranks of `comm` (device pointers: this rank's block shard of len / world elements)
     void extend_sharded(const Comm& comm, const Elem* in, Elem* out, size_t e, Moiety m, void* stream) const { check(ecfft_extend_sharded(ctx_, comm.raw(), in, out, e, (int)m, stream)); }

@@ -100,6 +100,15 @@ int ecfft_exit_many(ecfft_ctx* ctx, const void* evals, void* coeffs, size_t n, s
  * of T_{2e}; vectors are laid end to end (count = 1 is FFTree::extend).  (An even batch of >= 2^20 elements of vectors with
  * e >= 2^19 runs as two half-batches on two streams, like the batched ENTER / EXIT.) */
 int ecfft_extend(ecfft_ctx* ctx, const void* in, void* out, size_t e, int moiety, size_t count, int mem, void* stream);
+/* c = a * b in coefficient form; no reference counterpart (the enter -> pointwise -> exit composition of
+ * src/fftree.rs:164-167, 227-230 that a user of the crate writes by hand).  a: count x na, b: count x nb,
+ * out: count x (na + nb - 1) coefficients, each polynomial laid end to end.  na, nb >= 1, any length (not only powers of two).
+ * Needs the context's tree to hold N = next_pow2(na + nb - 1) leaves, else ECFFT_ERR_TREE_TOO_SMALL.
+ * a == b with na == nb is a squaring (one forward transform).  out must not overlap a or b.
+ * An operand of at most N/2 coefficients is entered at its own size and lifted to N by EXTENDs (with its high half zero, ENTER of
+ * 2m coefficients is the ENTER of m interleaved with its EXTEND onto S1), so the call costs about one ENTER_N + one EXIT_N plus
+ * the pointwise product.  Memory, stream and threading as for ecfft_enter_many; temporaries are pooled (ecfft_ctx_trim). */
+int ecfft_poly_mul(ecfft_ctx* ctx, const void* a, size_t na, const void* b, size_t nb, void* out, size_t count, int mem, void* stream);
 
 /* The remaining FFTree algorithms, composed from the same GPU kernels.  Synchronous.
  *   ecfft_mextend         <-> FFTree::mextend(&self, &[F], Moiety)      src/fftree.rs:138-141
