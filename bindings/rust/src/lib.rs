@@ -52,6 +52,8 @@ pub mod ffi {
         pub fn ecfft_exit_many(ctx: *mut EcfftCtx, evals: *const c_void, coeffs: *mut c_void, n: usize, count: usize, mem: i32, stream: *mut c_void) -> i32;
         pub fn ecfft_extend(ctx: *mut EcfftCtx, inp: *const c_void, out: *mut c_void, e: usize, moiety: i32, count: usize, mem: i32, stream: *mut c_void) -> i32;
         pub fn ecfft_poly_mul(ctx: *mut EcfftCtx, a: *const c_void, na: usize, b: *const c_void, nb: usize, out: *mut c_void, count: usize, mem: i32, stream: *mut c_void) -> i32;
+        pub fn ecfft_poly_inv_series(ctx: *mut EcfftCtx, f: *const c_void, nf: usize, out: *mut c_void, k: usize, count: usize, mem: i32, stream: *mut c_void) -> i32;
+        pub fn ecfft_poly_divrem(ctx: *mut EcfftCtx, a: *const c_void, na: usize, b: *const c_void, nb: usize, q: *mut c_void, r: *mut c_void, count: usize, mem: i32, stream: *mut c_void) -> i32;
         pub fn ecfft_mextend(ctx: *mut EcfftCtx, inp: *const c_void, out: *mut c_void, e: usize, moiety: i32, count: usize, mem: i32, stream: *mut c_void) -> i32;
         pub fn ecfft_redc(ctx: *mut EcfftCtx, evals: *const c_void, a: *const c_void, out: *mut c_void, n: usize, moiety: i32, mem: i32, stream: *mut c_void) -> i32;
         pub fn ecfft_modular_reduce(ctx: *mut EcfftCtx, evals: *const c_void, a: *const c_void, c: *const c_void, out: *mut c_void, n: usize, mem: i32, stream: *mut c_void) -> i32;
@@ -225,6 +227,35 @@ impl<F: HipField> HipFFTree<F> {
         let mut out = Self::out_vec(n);
         check(unsafe { ffi::ecfft_poly_mul(self.ctx, a.as_ptr().cast(), a.len(), b.as_ptr().cast(), b.len(), out.as_mut_ptr().cast(), 1, ffi::MEM_HOST, core::ptr::null_mut()) });
         unsafe { out.set_len(n) };
+        out
+    }
+
+    /// `ecfft::utils::div_rem` (src/utils.rs:184-193) with the quotient too: `(q, r)` with `a = b*q + r`, `deg r < deg b`; `q` has
+    /// `a.len() - b.len() + 1` coefficients (none when `a` is shorter), `r` has `b.len() - 1`, zero-padded above its degree.
+    /// `b`'s last coefficient must be nonzero.  Tree rule: include/ecfft_hip.h.
+    pub fn div_rem(&self, a: &[F], b: &[F]) -> (Vec<F>, Vec<F>) {
+        assert!(!a.is_empty() && !b.is_empty());
+        let nq = if a.len() >= b.len() { a.len() - b.len() + 1 } else { 0 };
+        let nr = b.len() - 1;
+        let mut q = Self::out_vec(nq);
+        let mut r = Self::out_vec(nr);
+        let pq = if nq > 0 { q.as_mut_ptr().cast() } else { core::ptr::null_mut() };
+        let pr = if nr > 0 { r.as_mut_ptr().cast() } else { core::ptr::null_mut() };
+        check(unsafe { ffi::ecfft_poly_divrem(self.ctx, a.as_ptr().cast(), a.len(), b.as_ptr().cast(), b.len(), pq, pr, 1, ffi::MEM_HOST, core::ptr::null_mut()) });
+        unsafe {
+            q.set_len(nq);
+            r.set_len(nr);
+        }
+        (q, r)
+    }
+
+    /// `1/f mod x^k` (ecfft_poly_inv_series; no reference counterpart): `k` coefficients, `f[0]` nonzero; the tree must hold
+    /// `next_pow2(2k - 1)` leaves.
+    pub fn inv_series(&self, f: &[F], k: usize) -> Vec<F> {
+        assert!(!f.is_empty() && k > 0);
+        let mut out = Self::out_vec(k);
+        check(unsafe { ffi::ecfft_poly_inv_series(self.ctx, f.as_ptr().cast(), f.len(), out.as_mut_ptr().cast(), k, 1, ffi::MEM_HOST, core::ptr::null_mut()) });
+        unsafe { out.set_len(k) };
         out
     }
 

@@ -1614,17 +1614,154 @@ public:
     // from the size at which they meet, the last lift's interleave is the load of k_poly_pointwise, and one batched EXIT_N returns the
     // coefficients.  An operand longer than N/2 is zero-padded and entered at N.  a == b with na == nb (squaring) enters one operand.
     bool poly_mul(const E* a, size_t na, const E* b, size_t nb, E* out, size_t count, hipStream_t s) {
+        const bool ok = poly_mul_body(a, na, na, b, nb, nb, out, count, s);
+        temps_done();
+        return ok && hipGetLastError() == hipSuccess;
+    }
+
+    // ecfft_poly_inv_series (no reference counterpart): out_b = 1/f_b mod x^k for `count` series laid end to end (f: count x nf,
+    // out: count x k, crate representation).  The first p0 = ceil(k / 2^t) <= kSeriesBase coefficients come from the schoolbook
+    // recurrence (k_series_base, one workgroup per pair); each Newton step p -> p' = ceil(k / 2^(t-1)) is then one fused step on
+    // T_N, N = next_pow2(2p + p' - 2) (newton_step), the last one on next_pow2(2k - 1) leaves.  Device pointers; synchronous (the
+    // flag of a zero f_b[0] is read back: *singular).  Caller holds lock().
+    bool inv_series(const E* f, size_t nf, E* out, size_t k, size_t count, bool* singular, hipStream_t s) {
+        int* flag = new_flag(s);
+        const bool ok = inv_series_body(f, nf, nf, out, k, count, flag, s);
+        return finish_flagged(ok, flag, singular, s);
+    }
+
+    // ecfft_poly_divrem (utils::div_rem, src/utils.rs:184-193 = ark-poly divide_with_q_and_r): a_b = b_b q_b + r_b, deg r_b < deg b_b
+    // (a: count x na, b: count x nb, q: count x nq, nq = na - nb + 1 or 0, r: count x (nb - 1); q or r may be null).  With
+    // g = 1/rev(b) mod x^nq, q = rev(rev(a) g mod x^nq) and r = a - (b mod x^nr)(q mod x^nr) mod x^nr: one reciprocal and two
+    // products on poly_mul's lifts.  nb == 1 scales by 1/b_0; na < nb copies a into r.  Every path inverts (and checks) the
+    // divisor's leading coefficient on the device.  Synchronous; *singular = some b_b[nb-1] == 0.  Caller holds lock().
+    bool poly_divrem(const E* a, size_t na, const E* b, size_t nb, E* q, E* r, size_t count, bool* singular, hipStream_t s) {
+        int* flag = new_flag(s);
+        const size_t nq = na >= nb ? na - nb + 1 : 0, nr = nb - 1;
+        bool ok = true;
+        if (nq == 0 || nb == 1) {
+            E* binv = temp(count);                                // 1/b_{nb-1} of every pair, crate form
+            series_base(b + nb - 1, nb, 1, binv, 1, 1, count, flag, s);
+            if (nq == 0 && r) {
+                foreach_n(s, count * nr, [=] __device__(size_t i) { const size_t bi = i / nr, j = i - bi * nr; r[i] = j < na ? a[bi * na + j] : F::zero(); });
+            } else if (nq && q) {
+                const E rinv = rinv_;
+                foreach_n(s, count * na, [=] __device__(size_t i) { q[i] = F::canon(F::mul(F::mul(a[i], binv[i / na]), rinv)); });
+            }
+            return finish_flagged(ok, flag, singular, s);
+        }
+        const size_t nf = nq < nb ? nq : nb, np = 2 * nq - 1;    // rev(b) mod x^nq; rev(a) mod x^nq times g
+        E* fr = temp(count * nf); E* ar = temp(count * nq); E* g = temp(count * nq); E* pq = temp(count * np);
+        E* qq = q ? q : temp(count * nq);
+        foreach_n(s, count * nf, [=] __device__(size_t i) { const size_t bi = i / nf, j = i - bi * nf; fr[i] = b[bi * nb + nb - 1 - j]; });
+        foreach_n(s, count * nq, [=] __device__(size_t i) { const size_t bi = i / nq, j = i - bi * nq; ar[i] = a[bi * na + na - 1 - j]; });
+        ok = inv_series_body(fr, nf, nf, g, nq, count, flag, s) && ok;
+        ok = poly_mul_body(ar, nq, nq, g, nq, nq, pq, count, s) && ok;
+        foreach_n(s, count * nq, [=] __device__(size_t i) { const size_t bi = i / nq, j = i - bi * nq; qq[i] = pq[bi * np + nq - 1 - j]; });
+        if (r) {
+            const size_t mq = nq < nr ? nq : nr, npr = nr + mq - 1, total = count * nr;
+            E* pr = temp(count * npr);
+            ok = poly_mul_body(b, nr, nb, qq, mq, nq, pr, count, s) && ok;    // (b mod x^nr)(q mod x^nr): rows read in place
+            ECFFT_LAUNCH(KC_POINTWISE, sizeof(E) * 3.0 * (double)total, k_divrem_sub<F>, dim3(nblocks(total)), dim3(kBlock), 0, s,
+                         r, nr, a, na, (const E*)pr, npr, total);
+        }
+        return finish_flagged(ok, flag, singular, s);
+    }
+
+    // coefficients of the reciprocal computed by k_series_base before the Newton steps take over (K0).  64 = one wave per pair: a
+    // Newton step at p <= 64 costs a lift + EXIT in the latency regime, the recurrence's 63 tree sums a few us.
+    static constexpr size_t kSeriesBase = 64;
+    // poly_mul without releasing the temporaries (the division holds its own across several products); operand rows of len
+    // coefficients at a row stride of ld (>= len) elements
+    bool poly_mul_body(const E* a, size_t na, size_t lda, const E* b, size_t nb, size_t ldb, E* out, size_t count, hipStream_t s) {
         const size_t nc = na + nb - 1;
         size_t N = 1; while (N < nc) N <<= 1;
+        const int nops = (a == b && na == nb && lda == ldb) ? 1 : 2;
+        const E* src[2] = {a, b};
+        const size_t len[2] = {na, nb}, ld[2] = {lda, ldb};
+        PolyEvals<F> ev[2];
+        E* Y = nullptr;
+        bool ok = lift_operands(src, len, ld, nops, N, count, ev, Y, s);
+        const size_t total = count * N;
+        ECFFT_LAUNCH(KC_POINTWISE, sizeof(E) * (nops + 1.0) * (double)total, k_poly_pointwise<F>, dim3(nblocks(total)), dim3(kBlock), 0, s,
+                     Y, ev[0], ev[1], F::to_table(rinv_), ilog2(N), total);
+        return exit_rows(Y, out, nc, N, count, ok, s);
+    }
+    // EXIT_N of count rows of Y, keeping the first nc coefficients of each (the others are zero) in out (count x nc)
+    bool exit_rows(E* Y, E* out, size_t nc, size_t N, size_t count, bool ok, hipStream_t s) {
+        if (nc == N) ok = exit(Y, out, N, count, s) && ok;
+        else {
+            ok = exit(Y, Y, N, count, s) && ok;                  // coefficients nc .. N-1 are zero: keep the first nc of each row
+            ok = ok && hipMemcpy2DAsync(out, nc * sizeof(E), Y, N * sizeof(E), nc * sizeof(E), count, hipMemcpyDeviceToDevice, s) == hipSuccess;
+        }
+        return ok;
+    }
+    // k_series_base on count rows (grid chunks of at most 2^16 pairs)
+    void series_base(const E* f, size_t ldf, size_t nf, E* out, size_t ldo, size_t p0, size_t count, int* flag, hipStream_t s) {
+        const E r1 = F::to_mont(F::one());
+        for (size_t c0 = 0; c0 < count; c0 += (size_t)1 << 16) {
+            const size_t c = count - c0 < ((size_t)1 << 16) ? count - c0 : (size_t)1 << 16;
+            ECFFT_LAUNCH(KC_POINTWISE, sizeof(E) * 2.0 * (double)(c * p0), (k_series_base<F, (int)kSeriesBase>), dim3((unsigned)c),
+                         dim3((unsigned)kSeriesBase), 0, s, out + c0 * ldo, ldo, f + c0 * ldf, ldf, nf, (uint32_t)p0, rinv_, r1, flag);
+        }
+    }
+    // 1/f mod x^k (f: count rows of nf coefficients at a stride of ldf) into out (count x k); raises *flag on a zero f[0]
+    bool inv_series_body(const E* f, size_t nf, size_t ldf, E* out, size_t k, size_t count, int* flag, hipStream_t s) {
+        unsigned t = 0;
+        while (((k + ((size_t)1 << t) - 1) >> t) > kSeriesBase) ++t;
+        size_t p = (k + ((size_t)1 << t) - 1) >> t;
+        E* buf[2] = {t ? temp(count * k) : nullptr, t > 1 ? temp(count * k) : nullptr};
+        const E* g = t ? buf[0] : out;
+        series_base(f, ldf, nf, t ? buf[0] : out, t ? p : k, p, count, flag, s);
+        bool ok = true;
+        for (int side = 1; t > 0; --t, side ^= 1) {
+            const size_t p2 = (k + ((size_t)1 << (t - 1)) - 1) >> (t - 1);
+            E* dst = t == 1 ? out : buf[side];
+            ok = newton_step(f, nf, ldf, g, p, dst, p2, count, s) && ok;
+            g = dst; p = p2;
+        }
+        return ok;
+    }
+    // g (count x p, p coefficients of 1/f) -> out (count x p2) = g (2 - f g) mod x^p2: f mod x^p2 and g entered at their own size
+    // and lifted to N = next_pow2(2p + p2 - 2) on the joint launches of poly_mul, k_newton_pointwise, one batched EXIT_N.
+    // deg(g^2 f) < N, so nothing wraps.
+    bool newton_step(const E* f, size_t nf, size_t ldf, const E* g, size_t p, E* out, size_t p2, size_t count, hipStream_t s) {
+        size_t N = 1; while (N < 2 * p + p2 - 2) N <<= 1;
+        const E* src[2] = {f, g};
+        const size_t len[2] = {nf < p2 ? nf : p2, p}, ld[2] = {ldf, p};
+        PolyEvals<F> ev[2];
+        E* Y = nullptr;
+        bool ok = lift_operands(src, len, ld, 2, N, count, ev, Y, s);
+        const E R = F::to_mont(F::one()), r2 = F::mul(R, R);
+        const size_t total = count * N;
+        ECFFT_LAUNCH(KC_POINTWISE, sizeof(E) * 3.0 * (double)total, k_newton_pointwise<F>, dim3(nblocks(total)), dim3(kBlock), 0, s,
+                     Y, ev[0], ev[1], F::add(r2, r2), F::to_table(F::mul(rinv_, rinv_)), ilog2(N), total);
+        return exit_rows(Y, out, p2, N, count, ok, s);
+    }
+    int* new_flag(hipStream_t s) {
+        int* flag = reinterpret_cast<int*>(temp((sizeof(int) + sizeof(E) - 1) / sizeof(E)));
+        (void)hipMemsetAsync(flag, 0, sizeof(int), s);
+        return flag;
+    }
+    bool finish_flagged(bool ok, const int* flag, bool* singular, hipStream_t s) {
+        int h = 0;
+        ok = ok && hipMemcpyAsync(&h, flag, sizeof(int), hipMemcpyDeviceToHost, s) == hipSuccess;
+        ok = finish_api(s) && ok;
+        *singular = h != 0;
+        return ok;
+    }
+    // The lifting half of poly_mul: the nops operands (src[i]: count rows of len[i] coefficients at a row stride of ld[i]) entered
+    // at their own size and lifted to N, sharing the launches from the size at which they meet; ev[i] reads operand i's evaluations
+    // on the leaves of T_N (the last lift's interleave), Y is a free count x N buffer.  Takes temporaries.
+    bool lift_operands(const E* const* src, const size_t* len, const size_t* ld, int nops, size_t N, size_t count, PolyEvals<F>* ev, E*& Y,
+                       hipStream_t s) {
         const size_t h = N / 2;
         auto pow2_ceil = [](size_t n) { size_t m = 1; while (m < n) m <<= 1; return m; };
-        const int nops = (a == b && na == nb) ? 1 : 2;
-        const E* src[2] = {a, b};
-        const size_t len[2] = {na, nb}, m[2] = {pow2_ceil(na), pow2_ceil(nb)};
-        // count rows of n coefficients -> count rows of mm, zero-padded
-        auto pad = [&](E* dst, const E* p, size_t n, size_t mm) {
+        const size_t m[2] = {pow2_ceil(len[0]), pow2_ceil(len[1])};
+        // count rows of n coefficients (row stride ldp) -> count rows of mm, zero-padded
+        auto pad = [&](E* dst, const E* p, size_t n, size_t ldp, size_t mm) {
             const size_t mask = mm - 1; const unsigned lm = ilog2(mm);
-            foreach_n(s, count * mm, [=] __device__(size_t i) { const size_t j = i & mask; dst[i] = j < n ? p[(i >> lm) * n + j] : F::zero(); });
+            foreach_n(s, count * mm, [=] __device__(size_t i) { const size_t j = i & mask; dst[i] = j < n ? p[(i >> lm) * ldp + j] : F::zero(); });
         };
         // cnt vectors of mm evaluations on T_mm (cur) -> 2mm evaluations on T_2mm (dst): interleave(cur, EXTEND_S1(cur)); ext: work
         auto lift = [&](const E* cur, E* dst, E* ext, size_t mm, size_t cnt) -> bool {
@@ -1633,13 +1770,12 @@ public:
             return true;
         };
         bool ok = true;
-        PolyEvals<F> ev[2];
         int slot[2] = {-1, -1}, nl = 0;                           // lifted operands: slot q of the joint buffer
         for (int i = 0; i < nops; ++i) {
             if (m[i] < N) { slot[i] = nl++; continue; }
             E* P = temp(count * N);                               // longer than N/2: ENTER_N of the zero-padded vector
-            if (len[i] == N) ok = enter(src[i], P, N, count, s) && ok;
-            else { pad(P, src[i], len[i], N); ok = enter(P, P, N, count, s) && ok; }
+            if (len[i] == N && ld[i] == N) ok = enter(src[i], P, N, count, s) && ok;
+            else { pad(P, src[i], len[i], ld[i], N); ok = enter(P, P, N, count, s) && ok; }
             ev[i] = PolyEvals<F>{P, P + 1, N, 2u};
         }
         E *U = nullptr, *V = nullptr;
@@ -1652,13 +1788,13 @@ public:
             for (int i = 0; i < nops; ++i) if (slot[i] >= 0 && m[i] > hi) hi = m[i];
             int nbig = 0, q0 = -1;
             for (int i = 0; i < nops; ++i)
-                if (slot[i] >= 0 && m[i] == hi) { pad(U + slot[i] * count * hi, src[i], len[i], hi); ++nbig; if (q0 < 0) q0 = slot[i]; }
+                if (slot[i] >= 0 && m[i] == hi) { pad(U + slot[i] * count * hi, src[i], len[i], ld[i], hi); ++nbig; if (q0 < 0) q0 = slot[i]; }
             ok = enter(U + q0 * count * hi, U + q0 * count * hi, hi, nbig * count, s) && ok;   // the slots at `hi` are adjacent
             for (int i = 0; i < nops; ++i) {
                 if (slot[i] < 0 || m[i] == hi) continue;
                 // the shorter operand alone up to `hi`: ping-pong in V (each half holds count*h >= count*hi/2), last lift into its slot
                 E* c = V;
-                pad(V, src[i], len[i], m[i]);
+                pad(V, src[i], len[i], ld[i], m[i]);
                 ok = enter(V, V, m[i], count, s) && ok;
                 for (size_t mm = m[i]; mm < hi; mm *= 2) {
                     E* dst = 2 * mm == hi ? U + slot[i] * count * hi : (c == V ? V + count * h : V);
@@ -1674,17 +1810,8 @@ public:
                 if (slot[i] >= 0) ev[i] = PolyEvals<F>{cur + slot[i] * count * h, X + slot[i] * count * h, h, 1u};
         }
         if (nops == 1) ev[1] = ev[0];
-        E* Y = nl ? (cur == U ? V : U) : temp(count * N);
-        const size_t total = count * N;
-        ECFFT_LAUNCH(KC_POINTWISE, sizeof(E) * (nops + 1.0) * (double)total, k_poly_pointwise<F>, dim3(nblocks(total)), dim3(kBlock), 0, s,
-                     Y, ev[0], ev[1], F::to_table(rinv_), ilog2(N), total);
-        if (nc == N) ok = exit(Y, out, N, count, s) && ok;
-        else {
-            ok = exit(Y, Y, N, count, s) && ok;                  // coefficients nc .. N-1 are zero: keep the first nc of each row
-            ok = ok && hipMemcpy2DAsync(out, nc * sizeof(E), Y, N * sizeof(E), nc * sizeof(E), count, hipMemcpyDeviceToDevice, s) == hipSuccess;
-        }
-        temps_done();
-        return ok && hipGetLastError() == hipSuccess;
+        Y = nl ? (cur == U ? V : U) : temp(count * N);
+        return ok;
     }
 
     // ------------------------------------------------------------------------------------------

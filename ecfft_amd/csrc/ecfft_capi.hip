@@ -177,6 +177,87 @@ int run_poly_mul(ecfft_ctx* c, DeviceChain<F>& ch, const void* a, size_t na, con
     return ECFFT_OK;
 }
 
+// ecfft_poly_divrem / ecfft_poly_inv_series: staging, lock and cross-stream event as run_poly_mul; synchronous (the chain reads back
+// the device flag of a zero divisor leading coefficient / f[0], reported as ECFFT_ERR_BAD_ARG)
+template <class F>
+int run_poly_divrem(ecfft_ctx* c, DeviceChain<F>& ch, const void* a, size_t na, const void* b, size_t nb, void* q, void* r, size_t count,
+                    int mem, void* stream) {
+    using E = typename F::elem;
+    if (!a || !b || (!q && !r)) return ECFFT_ERR_BAD_ARG;
+    const size_t lim = SIZE_MAX / (64 * sizeof(E));
+    if (na > lim || nb > lim) return ECFFT_ERR_BAD_ARG;
+    const size_t nq = na >= nb ? na - nb + 1 : 0, nr = nb - 1;
+    size_t N = 1;
+    if (nq && nr) {                                                         // nb == 1 (scaling) and na < nb (copy): no transform
+        const size_t mq = nq < nr ? nq : nr, need = 2 * nq - 1 > nr + mq - 1 ? 2 * nq - 1 : nr + mq - 1;
+        while (N < need) N <<= 1;
+        if (N > ch.size()) return ECFFT_ERR_TREE_TOO_SMALL;
+    }
+    const size_t per = N > na + nb ? N : na + nb;
+    if (count > SIZE_MAX / (8 * per * sizeof(E))) return ECFFT_ERR_BAD_ARG; // byte counts of the temporaries must not wrap
+    if (mem != ECFFT_MEM_HOST && mem != ECFFT_MEM_DEVICE) return ECFFT_ERR_BAD_ARG;
+    hipStream_t s = (hipStream_t)stream;
+    DeviceGuard dev(c->device);
+    if (!dev.ok) return ECFFT_ERR_HIP;
+    std::lock_guard<std::mutex> guard(ch.lock());
+    OpScope scope(c, s);
+    if (!scope.ok) return ECFFT_ERR_HIP;
+    const size_t ba = na * count * sizeof(E), bb = nb * count * sizeof(E), bq = q ? nq * count * sizeof(E) : 0, br = r ? nr * count * sizeof(E) : 0;
+    const E *da = (const E*)a, *db = (const E*)b; E *dq = (E*)q, *dr = (E*)r;
+    if (mem == ECFFT_MEM_HOST) {
+        if (!ensure_stage(c, ba + bb + bq + br)) return ECFFT_ERR_HIP;
+        char* st = (char*)c->stage;
+        da = (const E*)st; db = (const E*)(st + ba);
+        dq = q ? (E*)(st + ba + bb) : nullptr; dr = r ? (E*)(st + ba + bb + bq) : nullptr;
+        if (hipMemcpyAsync((void*)da, a, ba, hipMemcpyHostToDevice, s) != hipSuccess) return ECFFT_ERR_HIP;
+        if (hipMemcpyAsync((void*)db, b, bb, hipMemcpyHostToDevice, s) != hipSuccess) return ECFFT_ERR_HIP;
+    }
+    bool singular = false;
+    if (!ch.poly_divrem(da, na, db, nb, dq, dr, count, &singular, s)) return ECFFT_ERR_HIP;
+    if (singular) return ECFFT_ERR_BAD_ARG;                                 // a zero leading coefficient of b in some pair
+    if (mem == ECFFT_MEM_HOST) {
+        if (bq && hipMemcpyAsync(q, dq, bq, hipMemcpyDeviceToHost, s) != hipSuccess) return ECFFT_ERR_HIP;
+        if (br && hipMemcpyAsync(r, dr, br, hipMemcpyDeviceToHost, s) != hipSuccess) return ECFFT_ERR_HIP;
+        if (hipStreamSynchronize(s) != hipSuccess) return ECFFT_ERR_HIP;
+    }
+    return ECFFT_OK;
+}
+
+template <class F>
+int run_inv_series(ecfft_ctx* c, DeviceChain<F>& ch, const void* f, size_t nf, void* out, size_t k, size_t count, int mem, void* stream) {
+    using E = typename F::elem;
+    if (!f || !out) return ECFFT_ERR_BAD_ARG;
+    const size_t lim = SIZE_MAX / (64 * sizeof(E));
+    if (nf > lim || k > lim) return ECFFT_ERR_BAD_ARG;
+    size_t N = 1;
+    while (N < 2 * k - 1) N <<= 1;
+    if (N > ch.size()) return ECFFT_ERR_TREE_TOO_SMALL;                     // k = 1: N = 1, any tree
+    const size_t per = N > nf + k ? N : nf + k;
+    if (count > SIZE_MAX / (8 * per * sizeof(E))) return ECFFT_ERR_BAD_ARG;
+    if (mem != ECFFT_MEM_HOST && mem != ECFFT_MEM_DEVICE) return ECFFT_ERR_BAD_ARG;
+    hipStream_t s = (hipStream_t)stream;
+    DeviceGuard dev(c->device);
+    if (!dev.ok) return ECFFT_ERR_HIP;
+    std::lock_guard<std::mutex> guard(ch.lock());
+    OpScope scope(c, s);
+    if (!scope.ok) return ECFFT_ERR_HIP;
+    const size_t bf = nf * count * sizeof(E), bo = k * count * sizeof(E);
+    const E* df = (const E*)f; E* dout = (E*)out;
+    if (mem == ECFFT_MEM_HOST) {
+        if (!ensure_stage(c, bf + bo)) return ECFFT_ERR_HIP;
+        df = (const E*)c->stage; dout = (E*)((char*)c->stage + bf);
+        if (hipMemcpyAsync((void*)df, f, bf, hipMemcpyHostToDevice, s) != hipSuccess) return ECFFT_ERR_HIP;
+    }
+    bool singular = false;
+    if (!ch.inv_series(df, nf, dout, k, count, &singular, s)) return ECFFT_ERR_HIP;
+    if (singular) return ECFFT_ERR_BAD_ARG;                                 // f[0] == 0 in some pair: no power-series inverse
+    if (mem == ECFFT_MEM_HOST) {
+        if (hipMemcpyAsync(out, dout, bo, hipMemcpyDeviceToHost, s) != hipSuccess) return ECFFT_ERR_HIP;
+        if (hipStreamSynchronize(s) != hipSuccess) return ECFFT_ERR_HIP;
+    }
+    return ECFFT_OK;
+}
+
 // standard = true: plain standard-form residues (the FFTree wire format) instead of the crate's in-memory representation
 template <class F>
 int table_of(DeviceChain<F>& ch, size_t m, int which, void* host_out, size_t cap, size_t* count, bool standard = false) {
@@ -886,6 +967,16 @@ int ecfft_poly_mul(ecfft_ctx* ctx, const void* a, size_t na, const void* b, size
     if (!ctx || shard_only(ctx) || na == 0 || nb == 0 || count == 0) return ECFFT_ERR_BAD_ARG;
     return guarded([&] { return ctx->field == ECFFT_FIELD_SECP256K1 ? run_poly_mul(ctx, *ctx->secp, a, na, b, nb, out, count, mem, stream)
                                                : run_poly_mul(ctx, *ctx->m31, a, na, b, nb, out, count, mem, stream); });
+}
+int ecfft_poly_inv_series(ecfft_ctx* ctx, const void* f, size_t nf, void* out, size_t k, size_t count, int mem, void* stream) {
+    if (!ctx || shard_only(ctx) || nf == 0 || k == 0 || count == 0) return ECFFT_ERR_BAD_ARG;
+    return guarded([&] { return ctx->field == ECFFT_FIELD_SECP256K1 ? run_inv_series(ctx, *ctx->secp, f, nf, out, k, count, mem, stream)
+                                               : run_inv_series(ctx, *ctx->m31, f, nf, out, k, count, mem, stream); });
+}
+int ecfft_poly_divrem(ecfft_ctx* ctx, const void* a, size_t na, const void* b, size_t nb, void* q, void* r, size_t count, int mem, void* stream) {
+    if (!ctx || shard_only(ctx) || na == 0 || nb == 0 || count == 0) return ECFFT_ERR_BAD_ARG;
+    return guarded([&] { return ctx->field == ECFFT_FIELD_SECP256K1 ? run_poly_divrem(ctx, *ctx->secp, a, na, b, nb, q, r, count, mem, stream)
+                                               : run_poly_divrem(ctx, *ctx->m31, a, na, b, nb, q, r, count, mem, stream); });
 }
 
 int ecfft_extend_top_cyclic(ecfft_ctx* ctx, void* buf, size_t e, int moiety, unsigned log_p, unsigned rank, int recombine, int mem, void* stream) {

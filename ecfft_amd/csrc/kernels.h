@@ -2103,6 +2103,70 @@ __global__ __launch_bounds__(kBlock) void k_poly_pointwise(typename F::elem* __r
 }
 
 // ---------------------------------------------------------------------------------------------
+// ecfft_poly_inv_series / ecfft_poly_divrem (division with remainder; the reference's utils::div_rem, src/utils.rs:184-193,
+// runs ark-poly's schoolbook divide_with_q_and_r on the CPU).  The reciprocal 1/f mod x^k starts from the first p0 <= K0
+// coefficients (k_series_base) and doubles its precision by Newton steps g' = g (2 - f g), each one pointwise product on the
+// leaves of T_N (k_newton_pointwise).
+// ---------------------------------------------------------------------------------------------
+// One workgroup of K0 threads per pair: g_0 = 1/f_0, g_j = -g_0 * sum_{i=1..j} f_i g_{j-i} for j < p0 <= K0, on plain residues
+// in LDS (one tree sum per coefficient).  f: row b at f + b*ldf, nf coefficients (crate form); out: row b at out + b*ldo, p0
+// coefficients (crate form).  A pair with f_0 == 0 stores 1 to *flag (its row is then zero).  rinv = R^-1, r1 = R (plain).
+template <class F, int K0>
+__global__ __launch_bounds__(K0) void k_series_base(typename F::elem* __restrict__ out, size_t ldo, const typename F::elem* __restrict__ f,
+                                                   size_t ldf, size_t nf, uint32_t p0, typename F::elem rinv, typename F::elem r1,
+                                                   int* __restrict__ flag) {
+    using E = typename F::elem;
+    __shared__ E sf[K0], sg[K0], red[K0];
+    const uint32_t t = threadIdx.x;
+    const size_t b = blockIdx.x;
+    sf[t] = (t < p0 && t < nf) ? F::canon(F::mul(f[b * ldf + t], rinv)) : F::zero();
+    __syncthreads();
+    if (t == 0) {
+        if (F::is_zero(sf[0])) *flag = 1;
+        sg[0] = F::canon(F::inv(sf[0]));                 // inv(0) = 0: the row of a flagged pair stays zero
+    }
+    __syncthreads();
+    const E g0 = sg[0];
+    for (uint32_t j = 1; j < p0; ++j) {
+        red[t] = (t >= 1 && t <= j) ? F::mul(sf[t], sg[j - t]) : F::zero();
+        __syncthreads();
+        for (uint32_t w = K0 / 2; w > 0; w >>= 1) {
+            if (t < w) red[t] = F::add(red[t], red[t + w]);
+            __syncthreads();
+        }
+        if (t == 0) sg[j] = F::canon(F::neg(F::mul(g0, red[0])));
+        __syncthreads();
+    }
+    if (t < p0) out[b * ldo + t] = F::canon(F::mul(sg[t], r1));
+}
+// One Newton step's pointwise product on the N leaves of T_N: out = G (2 - F G), read like k_poly_pointwise (PolyEvals).  User
+// data is x*R, so F::mul(F^, G^) carries R^2: subtracted from two_r2 = 2R^2 and multiplied by G^ it carries R^3, and one table
+// multiply by rinv2 = R^-2 puts it back in the crate's form.  M31 has R = 1.
+template <class F>
+__global__ __launch_bounds__(kBlock) void k_newton_pointwise(typename F::elem* __restrict__ out, PolyEvals<F> f, PolyEvals<F> g,
+                                                             typename F::elem two_r2, typename F::telem rinv2, uint32_t log_n, size_t total) {
+    using E = typename F::elem;
+    const size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= total) return;
+    const size_t bi = i >> log_n, j = i & (((size_t)1 << log_n) - 1), k = j >> 1;
+    const E* pf = (j & 1) ? f.odd : f.even;
+    const E* pg = (j & 1) ? g.odd : g.even;
+    const E gv = pg[bi * g.batch + k * g.stride];
+    E r = F::mul(F::sub(two_r2, F::mul(pf[bi * f.batch + k * f.stride], gv)), gv);
+    if constexpr (sizeof(E) == 32) r = F::tmul(rinv2, r);
+    out[i] = F::canon(r);
+}
+// remainder of ecfft_poly_divrem: r[b*nr + j] = a[b*lda + j] - p[b*ldp + j] for j < nr (p = (b mod x^nr)(q mod x^nr))
+template <class F>
+__global__ __launch_bounds__(kBlock) void k_divrem_sub(typename F::elem* __restrict__ r, size_t nr, const typename F::elem* __restrict__ a,
+                                                       size_t lda, const typename F::elem* __restrict__ p, size_t ldp, size_t total) {
+    const size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= total) return;
+    const size_t bi = i / nr, j = i - bi * nr;
+    r[i] = F::canon(F::sub(a[bi * lda + j], F::canon(p[bi * ldp + j])));
+}
+
+// ---------------------------------------------------------------------------------------------
 // generic element-wise helper for tree construction: functor(i) for i < n
 // ---------------------------------------------------------------------------------------------
 template <class Fn>

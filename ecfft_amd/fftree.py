@@ -32,7 +32,7 @@ EXPORTS = ["ecfft_elem_size", "ecfft_build_fftree", "ecfft_fftree_new", "ecfft_c
            "ecfft_comm_get_unique_id", "ecfft_comm_init_rank", "ecfft_comm_init_callback", "ecfft_comm_destroy", "ecfft_comm_rank", "ecfft_comm_world",
            "ecfft_comm_stats_enable", "ecfft_comm_stats_read", "ecfft_extend_sharded", "ecfft_enter_sharded", "ecfft_exit_sharded", "ecfft_device_copy", "ecfft_shader_clock", "ecfft_device_alloc", "ecfft_device_free", "ecfft_device_sync", "ecfft_build_extend_shard", "ecfft_ctx_device_bytes", "ecfft_extend_sharded_layout", "ecfft_build_enter_shard", "ecfft_build_exit_shard", "ecfft_build_exit_shard_opts",
            "ecfft_fftree_serialize", "ecfft_fftree_deserialize", "ecfft_tree_rational_maps", "ecfft_ctx_trim", "ecfft_comm_abort", "ecfft_comm_set_rccl_library", "ecfft_comm_set_link_striping",
-           "ecfft_poly_mul"]
+           "ecfft_poly_mul", "ecfft_poly_inv_series", "ecfft_poly_divrem"]
 
 # include/ecfft_hip_hooks.h: only in a build with -DECFFT_TEST_HOOKS (tests/hooks/libecfft_hip_hooks.so), never in the shipped library
 HOOK_EXPORTS = ['ecfft_selftest_field', 'ecfft_selfcheck_pointwise_z', 'ecfft_test_fail_next_collective', 'ecfft_selftest_blk16', 'ecfft_selftest_blk16_small', 'ecfft_test_fail_build_rank', 'ecfft_comm_init_projection', 'ecfft_selftest_blk32', 'ecfft_ctx_low_map']
@@ -67,6 +67,8 @@ def _bind(L):
     L.ecfft_exit.restype, L.ecfft_exit.argtypes = ci, [vp, vp, vp, sz, ci, vp]
     L.ecfft_extend.restype, L.ecfft_extend.argtypes = ci, [vp, vp, vp, sz, ci, sz, ci, vp]
     L.ecfft_poly_mul.restype, L.ecfft_poly_mul.argtypes = ci, [vp, vp, sz, vp, sz, vp, sz, ci, vp]
+    L.ecfft_poly_inv_series.restype, L.ecfft_poly_inv_series.argtypes = ci, [vp, vp, sz, vp, sz, sz, ci, vp]
+    L.ecfft_poly_divrem.restype, L.ecfft_poly_divrem.argtypes = ci, [vp, vp, sz, vp, sz, vp, vp, sz, ci, vp]
     L.ecfft_tree_table.restype, L.ecfft_tree_table.argtypes = ci, [vp, sz, ci, vp, sz, ctypes.POINTER(sz)]
     L.ecfft_build_points.restype, L.ecfft_build_points.argtypes = ci, [ci, sz, vp, vp, vp]
     L.ecfft_device_info.restype, L.ecfft_device_info.argtypes = ci, [ci, ctypes.c_char_p, sz]
@@ -411,6 +413,57 @@ class FFTree:
         rc = self._L.ecfft_poly_mul(self._h, pa, na // count, pb, nb // count, pout, count, mem, stream)
         if rc == ERR_BAD_ARG:
             raise ValueError("poly_mul: empty operand, count = 0 or a context that holds no full tree")
+        _check(rc)
+        return out
+
+    def _poly_io(self, xs):
+        """numpy arrays (host) or contiguous CUDA tensors (device, all of the same kind) -> (arrays, pointers, new(rows), mem, stream)"""
+        if any(_is_torch(x) for x in xs):
+            import torch
+            assert all(_is_torch(x) for x in xs), "operands must all be numpy arrays or all CUDA tensors"
+            for x in xs:
+                assert x.is_cuda and x.is_contiguous(), "device tensors must be contiguous CUDA tensors"
+            x0 = xs[0]
+            return (xs, [x.data_ptr() for x in xs],
+                    lambda rows: torch.empty((rows,) + tuple(x0.shape[1:]), dtype=x0.dtype, device=x0.device),
+                    MEM_DEVICE, torch.cuda.current_stream(x0.device).cuda_stream)
+        xs = [np.ascontiguousarray(x, self.field.dtype) for x in xs]
+        return xs, [x.ctypes.data for x in xs], lambda rows: np.empty(self.field.shape(rows), self.field.dtype), MEM_HOST, None
+
+    @staticmethod
+    def _ptr(x):
+        return x.data_ptr() if _is_torch(x) else x.ctypes.data
+
+    def poly_divrem(self, a, b, count=1):
+        """(q, r) with a = b*q + r, deg r < deg b (ecfft_poly_divrem <-> utils::div_rem, src/utils.rs:184-193): `count` pairs laid end
+        to end, a of count * na and b of count * nb coefficients, b's leading coefficient nonzero in every pair.  q has count * nq
+        coefficients, nq = na - nb + 1 (none when na < nb); r has count * (nb - 1), zero-padded above its degree.  Needs a tree of
+        next_pow2(max(2 nq - 1, nr + min(nq, nr) - 1)) leaves when na >= nb >= 2.  numpy arrays (host) or contiguous CUDA tensors
+        (device, on the current stream), both of the same kind.  Synchronous."""
+        (a, b), (pa, pb), new, mem, stream = self._poly_io([a, b])
+        assert count > 0 and a.shape[0] % count == 0 and b.shape[0] % count == 0
+        na, nb = a.shape[0] // count, b.shape[0] // count
+        q, r = new(count * max(na - nb + 1, 0)), new(count * max(nb - 1, 0))
+        pq = self._ptr(q) if q.shape[0] else None
+        pr = self._ptr(r) if r.shape[0] else None
+        if pq is None and pr is None:
+            pr = self._ptr(r)                      # na = nb = 1 style shapes still report their errors
+        rc = self._L.ecfft_poly_divrem(self._h, pa, na, pb, nb, pq, pr, count, mem, stream)
+        if rc == ERR_BAD_ARG:
+            raise ValueError("poly_divrem: empty operand, a zero leading coefficient of b, count = 0 or a context that holds no full tree")
+        _check(rc)
+        return q, r
+
+    def poly_inv_series(self, f, k, count=1):
+        """1/f mod x^k, the power-series reciprocal (ecfft_poly_inv_series; no reference counterpart): `count` series laid end to end,
+        f of count * nf coefficients with f[0] nonzero in every pair; returns count * k coefficients.  Needs a tree of
+        next_pow2(2k - 1) leaves.  numpy arrays or contiguous CUDA tensors (current stream).  Synchronous."""
+        (f,), (pf,), new, mem, stream = self._poly_io([f])
+        assert count > 0 and f.shape[0] % count == 0
+        out = new(count * k)
+        rc = self._L.ecfft_poly_inv_series(self._h, pf, f.shape[0] // count, self._ptr(out) if k else None, k, count, mem, stream)
+        if rc == ERR_BAD_ARG:
+            raise ValueError("poly_inv_series: empty f, k = 0, a zero constant coefficient, count = 0 or a context that holds no full tree")
         _check(rc)
         return out
 

@@ -162,6 +162,22 @@ public:
         check(ecfft_poly_mul(ctx_, a.data(), a.size(), b.data(), b.size(), out.data(), 1, ECFFT_MEM_HOST, nullptr));
         return out;
     }
+    // a = b*q + r, deg r < deg b (ecfft_poly_divrem <-> utils::div_rem, src/utils.rs:184-193): {q, r}, q of a.size() - b.size() + 1
+    // coefficients (none when a is shorter), r of b.size() - 1 (zero-padded); b.back() != 0.  Tree rule in ecfft_hip.h.  Synchronous.
+    std::pair<std::vector<Elem>, std::vector<Elem>> divrem(const std::vector<Elem>& a, const std::vector<Elem>& b) const {
+        require(!a.empty() && !b.empty(), "divrem: operands must not be empty");
+        std::vector<Elem> q(a.size() >= b.size() ? a.size() - b.size() + 1 : 0), r(b.size() - 1);
+        check(ecfft_poly_divrem(ctx_, a.data(), a.size(), b.data(), b.size(), q.empty() ? nullptr : q.data(), r.empty() ? nullptr : r.data(),
+                                1, ECFFT_MEM_HOST, nullptr));
+        return {std::move(q), std::move(r)};
+    }
+    // 1/f mod x^k (ecfft_poly_inv_series; no reference counterpart): k coefficients, f[0] != 0; the tree must hold next_pow2(2k - 1) leaves
+    std::vector<Elem> inv_series(const std::vector<Elem>& f, size_t k) const {
+        require(!f.empty() && k > 0, "inv_series: f must not be empty and k must be positive");
+        std::vector<Elem> out(k);
+        check(ecfft_poly_inv_series(ctx_, f.data(), f.size(), out.data(), k, 1, ECFFT_MEM_HOST, nullptr));
+        return out;
+    }
     size_t device_bytes() const { return ecfft_ctx_device_bytes(ctx_); }     // HBM held between calls: tables + scratch
     // device-resident variants (pointers into HBM, caller's stream)
     void enter_device(const Elem* coeffs, Elem* evals, size_t n, void* stream) const { check(ecfft_enter(ctx_, coeffs, evals, n, ECFFT_MEM_DEVICE, stream)); }
@@ -170,6 +186,14 @@ public:
     // count pairs: a count x na, b count x nb, out count x (na + nb - 1)
     void mul_device(const Elem* a, size_t na, const Elem* b, size_t nb, Elem* out, size_t count, void* stream) const {
         check(ecfft_poly_mul(ctx_, a, na, b, nb, out, count, ECFFT_MEM_DEVICE, stream));
+    }
+    // count pairs: a count x na, b count x nb, q count x (na - nb + 1), r count x (nb - 1); q or r may be null.  Synchronous.
+    void divrem_device(const Elem* a, size_t na, const Elem* b, size_t nb, Elem* q, Elem* r, size_t count, void* stream) const {
+        check(ecfft_poly_divrem(ctx_, a, na, b, nb, q, r, count, ECFFT_MEM_DEVICE, stream));
+    }
+    // count series: f count x nf, out count x k.  Synchronous.
+    void inv_series_device(const Elem* f, size_t nf, Elem* out, size_t k, size_t count, void* stream) const {
+        check(ecfft_poly_inv_series(ctx_, f, nf, out, k, count, ECFFT_MEM_DEVICE, stream));
     }
 
     // ONE transform split over the ranks of `comm` (device pointers: this rank's block shard of len / world elements)

@@ -109,6 +109,23 @@ int ecfft_extend(ecfft_ctx* ctx, const void* in, void* out, size_t e, int moiety
  * 2m coefficients is the ENTER of m interleaved with its EXTEND onto S1), so the call costs about one ENTER_N + one EXIT_N plus
  * the pointwise product.  Memory, stream and threading as for ecfft_enter_many; temporaries are pooled (ecfft_ctx_trim). */
 int ecfft_poly_mul(ecfft_ctx* ctx, const void* a, size_t na, const void* b, size_t nb, void* out, size_t count, int mem, void* stream);
+/* Division with remainder on the GPU:
+ *   ecfft_poly_divrem     <-> ecfft::utils::div_rem (src/utils.rs:184-193) = ark-poly DenseOrSparsePolynomial::divide_with_q_and_r
+ * a = b*q + r with deg r < deg b for `count` pairs laid end to end: a: count x na, b: count x nb with b[nb-1] != 0 in every pair
+ * (ark's DensePolynomial is always trimmed); q: count x nq, nq = na - nb + 1 (0 when na < nb); r: count x (nb - 1), zero-padded
+ * above its true degree.  q or r may be NULL (r only = utils::div_rem), not both.  Outputs must not overlap the inputs.
+ * ecfft_poly_inv_series: g = 1/f mod x^k (power-series reciprocal; no reference counterpart), f: count x nf with f[0] != 0, out: count x k.
+ * Algorithm: the first 64 coefficients of 1/f by the schoolbook recurrence (one workgroup per pair), then Newton steps
+ * g' = g (2 - f g), each one fused product on the leaves of T_N; q = rev(rev(a) * (1/rev(b) mod x^nq) mod x^nq) and
+ * r = a - (b mod x^nr)(q mod x^nr) mod x^nr.
+ * Tree: ecfft_poly_inv_series needs next_pow2(2k - 1) leaves (k = 1: any tree); ecfft_poly_divrem with na >= nb >= 2 needs
+ * N = next_pow2(max(2*nq - 1, nr + min(nq, nr) - 1)) leaves, nr = nb - 1; nb == 1 (scaling) and na < nb (copy) need no transform.
+ * Else ECFFT_ERR_TREE_TOO_SMALL.  ECFFT_ERR_BAD_ARG: a NULL input, both outputs NULL, a zero length or count, a context that holds
+ * no full tree, a byte count that would wrap — and a zero divisor leading coefficient / zero f[0] in any pair, which is checked
+ * on the device.  Because of that check both calls are SYNCHRONOUS (like ecfft_degree): they return after the work on `stream`
+ * is complete.  Memory and threading as for ecfft_poly_mul; temporaries are pooled (ecfft_ctx_trim). */
+int ecfft_poly_inv_series(ecfft_ctx* ctx, const void* f, size_t nf, void* out, size_t k, size_t count, int mem, void* stream);
+int ecfft_poly_divrem(ecfft_ctx* ctx, const void* a, size_t na, const void* b, size_t nb, void* q, void* r, size_t count, int mem, void* stream);
 
 /* The remaining FFTree algorithms, composed from the same GPU kernels.  Synchronous.
  *   ecfft_mextend         <-> FFTree::mextend(&self, &[F], Moiety)      src/fftree.rs:138-141
