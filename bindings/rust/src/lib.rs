@@ -54,6 +54,7 @@ pub mod ffi {
         pub fn ecfft_poly_mul(ctx: *mut EcfftCtx, a: *const c_void, na: usize, b: *const c_void, nb: usize, out: *mut c_void, count: usize, mem: i32, stream: *mut c_void) -> i32;
         pub fn ecfft_poly_inv_series(ctx: *mut EcfftCtx, f: *const c_void, nf: usize, out: *mut c_void, k: usize, count: usize, mem: i32, stream: *mut c_void) -> i32;
         pub fn ecfft_poly_divrem(ctx: *mut EcfftCtx, a: *const c_void, na: usize, b: *const c_void, nb: usize, q: *mut c_void, r: *mut c_void, count: usize, mem: i32, stream: *mut c_void) -> i32;
+        pub fn ecfft_poly_eval_points(ctx: *mut EcfftCtx, f: *const c_void, nf: usize, points: *const c_void, m: usize, out: *mut c_void, count: usize, mem: i32, stream: *mut c_void) -> i32;
         pub fn ecfft_mextend(ctx: *mut EcfftCtx, inp: *const c_void, out: *mut c_void, e: usize, moiety: i32, count: usize, mem: i32, stream: *mut c_void) -> i32;
         pub fn ecfft_redc(ctx: *mut EcfftCtx, evals: *const c_void, a: *const c_void, out: *mut c_void, n: usize, moiety: i32, mem: i32, stream: *mut c_void) -> i32;
         pub fn ecfft_modular_reduce(ctx: *mut EcfftCtx, evals: *const c_void, a: *const c_void, c: *const c_void, out: *mut c_void, n: usize, mem: i32, stream: *mut c_void) -> i32;
@@ -256,6 +257,16 @@ impl<F: HipField> HipFFTree<F> {
         let mut out = Self::out_vec(k);
         check(unsafe { ffi::ecfft_poly_inv_series(self.ctx, f.as_ptr().cast(), f.len(), out.as_mut_ptr().cast(), k, 1, ffi::MEM_HOST, core::ptr::null_mut()) });
         unsafe { out.set_len(k) };
+        out
+    }
+
+    /// `f` at arbitrary points (ecfft_poly_eval_points; no reference counterpart): `out[i] = f(points[i])`.  `f.len() <= 64` works on
+    /// any tree; a longer `f` needs a tree of `next_pow2(f.len())` leaves.
+    pub fn eval_points(&self, f: &[F], points: &[F]) -> Vec<F> {
+        assert!(!f.is_empty() && !points.is_empty());
+        let mut out = Self::out_vec(points.len());
+        check(unsafe { ffi::ecfft_poly_eval_points(self.ctx, f.as_ptr().cast(), f.len(), points.as_ptr().cast(), points.len(), out.as_mut_ptr().cast(), 1, ffi::MEM_HOST, core::ptr::null_mut()) });
+        unsafe { out.set_len(points.len()) };
         out
     }
 

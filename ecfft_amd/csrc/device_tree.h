@@ -24,6 +24,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <new>
+#include <algorithm>
 #include "kernels.h"
 #include "host_curve.h"
 #include "transport.h"
@@ -1814,6 +1815,134 @@ public:
         return ok;
     }
 
+    // ecfft_poly_eval_points (no reference counterpart): out[b*m + i] = f_b(points[i]) for `count` polynomials of nf coefficients
+    // (f: count x nf, crate form) at m arbitrary points shared by all of them.  Subproduct tree of the points in groups of
+    // G = max(B, next_pow2(nf)) (subproduct_tree), a remainder tree down to nodes of B = kEvalLeaf points (remainder_descent), Horner
+    // at the leaves (k_eval_leaves).  G == B: no tree, f itself is every block's remainder.  Device pointers; asynchronous on `s`
+    // (every node is monic, so nothing can fail on the data).  Caller holds lock() and checks the tree rule (G <= size() if G > B).
+    bool poly_eval_points(const E* f, size_t nf, const E* points, size_t m, E* out, size_t count, hipStream_t s) {
+        const size_t B = kEvalLeaf, G = eval_group(nf), P = (m + G - 1) / G * G;
+        bool ok = true;
+        const E* rem = f;
+        size_t ld_poly = nf, ld_row = 0, nc = nf;
+        if (G > B) {
+            SubproductTree st;
+            ok = subproduct_tree(points, m, G, st, s) && ok;
+            E* R = temp(count * P);
+            ok = remainder_descent(f, nf, st, count, R, s) && ok;
+            rem = R; ld_poly = P; ld_row = B; nc = B;
+        }
+        const size_t rows = count * (P / B);
+        ECFFT_LAUNCH(KC_POINTWISE, sizeof(E) * ((double)rows * nc + (double)count * m + (double)m), (k_eval_leaves<F, (int)kEvalLeaf>),
+                     dim3(nblocks(rows * B)), dim3(kBlock), 0, s, out, rem, ld_poly, ld_row, (uint32_t)nc, points, m, P / B, rows,
+                     F::to_table(rinv_));
+        temps_done();
+        return ok && hipGetLastError() == hipSuccess;
+    }
+    // leaf size B of the remainder tree: a node of B points is evaluated by Horner (B multiplies per point) instead of descending
+    static constexpr size_t kEvalLeaf = 64;
+    static size_t eval_group(size_t nf) { size_t G = kEvalLeaf; while (G < nf) G <<= 1; return G; }
+    // Per-level node data of the subproduct tree of npts points (a multiple of G, in groups of G): level k holds the npts / d nodes
+    // of d = B << k points (d = B .. G/2) laid end to end, each as M^ (its monic node polynomial M on the 2d leaves of T_2d, from the
+    // vanish recursion) and G^ (g = 1/rev(M) mod x^d, lifted to T_2d): 2 npts elements each per level.  Temporaries of the call.
+    struct NodeLevel { size_t d; E* Mh; E* Gh; };
+    struct SubproductTree { size_t npts = 0, G = 0; std::vector<NodeLevel> lv; };
+    // Phase A of ecfft_poly_eval_points: the vanish recursion over all groups at once up to nodes of G/2 points (a level is one
+    // pointwise pass and one batched MEXTEND, vanish_step), keeping the levels d >= B; then per kept level one batched EXIT_2d of M^
+    // (M's coefficients), one batched inv_series_body of rev(M) mod x^d over all nodes (rev(M)(0) = 1: never singular) and one lift.
+    bool subproduct_tree(const E* points, size_t m, size_t G, SubproductTree& st, hipStream_t s) {
+        const size_t P = (m + G - 1) / G * G;
+        const unsigned lB = ilog2(kEvalLeaf), lG = ilog2(G);
+        st.npts = P; st.G = G; st.lv.clear();
+        for (unsigned r = lB; r < lG; ++r) st.lv.push_back({(size_t)1 << r, temp(2 * P), temp(2 * P)});
+        const TempMark mark = temps_mark();
+        E* Q = temp(2 * P); E* Q2 = temp(2 * P); E* q0 = temp(P); E* q1 = temp(P);
+        vanish_base(points, m, Q, P, s, true);                   // the padding points of the last group are 0
+        for (unsigned r = 1; r < lG; ++r) {
+            E* dst = r >= lB ? st.lv[r - lB].Mh : Q2;
+            vanish_step(r, Q, dst, q0, q1, P, s, true);
+            if (r >= lB) Q = dst; else { Q2 = Q; Q = dst; }
+        }
+        bool ok = true;
+        E* Mc = temp(2 * P); E* rv = temp(P); E* g = temp(P);
+        int* flag = new_flag(s);                                 // k_series_base's flag: never raised, every node is monic
+        for (const NodeLevel& L : st.lv) {
+            const size_t d = L.d, nodes = P / d;
+            const unsigned ld = ilog2(d);
+            ok = exit(L.Mh, Mc, 2 * d, nodes, s) && ok;
+            foreach_n(s, P, [=] __device__(size_t i) { const size_t n = i >> ld, j = i & (d - 1); rv[i] = Mc[(n << (ld + 1)) + d - j]; });
+            const TempMark lvl = temps_mark();
+            ok = inv_series_body(rv, d, d, g, d, nodes, flag, s) && ok;
+            ok = lift_rows(g, d, nodes, L.Gh, s) && ok;
+            temps_release(lvl);
+        }
+        temps_release(mark);
+        return ok;
+    }
+    // Phase B: the remainders of count polynomials at every node of B points (rem: count x P, rows of B).  Per level, children of
+    // d points (parents of 2d coefficients; the top parent is f itself, read at a row stride of 0 by every group):
+    //   t   = rev(parent) mod x^d, lifted once per parent;
+    //   q_c = rev((t g_c) mod x^d): k_tree_pointwise against G^_c (both siblings read their parent's t), one batched EXIT_2d;
+    //   r_c = (parent mod x^d) - (M_c q_c mod x^d): q_c lifted, k_tree_pointwise against M^_c (deg M_c q_c < 2d: nothing wraps),
+    //         one batched EXIT_2d and the subtraction.
+    bool remainder_descent(const E* f, size_t nf, const SubproductTree& st, size_t count, E* rem, hipStream_t s) {
+        const size_t P = st.npts;
+        E* A = temp(count * P); E* C = temp(count * P); E* t = temp(count * P / 2); E* q = temp(count * P); E* Y = temp(2 * count * P);
+        const TE rinv = F::to_table(rinv_);
+        const E* par = f;
+        size_t ldb = nf, ldr = 0, plen = nf;                     // parent row (b, p) at par + b*ldb + p*ldr, plen coefficients
+        bool ok = true;
+        for (size_t k = st.lv.size(); k-- > 0;) {
+            const NodeLevel& L = st.lv[k];
+            const size_t d = L.d, nodes = P / d, npar = nodes / 2, rows = count * nodes, total = rows * 2 * d;
+            const unsigned ld = ilog2(d);
+            E* dst = k == 0 ? rem : (par == A ? C : A);
+            const TempMark lvl = temps_mark();
+            foreach_n(s, count * npar * d, [=] __device__(size_t i) {
+                const size_t pr = i >> ld, j = i & (d - 1), b = pr / npar, p = pr - b * npar, c = 2 * d - 1 - j;
+                t[i] = c < plen ? par[b * ldb + p * ldr + c] : F::zero();
+            });
+            PolyEvals<F> ev[2];
+            ok = lift_evals(t, d, count * npar, ev, s) && ok;
+            ECFFT_LAUNCH(KC_POINTWISE, sizeof(E) * 2.5 * (double)total, k_tree_pointwise<F>, dim3(nblocks(total)), dim3(kBlock), 0, s,
+                         Y, ev[0], 1u, (const E*)L.Gh, nodes, rinv, ld + 1, total);
+            ok = exit(Y, Y, 2 * d, rows, s) && ok;
+            foreach_n(s, rows * d, [=] __device__(size_t i) { const size_t r = i >> ld, j = i & (d - 1); q[i] = Y[(r << (ld + 1)) + d - 1 - j]; });
+            ok = lift_evals(q, d, rows, ev, s) && ok;
+            ECFFT_LAUNCH(KC_POINTWISE, sizeof(E) * 3.0 * (double)total, k_tree_pointwise<F>, dim3(nblocks(total)), dim3(kBlock), 0, s,
+                         Y, ev[0], 0u, (const E*)L.Mh, nodes, rinv, ld + 1, total);
+            ok = exit(Y, Y, 2 * d, rows, s) && ok;
+            foreach_n(s, rows * d, [=] __device__(size_t i) {
+                const size_t r = i >> ld, j = i & (d - 1), b = r / nodes, p = (r - b * nodes) >> 1;
+                const E a = j < plen ? par[b * ldb + p * ldr + j] : F::zero();
+                dst[i] = F::canon(F::sub(a, F::canon(Y[(r << (ld + 1)) + j])));
+            });
+            temps_release(lvl);
+            par = dst; ldb = P; ldr = d; plen = d;
+        }
+        return ok;
+    }
+    // count rows of d coefficients (a power of two) -> their evaluations on the 2d leaves of T_2d as poly_mul's last lift leaves them
+    // (ENTER_d, EXTEND_d onto S1: even / odd halves); takes temporaries
+    bool lift_evals(const E* src, size_t d, size_t count, PolyEvals<F>* ev, hipStream_t s) {
+        const E* srcs[2] = {src, src};
+        const size_t len[2] = {d, d}, ld[2] = {d, d};
+        E* Y = nullptr;
+        return lift_operands(srcs, len, ld, 1, 2 * d, count, ev, Y, s);
+    }
+    // ... materialised in natural leaf order (dst: count x 2d)
+    bool lift_rows(const E* src, size_t d, size_t count, E* dst, hipStream_t s) {
+        PolyEvals<F> ev[2];
+        const bool ok = lift_evals(src, d, count, ev, s);
+        const PolyEvals<F> e = ev[0];
+        const unsigned ld = ilog2(d);
+        foreach_n(s, count * 2 * d, [=] __device__(size_t i) {
+            const size_t r = i >> (ld + 1), k = (i & (2 * d - 1)) >> 1;
+            dst[i] = ((i & 1) ? e.odd : e.even)[r * e.batch + k * e.stride];
+        });
+        return ok;
+    }
+
     // ------------------------------------------------------------------------------------------
     // Public wrappers of the remaining FFTree algorithms on USER data (crate representation),
     // composed from the same EXTEND kernels.  Device pointers; synchronous (they drain `s` before returning
@@ -2008,6 +2137,14 @@ private:
         if (keep < ((size_t)256 << 20)) keep = (size_t)256 << 20;
         temps_trim(keep);                                    // rare: hipFree waits for the device
     }
+    // Temporaries taken after a mark can be handed back before the call ends, so that each level of a multi-level call reuses the
+    // previous level's: every later use is enqueued on the call's stream, after the kernels that read them.
+    using TempMark = std::vector<const void*>;
+    TempMark temps_mark() const { TempMark busy; for (const auto& b : pool_) if (b.busy) busy.push_back(b.p); return busy; }
+    void temps_release(const TempMark& mark) {
+        for (auto& b : pool_)
+            if (b.busy && std::find(mark.begin(), mark.end(), (const void*)b.p) == mark.end()) b.busy = false;
+    }
     size_t pool_bytes() const { size_t t = 0; for (const auto& b : pool_) t += b.bytes; return t; }
     // frees idle, unpinned blocks: those idle for > max_idle calls, then the largest ones until the idle total is <= keep bytes
     void temps_trim(size_t keep, unsigned max_idle = ~0u) {
@@ -2143,26 +2280,38 @@ private:
         const Tree& T = trees_[log_m];
         size_t e = T.e, m = T.m;
         E* Q = temp(m); E* Q2 = temp(m); E* q0 = temp(e); E* q1 = temp(e);
-        const E* f = f_; size_t N = N_; const E rinv = rinv_;
-        foreach_n(s, e, [=] __device__(size_t i) {        // T_2 leaves are the top tree's leaves 0 and N/2
-            E l0 = f[N], l1 = f[N + N / 2];
-            if (mont) { l0 = F::to_mont(l0); l1 = F::to_mont(l1); }
-            Q[2 * i] = F::sub(dom[i], l0); Q[2 * i + 1] = F::sub(dom[i], l1);
-        });
+        vanish_base(dom, e, Q, e, s, mont);
         unsigned le = ilog2(e);
         for (unsigned r = 1; r <= le; ++r) {
-            size_t bs = (size_t)1 << r;                     // size of the blocks being merged
-            foreach_n(s, e, [=] __device__(size_t g) {
-                size_t b = g >> r, i = g & (bs - 1);
-                E pr = F::mul(Q[(2 * b) * bs + i], Q[(2 * b + 1) * bs + i]);
-                q0[g] = mont ? F::mul(pr, rinv) : pr;
-            });
-            b_mextend(r + 1, q0, q1, e >> r, 1, s, mont);
             E* dstQ = (r == le) ? out : Q2;
-            foreach_n(s, e, [=] __device__(size_t g) { dstQ[2 * g] = q0[g]; dstQ[2 * g + 1] = q1[g]; });
+            vanish_step(r, Q, dstQ, q0, q1, e, s, mont);
             E* t = Q; Q = Q2; Q2 = t;
         }
         if (le == 0) (void)hipMemcpyAsync(out, Q, m * sizeof(E), hipMemcpyDeviceToDevice, s);
+    }
+    // the leaves of the vanish recursion: Q[2i], Q[2i+1] = (x - dom[i]) on the two leaves of T_2 for e points, dom[i] = 0 for i >= nd
+    void vanish_base(const E* dom, size_t nd, E* Q, size_t e, hipStream_t s, bool mont) {
+        const E* f = f_; size_t N = N_;
+        foreach_n(s, e, [=] __device__(size_t i) {        // T_2 leaves are the top tree's leaves 0 and N/2
+            E l0 = f[N], l1 = f[N + N / 2];
+            if (mont) { l0 = F::to_mont(l0); l1 = F::to_mont(l1); }
+            const E x = i < nd ? dom[i] : F::zero();
+            Q[2 * i] = F::sub(x, l0); Q[2 * i + 1] = F::sub(x, l1);
+        });
+    }
+    // one level of the vanish recursion (src/fftree.rs:291-308) over e points (a multiple of 2^r): Q holds, per block of 2^(r-1)
+    // points, their product on the 2^r leaves of T_(2^r); dst gets, per block of 2^r points, their product on the leaves of
+    // T_(2^(r+1)) — the pointwise product of two sibling blocks is the product on S0 = T_(2^r), MEXTEND gives S1.  q0, q1: e each.
+    void vanish_step(unsigned r, const E* Q, E* dst, E* q0, E* q1, size_t e, hipStream_t s, bool mont) {
+        const size_t bs = (size_t)1 << r;                   // size of the blocks being merged
+        const E rinv = rinv_;
+        foreach_n(s, e, [=] __device__(size_t g) {
+            size_t b = g >> r, i = g & (bs - 1);
+            E pr = F::mul(Q[(2 * b) * bs + i], Q[(2 * b + 1) * bs + i]);
+            q0[g] = mont ? F::mul(pr, rinv) : pr;
+        });
+        b_mextend(r + 1, q0, q1, e >> r, 1, s, mont);
+        foreach_n(s, e, [=] __device__(size_t g) { dst[2 * g] = q0[g]; dst[2 * g + 1] = q1[g]; });
     }
 
     // matrix-core tables of the innermost 16-point map (mfma_blk16.h), per source parity: 32-byte fields, trees with e >= 16

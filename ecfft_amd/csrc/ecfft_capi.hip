@@ -258,6 +258,43 @@ int run_inv_series(ecfft_ctx* c, DeviceChain<F>& ch, const void* f, size_t nf, v
     return ECFFT_OK;
 }
 
+// ecfft_poly_eval_points: staging, lock and cross-stream event as run_poly_mul; asynchronous on `stream` (nothing is data dependent)
+template <class F>
+int run_poly_eval_points(ecfft_ctx* c, DeviceChain<F>& ch, const void* f, size_t nf, const void* points, size_t m, void* out, size_t count,
+                         int mem, void* stream) {
+    using E = typename F::elem;
+    if (!f || !points || !out) return ECFFT_ERR_BAD_ARG;
+    const size_t lim = SIZE_MAX / (64 * sizeof(E));
+    if (nf > lim || m > lim) return ECFFT_ERR_BAD_ARG;
+    const size_t G = DeviceChain<F>::eval_group(nf), P = (m + G - 1) / G * G;
+    if (G > DeviceChain<F>::kEvalLeaf && G > ch.size()) return ECFFT_ERR_TREE_TOO_SMALL;    // nf <= 64: Horner only, any tree
+    if (P > SIZE_MAX / (8 * 64 * sizeof(E))) return ECFFT_ERR_BAD_ARG;     // node data: 4 P elements per level, < 64 levels
+    const size_t per = P > nf ? P : nf;
+    if (count > SIZE_MAX / (16 * per * sizeof(E))) return ECFFT_ERR_BAD_ARG; // byte counts of the temporaries must not wrap
+    if (mem != ECFFT_MEM_HOST && mem != ECFFT_MEM_DEVICE) return ECFFT_ERR_BAD_ARG;
+    hipStream_t s = (hipStream_t)stream;
+    DeviceGuard dev(c->device);
+    if (!dev.ok) return ECFFT_ERR_HIP;
+    std::lock_guard<std::mutex> guard(ch.lock());
+    OpScope scope(c, s);
+    if (!scope.ok) return ECFFT_ERR_HIP;
+    const size_t bf = nf * count * sizeof(E), bp = m * sizeof(E), bo = m * count * sizeof(E);
+    const E *df = (const E*)f, *dp = (const E*)points; E* dout = (E*)out;
+    if (mem == ECFFT_MEM_HOST) {
+        if (!ensure_stage(c, bf + bp + bo)) return ECFFT_ERR_HIP;
+        char* st = (char*)c->stage;
+        df = (const E*)st; dp = (const E*)(st + bf); dout = (E*)(st + bf + bp);
+        if (hipMemcpyAsync((void*)df, f, bf, hipMemcpyHostToDevice, s) != hipSuccess) return ECFFT_ERR_HIP;
+        if (hipMemcpyAsync((void*)dp, points, bp, hipMemcpyHostToDevice, s) != hipSuccess) return ECFFT_ERR_HIP;
+    }
+    if (!ch.poly_eval_points(df, nf, dp, m, dout, count, s)) return ECFFT_ERR_HIP;
+    if (mem == ECFFT_MEM_HOST) {
+        if (hipMemcpyAsync(out, dout, bo, hipMemcpyDeviceToHost, s) != hipSuccess) return ECFFT_ERR_HIP;
+        if (hipStreamSynchronize(s) != hipSuccess) return ECFFT_ERR_HIP;
+    }
+    return ECFFT_OK;
+}
+
 // standard = true: plain standard-form residues (the FFTree wire format) instead of the crate's in-memory representation
 template <class F>
 int table_of(DeviceChain<F>& ch, size_t m, int which, void* host_out, size_t cap, size_t* count, bool standard = false) {
@@ -977,6 +1014,12 @@ int ecfft_poly_divrem(ecfft_ctx* ctx, const void* a, size_t na, const void* b, s
     if (!ctx || shard_only(ctx) || na == 0 || nb == 0 || count == 0) return ECFFT_ERR_BAD_ARG;
     return guarded([&] { return ctx->field == ECFFT_FIELD_SECP256K1 ? run_poly_divrem(ctx, *ctx->secp, a, na, b, nb, q, r, count, mem, stream)
                                                : run_poly_divrem(ctx, *ctx->m31, a, na, b, nb, q, r, count, mem, stream); });
+}
+int ecfft_poly_eval_points(ecfft_ctx* ctx, const void* f, size_t nf, const void* points, size_t m, void* out, size_t count, int mem,
+                           void* stream) {
+    if (!ctx || shard_only(ctx) || nf == 0 || m == 0 || count == 0) return ECFFT_ERR_BAD_ARG;
+    return guarded([&] { return ctx->field == ECFFT_FIELD_SECP256K1 ? run_poly_eval_points(ctx, *ctx->secp, f, nf, points, m, out, count, mem, stream)
+                                               : run_poly_eval_points(ctx, *ctx->m31, f, nf, points, m, out, count, mem, stream); });
 }
 
 int ecfft_extend_top_cyclic(ecfft_ctx* ctx, void* buf, size_t e, int moiety, unsigned log_p, unsigned rank, int recombine, int mem, void* stream) {

@@ -2167,6 +2167,53 @@ __global__ __launch_bounds__(kBlock) void k_divrem_sub(typename F::elem* __restr
 }
 
 // ---------------------------------------------------------------------------------------------
+// ecfft_poly_eval_points (multipoint evaluation at arbitrary points; no reference counterpart): a remainder tree over the
+// subproduct tree of the points.  Every node of a level has the same degree d, so a level is one batched launch.
+// ---------------------------------------------------------------------------------------------
+// Pointwise product of a lifted operand with a cached node operand on the 2^log_n leaves of T_2d: out row i = A row (i >> a_shift)
+// times node row (i mod nodes), both in the natural leaf order EXIT reads.  The node operand (M^ or G^ of the subproduct tree) is
+// indexed by node, not by polynomial x node; a_shift = 1 lets both children of a parent read the parent's row.  Scaling as
+// k_poly_pointwise: the plain product of two user-form operands carries R^2, one table multiply by R^-1 puts it back (M31: R = 1).
+template <class F>
+__global__ __launch_bounds__(kBlock) void k_tree_pointwise(typename F::elem* __restrict__ out, PolyEvals<F> a, uint32_t a_shift,
+                                                           const typename F::elem* __restrict__ node, size_t nodes, typename F::telem rinv,
+                                                           uint32_t log_n, size_t total) {
+    using E = typename F::elem;
+    const size_t g = (size_t)blockIdx.x * kBlock + threadIdx.x;
+    if (g >= total) return;
+    const size_t bi = g >> log_n, j = g & (((size_t)1 << log_n) - 1), k = j >> 1, ai = bi >> a_shift, ni = bi % nodes;
+    const E* pa = (j & 1) ? a.odd : a.even;
+    E r = F::mul(pa[ai * a.batch + k * a.stride], node[(ni << log_n) + j]);
+    if constexpr (sizeof(E) == 32) r = F::tmul(rinv, r);
+    out[g] = F::canon(r);
+}
+// The leaves of the remainder tree: row r of `rows_per_poly` rows per polynomial holds the remainder (nc <= B coefficients, crate
+// form) of polynomial r / rows_per_poly at the B points of its leaf block; out[b*m + i] = that remainder at points[i], i < m.  One
+// thread per point, B threads per row: the row is staged in LDS and read by all of them as a broadcast.  The point is brought to
+// plain form once (x R^-1, one table multiply; M31: R = 1), so each Horner step is one F::mul and one F::add on the crate form.
+// Row stride ld_row = 0: every row of a polynomial is the same (the no-tree path, where f itself is every block's remainder).
+template <class F, int B>
+__global__ __launch_bounds__(kBlock) void k_eval_leaves(typename F::elem* __restrict__ out, const typename F::elem* __restrict__ rem,
+                                                        size_t ld_poly, size_t ld_row, uint32_t nc, const typename F::elem* __restrict__ points,
+                                                        size_t m, size_t rows_per_poly, size_t rows, typename F::telem rinv) {
+    static_assert(kBlock % B == 0, "a workgroup holds whole rows");
+    using E = typename F::elem;
+    __shared__ E sc[kBlock];
+    const uint32_t t = threadIdx.x, lane = t % B;
+    const size_t r = (size_t)blockIdx.x * (kBlock / B) + t / B;
+    const size_t b = r / rows_per_poly, rr = r - b * rows_per_poly, i = rr * B + lane;
+    sc[t] = (r < rows && lane < nc) ? rem[b * ld_poly + rr * ld_row + lane] : F::zero();
+    __syncthreads();
+    if (r >= rows || i >= m) return;
+    E x = points[i];
+    if constexpr (sizeof(E) == 32) x = F::tmul(rinv, x);
+    const E* c = sc + (t - lane);
+    E acc = F::zero();
+    for (uint32_t j = nc; j-- > 0;) acc = F::add(F::mul(acc, x), c[j]);
+    out[b * m + i] = F::canon(acc);
+}
+
+// ---------------------------------------------------------------------------------------------
 // generic element-wise helper for tree construction: functor(i) for i < n
 // ---------------------------------------------------------------------------------------------
 template <class Fn>

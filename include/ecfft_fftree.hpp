@@ -178,6 +178,14 @@ public:
         check(ecfft_poly_inv_series(ctx_, f.data(), f.size(), out.data(), k, 1, ECFFT_MEM_HOST, nullptr));
         return out;
     }
+    // f at arbitrary points (ecfft_poly_eval_points; no reference counterpart): out[i] = f(points[i]); f.size() <= 64 on any tree,
+    // otherwise the tree must hold next_pow2(f.size()) leaves
+    std::vector<Elem> eval_points(const std::vector<Elem>& f, const std::vector<Elem>& points) const {
+        require(!f.empty() && !points.empty(), "eval_points: f and points must not be empty");
+        std::vector<Elem> out(points.size());
+        check(ecfft_poly_eval_points(ctx_, f.data(), f.size(), points.data(), points.size(), out.data(), 1, ECFFT_MEM_HOST, nullptr));
+        return out;
+    }
     size_t device_bytes() const { return ecfft_ctx_device_bytes(ctx_); }     // HBM held between calls: tables + scratch
     // device-resident variants (pointers into HBM, caller's stream)
     void enter_device(const Elem* coeffs, Elem* evals, size_t n, void* stream) const { check(ecfft_enter(ctx_, coeffs, evals, n, ECFFT_MEM_DEVICE, stream)); }
@@ -194,6 +202,10 @@ public:
     // count series: f count x nf, out count x k.  Synchronous.
     void inv_series_device(const Elem* f, size_t nf, Elem* out, size_t k, size_t count, void* stream) const {
         check(ecfft_poly_inv_series(ctx_, f, nf, out, k, count, ECFFT_MEM_DEVICE, stream));
+    }
+    // count polynomials f count x nf at m shared points, out count x m.  Asynchronous on `stream`.
+    void eval_points_device(const Elem* f, size_t nf, const Elem* points, size_t m, Elem* out, size_t count, void* stream) const {
+        check(ecfft_poly_eval_points(ctx_, f, nf, points, m, out, count, ECFFT_MEM_DEVICE, stream));
     }
 
     // ONE transform split over the ranks of `comm` (device pointers: this rank's block shard of len / world elements)

@@ -126,6 +126,19 @@ int ecfft_poly_mul(ecfft_ctx* ctx, const void* a, size_t na, const void* b, size
  * is complete.  Memory and threading as for ecfft_poly_mul; temporaries are pooled (ecfft_ctx_trim). */
 int ecfft_poly_inv_series(ecfft_ctx* ctx, const void* f, size_t nf, void* out, size_t k, size_t count, int mem, void* stream);
 int ecfft_poly_divrem(ecfft_ctx* ctx, const void* a, size_t na, const void* b, size_t nb, void* q, void* r, size_t count, int mem, void* stream);
+/* Multipoint evaluation at arbitrary points on the GPU (no reference counterpart: the crate evaluates only on its own leaves):
+ * out[b*m + i] = f_b(points[i]) for `count` polynomials laid end to end, f: count x nf coefficients, points: m field elements
+ * shared by all of them, out: count x m.  Points are arbitrary (repeated, zero, leaves of the tree).  out must not overlap the inputs.
+ * Algorithm: the points in groups of G = max(64, next_pow2(nf)); the subproduct tree of every group (the vanish recursion, kept as
+ * evaluations on T_2d for every node of d = 64 .. G/2 points, with each node's 1/rev(M) mod x^d), a remainder tree from f down to
+ * nodes of 64 points (per level two lifts, two pointwise products and two EXITs), Horner at the leaves.
+ * Cost: what m' = max(m, next_pow2(nf)) points cost; the tree part is shared by the count polynomials.
+ * Tree: nf <= 64 needs no transform (any tree); otherwise next_pow2(nf) leaves (as ENTER of nf coefficients), else
+ * ECFFT_ERR_TREE_TOO_SMALL.  ECFFT_ERR_BAD_ARG: a NULL input or output, nf, m or count 0, a context that holds no full tree, a byte
+ * count that would wrap.  Every node is monic, so nothing fails on the data: the call is asynchronous on `stream`.  Memory, stream
+ * and threading as for ecfft_poly_mul; temporaries are pooled (ecfft_ctx_trim). */
+int ecfft_poly_eval_points(ecfft_ctx* ctx, const void* f, size_t nf, const void* points, size_t m, void* out, size_t count, int mem,
+                           void* stream);
 
 /* The remaining FFTree algorithms, composed from the same GPU kernels.  Synchronous.
  *   ecfft_mextend         <-> FFTree::mextend(&self, &[F], Moiety)      src/fftree.rs:138-141
