@@ -28,6 +28,67 @@ namespace {
 
 inline bool is_pow2(size_t n) { return n && (n & (n - 1)) == 0; }
 
+// ---- field dispatch ------------------------------------------------------------------------------------------------
+inline bool known_field(int field) { return field == ECFFT_FIELD_SECP256K1 || field == ECFFT_FIELD_M31; }
+template <class F> struct FieldTag { using type = F; };
+// fn(FieldTag<F>{}) for the field with id `field`; ECFFT_ERR_BAD_ARG for an unknown id
+template <class Fn>
+int with_field(int field, Fn&& fn) {
+    if (field == ECFFT_FIELD_SECP256K1) return fn(FieldTag<Secp256k1>{});
+    if (field == ECFFT_FIELD_M31) return fn(FieldTag<M31>{});
+    return ECFFT_ERR_BAD_ARG;
+}
+// fn(chain) with the context's chain
+template <class Fn>
+decltype(auto) with_chain(const ecfft_ctx* c, Fn&& fn) {
+    if (c->field == ECFFT_FIELD_SECP256K1) return fn(*c->secp);
+    return fn(*c->m31);
+}
+template <class F>
+std::unique_ptr<DeviceChain<F>>& slot_of(ecfft_ctx& c) {
+    if constexpr (std::is_same<F, Secp256k1>::value) return c.secp;
+    else return c.m31;
+}
+// the largest tree of each field: src/lib.rs:62-64, src/ec.rs:510-515
+template <class F> constexpr unsigned kMaxLogN = std::is_same<F, Secp256k1>::value ? 35 : 28;
+
+// the crate's in-memory representation <-> plain residues on host buffers: Montgomery for secp256k1, the identity for M31
+template <class F>
+void to_crate_host(typename F::elem* v, size_t n) {
+    if constexpr (std::is_same<F, Secp256k1>::value)
+        for (size_t i = 0; i < n; ++i) v[i] = Secp256k1::to_mont(v[i]);
+}
+template <class F>
+void from_crate_host(typename F::elem* v, size_t n) {
+    if constexpr (std::is_same<F, Secp256k1>::value) {     // x*2^256 -> x : multiply by 2^-256 = (2^32+977)^-1
+        Fe256 r = Secp256k1::zero(); r.l[0] = 977; r.l[1] = 1;
+        const Fe256 rinv = Secp256k1::inv(r);
+        for (size_t i = 0; i < n; ++i) v[i] = Secp256k1::mul(v[i], rinv);
+    }
+}
+// ecfft_elems_to_standard (to_standard) / ecfft_elems_from_standard
+int convert_elems(int field, const void* in, void* out, size_t n, bool to_standard) {
+    if (!in || !out) return ECFFT_ERR_BAD_ARG;
+    return with_field(field, [&](auto tag) -> int {
+        using E = typename decltype(tag)::type::elem;
+        if (in != out) memmove(out, in, n * sizeof(E));
+        if (to_standard) from_crate_host<typename decltype(tag)::type>((E*)out, n);
+        else to_crate_host<typename decltype(tag)::type>((E*)out, n);
+        return ECFFT_OK;
+    });
+}
+// rational maps -> the caller's arrays of 3 numerator / denominator coefficients per map, in the crate's representation
+template <class F>
+void maps_out(const std::vector<RatMap<F>>& maps, void* num3, void* den3) {
+    using E = typename F::elem;
+    for (size_t k = 0; k < maps.size(); ++k) {
+        RatMap<F> m = maps[k];
+        to_crate_host<F>(m.num, 3); to_crate_host<F>(m.den, 3);
+        if (num3) memcpy((E*)num3 + 3 * k, m.num, sizeof(m.num));
+        if (den3) memcpy((E*)den3 + 3 * k, m.den, sizeof(m.den));
+    }
+}
+
 bool have_device(int device) {
     int cnt = 0;
     if (hipGetDeviceCount(&cnt) != hipSuccess || cnt <= 0 || device < 0 || device >= cnt) {
@@ -47,24 +108,67 @@ struct DeviceGuard {
     }
     ~DeviceGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
 };
+
+// a hipMalloc'd temporary, freed on every exit path
+struct DeviceBuffer {
+    void* p = nullptr; bool ok;
+    explicit DeviceBuffer(size_t bytes) : ok(hipMalloc(&p, bytes) == hipSuccess) {}
+    ~DeviceBuffer() { if (p) (void)hipFree(p); }
+    DeviceBuffer(const DeviceBuffer&) = delete;
+    DeviceBuffer& operator=(const DeviceBuffer&) = delete;
+    template <class T> T* as() const { return (T*)p; }
+};
+
+// no C++ exception (allocation failure inside the chain) crosses the C ABI
+template <class Fn>
+int guarded(Fn fn) {
+    try { return fn(); }
+    catch (const std::bad_alloc&) { return ECFFT_ERR_HIP; }
+    catch (...) { return ECFFT_ERR_HIP; }
+}
+
+// ---- building a context --------------------------------------------------------------------------------------------
+// A new context of `field` on `device`: its chain is made and built by `build(chain)` with the device selected, under guarded.
+// The context is handed out only when that returns ECFFT_OK.
+template <class F, class Build>
+int new_ctx(int field, int device, ecfft_ctx** out, Build&& build) {
+    std::unique_ptr<ecfft_ctx> c(new (std::nothrow) ecfft_ctx());
+    if (!c) return ECFFT_ERR_HIP;
+    c->field = field; c->device = device;
+    std::unique_ptr<DeviceChain<F>>& slot = slot_of<F>(*c);
+    const int rc = guarded([&]() -> int {
+        slot.reset(new (std::nothrow) DeviceChain<F>());
+        if (!slot) return ECFFT_ERR_HIP;
+        DeviceGuard dev(device);
+        if (!dev.ok) return ECFFT_ERR_HIP;
+        return build(*slot);
+    });
+    if (rc == ECFFT_OK) *out = c.release();
+    return rc;
+}
+// FFTree::new on a host tree
 template <class F>
-int finish_build(HostTree<F>&& ht, int device, std::unique_ptr<DeviceChain<F>>& slot) {
-    slot.reset(new (std::nothrow) DeviceChain<F>());
-    if (!slot) return ECFFT_ERR_HIP;
-    DeviceGuard dev(device);
-    if (!dev.ok) return ECFFT_ERR_HIP;
-    if (slot->build(std::move(ht), device)) return ECFFT_OK;
-    return slot->bad_points() ? ECFFT_ERR_BAD_ARG : ECFFT_ERR_HIP;       // a leaf that is a pole of its isogeny map is a caller error
+int build_chain(DeviceChain<F>& ch, HostTree<F>&& ht, int device) {
+    if (ch.build(std::move(ht), device)) return ECFFT_OK;
+    return ch.bad_points() ? ECFFT_ERR_BAD_ARG : ECFFT_ERR_HIP;       // a leaf that is a pole of its isogeny map is a caller error
+}
+// ecfft_build_fftree and the shard builders after their own checks: the size limit of the field (it needs no device), the device,
+// the maps of the 2^log_n-leaf tree on the host (its leaves and layers are computed on the GPU: points_on_device), then
+// build(chain, host tree) on a new context
+template <class Build>
+int new_tree_ctx(int field, unsigned log_n, int device, ecfft_ctx** out, Build&& build) {
+    return with_field(field, [&](auto tag) -> int {
+        using F = typename decltype(tag)::type;
+        if (log_n > kMaxLogN<F>) return ECFFT_ERR_TREE_TOO_LARGE;
+        if (!have_device(device)) return ECFFT_ERR_HIP;
+        HostTree<F> ht;
+        const int r = build_host_tree<F>(log_n, ht, /*points=*/false);
+        if (r) return r == 1 ? ECFFT_ERR_TREE_TOO_LARGE : ECFFT_ERR_BAD_ARG;
+        return new_ctx<F>(field, device, out, [&](DeviceChain<F>& ch) -> int { return build(ch, std::move(ht)); });
+    });
 }
 
-// plain <-> crate representation on host buffers
-void secp_from_mont_host(Fe256* v, size_t n) {   // x*2^256 -> x : multiply by 2^-256 = (2^32+977)^-1
-    Fe256 r = Secp256k1::zero(); r.l[0] = 977; r.l[1] = 1;
-    Fe256 rinv = Secp256k1::inv(r);
-    for (size_t i = 0; i < n; ++i) v[i] = Secp256k1::mul(v[i], rinv);
-}
-void secp_to_mont_host(Fe256* v, size_t n) { for (size_t i = 0; i < n; ++i) v[i] = Secp256k1::to_mont(v[i]); }
-
+// ---- one call on a context -----------------------------------------------------------------------------------------
 bool ensure_stage(ecfft_ctx* c, size_t bytes) {
     if (c->stage_bytes >= bytes) return true;
     if (c->stage) (void)hipFree(c->stage);
@@ -74,26 +178,62 @@ bool ensure_stage(ecfft_ctx* c, size_t bytes) {
     return true;
 }
 
-// order this call after the previous one on the same context, whatever streams they use
-bool op_begin(ecfft_ctx* c, hipStream_t s) {
-    if (!c->last_op) return hipEventCreateWithFlags(&c->last_op, hipEventDisableTiming) == hipSuccess;
-    return hipStreamWaitEvent(s, c->last_op, 0) == hipSuccess;
-}
-bool op_end(ecfft_ctx* c, hipStream_t s) { return hipEventRecord(c->last_op, s) == hipSuccess; }
-
-// Orders a call after the previous one on the context (op_begin) and records its completion (op_end) on EVERY exit path
-// after a successful begin — an early error return must not leave `last_op` pointing before work that was enqueued.
-struct OpScope {
-    ecfft_ctx* c; hipStream_t s; bool ok;
-    OpScope(ecfft_ctx* c_, hipStream_t s_) : c(c_), s(s_), ok(op_begin(c_, s_)) {}
-    ~OpScope() { if (ok) (void)op_end(c, s); }
+// Device work on a context: selects its device, takes the chain lock, and orders the call after the previous one on the same
+// context, whatever streams they use.  Its completion is recorded in `last_op` on EVERY exit path after a successful begin — an
+// early error return must not leave `last_op` pointing before work that was enqueued.
+struct CallScope {
+    ecfft_ctx* c; hipStream_t s; DeviceGuard dev; std::unique_lock<std::mutex> lock; bool ok = false;
+    CallScope(ecfft_ctx* c_, std::mutex& m, hipStream_t s_) : c(c_), s(s_), dev(c_->device) {
+        if (!dev.ok) return;
+        lock = std::unique_lock<std::mutex>(m);
+        ok = c->last_op ? hipStreamWaitEvent(s, c->last_op, 0) == hipSuccess
+                        : hipEventCreateWithFlags(&c->last_op, hipEventDisableTiming) == hipSuccess;
+    }
+    ~CallScope() { if (ok) (void)hipEventRecord(c->last_op, s); }
 };
-// no C++ exception (allocation failure inside the chain) crosses the C ABI
-template <class Fn>
-int guarded(Fn fn) {
-    try { return fn(); }
-    catch (const std::bad_alloc&) { return ECFFT_ERR_HIP; }
-    catch (...) { return ECFFT_ERR_HIP; }
+
+struct In { const void* ptr; size_t bytes; };
+struct Out { void* ptr; size_t bytes; bool in_place = false; };   // in_place: the input with the same pointer, in its slot
+
+// A call in device memory (the pointers go to `body` as they are; asynchronous on `s`) or in host memory, staged through the
+// context's one grow-only device buffer: the inputs are uploaded in order, `body` runs on the staged copies and only if it returns
+// ECFFT_OK are the outputs downloaded and `s` drained.  A null pointer is an absent slot.  An input with the same pointer and size
+// as an earlier one is staged once: both get the same device pointer (a host-memory poly_mul(a, a) stays a squaring).
+template <class Chain, size_t NI, size_t NO, class Body>
+int staged(ecfft_ctx* c, Chain& ch, int mem, void* stream, const In (&in)[NI], const Out (&out)[NO], Body&& body) {
+    if (mem != ECFFT_MEM_HOST && mem != ECFFT_MEM_DEVICE) return ECFFT_ERR_BAD_ARG;
+    hipStream_t s = (hipStream_t)stream;
+    CallScope scope(c, ch.lock(), s);
+    if (!scope.ok) return ECFFT_ERR_HIP;
+    const void* din[NI]; void* dout[NO];
+    for (size_t i = 0; i < NI; ++i) din[i] = in[i].ptr;
+    for (size_t o = 0; o < NO; ++o) dout[o] = out[o].ptr;
+    if (mem == ECFFT_MEM_HOST) {
+        size_t off[NI + NO], total = 0;
+        auto same = [&](size_t i) { for (size_t j = 0; j < i; ++j) if (in[j].ptr == in[i].ptr && in[j].bytes == in[i].bytes) return j; return i; };
+        for (size_t i = 0; i < NI; ++i)
+            if (in[i].ptr && same(i) == i) { off[i] = total; total += in[i].bytes; }
+        for (size_t o = 0; o < NO; ++o)
+            if (out[o].ptr && !out[o].in_place) { off[NI + o] = total; total += out[o].bytes; }
+        if (!ensure_stage(c, total)) return ECFFT_ERR_HIP;
+        char* st = (char*)c->stage;
+        for (size_t i = 0; i < NI; ++i) {
+            if (!in[i].ptr) continue;
+            if (same(i) != i) { din[i] = din[same(i)]; continue; }
+            din[i] = st + off[i];
+            if (hipMemcpyAsync((void*)din[i], in[i].ptr, in[i].bytes, hipMemcpyHostToDevice, s) != hipSuccess) return ECFFT_ERR_HIP;
+        }
+        for (size_t o = 0; o < NO; ++o) {
+            if (!out[o].ptr) continue;
+            dout[o] = st + off[NI + o];
+            for (size_t i = 0; i < NI && out[o].in_place; ++i) if (in[i].ptr == out[o].ptr) dout[o] = (void*)din[i];
+        }
+    }
+    const int rc = body(din, dout);
+    if (rc != ECFFT_OK || mem != ECFFT_MEM_HOST) return rc;
+    for (size_t o = 0; o < NO; ++o)
+        if (out[o].ptr && out[o].bytes && hipMemcpyAsync(out[o].ptr, dout[o], out[o].bytes, hipMemcpyDeviceToHost, s) != hipSuccess) return ECFFT_ERR_HIP;
+    return hipStreamSynchronize(s) == hipSuccess ? ECFFT_OK : ECFFT_ERR_HIP;
 }
 
 enum Op { OP_ENTER, OP_EXIT, OP_EXTEND };
@@ -101,7 +241,13 @@ enum Op { OP_ENTER, OP_EXIT, OP_EXTEND };
 // a context made by ecfft_build_extend_shard / ecfft_build_enter_shard / ecfft_build_exit_shard holds one rank's share of the tables of ONE split transform
 // and nothing else: only that transform (ecfft_extend_sharded[_layout] / ecfft_enter_sharded / ecfft_exit_sharded with the same size, world and rank;
 // run_sharded checks) plus ecfft_tree_size, ecfft_field, ecfft_ctx_device_bytes, ecfft_profile_* and ecfft_ctx_destroy accept it
-inline bool shard_only(const ecfft_ctx* c) { return c->field == ECFFT_FIELD_SECP256K1 ? c->secp->shard_mode() : c->m31->shard_mode(); }
+inline bool shard_only(const ecfft_ctx* c) { return with_chain(c, [](auto& ch) { return ch.shard_mode(); }); }
+// a context-bound call: run(chain) under guarded, on a context that holds a full tree unless `shards` (the split transforms)
+template <class Run>
+int on_chain(ecfft_ctx* ctx, Run&& run, bool shards = false) {
+    if (!ctx || (!shards && shard_only(ctx))) return ECFFT_ERR_BAD_ARG;
+    return guarded([&] { return with_chain(ctx, run); });
+}
 
 template <class F>
 int run_op(ecfft_ctx* c, DeviceChain<F>& ch, Op op, const void* in, void* out, size_t len, size_t count, int moiety,
@@ -113,35 +259,21 @@ int run_op(ecfft_ctx* c, DeviceChain<F>& ch, Op op, const void* in, void* out, s
     size_t need_tree = (op == OP_EXTEND) ? len * 2 : len;
     if (need_tree > ch.size()) return ECFFT_ERR_TREE_TOO_SMALL;          // "FFTree is too small"
     if (op == OP_EXTEND && moiety != ECFFT_S0 && moiety != ECFFT_S1) return ECFFT_ERR_BAD_ARG;
-    hipStream_t s = (hipStream_t)stream;
-    if (mem != ECFFT_MEM_HOST && mem != ECFFT_MEM_DEVICE) return ECFFT_ERR_BAD_ARG;
-    DeviceGuard dev(c->device);
-    if (!dev.ok) return ECFFT_ERR_HIP;
-    std::lock_guard<std::mutex> guard(ch.lock());
-    OpScope scope(c, s);
-    if (!scope.ok) return ECFFT_ERR_HIP;
-    size_t total = len * count, bytes = total * sizeof(E);
-    const E* din = (const E*)in; E* dout = (E*)out;
-    if (mem == ECFFT_MEM_HOST) {
-        if (!ensure_stage(c, 2 * bytes)) return ECFFT_ERR_HIP;
-        din = (const E*)c->stage; dout = (E*)((char*)c->stage + bytes);
-        if (hipMemcpyAsync((void*)din, in, bytes, hipMemcpyHostToDevice, s) != hipSuccess) return ECFFT_ERR_HIP;
-    }
-    bool ok = true;
-    switch (op) {
-        case OP_ENTER: ok = ch.enter(din, dout, len, count, s); break;
-        case OP_EXIT: ok = ch.exit(din, dout, len, count, s); break;
-        case OP_EXTEND: ok = ch.extend_api(din, dout, len, count, moiety, s); break;
-    }
-    if (!ok || hipGetLastError() != hipSuccess) return ECFFT_ERR_HIP;
-    if (mem == ECFFT_MEM_HOST) {
-        if (hipMemcpyAsync(out, dout, bytes, hipMemcpyDeviceToHost, s) != hipSuccess) return ECFFT_ERR_HIP;
-        if (hipStreamSynchronize(s) != hipSuccess) return ECFFT_ERR_HIP;
-    }
-    return ECFFT_OK;
+    const size_t bytes = len * count * sizeof(E);
+    return staged(c, ch, mem, stream, {{in, bytes}}, {{out, bytes}}, [&](auto d, auto o) -> int {
+        const E* din = (const E*)d[0]; E* dout = (E*)o[0];
+        hipStream_t s = (hipStream_t)stream;
+        bool ok = true;
+        switch (op) {
+            case OP_ENTER: ok = ch.enter(din, dout, len, count, s); break;
+            case OP_EXIT: ok = ch.exit(din, dout, len, count, s); break;
+            case OP_EXTEND: ok = ch.extend_api(din, dout, len, count, moiety, s); break;
+        }
+        return !ok || hipGetLastError() != hipSuccess ? ECFFT_ERR_HIP : ECFFT_OK;
+    });
 }
 
-// ecfft_poly_mul: like run_op (staging, lock, cross-stream event), inputs of na and nb and an output of na + nb - 1 elements per pair
+// ecfft_poly_mul: inputs of na and nb and an output of na + nb - 1 elements per pair
 template <class F>
 int run_poly_mul(ecfft_ctx* c, DeviceChain<F>& ch, const void* a, size_t na, const void* b, size_t nb, void* out, size_t count,
                  int mem, void* stream) {
@@ -152,33 +284,14 @@ int run_poly_mul(ecfft_ctx* c, DeviceChain<F>& ch, const void* a, size_t na, con
     size_t N = 1; while (N < nc) N <<= 1;
     if (N > ch.size()) return ECFFT_ERR_TREE_TOO_SMALL;                   // "FFTree is too small"
     if (count > SIZE_MAX / (8 * N * sizeof(E))) return ECFFT_ERR_BAD_ARG;  // byte counts of the temporaries must not wrap
-    if (mem != ECFFT_MEM_HOST && mem != ECFFT_MEM_DEVICE) return ECFFT_ERR_BAD_ARG;
-    hipStream_t s = (hipStream_t)stream;
-    DeviceGuard dev(c->device);
-    if (!dev.ok) return ECFFT_ERR_HIP;
-    std::lock_guard<std::mutex> guard(ch.lock());
-    OpScope scope(c, s);
-    if (!scope.ok) return ECFFT_ERR_HIP;
-    const bool sq = a == b && na == nb;
-    const size_t ba = na * count * sizeof(E), bb = sq ? 0 : nb * count * sizeof(E), bc = nc * count * sizeof(E);
-    const E *da = (const E*)a, *db = (const E*)b; E* dout = (E*)out;
-    if (mem == ECFFT_MEM_HOST) {
-        if (!ensure_stage(c, ba + bb + bc)) return ECFFT_ERR_HIP;
-        char* st = (char*)c->stage;
-        da = (const E*)st; db = sq ? da : (const E*)(st + ba); dout = (E*)(st + ba + bb);
-        if (hipMemcpyAsync((void*)da, a, ba, hipMemcpyHostToDevice, s) != hipSuccess) return ECFFT_ERR_HIP;
-        if (!sq && hipMemcpyAsync((void*)db, b, bb, hipMemcpyHostToDevice, s) != hipSuccess) return ECFFT_ERR_HIP;
-    }
-    if (!ch.poly_mul(da, na, db, nb, dout, count, s)) return ECFFT_ERR_HIP;
-    if (mem == ECFFT_MEM_HOST) {
-        if (hipMemcpyAsync(out, dout, bc, hipMemcpyDeviceToHost, s) != hipSuccess) return ECFFT_ERR_HIP;
-        if (hipStreamSynchronize(s) != hipSuccess) return ECFFT_ERR_HIP;
-    }
-    return ECFFT_OK;
+    const size_t eb = count * sizeof(E);
+    return staged(c, ch, mem, stream, {{a, na * eb}, {b, nb * eb}}, {{out, nc * eb}}, [&](auto d, auto o) -> int {
+        return ch.poly_mul((const E*)d[0], na, (const E*)d[1], nb, (E*)o[0], count, (hipStream_t)stream) ? ECFFT_OK : ECFFT_ERR_HIP;
+    });
 }
 
-// ecfft_poly_divrem / ecfft_poly_inv_series: staging, lock and cross-stream event as run_poly_mul; synchronous (the chain reads back
-// the device flag of a zero divisor leading coefficient / f[0], reported as ECFFT_ERR_BAD_ARG)
+// ecfft_poly_divrem / ecfft_poly_inv_series: synchronous (the chain reads back the device flag of a zero divisor leading
+// coefficient / f[0], reported as ECFFT_ERR_BAD_ARG)
 template <class F>
 int run_poly_divrem(ecfft_ctx* c, DeviceChain<F>& ch, const void* a, size_t na, const void* b, size_t nb, void* q, void* r, size_t count,
                     int mem, void* stream) {
@@ -195,32 +308,12 @@ int run_poly_divrem(ecfft_ctx* c, DeviceChain<F>& ch, const void* a, size_t na, 
     }
     const size_t per = N > na + nb ? N : na + nb;
     if (count > SIZE_MAX / (8 * per * sizeof(E))) return ECFFT_ERR_BAD_ARG; // byte counts of the temporaries must not wrap
-    if (mem != ECFFT_MEM_HOST && mem != ECFFT_MEM_DEVICE) return ECFFT_ERR_BAD_ARG;
-    hipStream_t s = (hipStream_t)stream;
-    DeviceGuard dev(c->device);
-    if (!dev.ok) return ECFFT_ERR_HIP;
-    std::lock_guard<std::mutex> guard(ch.lock());
-    OpScope scope(c, s);
-    if (!scope.ok) return ECFFT_ERR_HIP;
-    const size_t ba = na * count * sizeof(E), bb = nb * count * sizeof(E), bq = q ? nq * count * sizeof(E) : 0, br = r ? nr * count * sizeof(E) : 0;
-    const E *da = (const E*)a, *db = (const E*)b; E *dq = (E*)q, *dr = (E*)r;
-    if (mem == ECFFT_MEM_HOST) {
-        if (!ensure_stage(c, ba + bb + bq + br)) return ECFFT_ERR_HIP;
-        char* st = (char*)c->stage;
-        da = (const E*)st; db = (const E*)(st + ba);
-        dq = q ? (E*)(st + ba + bb) : nullptr; dr = r ? (E*)(st + ba + bb + bq) : nullptr;
-        if (hipMemcpyAsync((void*)da, a, ba, hipMemcpyHostToDevice, s) != hipSuccess) return ECFFT_ERR_HIP;
-        if (hipMemcpyAsync((void*)db, b, bb, hipMemcpyHostToDevice, s) != hipSuccess) return ECFFT_ERR_HIP;
-    }
-    bool singular = false;
-    if (!ch.poly_divrem(da, na, db, nb, dq, dr, count, &singular, s)) return ECFFT_ERR_HIP;
-    if (singular) return ECFFT_ERR_BAD_ARG;                                 // a zero leading coefficient of b in some pair
-    if (mem == ECFFT_MEM_HOST) {
-        if (bq && hipMemcpyAsync(q, dq, bq, hipMemcpyDeviceToHost, s) != hipSuccess) return ECFFT_ERR_HIP;
-        if (br && hipMemcpyAsync(r, dr, br, hipMemcpyDeviceToHost, s) != hipSuccess) return ECFFT_ERR_HIP;
-        if (hipStreamSynchronize(s) != hipSuccess) return ECFFT_ERR_HIP;
-    }
-    return ECFFT_OK;
+    const size_t eb = count * sizeof(E);
+    return staged(c, ch, mem, stream, {{a, na * eb}, {b, nb * eb}}, {{q, nq * eb}, {r, nr * eb}}, [&](auto d, auto o) -> int {
+        bool singular = false;
+        if (!ch.poly_divrem((const E*)d[0], na, (const E*)d[1], nb, (E*)o[0], (E*)o[1], count, &singular, (hipStream_t)stream)) return ECFFT_ERR_HIP;
+        return singular ? ECFFT_ERR_BAD_ARG : ECFFT_OK;                     // a zero leading coefficient of b in some pair
+    });
 }
 
 template <class F>
@@ -234,31 +327,15 @@ int run_inv_series(ecfft_ctx* c, DeviceChain<F>& ch, const void* f, size_t nf, v
     if (N > ch.size()) return ECFFT_ERR_TREE_TOO_SMALL;                     // k = 1: N = 1, any tree
     const size_t per = N > nf + k ? N : nf + k;
     if (count > SIZE_MAX / (8 * per * sizeof(E))) return ECFFT_ERR_BAD_ARG;
-    if (mem != ECFFT_MEM_HOST && mem != ECFFT_MEM_DEVICE) return ECFFT_ERR_BAD_ARG;
-    hipStream_t s = (hipStream_t)stream;
-    DeviceGuard dev(c->device);
-    if (!dev.ok) return ECFFT_ERR_HIP;
-    std::lock_guard<std::mutex> guard(ch.lock());
-    OpScope scope(c, s);
-    if (!scope.ok) return ECFFT_ERR_HIP;
-    const size_t bf = nf * count * sizeof(E), bo = k * count * sizeof(E);
-    const E* df = (const E*)f; E* dout = (E*)out;
-    if (mem == ECFFT_MEM_HOST) {
-        if (!ensure_stage(c, bf + bo)) return ECFFT_ERR_HIP;
-        df = (const E*)c->stage; dout = (E*)((char*)c->stage + bf);
-        if (hipMemcpyAsync((void*)df, f, bf, hipMemcpyHostToDevice, s) != hipSuccess) return ECFFT_ERR_HIP;
-    }
-    bool singular = false;
-    if (!ch.inv_series(df, nf, dout, k, count, &singular, s)) return ECFFT_ERR_HIP;
-    if (singular) return ECFFT_ERR_BAD_ARG;                                 // f[0] == 0 in some pair: no power-series inverse
-    if (mem == ECFFT_MEM_HOST) {
-        if (hipMemcpyAsync(out, dout, bo, hipMemcpyDeviceToHost, s) != hipSuccess) return ECFFT_ERR_HIP;
-        if (hipStreamSynchronize(s) != hipSuccess) return ECFFT_ERR_HIP;
-    }
-    return ECFFT_OK;
+    const size_t eb = count * sizeof(E);
+    return staged(c, ch, mem, stream, {{f, nf * eb}}, {{out, k * eb}}, [&](auto d, auto o) -> int {
+        bool singular = false;
+        if (!ch.inv_series((const E*)d[0], nf, (E*)o[0], k, count, &singular, (hipStream_t)stream)) return ECFFT_ERR_HIP;
+        return singular ? ECFFT_ERR_BAD_ARG : ECFFT_OK;                     // f[0] == 0 in some pair: no power-series inverse
+    });
 }
 
-// ecfft_poly_eval_points: staging, lock and cross-stream event as run_poly_mul; asynchronous on `stream` (nothing is data dependent)
+// ecfft_poly_eval_points: asynchronous on `stream` in device memory (nothing is data dependent)
 template <class F>
 int run_poly_eval_points(ecfft_ctx* c, DeviceChain<F>& ch, const void* f, size_t nf, const void* points, size_t m, void* out, size_t count,
                          int mem, void* stream) {
@@ -271,28 +348,10 @@ int run_poly_eval_points(ecfft_ctx* c, DeviceChain<F>& ch, const void* f, size_t
     if (P > SIZE_MAX / (8 * 64 * sizeof(E))) return ECFFT_ERR_BAD_ARG;     // node data: 4 P elements per level, < 64 levels
     const size_t per = P > nf ? P : nf;
     if (count > SIZE_MAX / (16 * per * sizeof(E))) return ECFFT_ERR_BAD_ARG; // byte counts of the temporaries must not wrap
-    if (mem != ECFFT_MEM_HOST && mem != ECFFT_MEM_DEVICE) return ECFFT_ERR_BAD_ARG;
-    hipStream_t s = (hipStream_t)stream;
-    DeviceGuard dev(c->device);
-    if (!dev.ok) return ECFFT_ERR_HIP;
-    std::lock_guard<std::mutex> guard(ch.lock());
-    OpScope scope(c, s);
-    if (!scope.ok) return ECFFT_ERR_HIP;
-    const size_t bf = nf * count * sizeof(E), bp = m * sizeof(E), bo = m * count * sizeof(E);
-    const E *df = (const E*)f, *dp = (const E*)points; E* dout = (E*)out;
-    if (mem == ECFFT_MEM_HOST) {
-        if (!ensure_stage(c, bf + bp + bo)) return ECFFT_ERR_HIP;
-        char* st = (char*)c->stage;
-        df = (const E*)st; dp = (const E*)(st + bf); dout = (E*)(st + bf + bp);
-        if (hipMemcpyAsync((void*)df, f, bf, hipMemcpyHostToDevice, s) != hipSuccess) return ECFFT_ERR_HIP;
-        if (hipMemcpyAsync((void*)dp, points, bp, hipMemcpyHostToDevice, s) != hipSuccess) return ECFFT_ERR_HIP;
-    }
-    if (!ch.poly_eval_points(df, nf, dp, m, dout, count, s)) return ECFFT_ERR_HIP;
-    if (mem == ECFFT_MEM_HOST) {
-        if (hipMemcpyAsync(out, dout, bo, hipMemcpyDeviceToHost, s) != hipSuccess) return ECFFT_ERR_HIP;
-        if (hipStreamSynchronize(s) != hipSuccess) return ECFFT_ERR_HIP;
-    }
-    return ECFFT_OK;
+    const size_t eb = count * sizeof(E);
+    return staged(c, ch, mem, stream, {{f, nf * eb}, {points, m * sizeof(E)}}, {{out, m * eb}}, [&](auto d, auto o) -> int {
+        return ch.poly_eval_points((const E*)d[0], nf, (const E*)d[1], m, (E*)o[0], count, (hipStream_t)stream) ? ECFFT_OK : ECFFT_ERR_HIP;
+    });
 }
 
 // standard = true: plain standard-form residues (the FFTree wire format) instead of the crate's in-memory representation
@@ -321,36 +380,24 @@ int table_of(DeviceChain<F>& ch, size_t m, int which, void* host_out, size_t cap
     if (!host_out) return ECFFT_OK;
     if (cap < cnt) return ECFFT_ERR_BAD_ARG;
     E* o = (E*)host_out;
-    if (which == ECFFT_TBL_RECOMBINE || which == ECFFT_TBL_DECOMPOSE) {
+    if (which == ECFFT_TBL_RECOMBINE || which == ECFFT_TBL_DECOMPOSE || which == ECFFT_TBL_F) {
+        // the matrices, and f of T_m: every (N/m)-th element of each layer of the top tree (src/fftree.rs:471-478), gathered on the
+        // device — only the entries asked for cross the bus
         std::lock_guard<std::mutex> guard(ch.lock());
-        void* d = nullptr;
-        if (hipMalloc(&d, cnt * sizeof(E)) != hipSuccess) return ECFFT_ERR_HIP;
-        bool ok = ch.export_matrices(l, which == ECFFT_TBL_DECOMPOSE, (E*)d, nullptr, standard) &&
-                  hipMemcpy(o, d, cnt * sizeof(E), hipMemcpyDeviceToHost) == hipSuccess;
-        (void)hipFree(d);
-        return ok ? ECFFT_OK : ECFFT_ERR_HIP;      // already in the crate representation
-    }
-    if (which == ECFFT_TBL_F) {
-        // f of T_m: every (N/m)-th element of each layer of the top tree (src/fftree.rs:471-478), gathered on the device — only
-        // the 2m entries asked for cross the bus
-        std::lock_guard<std::mutex> guard(ch.lock());
-        void* d = nullptr;
-        if (hipMalloc(&d, cnt * sizeof(E)) != hipSuccess) return ECFFT_ERR_HIP;
-        bool ok = ch.gather_f(l, (E*)d, nullptr) && hipMemcpy(o, d, cnt * sizeof(E), hipMemcpyDeviceToHost) == hipSuccess;
-        (void)hipFree(d);
-        if (!ok) return ECFFT_ERR_HIP;
+        DeviceBuffer d(cnt * sizeof(E));
+        if (!d.ok) return ECFFT_ERR_HIP;
+        const bool ok = which == ECFFT_TBL_F ? ch.gather_f(l, d.as<E>(), nullptr)
+                                             : ch.export_matrices(l, which == ECFFT_TBL_DECOMPOSE, d.as<E>(), nullptr, standard);
+        if (!ok || hipMemcpy(o, d.p, cnt * sizeof(E), hipMemcpyDeviceToHost) != hipSuccess) return ECFFT_ERR_HIP;
+        if (which != ECFFT_TBL_F) return ECFFT_OK;      // the matrices are already in the crate representation
     } else if (cnt) {
         if (!src) return ECFFT_ERR_BAD_ARG;
         if (hipMemcpy(o, src, cnt * sizeof(E), hipMemcpyDeviceToHost) != hipSuccess) return ECFFT_ERR_HIP;
     }
-    if (standard) return ECFFT_OK;
-    if constexpr (std::is_same<F, Secp256k1>::value) secp_to_mont_host(o, cnt);
+    if (!standard) to_crate_host<F>(o, cnt);
     return ECFFT_OK;
 }
 
-}  // namespace
-
-namespace {
 template <class F>
 int run_shard(ecfft_ctx* c, DeviceChain<F>& ch, void* buf, size_t e, int moiety, unsigned log_p, unsigned rank, int which, int mem, void* stream) {
     using E = typename F::elem;
@@ -359,33 +406,19 @@ int run_shard(ecfft_ctx* c, DeviceChain<F>& ch, void* buf, size_t e, int moiety,
     if (2 * e > ch.size()) return ECFFT_ERR_TREE_TOO_SMALL;
     if (moiety != ECFFT_S0 && moiety != ECFFT_S1) return ECFFT_ERR_BAD_ARG;
     if (((size_t)2 << log_p) > e || rank >= (1u << log_p)) return ECFFT_ERR_BAD_ARG;   // need >= 2 elements per rank
-    if (mem != ECFFT_MEM_HOST && mem != ECFFT_MEM_DEVICE) return ECFFT_ERR_BAD_ARG;
-    DeviceGuard dev(c->device);
-    if (!dev.ok) return ECFFT_ERR_HIP;
-    hipStream_t s = (hipStream_t)stream;
-    std::lock_guard<std::mutex> guard(ch.lock());
-    OpScope scope(c, s);
-    if (!scope.ok) return ECFFT_ERR_HIP;
-    size_t bytes = (e >> log_p) * sizeof(E);
-    E* d = (E*)buf;
-    if (mem == ECFFT_MEM_HOST) {
-        if (!ensure_stage(c, bytes)) return ECFFT_ERR_HIP;
-        d = (E*)c->stage;
-        if (hipMemcpyAsync(d, buf, bytes, hipMemcpyHostToDevice, s) != hipSuccess) return ECFFT_ERR_HIP;
-    }
-    if (which == 2) ch.extend_local_block(d, e, moiety, log_p, s);
-    else ch.extend_top_cyclic(d, e, moiety, log_p, rank, which == 1, s);
-    if (hipGetLastError() != hipSuccess) return ECFFT_ERR_HIP;
-    if (mem == ECFFT_MEM_HOST) {
-        if (hipMemcpyAsync(buf, d, bytes, hipMemcpyDeviceToHost, s) != hipSuccess) return ECFFT_ERR_HIP;
-        if (hipStreamSynchronize(s) != hipSuccess) return ECFFT_ERR_HIP;
-    }
-    return ECFFT_OK;
+    const size_t bytes = (e >> log_p) * sizeof(E);
+    return staged(c, ch, mem, stream, {{buf, bytes}}, {{buf, bytes, /*in_place=*/true}}, [&](auto, auto o) -> int {
+        E* d = (E*)o[0];
+        hipStream_t s = (hipStream_t)stream;
+        if (which == 2) ch.extend_local_block(d, e, moiety, log_p, s);
+        else ch.extend_top_cyclic(d, e, moiety, log_p, rank, which == 1, s);
+        return hipGetLastError() != hipSuccess ? ECFFT_ERR_HIP : ECFFT_OK;
+    });
 }
+
 }  // namespace
 
-
-// ---- remaining algorithms: generic driver with up to 3 inputs and 1 output, staged through device temporaries for host buffers
+// ---- remaining algorithms: up to 3 inputs and 1 output
 enum Alg { ALG_MEXTEND, ALG_REDC, ALG_MOD, ALG_VANISH, ALG_DEGREE };
 template <class F>
 int run_alg(ecfft_ctx* c, DeviceChain<F>& ch, Alg alg, const void* in0, const void* in1, const void* in2, void* out, size_t len,
@@ -400,34 +433,15 @@ int run_alg(ecfft_ctx* c, DeviceChain<F>& ch, Alg alg, const void* in0, const vo
     size_t need = (alg == ALG_MEXTEND || alg == ALG_VANISH) ? 2 * len : len;
     if (need > ch.size()) return ECFFT_ERR_TREE_TOO_SMALL;
     if ((alg == ALG_MEXTEND || alg == ALG_REDC) && moiety != ECFFT_S0 && moiety != ECFFT_S1) return ECFFT_ERR_BAD_ARG;
-    if (mem != ECFFT_MEM_HOST && mem != ECFFT_MEM_DEVICE) return ECFFT_ERR_BAD_ARG;
     if ((alg == ALG_REDC || alg == ALG_MOD) && len < 2) {   // size-1 tree has no moieties: the reference would index out of bounds
         return ECFFT_ERR_BAD_ARG;
     }
-    DeviceGuard dev(c->device);
-    if (!dev.ok) return ECFFT_ERR_HIP;
-    hipStream_t s = (hipStream_t)stream;
-    std::lock_guard<std::mutex> guard(ch.lock());
-    OpScope scope(c, s);
-    if (!scope.ok) return ECFFT_ERR_HIP;
-    size_t n_in = len * count, n_out = (alg == ALG_VANISH ? 2 * len : len) * count;
-    const E *d0 = (const E*)in0, *d1 = (const E*)in1, *d2 = (const E*)in2; E* dout = (E*)out;
-    bool ok = true;
-    if (mem == ECFFT_MEM_HOST) {
-        // host buffers: inputs and the output are staged through ONE context-owned device buffer that grows on demand
-        // and is reused by later calls (no hipMalloc / hipFree per call)
-        size_t need = n_in + (in1 ? len : 0) + (in2 ? len : 0) + (alg != ALG_DEGREE ? n_out : 0);
-        if (!ensure_stage(c, need * sizeof(E))) return ECFFT_ERR_HIP;
-        E* p = (E*)c->stage;
-        auto stage_in = [&](const void* h, size_t n, const E** d) -> bool {
-            if (!h) return true;
-            if (hipMemcpyAsync(p, h, n * sizeof(E), hipMemcpyHostToDevice, s) != hipSuccess) return false;
-            *d = p; p += n; return true;
-        };
-        ok = stage_in(in0, n_in, &d0) && stage_in(in1, len, &d1) && stage_in(in2, len, &d2);
-        if (alg != ALG_DEGREE) dout = p;
-    }
-    if (ok) {
+    const size_t n_in = len * count, n_out = (alg == ALG_VANISH ? 2 * len : len) * count;
+    return staged(c, ch, mem, stream, {{in0, n_in * sizeof(E)}, {in1, len * sizeof(E)}, {in2, len * sizeof(E)}},
+                  {{alg != ALG_DEGREE ? out : nullptr, n_out * sizeof(E)}}, [&](auto d, auto o) -> int {
+        const E *d0 = (const E*)d[0], *d1 = (const E*)d[1], *d2 = (const E*)d[2]; E* dout = (E*)o[0];
+        hipStream_t s = (hipStream_t)stream;
+        bool ok = true;
         switch (alg) {
             case ALG_MEXTEND: ok = ch.api_mextend(d0, dout, len, count, moiety, s); break;
             case ALG_REDC: ok = ch.api_redc(d0, d1, dout, len, moiety, s); break;
@@ -435,12 +449,9 @@ int run_alg(ecfft_ctx* c, DeviceChain<F>& ch, Alg alg, const void* in0, const vo
             case ALG_VANISH: ok = ch.api_vanish(d0, dout, len, s); break;
             case ALG_DEGREE: ok = ch.api_degree(d0, len, s, degree); break;
         }
-    }
-    if (ok && mem == ECFFT_MEM_HOST && alg != ALG_DEGREE)
-        ok = hipMemcpyAsync(out, dout, n_out * sizeof(E), hipMemcpyDeviceToHost, s) == hipSuccess && hipStreamSynchronize(s) == hipSuccess;
-    return ok ? ECFFT_OK : ECFFT_ERR_HIP;
+        return ok ? ECFFT_OK : ECFFT_ERR_HIP;
+    });
 }
-#define ECFFT_DISPATCH_ALG(...) (ctx->field == ECFFT_FIELD_SECP256K1 ? run_alg(ctx, *ctx->secp, __VA_ARGS__) : run_alg(ctx, *ctx->m31, __VA_ARGS__))
 
 namespace {
 template <class F>
@@ -451,29 +462,31 @@ int run_table_fma(ecfft_ctx* c, DeviceChain<F>& ch, void* out, const void* x, co
     if (!is_pow2(m)) return ECFFT_ERR_NOT_POW2;
     if (m > ch.size()) return ECFFT_ERR_TREE_TOO_SMALL;
     if (cnt == 0) return ECFFT_OK;
-    DeviceGuard dev(c->device);
-    if (!dev.ok) return ECFFT_ERR_HIP;
-    hipStream_t s = (hipStream_t)stream;
-    std::lock_guard<std::mutex> guard(ch.lock());
-    OpScope scope(c, s);                                          // after the context's previous call, whatever stream it ran on (staging buffer, pooled temporaries)
-    if (!scope.ok) return ECFFT_ERR_HIP;
-    const E *dx = (const E*)x, *dy = (const E*)y; E* dout = (E*)out;
-    size_t bytes = cnt * sizeof(E);
-    if (mem == ECFFT_MEM_HOST) {
-        if (!ensure_stage(c, 3 * bytes)) return ECFFT_ERR_HIP;
-        E* st = (E*)c->stage;
-        if (hipMemcpyAsync(st, x, bytes, hipMemcpyHostToDevice, s) != hipSuccess) return ECFFT_ERR_HIP;
-        dx = st;
-        if (y) { if (hipMemcpyAsync(st + cnt, y, bytes, hipMemcpyHostToDevice, s) != hipSuccess) return ECFFT_ERR_HIP; dy = st + cnt; }
-        dout = st + 2 * cnt;
-    } else if (mem != ECFFT_MEM_DEVICE) return ECFFT_ERR_BAD_ARG;
-    if (!ch.table_fma(dout, dx, dy, cnt, ilog2(m), which, t_off, t_stride, mode, s)) return ECFFT_ERR_BAD_ARG;
-    if (mem == ECFFT_MEM_HOST) {
-        if (hipMemcpyAsync(out, dout, bytes, hipMemcpyDeviceToHost, s) != hipSuccess) return ECFFT_ERR_HIP;
-        if (hipStreamSynchronize(s) != hipSuccess) return ECFFT_ERR_HIP;
-    }
-    return ECFFT_OK;
+    const size_t bytes = cnt * sizeof(E);
+    return staged(c, ch, mem, stream, {{x, bytes}, {y, bytes}}, {{out, bytes}}, [&](auto d, auto o) -> int {
+        return ch.table_fma((E*)o[0], (const E*)d[0], (const E*)d[1], cnt, ilog2(m), which, t_off, t_stride, mode, (hipStream_t)stream)
+                   ? ECFFT_OK : ECFFT_ERR_BAD_ARG;
+    });
 }
+
+#ifdef ECFFT_TEST_HOOKS
+// the matrix-core selftests: the matrix (tn elements) and x uploaded, then launch(matrix, x, its expanded form of `ab` bytes,
+// a scratch of `scratch` bytes) on the null stream, then x downloaded into out
+template <class Launch>
+int run_blk_selftest(const void* matrix, size_t tn, const void* x, void* out, size_t n, size_t ab, size_t scratch, int device, Launch&& launch) {
+    if (!have_device(device)) return ECFFT_ERR_HIP;
+    DeviceGuard dev(device);
+    if (!dev.ok) return ECFFT_ERR_HIP;
+    DeviceBuffer dT(tn * sizeof(Fe256)), dx(n * sizeof(Fe256)), dA(ab), dS(scratch);
+    bool ok = dT.ok && dx.ok && dA.ok && dS.ok;
+    ok = ok && hipMemcpy(dT.p, matrix, tn * sizeof(Fe256), hipMemcpyHostToDevice) == hipSuccess && hipMemcpy(dx.p, x, n * sizeof(Fe256), hipMemcpyHostToDevice) == hipSuccess;
+    if (ok) {
+        launch(dT.as<Fe256>(), dx.as<Fe256>(), dA.as<uint8_t>(), dS.as<Fe256>());
+        ok = hipDeviceSynchronize() == hipSuccess && hipMemcpy(out, dx.p, n * sizeof(Fe256), hipMemcpyDeviceToHost) == hipSuccess;
+    }
+    return ok ? ECFFT_OK : ECFFT_ERR_HIP;
+}
+#endif  // ECFFT_TEST_HOOKS
 }  // namespace
 
 #ifdef ECFFT_TEST_HOOKS
@@ -484,13 +497,13 @@ int run_selftest(int op, const void* a, const void* b, const void* c, void* out,
     if (!have_device(device)) return ECFFT_ERR_HIP;
     DeviceGuard dev(device);
     if (!dev.ok) return ECFFT_ERR_HIP;
-    E *da = nullptr, *db = nullptr, *dc = nullptr, *dout = nullptr;
-    size_t bytes = n * sizeof(E);
-    bool ok = hipMalloc(&da, bytes) == hipSuccess && hipMalloc(&db, bytes) == hipSuccess && hipMalloc(&dc, bytes) == hipSuccess && hipMalloc(&dout, bytes) == hipSuccess;
-    ok = ok && hipMemcpy(da, a, bytes, hipMemcpyHostToDevice) == hipSuccess && hipMemcpy(db, b, bytes, hipMemcpyHostToDevice) == hipSuccess;
-    if (ok && c) ok = hipMemcpy(dc, c, bytes, hipMemcpyHostToDevice) == hipSuccess;
+    const size_t bytes = n * sizeof(E);
+    DeviceBuffer da(bytes), db(bytes), dc(bytes), dout(bytes);
+    bool ok = da.ok && db.ok && dc.ok && dout.ok;
+    ok = ok && hipMemcpy(da.p, a, bytes, hipMemcpyHostToDevice) == hipSuccess && hipMemcpy(db.p, b, bytes, hipMemcpyHostToDevice) == hipSuccess;
+    if (ok && c) ok = hipMemcpy(dc.p, c, bytes, hipMemcpyHostToDevice) == hipSuccess;
     if (ok) {
-        const E *pa = da, *pb = db, *pc = dc; E* po = dout;
+        const E *pa = da.as<E>(), *pb = db.as<E>(), *pc = dc.as<E>(); E* po = dout.as<E>();
         foreach_n(nullptr, n, [=] __device__(size_t i) {
             E r;
             if (op == 0) r = F::mul_add(pa[i], pb[i], pc[i]);
@@ -501,13 +514,12 @@ int run_selftest(int op, const void* a, const void* b, const void* c, void* out,
             else r = F::tmul(F::to_table(pa[i]), pb[i]);
             po[i] = r;
         });
-        ok = hipDeviceSynchronize() == hipSuccess && hipMemcpy(out, dout, bytes, hipMemcpyDeviceToHost) == hipSuccess;
+        ok = hipDeviceSynchronize() == hipSuccess && hipMemcpy(out, dout.p, bytes, hipMemcpyDeviceToHost) == hipSuccess;
     }
-    (void)hipFree(da); (void)hipFree(db); (void)hipFree(dc); (void)hipFree(dout);
     return ok ? ECFFT_OK : ECFFT_ERR_HIP;
 }
-#endif  // ECFFT_TEST_HOOKS
 
+#endif  // ECFFT_TEST_HOOKS
 // dependent chain x <- T*x + c per lane: the table multiply of the butterfly kernels with nothing else around it
 template <class F>
 __global__ __launch_bounds__(256) void k_mul_chain(const typename F::elem* t, typename F::elem* x, int iters) {
@@ -546,16 +558,15 @@ int run_shader_clock(int device, double* mhz) {
     const size_t n = (size_t)blocks * 256;
     std::vector<E> h(n);
     memset(h.data(), 0x35, n * sizeof(E));
-    E *dt = nullptr, *dx = nullptr; ClockStamp* ds = nullptr;
     std::vector<ClockStamp> hs(blocks);
-    bool ok = hipMalloc(&dt, n * sizeof(E)) == hipSuccess && hipMalloc(&dx, n * sizeof(E)) == hipSuccess && hipMalloc(&ds, blocks * sizeof(ClockStamp)) == hipSuccess &&
-              hipMemcpy(dt, h.data(), n * sizeof(E), hipMemcpyHostToDevice) == hipSuccess && hipMemcpy(dx, h.data(), n * sizeof(E), hipMemcpyHostToDevice) == hipSuccess;
+    DeviceBuffer dt(n * sizeof(E)), dx(n * sizeof(E)), ds(blocks * sizeof(ClockStamp));
+    bool ok = dt.ok && dx.ok && ds.ok &&
+              hipMemcpy(dt.p, h.data(), n * sizeof(E), hipMemcpyHostToDevice) == hipSuccess && hipMemcpy(dx.p, h.data(), n * sizeof(E), hipMemcpyHostToDevice) == hipSuccess;
     for (int r = 0; ok && r < 2; ++r) {
-        hipLaunchKernelGGL(k_clock_probe<F>, dim3(blocks), dim3(256), 0, nullptr, (const E*)dt, dx, ds, iters);
+        hipLaunchKernelGGL(k_clock_probe<F>, dim3(blocks), dim3(256), 0, nullptr, dt.as<const E>(), dx.as<E>(), ds.as<ClockStamp>(), iters);
         ok = hipDeviceSynchronize() == hipSuccess;
     }
-    ok = ok && hipMemcpy(hs.data(), ds, blocks * sizeof(ClockStamp), hipMemcpyDeviceToHost) == hipSuccess;
-    (void)hipFree(dt); (void)hipFree(dx); (void)hipFree(ds);
+    ok = ok && hipMemcpy(hs.data(), ds.p, blocks * sizeof(ClockStamp), hipMemcpyDeviceToHost) == hipSuccess;
     if (!ok) return ECFFT_ERR_HIP;
     double cyc = 0, wall = 0;
     for (const ClockStamp& c : hs) { cyc += (double)c.cyc; wall += (double)c.wall; }
@@ -580,22 +591,21 @@ int run_mul_ceiling(int device, int waves_per_simd, double* mul_per_s) {
         for (size_t k = 0; k < sizeof(E); ++k) { sd ^= sd << 13; sd ^= sd >> 7; sd ^= sd << 17; b[k] = (unsigned char)(sd >> 24); }
         b[sizeof(E) - 1] &= 0x3F;                                                    // < p for both fields
     }
-    E *dt = nullptr, *dx = nullptr;
+    DeviceBuffer dt(n * sizeof(E)), dx(n * sizeof(E));
     hipEvent_t e0 = nullptr, e1 = nullptr;
-    bool ok = hipMalloc(&dt, n * sizeof(E)) == hipSuccess && hipMalloc(&dx, n * sizeof(E)) == hipSuccess &&
-              hipMemcpy(dt, h.data(), n * sizeof(E), hipMemcpyHostToDevice) == hipSuccess && hipMemcpy(dx, h.data(), n * sizeof(E), hipMemcpyHostToDevice) == hipSuccess &&
+    bool ok = dt.ok && dx.ok &&
+              hipMemcpy(dt.p, h.data(), n * sizeof(E), hipMemcpyHostToDevice) == hipSuccess && hipMemcpy(dx.p, h.data(), n * sizeof(E), hipMemcpyHostToDevice) == hipSuccess &&
               hipEventCreate(&e0) == hipSuccess && hipEventCreate(&e1) == hipSuccess;
     float best = 1e30f;
     for (int r = 0; ok && r < 4; ++r) {
         ok = hipEventRecord(e0, nullptr) == hipSuccess;
-        hipLaunchKernelGGL(k_mul_chain<F>, dim3(blocks), dim3(256), 0, nullptr, (const E*)dt, dx, iters);
+        hipLaunchKernelGGL(k_mul_chain<F>, dim3(blocks), dim3(256), 0, nullptr, dt.as<const E>(), dx.as<E>(), iters);
         ok = ok && hipEventRecord(e1, nullptr) == hipSuccess && hipEventSynchronize(e1) == hipSuccess;
         float ms = 0; ok = ok && hipEventElapsedTime(&ms, e0, e1) == hipSuccess;
         if (ok && r > 0 && ms < best) best = ms;
     }
     if (e0) (void)hipEventDestroy(e0);
     if (e1) (void)hipEventDestroy(e1);
-    (void)hipFree(dt); (void)hipFree(dx);
     if (!ok) return ECFFT_ERR_HIP;
     *mul_per_s = (double)n * iters / (best * 1e-3);
     return ECFFT_OK;
@@ -624,10 +634,7 @@ int run_sharded(ecfft_ctx* c, DeviceChain<F>& ch, ecfft_comm* comm, Op op, const
     }
     if ((in_layout != ECFFT_LAYOUT_BLOCK && in_layout != ECFFT_LAYOUT_CYCLIC) || (out_layout != ECFFT_LAYOUT_BLOCK && out_layout != ECFFT_LAYOUT_CYCLIC)) return ECFFT_ERR_BAD_ARG;
     hipStream_t s = (hipStream_t)stream;
-    DeviceGuard dev(c->device);
-    if (!dev.ok) return ECFFT_ERR_HIP;
-    std::lock_guard<std::mutex> guard(ch.lock());
-    OpScope scope(c, s);
+    CallScope scope(c, ch.lock(), s);
     if (!scope.ok) return ECFFT_ERR_HIP;
     bool ok = false;
     switch (op) {
@@ -704,8 +711,7 @@ int wire_write(DeviceChain<F>& ch, int compress, uint8_t* buf) {
 // (the bounds-checked parse itself — cursor, canonicality check, level structure — lives in wire_parse.h: pure host C++ that
 // tests/cpp/wire_fuzz.cpp also drives under AddressSanitizer + UBSan without a GPU)
 template <class F>
-int wire_read(int field, const uint8_t* data, size_t len, int compress, int device, int verify, ecfft_ctx** out,
-              std::unique_ptr<DeviceChain<F>> ecfft_ctx::*slot) {
+int wire_read(int field, const uint8_t* data, size_t len, int compress, int device, int verify, ecfft_ctx** out) {
     using E = typename F::elem;
     const size_t eb = sizeof(E);
     static_assert(sizeof(E) == 32 || sizeof(E) == 4, "element sizes of the two fields");
@@ -726,23 +732,18 @@ int wire_read(int field, const uint8_t* data, size_t len, int compress, int devi
     ht.n = n; ht.f.assign(2 * n, F::zero());
     memcpy(ht.f.data() + n, levels[0].tbl[ECFFT_TBL_F] + n * eb, n * eb);
     ht.leaves_only = true;
-    std::unique_ptr<ecfft_ctx> c(new (std::nothrow) ecfft_ctx());
-    if (!c) return ECFFT_ERR_HIP;
-    c->field = field; c->device = device;
-    int rc = guarded([&] { return finish_build(std::move(ht), device, (*c).*slot); });
-    if (rc != ECFFT_OK) return rc;
-    {   // verify == 0 still checks the internal layers of every `f` (they follow from the leaves and the maps: cheap, and a file
+    return new_ctx<F>(field, device, out, [&](DeviceChain<F>& ch) -> int {
+        int rc = build_chain(ch, std::move(ht), device);
+        if (rc != ECFFT_OK) return rc;
+        // verify == 0 still checks the internal layers of every `f` (they follow from the leaves and the maps: cheap, and a file
         // whose layers disagree with its maps would otherwise load as a different tree than the reference's deserialize builds)
-        DeviceGuard dev(device);
-        if (!dev.ok) return ECFFT_ERR_HIP;
-        DeviceChain<F>& ch = *((*c).*slot);
         std::vector<E> got;
         for (const WireLevel& lv : levels)
             for (int which = 0; which < 11; ++which) {
                 if (!verify && which != ECFFT_TBL_F) continue;
                 if (!lv.tbl[which] && lv.cnt[which] == 0) continue;
                 got.resize(lv.cnt[which] ? lv.cnt[which] : 1);
-                rc = guarded([&] { return table_of(ch, lv.n, which, got.data(), lv.cnt[which], nullptr, true); });
+                rc = table_of(ch, lv.n, which, got.data(), lv.cnt[which], nullptr, true);
                 if (rc != ECFFT_OK) return rc;
                 const size_t skip = which == ECFFT_TBL_F ? 1 : 0;           // heap index 0 is unused (src/utils.rs:228-252)
                 if (verify && which == ECFFT_TBL_F && lv.cnt[which] > 0) {  // ... and zero in every tree the crate builds (src/fftree.rs:50, 471): a verified
@@ -755,9 +756,8 @@ int wire_read(int field, const uint8_t* data, size_t len, int compress, int devi
                     return ECFFT_ERR_BAD_ARG;
                 }
             }
-    }
-    *out = c.release();
-    return ECFFT_OK;
+        return ECFFT_OK;
+    });
 }
 }  // namespace
 
@@ -769,32 +769,8 @@ int ecfft_build_fftree(int field, size_t n, int device, ecfft_ctx** out) {
     if (!out) return ECFFT_ERR_BAD_ARG;
     *out = nullptr;
     if (!is_pow2(n)) return ECFFT_ERR_NOT_POW2;                           // assert!(n.is_power_of_two())
-    if (field != ECFFT_FIELD_SECP256K1 && field != ECFFT_FIELD_M31) return ECFFT_ERR_BAD_ARG;
-    unsigned log_n = ilog2(n);
-    // size limits first (they do not need a device): src/lib.rs:62-64, src/ec.rs:510-515
-    if (field == ECFFT_FIELD_SECP256K1 && log_n >= 36) return ECFFT_ERR_TREE_TOO_LARGE;
-    if (field == ECFFT_FIELD_M31 && log_n > 28) return ECFFT_ERR_TREE_TOO_LARGE;
-    if (!have_device(device)) return ECFFT_ERR_HIP;
-    std::unique_ptr<ecfft_ctx> c(new (std::nothrow) ecfft_ctx());
-    if (!c) return ECFFT_ERR_HIP;
-    c->field = field; c->device = device;
-    int rc;
-    if (field == ECFFT_FIELD_SECP256K1) {
-        HostTree<Secp256k1> ht;
-        int r = build_host_tree<Secp256k1>(log_n, ht, /*points=*/false);   // leaves and layers are computed on the GPU (points_on_device)
-        if (r == 1) return ECFFT_ERR_TREE_TOO_LARGE;
-        if (r) return ECFFT_ERR_BAD_ARG;
-        rc = guarded([&] { return finish_build(std::move(ht), device, c->secp); });
-    } else {
-        HostTree<M31> ht;
-        int r = build_host_tree<M31>(log_n, ht, /*points=*/false);   // leaves and layers are computed on the GPU (points_on_device)
-        if (r == 1) return ECFFT_ERR_TREE_TOO_LARGE;
-        if (r) return ECFFT_ERR_BAD_ARG;
-        rc = guarded([&] { return finish_build(std::move(ht), device, c->m31); });
-    }
-    if (rc != ECFFT_OK) return rc;
-    *out = c.release();
-    return ECFFT_OK;
+    if (!known_field(field)) return ECFFT_ERR_BAD_ARG;
+    return new_tree_ctx(field, ilog2(n), device, out, [&](auto& ch, auto&& ht) -> int { return build_chain(ch, std::move(ht), device); });
 }
 
 namespace {
@@ -803,45 +779,17 @@ int build_shard_ctx(int kind, int field, size_t len, int device, int world, int 
     if (!out) return ECFFT_ERR_BAD_ARG;
     *out = nullptr;
     if (!is_pow2(len) || !is_pow2((size_t)(world > 0 ? world : 0))) return ECFFT_ERR_NOT_POW2;
-    if (field != ECFFT_FIELD_SECP256K1 && field != ECFFT_FIELD_M31) return ECFFT_ERR_BAD_ARG;
+    if (!known_field(field)) return ECFFT_ERR_BAD_ARG;
     if (world > 64 || rank < 0 || rank >= world || (kind >= 2 && world < 2)) return ECFFT_ERR_BAD_ARG;
     if (kind == 3 && (!comm || !comm->t)) return ECFFT_ERR_BAD_ARG;
     if (len / (size_t)world < 2 * (size_t)world) return ECFFT_ERR_BAD_ARG;   // same bound as the sharded transforms
     const unsigned log_n = ilog2(len) + (kind == 1 ? 1 : 0), log_p = ilog2((size_t)world);
-    if (field == ECFFT_FIELD_SECP256K1 && log_n >= 36) return ECFFT_ERR_TREE_TOO_LARGE;
-    if (field == ECFFT_FIELD_M31 && log_n > 28) return ECFFT_ERR_TREE_TOO_LARGE;
-    if (!have_device(device)) return ECFFT_ERR_HIP;
-    std::unique_ptr<ecfft_ctx> c(new (std::nothrow) ecfft_ctx());
-    if (!c) return ECFFT_ERR_HIP;
-    c->field = field; c->device = device;
-    auto finish = [&](auto&& ht, auto& slot) {
-        using Chain = typename std::remove_reference<decltype(*slot)>::type;
-        slot.reset(new (std::nothrow) Chain());
-        if (!slot) return (int)ECFFT_ERR_HIP;
-        DeviceGuard dev(device);
-        if (!dev.ok) return (int)ECFFT_ERR_HIP;
-        const bool ok = kind == 1 ? slot->build_extend_shard(std::move(ht), device, log_p, (unsigned)rank)
-                      : kind == 2 ? slot->build_enter_shard(std::move(ht), device, log_p, (unsigned)rank)
-                                  : slot->build_exit_shard(std::move(ht), device, *comm->t, (flags & ECFFT_EXIT_SHARD_MIN_MEMORY) != 0);
-        return ok ? (int)ECFFT_OK : (int)ECFFT_ERR_HIP;
-    };
-    int rc;
-    if (field == ECFFT_FIELD_SECP256K1) {
-        HostTree<Secp256k1> ht;
-        int r = build_host_tree<Secp256k1>(log_n, ht, /*points=*/false);   // leaves and layers are computed on the GPU (points_on_device)
-        if (r == 1) return ECFFT_ERR_TREE_TOO_LARGE;
-        if (r) return ECFFT_ERR_BAD_ARG;
-        rc = guarded([&] { return finish(std::move(ht), c->secp); });
-    } else {
-        HostTree<M31> ht;
-        int r = build_host_tree<M31>(log_n, ht, /*points=*/false);   // leaves and layers are computed on the GPU (points_on_device)
-        if (r == 1) return ECFFT_ERR_TREE_TOO_LARGE;
-        if (r) return ECFFT_ERR_BAD_ARG;
-        rc = guarded([&] { return finish(std::move(ht), c->m31); });
-    }
-    if (rc != ECFFT_OK) return rc;
-    *out = c.release();
-    return ECFFT_OK;
+    return new_tree_ctx(field, log_n, device, out, [&](auto& ch, auto&& ht) -> int {
+        const bool ok = kind == 1 ? ch.build_extend_shard(std::move(ht), device, log_p, (unsigned)rank)
+                      : kind == 2 ? ch.build_enter_shard(std::move(ht), device, log_p, (unsigned)rank)
+                                  : ch.build_exit_shard(std::move(ht), device, *comm->t, (flags & ECFFT_EXIT_SHARD_MIN_MEMORY) != 0);
+        return ok ? ECFFT_OK : ECFFT_ERR_HIP;
+    });
 }
 }  // namespace
 int ecfft_build_extend_shard(int field, size_t e, int device, int world, int rank, ecfft_ctx** out) { return build_shard_ctx(1, field, e, device, world, rank, out); }
@@ -860,70 +808,40 @@ int ecfft_fftree_new(int field, const void* leaves, size_t n, const void* map_nu
     *out = nullptr;
     if (!leaves || (n > 1 && (!map_num3 || !map_den3))) return ECFFT_ERR_BAD_ARG;
     if (!is_pow2(n)) return ECFFT_ERR_NOT_POW2;
-    if (field != ECFFT_FIELD_SECP256K1 && field != ECFFT_FIELD_M31) return ECFFT_ERR_BAD_ARG;
+    if (!known_field(field)) return ECFFT_ERR_BAD_ARG;
     if (!have_device(device)) return ECFFT_ERR_HIP;
-    unsigned log_n = ilog2(n);
-    std::unique_ptr<ecfft_ctx> c(new (std::nothrow) ecfft_ctx());
-    if (!c) return ECFFT_ERR_HIP;
-    c->field = field; c->device = device;
-    int rc;
-    if (field == ECFFT_FIELD_SECP256K1) {
-        HostTree<Secp256k1> ht; ht.n = n; ht.f.assign(2 * n, Secp256k1::zero()); ht.maps.resize(log_n);
-        memcpy(ht.f.data() + n, leaves, n * 32);
-        secp_from_mont_host(ht.f.data() + n, n);
+    const unsigned log_n = ilog2(n);
+    return with_field(field, [&](auto tag) -> int {
+        using F = typename decltype(tag)::type;
+        using E = typename F::elem;
+        HostTree<F> ht; ht.n = n; ht.f.assign(2 * n, F::zero()); ht.maps.resize(log_n);
+        memcpy(ht.f.data() + n, leaves, n * sizeof(E));
+        from_crate_host<F>(ht.f.data() + n, n);
         for (unsigned k = 0; k < log_n; ++k) {
-            memcpy(ht.maps[k].num, (const char*)map_num3 + 96 * k, 96); memcpy(ht.maps[k].den, (const char*)map_den3 + 96 * k, 96);
-            secp_from_mont_host(ht.maps[k].num, 3); secp_from_mont_host(ht.maps[k].den, 3);
-            if (!Secp256k1::is_zero(ht.maps[k].den[2])) return ECFFT_ERR_BAD_ARG;   // x-map denominators have degree 1
+            RatMap<F>& m = ht.maps[k];
+            memcpy(m.num, (const E*)map_num3 + 3 * k, sizeof(m.num)); memcpy(m.den, (const E*)map_den3 + 3 * k, sizeof(m.den));
+            from_crate_host<F>(m.num, 3); from_crate_host<F>(m.den, 3);
+            if (!F::is_zero(m.den[2])) return ECFFT_ERR_BAD_ARG;           // x-map denominators have degree 1
         }
-        ht.leaves_only = true;                                     // the layers psi_k(L_k) are computed on the GPU (points_on_device)
-        rc = guarded([&] { return finish_build(std::move(ht), device, c->secp); });
-    } else {
-        HostTree<M31> ht; ht.n = n; ht.f.assign(2 * n, 0); ht.maps.resize(log_n);
-        memcpy(ht.f.data() + n, leaves, n * 4);
-        for (unsigned k = 0; k < log_n; ++k) {
-            memcpy(ht.maps[k].num, (const char*)map_num3 + 12 * k, 12); memcpy(ht.maps[k].den, (const char*)map_den3 + 12 * k, 12);
-            if (ht.maps[k].den[2] != 0) return ECFFT_ERR_BAD_ARG;
-        }
-        ht.leaves_only = true;
-        rc = guarded([&] { return finish_build(std::move(ht), device, c->m31); });
-    }
-    if (rc != ECFFT_OK) return rc;
-    *out = c.release();
-    return ECFFT_OK;
+        ht.leaves_only = true;                                         // the layers psi_k(L_k) are computed on the GPU (points_on_device)
+        return new_ctx<F>(field, device, out, [&](DeviceChain<F>& ch) -> int { return build_chain(ch, std::move(ht), device); });
+    });
 }
 
 int ecfft_build_points(int field, size_t n, void* f_out, void* map_num3_out, void* map_den3_out) {
     if (!f_out) return ECFFT_ERR_BAD_ARG;
     if (!is_pow2(n)) return ECFFT_ERR_NOT_POW2;
     unsigned log_n = ilog2(n);
-    if (field == ECFFT_FIELD_SECP256K1) {
-        HostTree<Secp256k1> ht;
-        int r = build_host_tree<Secp256k1>(log_n, ht);
-        if (r == 1) return ECFFT_ERR_TREE_TOO_LARGE;
-        if (r) return ECFFT_ERR_BAD_ARG;
-        secp_to_mont_host(ht.f.data(), 2 * n);
-        memcpy(f_out, ht.f.data(), 2 * n * 32);
-        for (unsigned k = 0; k < log_n; ++k) {
-            secp_to_mont_host(ht.maps[k].num, 3); secp_to_mont_host(ht.maps[k].den, 3);
-            if (map_num3_out) memcpy((char*)map_num3_out + 96 * k, ht.maps[k].num, 96);
-            if (map_den3_out) memcpy((char*)map_den3_out + 96 * k, ht.maps[k].den, 96);
-        }
+    return with_field(field, [&](auto tag) -> int {
+        using F = typename decltype(tag)::type;
+        HostTree<F> ht;
+        int r = build_host_tree<F>(log_n, ht);
+        if (r) return r == 1 ? ECFFT_ERR_TREE_TOO_LARGE : ECFFT_ERR_BAD_ARG;
+        to_crate_host<F>(ht.f.data(), 2 * n);
+        memcpy(f_out, ht.f.data(), 2 * n * sizeof(typename F::elem));
+        maps_out(ht.maps, map_num3_out, map_den3_out);
         return ECFFT_OK;
-    }
-    if (field == ECFFT_FIELD_M31) {
-        HostTree<M31> ht;
-        int r = build_host_tree<M31>(log_n, ht);
-        if (r == 1) return ECFFT_ERR_TREE_TOO_LARGE;
-        if (r) return ECFFT_ERR_BAD_ARG;
-        memcpy(f_out, ht.f.data(), 2 * n * 4);
-        for (unsigned k = 0; k < log_n; ++k) {
-            if (map_num3_out) memcpy((char*)map_num3_out + 12 * k, ht.maps[k].num, 12);
-            if (map_den3_out) memcpy((char*)map_den3_out + 12 * k, ht.maps[k].den, 12);
-        }
-        return ECFFT_OK;
-    }
-    return ECFFT_ERR_BAD_ARG;
+    });
 }
 
 void ecfft_ctx_destroy(ecfft_ctx* ctx) {
@@ -934,24 +852,23 @@ void ecfft_ctx_destroy(ecfft_ctx* ctx) {
 
 size_t ecfft_tree_size(const ecfft_ctx* ctx) {
     if (!ctx) return 0;
-    return ctx->field == ECFFT_FIELD_SECP256K1 ? ctx->secp->size() : ctx->m31->size();
+    return with_chain(ctx, [](auto& ch) { return ch.size(); });
 }
 int ecfft_field(const ecfft_ctx* ctx) { return ctx ? ctx->field : -1; }
 #ifdef ECFFT_TEST_HOOKS
 long ecfft_selfcheck_pointwise_z(ecfft_ctx* ctx, size_t m) {
     if (!ctx || !is_pow2(m)) return -1;
     return guarded([&] {
-        DeviceGuard dev(ctx->device);
-        if (!dev.ok) return -1;
-        std::lock_guard<std::mutex> guard(ctx->field == ECFFT_FIELD_SECP256K1 ? ctx->secp->lock() : ctx->m31->lock());
-        OpScope scope(ctx, nullptr);                              // its pooled temporaries may still be in use by the previous asynchronous call
-        if (!scope.ok) return -1;
-        return (int)(ctx->field == ECFFT_FIELD_SECP256K1 ? ctx->secp->selfcheck_pointwise_z(m) : ctx->m31->selfcheck_pointwise_z(m));
+        return with_chain(ctx, [&](auto& ch) -> int {
+            CallScope scope(ctx, ch.lock(), nullptr);                 // its pooled temporaries may still be in use by the previous asynchronous call
+            if (!scope.ok) return -1;
+            return (int)ch.selfcheck_pointwise_z(m);
+        });
     });
 }
 int ecfft_test_fail_next_collective(ecfft_ctx* ctx) {
     if (!ctx) return ECFFT_ERR_BAD_ARG;
-    if (ctx->field == ECFFT_FIELD_SECP256K1) ctx->secp->test_fail_next_collective(); else ctx->m31->test_fail_next_collective();
+    with_chain(ctx, [](auto& ch) { ch.test_fail_next_collective(); });
     return ECFFT_OK;
 }
 int ecfft_test_fail_build_rank(int rank) {
@@ -966,92 +883,69 @@ int ecfft_ctx_trim(ecfft_ctx* ctx) {
     if (!dev.ok) return ECFFT_ERR_HIP;
     // the staging buffer is used under the chain lock by every host-memory call: it is freed under that lock too
     auto free_stage = [ctx] { if (ctx->stage) { (void)hipFree(ctx->stage); ctx->stage = nullptr; ctx->stage_bytes = 0; } };
-    if (ctx->field == ECFFT_FIELD_SECP256K1) ctx->secp->trim(free_stage); else ctx->m31->trim(free_stage);
+    with_chain(ctx, [&](auto& ch) { ch.trim(free_stage); });
     return ECFFT_OK;
 }
 size_t ecfft_ctx_device_bytes(const ecfft_ctx* ctx) {
     if (!ctx) return 0;
-    return ctx->field == ECFFT_FIELD_SECP256K1 ? ctx->secp->device_bytes() : ctx->m31->device_bytes();
+    return with_chain(ctx, [](auto& ch) { return ch.device_bytes(); });
 }
 
 int ecfft_enter(ecfft_ctx* ctx, const void* coeffs, void* evals, size_t n, int mem, void* stream) {
-    if (!ctx || shard_only(ctx)) return ECFFT_ERR_BAD_ARG;
-    return guarded([&] { return ctx->field == ECFFT_FIELD_SECP256K1 ? run_op(ctx, *ctx->secp, OP_ENTER, coeffs, evals, n, 1, 0, mem, stream)
-                                               : run_op(ctx, *ctx->m31, OP_ENTER, coeffs, evals, n, 1, 0, mem, stream); });
+    return on_chain(ctx, [&](auto& ch) { return run_op(ctx, ch, OP_ENTER, coeffs, evals, n, 1, 0, mem, stream); });
 }
 int ecfft_exit(ecfft_ctx* ctx, const void* evals, void* coeffs, size_t n, int mem, void* stream) {
-    if (!ctx || shard_only(ctx)) return ECFFT_ERR_BAD_ARG;
-    return guarded([&] { return ctx->field == ECFFT_FIELD_SECP256K1 ? run_op(ctx, *ctx->secp, OP_EXIT, evals, coeffs, n, 1, 0, mem, stream)
-                                               : run_op(ctx, *ctx->m31, OP_EXIT, evals, coeffs, n, 1, 0, mem, stream); });
+    return on_chain(ctx, [&](auto& ch) { return run_op(ctx, ch, OP_EXIT, evals, coeffs, n, 1, 0, mem, stream); });
 }
 int ecfft_enter_many(ecfft_ctx* ctx, const void* coeffs, void* evals, size_t n, size_t count, int mem, void* stream) {
-    if (!ctx || shard_only(ctx)) return ECFFT_ERR_BAD_ARG;
-    return guarded([&] { return ctx->field == ECFFT_FIELD_SECP256K1 ? run_op(ctx, *ctx->secp, OP_ENTER, coeffs, evals, n, count, 0, mem, stream)
-                                               : run_op(ctx, *ctx->m31, OP_ENTER, coeffs, evals, n, count, 0, mem, stream); });
+    return on_chain(ctx, [&](auto& ch) { return run_op(ctx, ch, OP_ENTER, coeffs, evals, n, count, 0, mem, stream); });
 }
 int ecfft_exit_many(ecfft_ctx* ctx, const void* evals, void* coeffs, size_t n, size_t count, int mem, void* stream) {
-    if (!ctx || shard_only(ctx)) return ECFFT_ERR_BAD_ARG;
-    return guarded([&] { return ctx->field == ECFFT_FIELD_SECP256K1 ? run_op(ctx, *ctx->secp, OP_EXIT, evals, coeffs, n, count, 0, mem, stream)
-                                               : run_op(ctx, *ctx->m31, OP_EXIT, evals, coeffs, n, count, 0, mem, stream); });
+    return on_chain(ctx, [&](auto& ch) { return run_op(ctx, ch, OP_EXIT, evals, coeffs, n, count, 0, mem, stream); });
 }
 int ecfft_extend(ecfft_ctx* ctx, const void* in, void* out, size_t e, int moiety, size_t count, int mem, void* stream) {
-    if (!ctx || shard_only(ctx)) return ECFFT_ERR_BAD_ARG;
-    return guarded([&] { return ctx->field == ECFFT_FIELD_SECP256K1 ? run_op(ctx, *ctx->secp, OP_EXTEND, in, out, e, count, moiety, mem, stream)
-                                               : run_op(ctx, *ctx->m31, OP_EXTEND, in, out, e, count, moiety, mem, stream); });
+    return on_chain(ctx, [&](auto& ch) { return run_op(ctx, ch, OP_EXTEND, in, out, e, count, moiety, mem, stream); });
 }
 
 int ecfft_poly_mul(ecfft_ctx* ctx, const void* a, size_t na, const void* b, size_t nb, void* out, size_t count, int mem, void* stream) {
-    if (!ctx || shard_only(ctx) || na == 0 || nb == 0 || count == 0) return ECFFT_ERR_BAD_ARG;
-    return guarded([&] { return ctx->field == ECFFT_FIELD_SECP256K1 ? run_poly_mul(ctx, *ctx->secp, a, na, b, nb, out, count, mem, stream)
-                                               : run_poly_mul(ctx, *ctx->m31, a, na, b, nb, out, count, mem, stream); });
+    if (na == 0 || nb == 0 || count == 0) return ECFFT_ERR_BAD_ARG;
+    return on_chain(ctx, [&](auto& ch) { return run_poly_mul(ctx, ch, a, na, b, nb, out, count, mem, stream); });
 }
 int ecfft_poly_inv_series(ecfft_ctx* ctx, const void* f, size_t nf, void* out, size_t k, size_t count, int mem, void* stream) {
-    if (!ctx || shard_only(ctx) || nf == 0 || k == 0 || count == 0) return ECFFT_ERR_BAD_ARG;
-    return guarded([&] { return ctx->field == ECFFT_FIELD_SECP256K1 ? run_inv_series(ctx, *ctx->secp, f, nf, out, k, count, mem, stream)
-                                               : run_inv_series(ctx, *ctx->m31, f, nf, out, k, count, mem, stream); });
+    if (nf == 0 || k == 0 || count == 0) return ECFFT_ERR_BAD_ARG;
+    return on_chain(ctx, [&](auto& ch) { return run_inv_series(ctx, ch, f, nf, out, k, count, mem, stream); });
 }
 int ecfft_poly_divrem(ecfft_ctx* ctx, const void* a, size_t na, const void* b, size_t nb, void* q, void* r, size_t count, int mem, void* stream) {
-    if (!ctx || shard_only(ctx) || na == 0 || nb == 0 || count == 0) return ECFFT_ERR_BAD_ARG;
-    return guarded([&] { return ctx->field == ECFFT_FIELD_SECP256K1 ? run_poly_divrem(ctx, *ctx->secp, a, na, b, nb, q, r, count, mem, stream)
-                                               : run_poly_divrem(ctx, *ctx->m31, a, na, b, nb, q, r, count, mem, stream); });
+    if (na == 0 || nb == 0 || count == 0) return ECFFT_ERR_BAD_ARG;
+    return on_chain(ctx, [&](auto& ch) { return run_poly_divrem(ctx, ch, a, na, b, nb, q, r, count, mem, stream); });
 }
 int ecfft_poly_eval_points(ecfft_ctx* ctx, const void* f, size_t nf, const void* points, size_t m, void* out, size_t count, int mem,
                            void* stream) {
-    if (!ctx || shard_only(ctx) || nf == 0 || m == 0 || count == 0) return ECFFT_ERR_BAD_ARG;
-    return guarded([&] { return ctx->field == ECFFT_FIELD_SECP256K1 ? run_poly_eval_points(ctx, *ctx->secp, f, nf, points, m, out, count, mem, stream)
-                                               : run_poly_eval_points(ctx, *ctx->m31, f, nf, points, m, out, count, mem, stream); });
+    if (nf == 0 || m == 0 || count == 0) return ECFFT_ERR_BAD_ARG;
+    return on_chain(ctx, [&](auto& ch) { return run_poly_eval_points(ctx, ch, f, nf, points, m, out, count, mem, stream); });
 }
 
 int ecfft_extend_top_cyclic(ecfft_ctx* ctx, void* buf, size_t e, int moiety, unsigned log_p, unsigned rank, int recombine, int mem, void* stream) {
-    if (!ctx || shard_only(ctx)) return ECFFT_ERR_BAD_ARG;
-    return guarded([&] { return ctx->field == ECFFT_FIELD_SECP256K1 ? run_shard(ctx, *ctx->secp, buf, e, moiety, log_p, rank, recombine ? 1 : 0, mem, stream)
-                                               : run_shard(ctx, *ctx->m31, buf, e, moiety, log_p, rank, recombine ? 1 : 0, mem, stream); });
+    return on_chain(ctx, [&](auto& ch) { return run_shard(ctx, ch, buf, e, moiety, log_p, rank, recombine ? 1 : 0, mem, stream); });
 }
 int ecfft_extend_local_block(ecfft_ctx* ctx, void* buf, size_t e, int moiety, unsigned log_p, int mem, void* stream) {
-    if (!ctx || shard_only(ctx)) return ECFFT_ERR_BAD_ARG;
-    return guarded([&] { return ctx->field == ECFFT_FIELD_SECP256K1 ? run_shard(ctx, *ctx->secp, buf, e, moiety, log_p, 0, 2, mem, stream)
-                                               : run_shard(ctx, *ctx->m31, buf, e, moiety, log_p, 0, 2, mem, stream); });
+    return on_chain(ctx, [&](auto& ch) { return run_shard(ctx, ch, buf, e, moiety, log_p, 0, 2, mem, stream); });
 }
 
 int ecfft_mextend(ecfft_ctx* ctx, const void* in, void* out, size_t e, int moiety, size_t count, int mem, void* stream) {
-    if (!ctx || shard_only(ctx)) return ECFFT_ERR_BAD_ARG;
-    return guarded([&] { return ECFFT_DISPATCH_ALG(ALG_MEXTEND, in, nullptr, nullptr, out, e, count, moiety, mem, stream, nullptr); });
+    return on_chain(ctx, [&](auto& ch) { return run_alg(ctx, ch, ALG_MEXTEND, in, nullptr, nullptr, out, e, count, moiety, mem, stream, nullptr); });
 }
 int ecfft_redc(ecfft_ctx* ctx, const void* evals, const void* a, void* out, size_t n, int moiety, int mem, void* stream) {
-    if (!ctx || shard_only(ctx)) return ECFFT_ERR_BAD_ARG;
-    return guarded([&] { return ECFFT_DISPATCH_ALG(ALG_REDC, evals, a, nullptr, out, n, 1, moiety, mem, stream, nullptr); });
+    return on_chain(ctx, [&](auto& ch) { return run_alg(ctx, ch, ALG_REDC, evals, a, nullptr, out, n, 1, moiety, mem, stream, nullptr); });
 }
 int ecfft_modular_reduce(ecfft_ctx* ctx, const void* evals, const void* a, const void* c, void* out, size_t n, int mem, void* stream) {
-    if (!ctx || shard_only(ctx)) return ECFFT_ERR_BAD_ARG;
-    return guarded([&] { return ECFFT_DISPATCH_ALG(ALG_MOD, evals, a, c, out, n, 1, 0, mem, stream, nullptr); });
+    return on_chain(ctx, [&](auto& ch) { return run_alg(ctx, ch, ALG_MOD, evals, a, c, out, n, 1, 0, mem, stream, nullptr); });
 }
 int ecfft_vanish(ecfft_ctx* ctx, const void* domain, void* out, size_t nd, int mem, void* stream) {
-    if (!ctx || shard_only(ctx)) return ECFFT_ERR_BAD_ARG;
-    return guarded([&] { return ECFFT_DISPATCH_ALG(ALG_VANISH, domain, nullptr, nullptr, out, nd, 1, 0, mem, stream, nullptr); });
+    return on_chain(ctx, [&](auto& ch) { return run_alg(ctx, ch, ALG_VANISH, domain, nullptr, nullptr, out, nd, 1, 0, mem, stream, nullptr); });
 }
 int ecfft_degree(ecfft_ctx* ctx, const void* evals, size_t n, int mem, void* stream, size_t* degree) {
-    if (!ctx || shard_only(ctx)) return ECFFT_ERR_BAD_ARG;
-    return guarded([&] { return ECFFT_DISPATCH_ALG(ALG_DEGREE, evals, nullptr, nullptr, nullptr, n, 1, 0, mem, stream, degree); });
+    return on_chain(ctx, [&](auto& ch) { return run_alg(ctx, ch, ALG_DEGREE, evals, nullptr, nullptr, nullptr, n, 1, 0, mem, stream, degree); });
 }
 
 // ---- one transform split over several GPUs -------------------------------------------------------------------------
@@ -1140,32 +1034,23 @@ int ecfft_comm_stats_read(ecfft_comm* comm, double* comm_ms, double* exchanges, 
 }
 
 
+
 int ecfft_extend_sharded(ecfft_ctx* ctx, ecfft_comm* comm, const void* in, void* out, size_t e, int moiety, void* stream) {
-    if (!ctx) return ECFFT_ERR_BAD_ARG;
-    return guarded([&] { return ctx->field == ECFFT_FIELD_SECP256K1 ? run_sharded(ctx, *ctx->secp, comm, OP_EXTEND, in, out, e, moiety, stream)
-                                                                    : run_sharded(ctx, *ctx->m31, comm, OP_EXTEND, in, out, e, moiety, stream); });
+    return on_chain(ctx, [&](auto& ch) { return run_sharded(ctx, ch, comm, OP_EXTEND, in, out, e, moiety, stream); }, true);
 }
 int ecfft_extend_sharded_layout(ecfft_ctx* ctx, ecfft_comm* comm, const void* in, void* out, size_t e, int moiety, int in_layout, int out_layout, void* stream) {
-    if (!ctx) return ECFFT_ERR_BAD_ARG;
-    return guarded([&] { return ctx->field == ECFFT_FIELD_SECP256K1 ? run_sharded(ctx, *ctx->secp, comm, OP_EXTEND, in, out, e, moiety, stream, in_layout, out_layout)
-                                                                    : run_sharded(ctx, *ctx->m31, comm, OP_EXTEND, in, out, e, moiety, stream, in_layout, out_layout); });
+    return on_chain(ctx, [&](auto& ch) { return run_sharded(ctx, ch, comm, OP_EXTEND, in, out, e, moiety, stream, in_layout, out_layout); }, true);
 }
 int ecfft_enter_sharded(ecfft_ctx* ctx, ecfft_comm* comm, const void* coeffs, void* evals, size_t n, void* stream) {
-    if (!ctx) return ECFFT_ERR_BAD_ARG;
-    return guarded([&] { return ctx->field == ECFFT_FIELD_SECP256K1 ? run_sharded(ctx, *ctx->secp, comm, OP_ENTER, coeffs, evals, n, 0, stream)
-                                                                    : run_sharded(ctx, *ctx->m31, comm, OP_ENTER, coeffs, evals, n, 0, stream); });
+    return on_chain(ctx, [&](auto& ch) { return run_sharded(ctx, ch, comm, OP_ENTER, coeffs, evals, n, 0, stream); }, true);
 }
 int ecfft_exit_sharded(ecfft_ctx* ctx, ecfft_comm* comm, const void* evals, void* coeffs, size_t n, void* stream) {
-    if (!ctx) return ECFFT_ERR_BAD_ARG;
-    return guarded([&] { return ctx->field == ECFFT_FIELD_SECP256K1 ? run_sharded(ctx, *ctx->secp, comm, OP_EXIT, evals, coeffs, n, 0, stream)
-                                                                    : run_sharded(ctx, *ctx->m31, comm, OP_EXIT, evals, coeffs, n, 0, stream); });
+    return on_chain(ctx, [&](auto& ch) { return run_sharded(ctx, ch, comm, OP_EXIT, evals, coeffs, n, 0, stream); }, true);
 }
 
 int ecfft_table_fma(ecfft_ctx* ctx, void* out, const void* x, const void* y, size_t cnt, size_t m, int which, size_t t_off,
                     size_t t_stride, int mode, int mem, void* stream) {
-    if (!ctx || shard_only(ctx)) return ECFFT_ERR_BAD_ARG;
-    return guarded([&] { return ctx->field == ECFFT_FIELD_SECP256K1 ? run_table_fma(ctx, *ctx->secp, out, x, y, cnt, m, which, t_off, t_stride, mode, mem, stream)
-                                               : run_table_fma(ctx, *ctx->m31, out, x, y, cnt, m, which, t_off, t_stride, mode, mem, stream); });
+    return on_chain(ctx, [&](auto& ch) { return run_table_fma(ctx, ch, out, x, y, cnt, m, which, t_off, t_stride, mode, mem, stream); });
 }
 
 int ecfft_tree_table(ecfft_ctx* ctx, size_t m, int which, void* host_out, size_t cap, size_t* count) {
@@ -1174,13 +1059,12 @@ int ecfft_tree_table(ecfft_ctx* ctx, size_t m, int which, void* host_out, size_t
     if (!dev.ok) return ECFFT_ERR_HIP;
     // reads immutable tables only (its device temporaries are its own hipMalloc blocks, not the pool): no ordering against
     // transform calls in flight is needed
-    return guarded([&] { return ctx->field == ECFFT_FIELD_SECP256K1 ? table_of(*ctx->secp, m, which, host_out, cap, count)
-                                                                    : table_of(*ctx->m31, m, which, host_out, cap, count); });
+    return guarded([&] { return with_chain(ctx, [&](auto& ch) { return table_of(ch, m, which, host_out, cap, count); }); });
 }
 
 int ecfft_profile_enable(ecfft_ctx* ctx, int on) {
     if (!ctx) return ECFFT_ERR_BAD_ARG;
-    Profiler& p = ctx->field == ECFFT_FIELD_SECP256K1 ? ctx->secp->profiler() : ctx->m31->profiler();
+    Profiler& p = with_chain(ctx, [](auto& ch) -> Profiler& { return ch.profiler(); });
     DeviceGuard dev(ctx->device);
     if (!dev.ok || hipDeviceSynchronize() != hipSuccess) return ECFFT_ERR_HIP;
     p.reset(); p.on = on != 0;
@@ -1190,7 +1074,7 @@ int ecfft_profile_classes(void) { return KC_COUNT; }
 int ecfft_profile_read(ecfft_ctx* ctx, int cls, char* name, size_t cap, uint64_t* launches, double* ms_total,
                        double* alg_bytes_total) {
     if (!ctx || cls < 0 || cls >= KC_COUNT) return ECFFT_ERR_BAD_ARG;
-    Profiler& p = ctx->field == ECFFT_FIELD_SECP256K1 ? ctx->secp->profiler() : ctx->m31->profiler();
+    Profiler& p = with_chain(ctx, [](auto& ch) -> Profiler& { return ch.profiler(); });
     DeviceGuard dev(ctx->device);
     if (!dev.ok || hipDeviceSynchronize() != hipSuccess) return ECFFT_ERR_HIP;
     p.collect();
@@ -1203,130 +1087,77 @@ int ecfft_profile_read(ecfft_ctx* ctx, int cls, char* name, size_t cap, uint64_t
 
 int ecfft_tree_rational_maps(ecfft_ctx* ctx, void* map_num3_out, void* map_den3_out) {
     if (!ctx || shard_only(ctx)) return ECFFT_ERR_BAD_ARG;
-    if (ctx->field == ECFFT_FIELD_SECP256K1) {
-        const auto& maps = ctx->secp->host().maps;
-        for (size_t k = 0; k < maps.size(); ++k) {
-            RatMap<Secp256k1> m = maps[k];
-            secp_to_mont_host(m.num, 3); secp_to_mont_host(m.den, 3);
-            if (map_num3_out) memcpy((char*)map_num3_out + 96 * k, m.num, 96);
-            if (map_den3_out) memcpy((char*)map_den3_out + 96 * k, m.den, 96);
-        }
-    } else {
-        const auto& maps = ctx->m31->host().maps;
-        for (size_t k = 0; k < maps.size(); ++k) {
-            if (map_num3_out) memcpy((char*)map_num3_out + 12 * k, maps[k].num, 12);
-            if (map_den3_out) memcpy((char*)map_den3_out + 12 * k, maps[k].den, 12);
-        }
-    }
+    with_chain(ctx, [&](auto& ch) { maps_out(ch.host().maps, map_num3_out, map_den3_out); });
     return ECFFT_OK;
 }
 
 int ecfft_fftree_serialize(ecfft_ctx* ctx, int compress, void* buf, size_t cap, size_t* len) {
     if (!ctx || shard_only(ctx)) return ECFFT_ERR_BAD_ARG;
-    const size_t need = ctx->field == ECFFT_FIELD_SECP256K1 ? wire_size(*ctx->secp, compress) : wire_size(*ctx->m31, compress);
+    const size_t need = with_chain(ctx, [&](auto& ch) { return wire_size(ch, compress); });
     if (len) *len = need;
     if (!buf) return ECFFT_OK;
     if (cap < need) return ECFFT_ERR_BAD_ARG;
     DeviceGuard dev(ctx->device);
     if (!dev.ok) return ECFFT_ERR_HIP;
-    return guarded([&] { return ctx->field == ECFFT_FIELD_SECP256K1 ? wire_write(*ctx->secp, compress, (uint8_t*)buf)
-                                                                    : wire_write(*ctx->m31, compress, (uint8_t*)buf); });
+    return guarded([&] { return with_chain(ctx, [&](auto& ch) { return wire_write(ch, compress, (uint8_t*)buf); }); });
 }
 
 int ecfft_fftree_deserialize(int field, const void* bytes, size_t len, int compress, int device, int verify, ecfft_ctx** out) {
     if (!out) return ECFFT_ERR_BAD_ARG;
     *out = nullptr;
     if (!bytes) return ECFFT_ERR_BAD_ARG;
-    if (field != ECFFT_FIELD_SECP256K1 && field != ECFFT_FIELD_M31) return ECFFT_ERR_BAD_ARG;
+    if (!known_field(field)) return ECFFT_ERR_BAD_ARG;
     if (!have_device(device)) return ECFFT_ERR_HIP;
-    return guarded([&] { return field == ECFFT_FIELD_SECP256K1
-        ? wire_read<Secp256k1>(field, (const uint8_t*)bytes, len, compress, device, verify, out, &ecfft_ctx::secp)
-        : wire_read<M31>(field, (const uint8_t*)bytes, len, compress, device, verify, out, &ecfft_ctx::m31); });
+    return guarded([&] {
+        return with_field(field, [&](auto tag) {
+            return wire_read<typename decltype(tag)::type>(field, (const uint8_t*)bytes, len, compress, device, verify, out);
+        });
+    });
 }
 
-int ecfft_elems_to_standard(int field, const void* in, void* out, size_t n) {
-    if (!in || !out) return ECFFT_ERR_BAD_ARG;
-    if (field == ECFFT_FIELD_M31) { if (in != out) memmove(out, in, n * 4); return ECFFT_OK; }
-    if (field != ECFFT_FIELD_SECP256K1) return ECFFT_ERR_BAD_ARG;
-    if (in != out) memmove(out, in, n * 32);
-    secp_from_mont_host((Fe256*)out, n);
-    return ECFFT_OK;
-}
-int ecfft_elems_from_standard(int field, const void* in, void* out, size_t n) {
-    if (!in || !out) return ECFFT_ERR_BAD_ARG;
-    if (field == ECFFT_FIELD_M31) { if (in != out) memmove(out, in, n * 4); return ECFFT_OK; }
-    if (field != ECFFT_FIELD_SECP256K1) return ECFFT_ERR_BAD_ARG;
-    if (in != out) memmove(out, in, n * 32);
-    secp_to_mont_host((Fe256*)out, n);
-    return ECFFT_OK;
-}
+int ecfft_elems_to_standard(int field, const void* in, void* out, size_t n) { return convert_elems(field, in, out, n, true); }
+int ecfft_elems_from_standard(int field, const void* in, void* out, size_t n) { return convert_elems(field, in, out, n, false); }
 
 #ifdef ECFFT_TEST_HOOKS
 int ecfft_selftest_field(int field, int op, const void* a, const void* b, const void* c, void* out, size_t n, int device) {
-    if (field == ECFFT_FIELD_SECP256K1) return run_selftest<Secp256k1>(op, a, b, c, out, n, device);
-    if (field == ECFFT_FIELD_M31) return run_selftest<M31>(op, a, b, c, out, n, device);
-    return ECFFT_ERR_BAD_ARG;
+    return with_field(field, [&](auto tag) { return run_selftest<typename decltype(tag)::type>(op, a, b, c, out, n, device); });
 }
 
-int ecfft_selftest_blk16(const void* matrix256, const void* x, void* out, size_t n, int device) {
-    if (!matrix256 || !x || !out || !n || n % Blk16::kSub) return ECFFT_ERR_BAD_ARG;
-    if (!have_device(device)) return ECFFT_ERR_HIP;
-    DeviceGuard dev(device);
-    if (!dev.ok) return ECFFT_ERR_HIP;
-    Fe256 *dT = nullptr, *dx = nullptr; uint8_t* dA = nullptr;
-    bool ok = hipMalloc(&dT, 256 * sizeof(Fe256)) == hipSuccess && hipMalloc(&dx, n * sizeof(Fe256)) == hipSuccess &&
-              hipMalloc(&dA, Blk16::kABytes + Blk16::kKWords * 8) == hipSuccess;
-    ok = ok && hipMemcpy(dT, matrix256, 256 * sizeof(Fe256), hipMemcpyHostToDevice) == hipSuccess && hipMemcpy(dx, x, n * sizeof(Fe256), hipMemcpyHostToDevice) == hipSuccess;
-    if (ok) {
+}  // extern "C"
+namespace {
+// mode 0: k_blk16_apply, 1..4: k_blk16_apply_n16<mode>
+int run_blk16_selftest(const void* matrix256, const void* x, void* out, size_t n, int mode, int device) {
+    return run_blk_selftest(matrix256, 256, x, out, n, Blk16::kABytes + Blk16::kKWords * 8, 0, device, [&](Fe256* dT, Fe256* dx, uint8_t* dA, Fe256*) {
         unsigned long long* dK = reinterpret_cast<unsigned long long*>(dA + Blk16::kABytes);
         hipLaunchKernelGGL(k_blk16_from_matrix, dim3(1), dim3(256), 0, nullptr, dT, dA, dK, false);
-        hipLaunchKernelGGL(k_blk16_apply, dim3((unsigned)(n / Blk16::kSub)), dim3(512), 0, nullptr, dx, dA, dK);
-        ok = hipDeviceSynchronize() == hipSuccess && hipMemcpy(out, dx, n * sizeof(Fe256), hipMemcpyDeviceToHost) == hipSuccess;
-    }
-    (void)hipFree(dT); (void)hipFree(dx); (void)hipFree(dA);
-    return ok ? ECFFT_OK : ECFFT_ERR_HIP;
-}
-
-int ecfft_selftest_blk16_small(const void* matrix256, const void* x, void* out, size_t n, int mode, int device) {
-    if (!matrix256 || !x || !out || !n || n % 256 || mode < 1 || mode > 4) return ECFFT_ERR_BAD_ARG;
-    if (!have_device(device)) return ECFFT_ERR_HIP;
-    DeviceGuard dev(device);
-    if (!dev.ok) return ECFFT_ERR_HIP;
-    Fe256 *dT = nullptr, *dx = nullptr; uint8_t* dA = nullptr;
-    bool ok = hipMalloc(&dT, 256 * sizeof(Fe256)) == hipSuccess && hipMalloc(&dx, n * sizeof(Fe256)) == hipSuccess &&
-              hipMalloc(&dA, Blk16::kABytes + Blk16::kKWords * 8) == hipSuccess;
-    ok = ok && hipMemcpy(dT, matrix256, 256 * sizeof(Fe256), hipMemcpyHostToDevice) == hipSuccess && hipMemcpy(dx, x, n * sizeof(Fe256), hipMemcpyHostToDevice) == hipSuccess;
-    if (ok) {
-        unsigned long long* dK = reinterpret_cast<unsigned long long*>(dA + Blk16::kABytes);
-        hipLaunchKernelGGL(k_blk16_from_matrix, dim3(1), dim3(256), 0, nullptr, dT, dA, dK, false);
-        if (mode == 1) hipLaunchKernelGGL(k_blk16_apply_n16<1>, dim3((unsigned)(n / 256)), dim3(256), 0, nullptr, dx, dA, dK);
+        if (mode == 0) hipLaunchKernelGGL(k_blk16_apply, dim3((unsigned)(n / Blk16::kSub)), dim3(512), 0, nullptr, dx, dA, dK);
+        else if (mode == 1) hipLaunchKernelGGL(k_blk16_apply_n16<1>, dim3((unsigned)(n / 256)), dim3(256), 0, nullptr, dx, dA, dK);
         else if (mode == 2) hipLaunchKernelGGL(k_blk16_apply_n16<2>, dim3((unsigned)(n / 256)), dim3(128), 0, nullptr, dx, dA, dK);
         else if (mode == 3) hipLaunchKernelGGL(k_blk16_apply_n16<3>, dim3((unsigned)(n / 128)), dim3(128), 0, nullptr, dx, dA, dK);
         else hipLaunchKernelGGL(k_blk16_apply_n16<4>, dim3((unsigned)(n / 256)), dim3(256), 0, nullptr, dx, dA, dK);
-        ok = hipDeviceSynchronize() == hipSuccess && hipMemcpy(out, dx, n * sizeof(Fe256), hipMemcpyDeviceToHost) == hipSuccess;
-    }
-    (void)hipFree(dT); (void)hipFree(dx); (void)hipFree(dA);
-    return ok ? ECFFT_OK : ECFFT_ERR_HIP;
+    });
+}
+}  // namespace
+extern "C" {
+
+int ecfft_selftest_blk16(const void* matrix256, const void* x, void* out, size_t n, int device) {
+    if (!matrix256 || !x || !out || !n || n % Blk16::kSub) return ECFFT_ERR_BAD_ARG;
+    return run_blk16_selftest(matrix256, x, out, n, 0, device);
+}
+int ecfft_selftest_blk16_small(const void* matrix256, const void* x, void* out, size_t n, int mode, int device) {
+    if (!matrix256 || !x || !out || !n || n % 256 || mode < 1 || mode > 4) return ECFFT_ERR_BAD_ARG;
+    return run_blk16_selftest(matrix256, x, out, n, mode, device);
 }
 
 int ecfft_selftest_blk32(const void* matrix1024, const void* x, void* out, size_t n, int device) {
     if (!matrix1024 || !x || !out || !n || n % 1024) return ECFFT_ERR_BAD_ARG;
-    if (!have_device(device)) return ECFFT_ERR_HIP;
-    DeviceGuard dev(device);
-    if (!dev.ok) return ECFFT_ERR_HIP;
-    Fe256 *dT = nullptr, *dx = nullptr, *dcs = nullptr; uint8_t* dA = nullptr;
-    bool ok = hipMalloc(&dT, 1024 * sizeof(Fe256)) == hipSuccess && hipMalloc(&dcs, 1024 * sizeof(Fe256)) == hipSuccess && hipMalloc(&dx, n * sizeof(Fe256)) == hipSuccess &&
-              hipMalloc(&dA, Blk16::kABytes32 + Blk16::kKWords32 * 8) == hipSuccess;
-    ok = ok && hipMemcpy(dT, matrix1024, 1024 * sizeof(Fe256), hipMemcpyHostToDevice) == hipSuccess && hipMemcpy(dx, x, n * sizeof(Fe256), hipMemcpyHostToDevice) == hipSuccess;
-    if (ok) {
+    return run_blk_selftest(matrix1024, 1024, x, out, n, Blk16::kABytes32 + Blk16::kKWords32 * 8, 1024 * sizeof(Fe256), device,
+                            [&](Fe256* dT, Fe256* dx, uint8_t* dA, Fe256* dcs) {
         unsigned long long* dK = reinterpret_cast<unsigned long long*>(dA + Blk16::kABytes32);
         hipLaunchKernelGGL(k_blk32_expand, dim3(4), dim3(256), 0, nullptr, (const Fe256*)dT, dA, dcs, false);
         hipLaunchKernelGGL(k_blk32_seeds, dim3(1), dim3(32), 0, nullptr, (const Fe256*)dcs, dK);
         hipLaunchKernelGGL(k_blk32_apply, dim3((unsigned)(n / 1024)), dim3(512), 0, nullptr, dx, dA, dK);
-        ok = hipDeviceSynchronize() == hipSuccess && hipMemcpy(out, dx, n * sizeof(Fe256), hipMemcpyDeviceToHost) == hipSuccess;
-    }
-    (void)hipFree(dT); (void)hipFree(dx); (void)hipFree(dA); (void)hipFree(dcs);
-    return ok ? ECFFT_OK : ECFFT_ERR_HIP;
+    });
 }
 // which composite map the 1024-element low-level kernels of this context run for the lowest levels of ENTER (dir 0) / EXIT (dir 1):
 // 32 (levels 1..5), 16 (levels 1..4) or 0 (level code)
@@ -1337,9 +1168,7 @@ int ecfft_ctx_low_map(const ecfft_ctx* ctx, int dir) {
 
 #endif  // ECFFT_TEST_HOOKS
 int ecfft_mul_ceiling(int field, int device, int waves_per_simd, double* mul_per_s) {
-    if (field == ECFFT_FIELD_SECP256K1) return run_mul_ceiling<Secp256k1>(device, waves_per_simd, mul_per_s);
-    if (field == ECFFT_FIELD_M31) return run_mul_ceiling<M31>(device, waves_per_simd, mul_per_s);
-    return ECFFT_ERR_BAD_ARG;
+    return with_field(field, [&](auto tag) { return run_mul_ceiling<typename decltype(tag)::type>(device, waves_per_simd, mul_per_s); });
 }
 
 int ecfft_device_alloc(int device, size_t bytes, void** out) {
@@ -1357,9 +1186,7 @@ int ecfft_device_sync(int device) {
 }
 
 int ecfft_shader_clock(int field, int device, double* mhz) {
-    if (field == ECFFT_FIELD_SECP256K1) return run_shader_clock<Secp256k1>(device, mhz);
-    if (field == ECFFT_FIELD_M31) return run_shader_clock<M31>(device, mhz);
-    return ECFFT_ERR_BAD_ARG;
+    return with_field(field, [&](auto tag) { return run_shader_clock<typename decltype(tag)::type>(device, mhz); });
 }
 
 int ecfft_device_copy(void* dst, const void* src, size_t bytes, int kind) {

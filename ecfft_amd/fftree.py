@@ -208,45 +208,34 @@ class Field:
     def shape(self, n):
         return (n, self.limbs) if self.limbs > 1 else (n,)
 
-    def build_fftree(self, n, device=0):
-        """`F::build_fftree(n)`: None if n exceeds the curve's 2-adicity (src/lib.rs:62-64, src/ec.rs:513-515)."""
+    def _new_tree(self, make, device):
+        """make(byref(handle)) -> rc of one of the context builders: None if the tree is too large for the curve"""
         h = ctypes.c_void_p()
-        rc = lib().ecfft_build_fftree(self.id, n, device, ctypes.byref(h))
+        rc = make(ctypes.byref(h))
         if rc == ERR_TREE_TOO_LARGE:
             return None
         _check(rc)
         return FFTree(self, h, device)
+
+    def build_fftree(self, n, device=0):
+        """`F::build_fftree(n)`: None if n exceeds the curve's 2-adicity (src/lib.rs:62-64, src/ec.rs:513-515)."""
+        return self._new_tree(lambda out: lib().ecfft_build_fftree(self.id, n, device, out), device)
 
     def build_extend_shard(self, e, world, rank, device=0):
         """Sharded EXTEND-only context (include/ecfft_hip.h ecfft_build_extend_shard): this rank's share of the tables of ONE
         EXTEND of e evaluations over `world` GPUs; only `extend_sharded` works on it.  None if T_2e is too large for the curve."""
-        h = ctypes.c_void_p()
-        rc = lib().ecfft_build_extend_shard(self.id, e, device, world, rank, ctypes.byref(h))
-        if rc == ERR_TREE_TOO_LARGE:
-            return None
-        _check(rc)
-        return FFTree(self, h, device)
+        return self._new_tree(lambda out: lib().ecfft_build_extend_shard(self.id, e, device, world, rank, out), device)
 
     def build_enter_shard(self, n, world, rank, device=0):
         """Sharded ENTER-only context (ecfft_build_enter_shard): the chain up to n/world plus this rank's share of the top
         log2(world) trees; only `enter_sharded` works on it.  None if T_n is too large for the curve."""
-        h = ctypes.c_void_p()
-        rc = lib().ecfft_build_enter_shard(self.id, n, device, world, rank, ctypes.byref(h))
-        if rc == ERR_TREE_TOO_LARGE:
-            return None
-        _check(rc)
-        return FFTree(self, h, device)
+        return self._new_tree(lambda out: lib().ecfft_build_enter_shard(self.id, n, device, world, rank, out), device)
 
     def build_exit_shard(self, n, comm, device=0, min_memory=False):
         """Sharded EXIT-only context (ecfft_build_exit_shard[_opts]) — COLLECTIVE over the ranks of `comm`: the chain up to n/world plus
         this rank's share of the top trees, z0z0_rem_xnn_s built distributed; only `exit_sharded` works on it.  min_memory: never
         keep T_2c for the redundant pair level (ECFFT_EXIT_SHARD_MIN_MEMORY)."""
-        h = ctypes.c_void_p()
-        rc = lib().ecfft_build_exit_shard_opts(self.id, n, device, comm._h, 1 if min_memory else 0, ctypes.byref(h))
-        if rc == ERR_TREE_TOO_LARGE:
-            return None
-        _check(rc)
-        return FFTree(self, h, device)
+        return self._new_tree(lambda out: lib().ecfft_build_exit_shard_opts(self.id, n, device, comm._h, 1 if min_memory else 0, out), device)
 
     def selftest(self, op, a, b, c=None, device=0):
         """device field arithmetic on raw residues (test hook): op 0 a*b+c, 1 a*b, 2 a-b, 3 a+b, 4/5 the kernels' table multiply a*b+c / a*b"""
@@ -395,23 +384,13 @@ class FFTree:
         count * na and b of count * nb coefficients, any lengths; returns count * (na + nb - 1) coefficients.  Needs a tree of
         next_pow2(na + nb - 1) leaves.  Passing the same object as a and b is a squaring (one forward transform).  numpy arrays
         (host) or contiguous CUDA tensors (device, on the tensor's current stream), both of the same kind."""
-        if _is_torch(a) or _is_torch(b):
-            import torch
-            assert _is_torch(a) and _is_torch(b), "a and b must both be numpy arrays or both CUDA tensors"
-            for x in (a, b):
-                assert x.is_cuda and x.is_contiguous(), "device tensors must be contiguous CUDA tensors"
-            na, nb = a.shape[0], b.shape[0]
-            out = torch.empty((count * max(na // count + nb // count - 1, 0),) + tuple(a.shape[1:]), dtype=a.dtype, device=a.device)
-            pa, pb, pout, mem, stream = a.data_ptr(), b.data_ptr(), out.data_ptr(), MEM_DEVICE, torch.cuda.current_stream(a.device).cuda_stream
-        else:
-            sq = a is b
-            a = np.ascontiguousarray(a, self.field.dtype)
-            b = a if sq else np.ascontiguousarray(b, self.field.dtype)
-            na, nb = a.shape[0], b.shape[0]
-            out = np.empty(self.field.shape(count * max(na // count + nb // count - 1, 0)), self.field.dtype)
-            pa, pb, pout, mem, stream = a.ctypes.data, b.ctypes.data, out.ctypes.data, MEM_HOST, None
-        assert count > 0 and na % count == 0 and nb % count == 0
-        rc = self._L.ecfft_poly_mul(self._h, pa, na // count, pb, nb // count, pout, count, mem, stream)
+        assert _is_torch(a) == _is_torch(b), "a and b must both be numpy arrays or both CUDA tensors"
+        xs, ptrs, new, mem, stream = self._poly_io([a] if a is b else [a, b])     # a squaring converts its operand once
+        (a, b), (pa, pb) = (xs * 2, ptrs * 2) if a is b else (xs, ptrs)
+        assert count > 0 and a.shape[0] % count == 0 and b.shape[0] % count == 0
+        na, nb = a.shape[0] // count, b.shape[0] // count
+        out = new(count * max(na + nb - 1, 0))
+        rc = self._L.ecfft_poly_mul(self._h, pa, na, pb, nb, self._ptr(out), count, mem, stream)
         if rc == ERR_BAD_ARG:
             raise ValueError("poly_mul: empty operand, count = 0 or a context that holds no full tree")
         _check(rc)

@@ -261,6 +261,7 @@ def test_bad_args(field):
     assert L.ecfft_poly_inv_series(t._h, pa, 10, po, 0, 1, H, None) == FT.ERR_BAD_ARG
     assert L.ecfft_poly_inv_series(t._h, pa, 10, po, 10, 0, H, None) == FT.ERR_BAD_ARG
     assert L.ecfft_poly_inv_series(t._h, pa, 10, po, 10, (1 << 64) // 3, H, None) == FT.ERR_BAD_ARG
+    assert L.ecfft_poly_inv_series(t._h, pa, 10, po, 10, 1, 7, None) == FT.ERR_BAD_ARG                 # unknown memory kind
     shard = ecfft_amd.FIELDS[field].build_extend_shard(1024, 1, 0)       # EXTEND-only context: holds no full tree
     assert L.ecfft_poly_divrem(shard._h, pa, 8, pb, 4, po, po, 1, H, None) == FT.ERR_BAD_ARG
     assert L.ecfft_poly_inv_series(shard._h, pa, 8, po, 4, 1, H, None) == FT.ERR_BAD_ARG

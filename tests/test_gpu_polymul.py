@@ -151,8 +151,33 @@ def test_limits(field):
     assert L.ecfft_poly_mul(t._h, p, 0, p, 1, out.ctypes.data, 1, FT.MEM_HOST, None) == FT.ERR_BAD_ARG
     assert L.ecfft_poly_mul(t._h, p, 1, p, 0, out.ctypes.data, 1, FT.MEM_HOST, None) == FT.ERR_BAD_ARG
     assert L.ecfft_poly_mul(t._h, p, 1, p, 1, out.ctypes.data, 0, FT.MEM_HOST, None) == FT.ERR_BAD_ARG
+    assert L.ecfft_poly_mul(t._h, None, 4, p, 4, out.ctypes.data, 1, FT.MEM_HOST, None) == FT.ERR_BAD_ARG     # NULL operands / output
+    assert L.ecfft_poly_mul(t._h, p, 4, None, 4, out.ctypes.data, 1, FT.MEM_HOST, None) == FT.ERR_BAD_ARG
+    assert L.ecfft_poly_mul(t._h, p, 4, p, 4, None, 1, FT.MEM_HOST, None) == FT.ERR_BAD_ARG
+    assert L.ecfft_poly_mul(t._h, p, 4, p, 4, out.ctypes.data, 1, 7, None) == FT.ERR_BAD_ARG                 # unknown memory kind
     shard = ecfft_amd.FIELDS[field].build_extend_shard(1024, 1, 0)       # EXTEND-only context: holds no full tree
     assert L.ecfft_poly_mul(shard._h, p, 4, p, 4, out.ctypes.data, 1, FT.MEM_HOST, None) == FT.ERR_BAD_ARG
+
+
+@pytest.mark.parametrize("field", FIELDS)
+def test_host_squaring_is_one_operand_inside_the_library(field):
+    """a host-memory poly_mul(a, a) reaches the device as ONE staged operand, so the library squares: its lift moves half the
+    rows of poly_mul(a, a.copy()).  (Launch counts cannot tell: two operands of equal length share every launch of the lift.)
+    The profiler's alg_bytes are computed from the launch arguments, not measured."""
+    t = tree(field, 4096)
+    a = rand_elems_fast(field, 300, 91)
+
+    def alg_bytes(b):
+        t.profile(True)
+        c = t.poly_mul(a, b)
+        total = sum(r["alg_bytes"] for r in t.profile_read())
+        t.profile(False)
+        return c, total
+
+    sq, sq_bytes = alg_bytes(a)
+    pr, pr_bytes = alg_bytes(a.copy())
+    assert np.array_equal(sq, pr)
+    assert 0 < sq_bytes < pr_bytes
 
 
 @pytest.mark.parametrize("field", FIELDS)
