@@ -99,15 +99,20 @@ def test_device_tensors_match_host(field):
     assert np.array_equal(got, want)
 
 
-def test_batched_large_two_streams():
-    """2 pairs of 2^18 x 2^18 (N = 2^19): the joint ENTER of 4 x 2^18 runs as two half-batches on two streams"""
+def test_batched_large_two_streams(oracle_mod):
+    """2 pairs of 2^18 x 2^18 (N = 2^19): the joint ENTER of 4 x 2^18 runs as two half-batches on two streams.  Every pair is
+    checked against the reference (Schwartz-Zippel with the oracle's Horner) and against the single call, whose lift, pointwise
+    and EXIT code it shares"""
+    F = oracle_mod.field("secp256k1")
     t = tree("secp256k1", 1 << 20)
     n = 1 << 18
     a = rand_elems_fast("secp256k1", 2 * n, 21)
     b = rand_elems_fast("secp256k1", 2 * n, 22)
     c = t.poly_mul(a, b, count=2)
     for i in range(2):
-        assert np.array_equal(c[i * (2 * n - 1):(i + 1) * (2 * n - 1)], t.poly_mul(a[i * n:(i + 1) * n], b[i * n:(i + 1) * n])), i
+        ai, bi, ci = a[i * n:(i + 1) * n], b[i * n:(i + 1) * n], c[i * (2 * n - 1):(i + 1) * (2 * n - 1)]
+        _schwartz_zippel(F, "secp256k1", ai, bi, ci, 23 + i)
+        assert np.array_equal(ci, t.poly_mul(ai, bi)), i
 
 
 def _schwartz_zippel(F, field, a, b, c, seed):
