@@ -55,6 +55,7 @@ pub mod ffi {
         pub fn ecfft_poly_inv_series(ctx: *mut EcfftCtx, f: *const c_void, nf: usize, out: *mut c_void, k: usize, count: usize, mem: i32, stream: *mut c_void) -> i32;
         pub fn ecfft_poly_divrem(ctx: *mut EcfftCtx, a: *const c_void, na: usize, b: *const c_void, nb: usize, q: *mut c_void, r: *mut c_void, count: usize, mem: i32, stream: *mut c_void) -> i32;
         pub fn ecfft_poly_eval_points(ctx: *mut EcfftCtx, f: *const c_void, nf: usize, points: *const c_void, m: usize, out: *mut c_void, count: usize, mem: i32, stream: *mut c_void) -> i32;
+        pub fn ecfft_poly_interpolate(ctx: *mut EcfftCtx, points: *const c_void, m: usize, values: *const c_void, out: *mut c_void, count: usize, mem: i32, stream: *mut c_void) -> i32;
         pub fn ecfft_mextend(ctx: *mut EcfftCtx, inp: *const c_void, out: *mut c_void, e: usize, moiety: i32, count: usize, mem: i32, stream: *mut c_void) -> i32;
         pub fn ecfft_redc(ctx: *mut EcfftCtx, evals: *const c_void, a: *const c_void, out: *mut c_void, n: usize, moiety: i32, mem: i32, stream: *mut c_void) -> i32;
         pub fn ecfft_modular_reduce(ctx: *mut EcfftCtx, evals: *const c_void, a: *const c_void, c: *const c_void, out: *mut c_void, n: usize, mem: i32, stream: *mut c_void) -> i32;
@@ -266,6 +267,18 @@ impl<F: HipField> HipFFTree<F> {
         assert!(!f.is_empty() && !points.is_empty());
         let mut out = Self::out_vec(points.len());
         check(unsafe { ffi::ecfft_poly_eval_points(self.ctx, f.as_ptr().cast(), f.len(), points.as_ptr().cast(), points.len(), out.as_mut_ptr().cast(), 1, ffi::MEM_HOST, core::ptr::null_mut()) });
+        unsafe { out.set_len(points.len()) };
+        out
+    }
+
+    /// The polynomial through arbitrary points (ecfft_poly_interpolate; no reference counterpart), the inverse of `eval_points`:
+    /// the coefficients of `f` of degree `< points.len()` with `f(points[i]) = values[i]`.  The points must be pairwise distinct
+    /// (a repeated point panics like any other argument error).  Up to 64 points work on any tree; more need a tree of
+    /// `next_pow2(points.len())` leaves.
+    pub fn interpolate(&self, points: &[F], values: &[F]) -> Vec<F> {
+        assert!(!points.is_empty() && points.len() == values.len());
+        let mut out = Self::out_vec(points.len());
+        check(unsafe { ffi::ecfft_poly_interpolate(self.ctx, points.as_ptr().cast(), points.len(), values.as_ptr().cast(), out.as_mut_ptr().cast(), 1, ffi::MEM_HOST, core::ptr::null_mut()) });
         unsafe { out.set_len(points.len()) };
         out
     }

@@ -65,6 +65,12 @@ fn all_algorithms_match<F: HipField>(log_tree: u32) {
             assert_eq!(gpu.redc_z1(&v, &t.xnn_s), cpu.redc_z1(&v, &t.xnn_s), "REDC_z1 n={n}");
             assert_eq!(gpu.modular_reduce(&v, &t.xnn_s, &t.z0z0_rem_xnn_s), cpu.modular_reduce(&v, &t.xnn_s, &t.z0z0_rem_xnn_s), "MOD n={n}");
         }
+        // interpolation at the tree's own leaves is the crate's EXIT; a shorter prefix of the leaves round-trips through eval_points
+        assert_eq!(gpu.interpolate(&gpu.eval_domain(n), &v), cpu.exit(&v), "INTERPOLATE n={n}");
+        if n >= 4 {
+            let (x, f) = (&gpu.eval_domain(n)[..n - 3], &v[..n - 3]);
+            assert_eq!(gpu.interpolate(x, &gpu.eval_points(f, x)), f, "INTERPOLATE m={}", n - 3);
+        }
         n *= 2;
     }
     // a device tree mirrored from the CPU tree's point set (FFTree::new path) behaves identically

@@ -1943,6 +1943,103 @@ public:
         return ok;
     }
 
+    // ecfft_poly_interpolate (no reference counterpart): out (count x m) = the coefficients of the f_b of degree < m with
+    // f_b(points[i]) = values[b*m + i], for m pairwise distinct points shared by all `count` value vectors.  Lagrange form
+    // f = sum_i c_i M / (x - x_i), M = prod (x - x_i), c_i = y_i / M'(x_i), on ONE group of P = max(B, next_pow2(m)) points of
+    // eval_points' subproduct tree, the last k = P - m of them the pad point 0 with weight 0: the padded sum is x^k f.
+    //   weights (once per call): M from the two top nodes (interp_weights), M'(x_i) by one remainder descent + k_eval_leaves, inverted;
+    //   leaves: k_interp_leaves gives every block of B points its numerator's B coefficients, one lift brings them to T_2B;
+    //   ascent: per level k_interp_combine (N^ = N^_l M^_r + N^_r M^_l on T_2d) and one batched EXTEND onto S1 of T_4d for the next
+    //           level's odd half; one batched EXIT_P at the top, the output is that row shifted down by k.
+    // P == B: k_interp_leaves is the whole interpolation, no transform.  Device pointers; synchronous (the flag of a zero weight
+    // denominator is read back: *repeated = two equal points).  Caller holds lock() and checks the tree rule (P <= size() if P > B).
+    bool poly_interpolate(const E* points, size_t m, const E* values, E* out, size_t count, bool* repeated, hipStream_t s) {
+        const size_t B = kEvalLeaf, P = eval_group(m), k = P - m, rpv = P / B, rows = count * rpv;
+        const TE rinv = F::to_table(rinv_);
+        int* flag = new_flag(s);
+        bool ok = true;
+        SubproductTree st;
+        E* w = temp(m);                                          // plain 1 / M'(x_i)
+        if (P > B) {
+            ok = subproduct_tree(points, m, P, st, s) && ok;
+            ok = interp_weights(points, m, st, w, flag, s) && ok;
+        } else {
+            const E ri = rinv_;                                  // M'(x_i) = prod_{j != i} (x_i - x_j) over the m real points
+            foreach_n(s, m, [=] __device__(size_t i) {
+                const E xi = points[i];
+                E acc = F::one();
+                for (size_t j = 0; j < m; ++j) if (j != i) acc = F::mul(acc, F::mul(F::sub(xi, points[j]), ri));
+                acc = F::canon(acc);
+                if (F::is_zero(acc)) *flag = 1;
+                w[i] = acc;
+            });
+            batch_inv(w, w, m, s);
+        }
+        E* leaf = P > B ? temp(count * P) : (k ? temp(count * P) : out);
+        ECFFT_LAUNCH(KC_POINTWISE, sizeof(E) * ((double)rows * B + (double)count * m + 2.0 * (double)m), (k_interp_leaves<F, (int)kEvalLeaf>),
+                     dim3(nblocks(rows * B)), dim3(kBlock), 0, s, leaf, values, (const E*)w, points, m, rpv, rows, rinv);
+        const E* top = leaf;                                     // count rows of P coefficients of x^k f_b
+        if (P > B) {
+            E* Y[2] = {temp(count * P), st.lv.size() > 1 ? temp(count * P) : nullptr};
+            E* X = st.lv.size() > 1 ? temp(count * P) : nullptr;
+            const TempMark mark = temps_mark();                  // the lift's temporaries are read by the first level only
+            PolyEvals<F> ev[2];
+            ok = lift_evals(leaf, B, rows, ev, s) && ok;
+            PolyEvals<F> cur = ev[0];
+            for (size_t lvl = 0; lvl < st.lv.size(); ++lvl) {
+                const NodeLevel& L = st.lv[lvl];
+                const size_t d = L.d, nodes = P / d, total = count * P;           // count * nodes / 2 parents of 2d evaluations
+                E* dst = Y[lvl & 1];
+                ECFFT_LAUNCH(KC_POINTWISE, sizeof(E) * (2.0 * (double)total + 2.0 * (double)P), k_interp_combine<F>, dim3(nblocks(total)),
+                             dim3(kBlock), 0, s, dst, cur, (const E*)L.Mh, nodes, rinv, ilog2(d) + 1, total);
+                if (lvl == 0) temps_release(mark);
+                if (2 * d < P) {
+                    ok = extend_api(dst, X, 2 * d, count * nodes / 2, 1, s) && ok;
+                    cur = PolyEvals<F>{dst, X, 2 * d, 1u};
+                }
+                top = dst;
+            }
+            E* T = const_cast<E*>(top);
+            if (k == 0) ok = exit(T, out, P, count, s) && ok; else ok = exit(T, T, P, count, s) && ok;
+        }
+        if (k)
+            ok = ok && hipMemcpy2DAsync(out, m * sizeof(E), top + k, P * sizeof(E), m * sizeof(E), count, hipMemcpyDeviceToDevice, s) == hipSuccess;
+        return finish_flagged(ok, flag, repeated, s);
+    }
+    // The weights of ecfft_poly_interpolate: w[i] = 1 / M'(points[i]) in PLAIN form for i < m; raises *flag if some M'(x_i) is zero
+    // (a repeated point).  The padded top polynomial Mp = x^k M has degree exactly P and does not fit T_P; with the two top nodes
+    // M_l = x^(P/2) + A, M_r = x^(P/2) + B (one batched EXIT_P of the top level's M^): Mp = x^P + x^(P/2) (A + B) + A B, and A B
+    // has < P coefficients: one product on T_P.  M'_j = (j + 1) Mp_{k+j+1}, the plain constant j + 1 keeps the crate form.
+    bool interp_weights(const E* points, size_t m, const SubproductTree& st, E* w, int* flag, hipStream_t s) {
+        const size_t P = st.npts, h = P / 2, k = P - m, B = kEvalLeaf;
+        const TempMark mark = temps_mark();
+        E* Mc = temp(2 * P); E* AB = temp(P); E* dM = temp(m); E* rem = temp(P);
+        bool ok = exit(st.lv.back().Mh, Mc, P, 2, s);
+        ok = poly_mul_body(Mc, h, P, Mc + P, h, P, AB, 1, s) && ok;              // P - 1 coefficients
+        const E r1 = F::to_mont(F::one());
+        foreach_n(s, m, [=] __device__(size_t j) {
+            const size_t c = k + j + 1;                                          // coefficient of Mp
+            E v = r1;
+            if (c < P) {
+                v = c < P - 1 ? AB[c] : F::zero();
+                if (c >= h) v = F::add(v, F::add(F::canon(Mc[c - h]), F::canon(Mc[P + c - h])));
+            }
+            dM[j] = F::canon(F::mul(v, F::from_u32((uint32_t)(j + 1))));
+        });
+        ok = remainder_descent(dM, m, st, 1, rem, s) && ok;
+        ECFFT_LAUNCH(KC_POINTWISE, sizeof(E) * ((double)P + 2.0 * (double)m), (k_eval_leaves<F, (int)kEvalLeaf>), dim3(nblocks(P)),
+                     dim3(kBlock), 0, s, w, (const E*)rem, P, B, (uint32_t)B, points, m, P / B, P / B, F::to_table(rinv_));
+        const E ri = rinv_;
+        foreach_n(s, m, [=] __device__(size_t i) {
+            const E v = F::canon(F::mul(w[i], ri));
+            if (F::is_zero(v)) *flag = 1;
+            w[i] = v;
+        });
+        batch_inv(w, w, m, s);
+        temps_release(mark);
+        return ok;
+    }
+
     // ------------------------------------------------------------------------------------------
     // Public wrappers of the remaining FFTree algorithms on USER data (crate representation),
     // composed from the same EXTEND kernels.  Device pointers; synchronous (they drain `s` before returning

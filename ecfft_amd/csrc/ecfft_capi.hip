@@ -354,6 +354,26 @@ int run_poly_eval_points(ecfft_ctx* c, DeviceChain<F>& ch, const void* f, size_t
     });
 }
 
+// ecfft_poly_interpolate: synchronous (the chain reads back the device flag of a zero weight denominator, i.e. two equal points,
+// reported as ECFFT_ERR_BAD_ARG)
+template <class F>
+int run_poly_interpolate(ecfft_ctx* c, DeviceChain<F>& ch, const void* points, size_t m, const void* values, void* out, size_t count,
+                         int mem, void* stream) {
+    using E = typename F::elem;
+    if (!points || !values || !out) return ECFFT_ERR_BAD_ARG;
+    if (m > SIZE_MAX / (64 * sizeof(E))) return ECFFT_ERR_BAD_ARG;
+    const size_t P = DeviceChain<F>::eval_group(m);
+    if (P > DeviceChain<F>::kEvalLeaf && P > ch.size()) return ECFFT_ERR_TREE_TOO_SMALL;    // m <= 64: no transform, any tree
+    if (P > SIZE_MAX / (8 * 64 * sizeof(E))) return ECFFT_ERR_BAD_ARG;     // node data: 4 P elements per level, < 64 levels
+    if (count > SIZE_MAX / (16 * P * sizeof(E))) return ECFFT_ERR_BAD_ARG; // byte counts of the temporaries must not wrap
+    const size_t eb = count * sizeof(E);
+    return staged(c, ch, mem, stream, {{points, m * sizeof(E)}, {values, m * eb}}, {{out, m * eb}}, [&](auto d, auto o) -> int {
+        bool repeated = false;
+        if (!ch.poly_interpolate((const E*)d[0], m, (const E*)d[1], (E*)o[0], count, &repeated, (hipStream_t)stream)) return ECFFT_ERR_HIP;
+        return repeated ? ECFFT_ERR_BAD_ARG : ECFFT_OK;                     // two equal points: no interpolant
+    });
+}
+
 // standard = true: plain standard-form residues (the FFTree wire format) instead of the crate's in-memory representation
 template <class F>
 int table_of(DeviceChain<F>& ch, size_t m, int which, void* host_out, size_t cap, size_t* count, bool standard = false) {
@@ -923,6 +943,11 @@ int ecfft_poly_eval_points(ecfft_ctx* ctx, const void* f, size_t nf, const void*
                            void* stream) {
     if (nf == 0 || m == 0 || count == 0) return ECFFT_ERR_BAD_ARG;
     return on_chain(ctx, [&](auto& ch) { return run_poly_eval_points(ctx, ch, f, nf, points, m, out, count, mem, stream); });
+}
+int ecfft_poly_interpolate(ecfft_ctx* ctx, const void* points, size_t m, const void* values, void* out, size_t count, int mem,
+                           void* stream) {
+    if (m == 0 || count == 0) return ECFFT_ERR_BAD_ARG;
+    return on_chain(ctx, [&](auto& ch) { return run_poly_interpolate(ctx, ch, points, m, values, out, count, mem, stream); });
 }
 
 int ecfft_extend_top_cyclic(ecfft_ctx* ctx, void* buf, size_t e, int moiety, unsigned log_p, unsigned rank, int recombine, int mem, void* stream) {

@@ -2214,6 +2214,66 @@ __global__ __launch_bounds__(kBlock) void k_eval_leaves(typename F::elem* __rest
 }
 
 // ---------------------------------------------------------------------------------------------
+// ecfft_poly_interpolate (interpolation from arbitrary points; no reference counterpart): the Lagrange form
+// f = sum_i c_i M / (x - x_i), c_i = y_i / M'(x_i), combined upwards over the subproduct tree of the points: a node's numerator is
+// N = N_l M_r + N_r M_l.  Every node of a level has the same degree, so a level is one batched launch.
+// ---------------------------------------------------------------------------------------------
+// The leaves of the combination, the mirror image of k_eval_leaves: row r of `rows_per_vec` rows per value vector holds the B
+// coefficients (crate form) of N = sum_i c_i prod_{j != i} (x - x_j) over the B points of its leaf block, c_i = y[b*m + i] * w[i]
+// (w: plain 1 / M'(x_i)); positions i >= m are the pad point 0 with c_i = 0.  One thread per coefficient, B steps over the block's
+// points keeping (M_t, N_t): M_{t+1} = M_t (x - x_t), N_{t+1} = N_t (x - x_t) + c_t M_t — the neighbour coefficient through LDS,
+// x_t and c_t as LDS broadcasts.  The point is brought to plain form once (as k_eval_leaves), M is a plain polynomial, N and c are
+// in crate form: 3 multiplies per thread and step, none of them crate x crate.
+template <class F, int B>
+__global__ __launch_bounds__(kBlock) void k_interp_leaves(typename F::elem* __restrict__ out, const typename F::elem* __restrict__ values,
+                                                          const typename F::elem* __restrict__ weights,
+                                                          const typename F::elem* __restrict__ points, size_t m, size_t rows_per_vec,
+                                                          size_t rows, typename F::telem rinv) {
+    static_assert(kBlock % B == 0, "a workgroup holds whole rows");
+    using E = typename F::elem;
+    __shared__ E sx[kBlock], sc[kBlock], sm[kBlock], sn[kBlock];
+    const uint32_t t = threadIdx.x, lane = t % B, base = t - lane;
+    const size_t r = (size_t)blockIdx.x * (kBlock / B) + t / B;
+    const size_t b = r / rows_per_vec, rr = r - b * rows_per_vec, i = rr * B + lane;
+    const bool real = r < rows && i < m;
+    E x = real ? points[i] : F::zero();
+    if constexpr (sizeof(E) == 32) x = F::tmul(rinv, x);
+    sx[t] = F::canon(x);
+    sc[t] = real ? F::canon(F::mul(values[b * m + i], weights[i])) : F::zero();
+    E M = lane == 0 ? F::one() : F::zero(), N = F::zero();
+    for (int step = 0; step < B; ++step) {
+        sm[t] = M; sn[t] = N;
+        __syncthreads();
+        const E xt = sx[base + step], ct = sc[base + step];
+        const E Mp = lane ? sm[t - 1] : F::zero(), Np = lane ? sn[t - 1] : F::zero();
+        __syncthreads();
+        N = F::canon(F::add(F::sub(Np, F::mul(xt, N)), F::mul(ct, M)));
+        M = F::canon(F::sub(Mp, F::mul(xt, M)));
+    }
+    if (r < rows) out[r * B + lane] = N;
+}
+// One level of the ascent in evaluation form: children of d points (2^log_n = 2d), parent row g >> log_n of `total >> log_n` rows
+// (vector x parent node): N^_parent = N^_l M^_r + N^_r M^_l on the 2d leaves of T_2d in the natural leaf order EXIT reads
+// (deg < 2d: nothing wraps).  The children's rows 2 row and 2 row + 1 are read through even / odd pointers like k_poly_pointwise,
+// the node operands from the cached M^ of the level indexed by node (not by vector x node).  Both products carry R^2, so ONE
+// table multiply by R^-1 on the sum puts the result back in the crate's form (M31: R = 1).
+template <class F>
+__global__ __launch_bounds__(kBlock) void k_interp_combine(typename F::elem* __restrict__ out, PolyEvals<F> a,
+                                                           const typename F::elem* __restrict__ node, size_t nodes, typename F::telem rinv,
+                                                           uint32_t log_n, size_t total) {
+    using E = typename F::elem;
+    const size_t g = (size_t)blockIdx.x * kBlock + threadIdx.x;
+    if (g >= total) return;
+    const size_t row = g >> log_n, j = g & (((size_t)1 << log_n) - 1), k = j >> 1, cl = 2 * row, nl = cl % nodes;
+    const E* pa = (j & 1) ? a.odd : a.even;
+    const E Nl = pa[cl * a.batch + k * a.stride], Nr = pa[(cl + 1) * a.batch + k * a.stride];
+    const E Ml = node[(nl << log_n) + j], Mr = node[((nl + 1) << log_n) + j];
+    E r = F::add(F::mul(Nl, Mr), F::mul(Nr, Ml));
+    if constexpr (sizeof(E) == 32) r = F::tmul(rinv, r);
+    out[g] = F::canon(r);
+}
+
+// ---------------------------------------------------------------------------------------------
 // generic element-wise helper for tree construction: functor(i) for i < n
 // ---------------------------------------------------------------------------------------------
 template <class Fn>

@@ -32,7 +32,7 @@ EXPORTS = ["ecfft_elem_size", "ecfft_build_fftree", "ecfft_fftree_new", "ecfft_c
            "ecfft_comm_get_unique_id", "ecfft_comm_init_rank", "ecfft_comm_init_callback", "ecfft_comm_destroy", "ecfft_comm_rank", "ecfft_comm_world",
            "ecfft_comm_stats_enable", "ecfft_comm_stats_read", "ecfft_extend_sharded", "ecfft_enter_sharded", "ecfft_exit_sharded", "ecfft_device_copy", "ecfft_shader_clock", "ecfft_device_alloc", "ecfft_device_free", "ecfft_device_sync", "ecfft_build_extend_shard", "ecfft_ctx_device_bytes", "ecfft_extend_sharded_layout", "ecfft_build_enter_shard", "ecfft_build_exit_shard", "ecfft_build_exit_shard_opts",
            "ecfft_fftree_serialize", "ecfft_fftree_deserialize", "ecfft_tree_rational_maps", "ecfft_ctx_trim", "ecfft_comm_abort", "ecfft_comm_set_rccl_library", "ecfft_comm_set_link_striping",
-           "ecfft_poly_mul", "ecfft_poly_inv_series", "ecfft_poly_divrem", "ecfft_poly_eval_points"]
+           "ecfft_poly_mul", "ecfft_poly_inv_series", "ecfft_poly_divrem", "ecfft_poly_eval_points", "ecfft_poly_interpolate"]
 
 # include/ecfft_hip_hooks.h: only in a build with -DECFFT_TEST_HOOKS (tests/hooks/libecfft_hip_hooks.so), never in the shipped library
 HOOK_EXPORTS = ['ecfft_selftest_field', 'ecfft_selfcheck_pointwise_z', 'ecfft_test_fail_next_collective', 'ecfft_selftest_blk16', 'ecfft_selftest_blk16_small', 'ecfft_test_fail_build_rank', 'ecfft_comm_init_projection', 'ecfft_selftest_blk32', 'ecfft_ctx_low_map']
@@ -70,6 +70,7 @@ def _bind(L):
     L.ecfft_poly_inv_series.restype, L.ecfft_poly_inv_series.argtypes = ci, [vp, vp, sz, vp, sz, sz, ci, vp]
     L.ecfft_poly_divrem.restype, L.ecfft_poly_divrem.argtypes = ci, [vp, vp, sz, vp, sz, vp, vp, sz, ci, vp]
     L.ecfft_poly_eval_points.restype, L.ecfft_poly_eval_points.argtypes = ci, [vp, vp, sz, vp, sz, vp, sz, ci, vp]
+    L.ecfft_poly_interpolate.restype, L.ecfft_poly_interpolate.argtypes = ci, [vp, vp, sz, vp, vp, sz, ci, vp]
     L.ecfft_tree_table.restype, L.ecfft_tree_table.argtypes = ci, [vp, sz, ci, vp, sz, ctypes.POINTER(sz)]
     L.ecfft_build_points.restype, L.ecfft_build_points.argtypes = ci, [ci, sz, vp, vp, vp]
     L.ecfft_device_info.restype, L.ecfft_device_info.argtypes = ci, [ci, ctypes.c_char_p, sz]
@@ -459,6 +460,23 @@ class FFTree:
         rc = self._L.ecfft_poly_eval_points(self._h, pf, f.shape[0] // count, pp, m, self._ptr(out) if m else None, count, mem, stream)
         if rc == ERR_BAD_ARG:
             raise ValueError("poly_eval_points: empty f or points, count = 0 or a context that holds no full tree")
+        _check(rc)
+        return out
+
+    def poly_interpolate(self, points, values, count=1):
+        """The polynomial through arbitrary points (ecfft_poly_interpolate; no reference counterpart), the inverse of
+        poly_eval_points: `points` of m pairwise distinct elements shared by `count` value vectors laid end to end (count * m values);
+        returns count * m coefficients, f_b of degree < m with f_b(points[i]) = values[b*m + i].  m <= 64 works on any tree, more
+        points need a tree of next_pow2(m) leaves.  numpy arrays (host) or contiguous CUDA tensors (device, on the current stream),
+        both of the same kind.  Synchronous (two equal points are detected on the device)."""
+        (points, values), (pp, pv), new, mem, stream = self._poly_io([points, values])
+        m = points.shape[0]
+        assert count > 0 and values.shape[0] == count * m
+        out = new(count * m)
+        rc = self._L.ecfft_poly_interpolate(self._h, pp, m, pv, self._ptr(out) if m else None, count, mem, stream)
+        if rc == ERR_BAD_ARG:
+            raise ValueError("poly_interpolate: a repeated point (the points must be pairwise distinct), no points, count = 0 or a "
+                             "context that holds no full tree")
         _check(rc)
         return out
 

@@ -186,6 +186,15 @@ public:
         check(ecfft_poly_eval_points(ctx_, f.data(), f.size(), points.data(), points.size(), out.data(), 1, ECFFT_MEM_HOST, nullptr));
         return out;
     }
+    // the polynomial through arbitrary points (ecfft_poly_interpolate; no reference counterpart), the inverse of eval_points: the
+    // coefficients of f of degree < points.size() with f(points[i]) = values[i]; the points pairwise distinct (else
+    // std::runtime_error, the C ABI's ECFFT_ERR_BAD_ARG); up to 64 points on any tree, otherwise the tree must hold next_pow2(points.size()) leaves
+    std::vector<Elem> interpolate(const std::vector<Elem>& points, const std::vector<Elem>& values) const {
+        require(!points.empty() && points.size() == values.size(), "interpolate: as many values as points, at least one");
+        std::vector<Elem> out(points.size());
+        check(ecfft_poly_interpolate(ctx_, points.data(), points.size(), values.data(), out.data(), 1, ECFFT_MEM_HOST, nullptr));
+        return out;
+    }
     size_t device_bytes() const { return ecfft_ctx_device_bytes(ctx_); }     // HBM held between calls: tables + scratch
     // device-resident variants (pointers into HBM, caller's stream)
     void enter_device(const Elem* coeffs, Elem* evals, size_t n, void* stream) const { check(ecfft_enter(ctx_, coeffs, evals, n, ECFFT_MEM_DEVICE, stream)); }
@@ -206,6 +215,10 @@ public:
     // count polynomials f count x nf at m shared points, out count x m.  Asynchronous on `stream`.
     void eval_points_device(const Elem* f, size_t nf, const Elem* points, size_t m, Elem* out, size_t count, void* stream) const {
         check(ecfft_poly_eval_points(ctx_, f, nf, points, m, out, count, ECFFT_MEM_DEVICE, stream));
+    }
+    // count value vectors (count x m) at m shared, pairwise distinct points, out count x m coefficients.  Synchronous.
+    void interpolate_device(const Elem* points, size_t m, const Elem* values, Elem* out, size_t count, void* stream) const {
+        check(ecfft_poly_interpolate(ctx_, points, m, values, out, count, ECFFT_MEM_DEVICE, stream));
     }
 
     // ONE transform split over the ranks of `comm` (device pointers: this rank's block shard of len / world elements)

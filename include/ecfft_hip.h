@@ -139,6 +139,23 @@ int ecfft_poly_divrem(ecfft_ctx* ctx, const void* a, size_t na, const void* b, s
  * and threading as for ecfft_poly_mul; temporaries are pooled (ecfft_ctx_trim). */
 int ecfft_poly_eval_points(ecfft_ctx* ctx, const void* f, size_t nf, const void* points, size_t m, void* out, size_t count, int mem,
                            void* stream);
+/* Interpolation from arbitrary points on the GPU, the inverse of ecfft_poly_eval_points (no reference counterpart: the crate
+ * interpolates only on its own leaves, EXIT): out: count x m coefficients; f_b of degree < m with f_b(points[i]) = values[b*m + i].
+ * points: m pairwise distinct field elements shared by all `count` value vectors (any values: 0, p - 1, leaves of the tree, in any
+ * order); values: count x m, laid end to end.  out must not overlap the inputs.
+ * Algorithm: Lagrange form f = sum_i c_i M / (x - x_i), c_i = y_i / M'(x_i), on one group of P = max(64, next_pow2(m)) points of
+ * ecfft_poly_eval_points' subproduct tree, padded with the point 0 at weight 0 (the padded sum is x^(P-m) f): M'(x_i) by one remainder
+ * descent, the numerators of every 64 points in one kernel, then per level N = N_l M_r + N_r M_l on the leaves of T_2d and one EXTEND,
+ * one EXIT_P per value vector at the top.
+ * Cost: the subproduct tree, one descent and one product of P coefficients, shared by the count vectors; per vector log2(P/64)
+ * pointwise passes and EXTENDs and one EXIT.
+ * Tree: m <= 64 needs no transform (any tree); otherwise next_pow2(m) leaves (as EXIT of m evaluations rounded up), else
+ * ECFFT_ERR_TREE_TOO_SMALL.  ECFFT_ERR_BAD_ARG: a NULL input or output, m or count 0, a context that holds no full tree, a byte
+ * count that would wrap — and two equal points, which is checked on the device (a zero weight denominator).  Because of that check
+ * the call is SYNCHRONOUS (like ecfft_poly_divrem); the context keeps working after the error.  Memory, stream and threading as
+ * for ecfft_poly_mul; temporaries are pooled (ecfft_ctx_trim). */
+int ecfft_poly_interpolate(ecfft_ctx* ctx, const void* points, size_t m, const void* values, void* out, size_t count, int mem,
+                           void* stream);
 
 /* The remaining FFTree algorithms, composed from the same GPU kernels.  Synchronous.
  *   ecfft_mextend         <-> FFTree::mextend(&self, &[F], Moiety)      src/fftree.rs:138-141
