@@ -56,6 +56,8 @@ pub mod ffi {
         pub fn ecfft_poly_divrem(ctx: *mut EcfftCtx, a: *const c_void, na: usize, b: *const c_void, nb: usize, q: *mut c_void, r: *mut c_void, count: usize, mem: i32, stream: *mut c_void) -> i32;
         pub fn ecfft_poly_eval_points(ctx: *mut EcfftCtx, f: *const c_void, nf: usize, points: *const c_void, m: usize, out: *mut c_void, count: usize, mem: i32, stream: *mut c_void) -> i32;
         pub fn ecfft_poly_interpolate(ctx: *mut EcfftCtx, points: *const c_void, m: usize, values: *const c_void, out: *mut c_void, count: usize, mem: i32, stream: *mut c_void) -> i32;
+        pub fn ecfft_poly_pow_mod(ctx: *mut EcfftCtx, a: *const c_void, na: usize, exp: *const c_void, exp_bytes: usize, modulus: *const c_void, nm: usize, out: *mut c_void, count: usize, mem: i32, stream: *mut c_void) -> i32;
+        pub fn ecfft_poly_mul_mod(ctx: *mut EcfftCtx, a: *const c_void, na: usize, b: *const c_void, nb: usize, modulus: *const c_void, nm: usize, out: *mut c_void, count: usize, mem: i32, stream: *mut c_void) -> i32;
         pub fn ecfft_mextend(ctx: *mut EcfftCtx, inp: *const c_void, out: *mut c_void, e: usize, moiety: i32, count: usize, mem: i32, stream: *mut c_void) -> i32;
         pub fn ecfft_redc(ctx: *mut EcfftCtx, evals: *const c_void, a: *const c_void, out: *mut c_void, n: usize, moiety: i32, mem: i32, stream: *mut c_void) -> i32;
         pub fn ecfft_modular_reduce(ctx: *mut EcfftCtx, evals: *const c_void, a: *const c_void, c: *const c_void, out: *mut c_void, n: usize, mem: i32, stream: *mut c_void) -> i32;
@@ -280,6 +282,31 @@ impl<F: HipField> HipFFTree<F> {
         let mut out = Self::out_vec(points.len());
         check(unsafe { ffi::ecfft_poly_interpolate(self.ctx, points.as_ptr().cast(), points.len(), values.as_ptr().cast(), out.as_mut_ptr().cast(), 1, ffi::MEM_HOST, core::ptr::null_mut()) });
         unsafe { out.set_len(points.len()) };
+        out
+    }
+
+    /// `ecfft::utils::pow_mod` (src/utils.rs:194-211): `a^exp mod modulus` as `modulus.len() - 1` coefficients, zero-padded above
+    /// the degree.  `exp_le` holds the exponent as little-endian bytes (`BigUint::to_bytes_le`; empty or all zero gives 1).  The
+    /// modulus has at least 2 coefficients, the last one nonzero.  Up to 65 modulus coefficients work on any tree; tree rule:
+    /// include/ecfft_hip.h.
+    pub fn pow_mod(&self, a: &[F], exp_le: &[u8], modulus: &[F]) -> Vec<F> {
+        assert!(!a.is_empty() && modulus.len() >= 2);
+        let n = modulus.len() - 1;
+        let mut out = Self::out_vec(n);
+        let pe = if exp_le.is_empty() { core::ptr::null() } else { exp_le.as_ptr().cast() };
+        check(unsafe { ffi::ecfft_poly_pow_mod(self.ctx, a.as_ptr().cast(), a.len(), pe, exp_le.len(), modulus.as_ptr().cast(), modulus.len(), out.as_mut_ptr().cast(), 1, ffi::MEM_HOST, core::ptr::null_mut()) });
+        unsafe { out.set_len(n) };
+        out
+    }
+
+    /// `div_rem(&a.naive_mul(&b), modulus)`, the step of `ecfft::utils::pow_mod` (src/utils.rs:205, 207): `modulus.len() - 1`
+    /// coefficients, zero-padded above the degree.
+    pub fn mul_mod(&self, a: &[F], b: &[F], modulus: &[F]) -> Vec<F> {
+        assert!(!a.is_empty() && !b.is_empty() && modulus.len() >= 2);
+        let n = modulus.len() - 1;
+        let mut out = Self::out_vec(n);
+        check(unsafe { ffi::ecfft_poly_mul_mod(self.ctx, a.as_ptr().cast(), a.len(), b.as_ptr().cast(), b.len(), modulus.as_ptr().cast(), modulus.len(), out.as_mut_ptr().cast(), 1, ffi::MEM_HOST, core::ptr::null_mut()) });
+        unsafe { out.set_len(n) };
         out
     }
 

@@ -1,7 +1,7 @@
 //! Bit-exact parity of the MI355X path with the real `ecfft` crate — the parity suite this repo could not run itself
 //! (no Rust in the build image).  UNCOMPILED SOURCE.  Shapes follow the reference's own tests (src/lib.rs:108-186, 239-278)
 //! and bench (benches/fftree.rs:19-62); every comparison is `assert_eq!` on `Vec<F>`, i.e. on canonical field elements.
-use ark_ff::{One, UniformRand};
+use ark_ff::{One, PrimeField, UniformRand, Zero};
 use ecfft::{FFTree, FftreeField, Moiety};
 use ecfft_hip::{ffi, HipFFTree, HipField};
 use rand::rngs::StdRng;
@@ -77,6 +77,39 @@ fn all_algorithms_match<F: HipField>(log_tree: u32) {
     let mirrored = HipFFTree::from_cpu_tree(&cpu, 0);
     let v: Vec<F> = rand_vec(n_tree, 99);
     assert_eq!(mirrored.enter(&v), cpu.enter(&v));
+}
+
+/// `pow_mod` / `mul_mod` against `ecfft::utils::pow_mod` (src/utils.rs:194-211): the reference trims its result, the GPU pads it
+fn pow_mod_matches<F: HipField>(log_tree: u32) {
+    use ark_poly::univariate::DensePolynomial;
+    use ark_poly::DenseUVPolynomial;
+    use num_bigint::BigUint;
+    let gpu: HipFFTree<F> = HipFFTree::build_fftree(1usize << log_tree).unwrap();
+    for (na, nm, exp) in [(1usize, 2usize, 5u64), (10, 4, 0), (3, 40, 1), (64, 65, 0xB6E5), (200, 66, 0xB6E5), (300, 301, 1234567), (700, 130, 77)] {
+        let (a, b) = (rand_vec::<F>(na, 7), rand_vec::<F>(na + 3, 9));
+        let mut m: Vec<F> = rand_vec(nm, 8);
+        if m[nm - 1] == F::zero() {
+            m[nm - 1] = F::one();
+        }
+        let (pa, pb, pm) = (DensePolynomial::from_coefficients_slice(&a), DensePolynomial::from_coefficients_slice(&b), DensePolynomial::from_coefficients_slice(&m));
+        let pad = |p: DensePolynomial<F>| { let mut c = p.coeffs; c.resize(nm - 1, F::zero()); c };
+        let e = BigUint::from(exp);
+        assert_eq!(gpu.pow_mod(&a, &e.to_bytes_le(), &m), pad(ecfft::utils::pow_mod(&pa, e.clone(), &pm)), "POW_MOD na={na} nm={nm}");
+        assert_eq!(gpu.mul_mod(&a, &b, &m), pad(ecfft::utils::div_rem(&pa.naive_mul(&pb), &pm)), "MUL_MOD na={na} nm={nm}");
+    }
+    // the full characteristic as the exponent (the power distinct_degree_factors takes)
+    let p: BigUint = F::MODULUS.into();
+    let (a, m): (Vec<F>, Vec<F>) = (rand_vec(30, 3), { let mut m = rand_vec::<F>(21, 4); m[20] = F::one(); m });
+    let want = ecfft::utils::pow_mod(&DensePolynomial::from_coefficients_slice(&a), p.clone(), &DensePolynomial::from_coefficients_slice(&m));
+    let mut want = want.coeffs;
+    want.resize(20, F::zero());
+    assert_eq!(gpu.pow_mod(&a, &p.to_bytes_le(), &m), want);
+}
+
+#[test]
+fn pow_mod_matches_the_crate() {
+    pow_mod_matches::<ecfft::secp256k1::Fp>(12);
+    pow_mod_matches::<ecfft::m31::Fp>(12);
 }
 
 #[test]

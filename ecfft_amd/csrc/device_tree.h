@@ -1668,6 +1668,167 @@ public:
         }
         return finish_flagged(ok, flag, singular, s);
     }
+    // The remainder half of poly_divrem inside a longer call (poly_pow_mod and poly_mul_mod reduce their operands with it): r_b =
+    // a_b mod f_b for nm >= 2 (r: count x (nm - 1)), the same reciprocal, products and subtraction, without the quotient's output,
+    // the read-back of the flag and the release of the temporaries.  na < nm copies a into r and checks the leading coefficient.
+    bool rem_body(const E* a, size_t na, const E* f, size_t nm, E* r, size_t count, int* flag, hipStream_t s) {
+        const size_t nq = na >= nm ? na - nm + 1 : 0, nr = nm - 1;
+        if (nq == 0) {
+            E* finv = temp(count);
+            series_base(f + nm - 1, nm, 1, finv, 1, 1, count, flag, s);
+            foreach_n(s, count * nr, [=] __device__(size_t i) { const size_t bi = i / nr, j = i - bi * nr; r[i] = j < na ? a[bi * na + j] : F::zero(); });
+            return true;
+        }
+        const size_t nf = nq < nm ? nq : nm, np = 2 * nq - 1;
+        E* fr = temp(count * nf); E* ar = temp(count * nq); E* g = temp(count * nq); E* pq = temp(count * np); E* qq = temp(count * nq);
+        foreach_n(s, count * nf, [=] __device__(size_t i) { const size_t bi = i / nf, j = i - bi * nf; fr[i] = f[bi * nm + nm - 1 - j]; });
+        foreach_n(s, count * nq, [=] __device__(size_t i) { const size_t bi = i / nq, j = i - bi * nq; ar[i] = a[bi * na + na - 1 - j]; });
+        bool ok = inv_series_body(fr, nf, nf, g, nq, count, flag, s);
+        ok = poly_mul_body(ar, nq, nq, g, nq, nq, pq, count, s) && ok;
+        foreach_n(s, count * nq, [=] __device__(size_t i) { const size_t bi = i / nq, j = i - bi * nq; qq[i] = pq[bi * np + nq - 1 - j]; });
+        const size_t mq = nq < nr ? nq : nr, npr = nr + mq - 1, total = count * nr;
+        E* pr = temp(count * npr);
+        ok = poly_mul_body(f, nr, nm, qq, mq, nq, pr, count, s) && ok;
+        ECFFT_LAUNCH(KC_POINTWISE, sizeof(E) * 3.0 * (double)total, k_divrem_sub<F>, dim3(nblocks(total)), dim3(kBlock), 0, s,
+                     r, nr, a, na, (const E*)pr, npr, total);
+        return ok;
+    }
+
+    // ecfft_poly_mul_mod (the step of utils::pow_mod, src/utils.rs:205, 207: div_rem(&a.naive_mul(&b), modulus)): out_b =
+    // a_b b_b mod f_b for `count` triples laid end to end (out: count x (nm - 1), zero-padded above its degree).  One poly_mul and one
+    // division on its output, the temporaries held across both.  Synchronous; *singular = some f_b[nm-1] == 0.  Caller holds lock().
+    bool poly_mul_mod(const E* a, size_t na, const E* b, size_t nb, const E* f, size_t nm, E* out, size_t count, bool* singular, hipStream_t s) {
+        int* flag = new_flag(s);
+        const size_t nc = na + nb - 1;
+        E* c = temp(count * nc);
+        bool ok = poly_mul_body(a, na, na, b, nb, nb, c, count, s);
+        ok = rem_body(c, nc, f, nm, out, count, flag, s) && ok;
+        return finish_flagged(ok, flag, singular, s);
+    }
+
+    // residues of at most this many coefficients are exponentiated by k_powmod_small (one workgroup per pair, no transform)
+    static constexpr size_t kPowSmall = 64;
+    // ecfft_poly_pow_mod (utils::pow_mod, src/utils.rs:194-211): out_b = a_b^e mod f_b for `count` pairs laid end to end (a: count x
+    // na, f: count x nm, out: count x d, d = nm - 1, zero-padded above its degree); e: `nbits` bits in little-endian HOST bytes with
+    // bit nbits - 1 set (nbits == 0: out_b = 1), shared by all pairs.  a is reduced below nm coefficients first (rem_body).
+    //   d <= kPowSmall: k_powmod_small, the whole scan in one launch.
+    //   otherwise, on T_N, N = next_pow2(2d - 1): g = 1/rev(f) mod x^(d-1) once (inv_series_body), then g, f mod x^d and the base
+    //   lifted ONCE to evaluations kept for the call (3 count N elements); res = a, then per bit below the top one a squaring and,
+    //   on a set bit, a product with the kept base.  A modular product (powmod_step) is three lifts and three batched EXIT_N:
+    //     c = x y                                  (2d - 1 coefficients; y is x itself or the kept base)
+    //     q = rev(rev(c) mod x^(d-1) g mod x^(d-1))   against the kept g   (2d - 3 coefficients before the cut)
+    //     res = (c mod x^d) - (f mod x^d) q mod x^d   against the kept f   (2d - 2 coefficients before the cut)
+    //   none of which wraps on N leaves.  No Newton step and no transform of g, f or the base inside the scan; a step's temporaries
+    //   go back to the pool after every product.
+    // Synchronous; *singular = some f_b[nm-1] == 0.  Caller holds lock() and checks the tree rule.
+    bool poly_pow_mod(const E* a, size_t na, const uint8_t* exp, size_t nbits, const E* f, size_t nm, E* out, size_t count, bool* singular,
+                      hipStream_t s) {
+        int* flag = new_flag(s);
+        const size_t d = nm - 1;
+        bool ok = true;
+        const E* ar = a;                                         // the base below nm coefficients: count rows of la at a stride of lda
+        size_t lda = na, la = na;
+        if (na >= nm) {
+            E* r = temp(count * d);
+            ok = rem_body(a, na, f, nm, r, count, flag, s) && ok;
+            ar = r; lda = la = d;
+        }
+        const E r1 = F::to_mont(F::one());
+        const TE rinv = F::to_table(rinv_);
+        if (d <= kPowSmall) {
+            const size_t nbytes = (nbits + 7) / 8;
+            uint8_t* dexp = reinterpret_cast<uint8_t*>(temp((nbytes + sizeof(E) - 1) / sizeof(E)));
+            if (nbytes) ok = hipMemcpyAsync(dexp, exp, nbytes, hipMemcpyHostToDevice, s) == hipSuccess && ok;
+            for (size_t c0 = 0; c0 < count; c0 += (size_t)1 << 16) {
+                const size_t c = count - c0 < ((size_t)1 << 16) ? count - c0 : (size_t)1 << 16;
+                ECFFT_LAUNCH(KC_POINTWISE, sizeof(E) * (double)c * (double)(la + nm + d) + (double)nbytes,
+                             (k_powmod_small<F, (int)kPowSmall>), dim3((unsigned)c), dim3((unsigned)kPowSmall), 0, s, out + c0 * d,
+                             ar + c0 * lda, lda, (uint32_t)la, f + c0 * nm, (uint32_t)d, (const uint8_t*)dexp, (uint32_t)nbits, rinv, r1, flag);
+            }
+            return finish_flagged(ok, flag, singular, s);
+        }
+        size_t N = 1; while (N < 2 * d - 1) N <<= 1;
+        const size_t h = N / 2, total = count * N;
+        const unsigned lN = ilog2(N);
+        // ---- once per call: g, then the evaluations of g | f mod x^d | base on T_N in the natural leaf order ----
+        E* kept = temp(3 * total);
+        {
+            const TempMark mark = temps_mark();
+            const size_t ng = d - 1;
+            E* fr = temp(count * ng); E* g = temp(count * ng); E* S = temp(3 * count * d);
+            foreach_n(s, count * ng, [=] __device__(size_t i) { const size_t b = i / ng, j = i - b * ng; fr[i] = f[b * nm + d - j]; });
+            ok = inv_series_body(fr, ng, ng, g, ng, count, flag, s) && ok;
+            const size_t cd = count * d;
+            foreach_n(s, 3 * cd, [=] __device__(size_t i) {
+                const size_t w = i / cd, k = i - w * cd, b = k / d, j = k - b * d;
+                S[i] = w == 0 ? (j < ng ? g[b * ng + j] : F::zero()) : w == 1 ? f[b * nm + j] : (j < la ? ar[b * lda + j] : F::zero());
+            });
+            E* U = temp(3 * count * h); E* V = temp(3 * count * h); E* X = temp(3 * count * h);
+            PolyEvals<F> ev;
+            ok = lift_one(S, d, d, false, 0, N, 3 * count, U, V, X, &ev, s) && ok;
+            foreach_n(s, 3 * total, [=] __device__(size_t i) {
+                const size_t r = i >> lN, k = (i & (N - 1)) >> 1;
+                kept[i] = ((i & 1) ? ev.odd : ev.even)[r * ev.batch + k * ev.stride];
+            });
+            temps_release(mark);
+        }
+        const E* kept_g = kept; const E* kept_f = kept + total; const E* kept_a = kept + 2 * total;
+        if (nbits == 0) foreach_n(s, count * d, [=] __device__(size_t i) { out[i] = i % d == 0 ? r1 : F::zero(); });
+        else foreach_n(s, count * d, [=] __device__(size_t i) { const size_t b = i / d, j = i - b * d; out[i] = j < la ? ar[b * lda + j] : F::zero(); });
+        for (size_t i = nbits > 0 ? nbits - 1 : 0; i-- > 0;) {
+            ok = powmod_step(out, nullptr, kept_g, kept_f, d, N, count, rinv, s) && ok;
+            if ((exp[i >> 3] >> (i & 7)) & 1) ok = powmod_step(out, kept_a, kept_g, kept_f, d, N, count, rinv, s) && ok;
+        }
+        return finish_flagged(ok, flag, singular, s);
+    }
+    // One modular product of poly_pow_mod in place: res (count x d) = res y mod f, y = res itself (kept_y == nullptr) or the kept base
+    bool powmod_step(E* res, const E* kept_y, const E* kept_g, const E* kept_f, size_t d, size_t N, size_t count, TE rinv, hipStream_t s) {
+        const size_t h = N / 2, total = count * N;
+        const unsigned lN = ilog2(N);
+        const TempMark mark = temps_mark();
+        E* U = temp(count * h); E* V = temp(count * h); E* X = temp(count * h); E* C = temp(total); E* T = temp(total);
+        PolyEvals<F> ev;
+        bool ok = lift_one(res, d, d, false, 0, N, count, U, V, X, &ev, s);
+        ECFFT_LAUNCH(KC_POINTWISE, sizeof(E) * (kept_y ? 3.0 : 2.0) * (double)total, k_powmod_pointwise<F>, dim3(nblocks(total)), dim3(kBlock), 0, s,
+                     C, ev, kept_y, rinv, lN, total);
+        ok = exit(C, C, N, count, s) && ok;                      // c = res y: 2d - 1 coefficients
+        ok = lift_one(C, d - 1, N, true, 2 * d - 2, N, count, U, V, X, &ev, s) && ok;
+        ECFFT_LAUNCH(KC_POINTWISE, sizeof(E) * 3.0 * (double)total, k_powmod_pointwise<F>, dim3(nblocks(total)), dim3(kBlock), 0, s,
+                     T, ev, kept_g, rinv, lN, total);
+        ok = exit(T, T, N, count, s) && ok;                      // rev(c) g: its first d - 1 coefficients are rev(q)
+        ok = lift_one(T, d - 1, N, true, d - 2, N, count, U, V, X, &ev, s) && ok;
+        ECFFT_LAUNCH(KC_POINTWISE, sizeof(E) * 3.0 * (double)total, k_powmod_pointwise<F>, dim3(nblocks(total)), dim3(kBlock), 0, s,
+                     T, ev, kept_f, rinv, lN, total);
+        ok = exit(T, T, N, count, s) && ok;                      // (f mod x^d) q
+        const size_t nres = count * d;
+        ECFFT_LAUNCH(KC_POINTWISE, sizeof(E) * 3.0 * (double)nres, k_powmod_sub<F>, dim3(nblocks(nres)), dim3(kBlock), 0, s,
+                     res, d, (const E*)C, (const E*)T, N, nres);
+        temps_release(mark);
+        return ok;
+    }
+    // lift_operands for ONE operand of at most N/2 coefficients with the reversal folded into its pad load: count rows of len
+    // coefficients at a row stride of ld (rev: read downwards from index top) entered at m = next_pow2(len) and lifted to N; *ev
+    // reads the evaluations on the leaves of T_N (the last lift's interleave).  U, V, X: count x N/2 elements of work each.
+    bool lift_one(const E* src, size_t len, size_t ld, bool rev, size_t top, size_t N, size_t count, E* U, E* V, E* X, PolyEvals<F>* ev,
+                  hipStream_t s) {
+        const size_t h = N / 2;
+        size_t m = 1; while (m < len) m <<= 1;
+        const size_t padded = count * m;
+        ECFFT_LAUNCH(KC_POINTWISE, sizeof(E) * ((double)count * (double)len + (double)padded), k_powmod_pad<F>, dim3(nblocks(padded)), dim3(kBlock),
+                     0, s, U, src, len, ld, rev ? 1u : 0u, top, ilog2(m), padded);
+        bool ok = enter(U, U, m, count, s);
+        E* c = U;
+        for (size_t mm = m; mm < h; mm *= 2) {
+            E* dst = c == U ? V : U;
+            const E* cur = c;
+            ok = extend_api(cur, X, mm, count, 1, s) && ok;
+            foreach_n(s, 2 * mm * count, [=] __device__(size_t i) { dst[i] = (i & 1) ? X[i >> 1] : cur[i >> 1]; });
+            c = dst;
+        }
+        ok = extend_api(c, X, h, count, 1, s) && ok;              // the last lift's EXTEND; its interleave is the pointwise load
+        *ev = PolyEvals<F>{c, X, h, 1u};
+        return ok;
+    }
 
     // coefficients of the reciprocal computed by k_series_base before the Newton steps take over (K0).  64 = one wave per pair: a
     // Newton step at p <= 64 costs a lift + EXIT in the latency regime, the recurrence's 63 tree sums a few us.

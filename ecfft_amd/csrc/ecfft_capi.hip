@@ -374,6 +374,77 @@ int run_poly_interpolate(ecfft_ctx* c, DeviceChain<F>& ch, const void* points, s
     });
 }
 
+// the leaves ecfft_poly_divrem(na, nb) needs (run_poly_divrem's rule; 1 = no transform)
+inline size_t divrem_leaves(size_t na, size_t nb) {
+    const size_t nq = na >= nb ? na - nb + 1 : 0, nr = nb - 1;
+    size_t N = 1;
+    if (nq && nr) {
+        const size_t mq = nq < nr ? nq : nr, need = 2 * nq - 1 > nr + mq - 1 ? 2 * nq - 1 : nr + mq - 1;
+        while (N < need) N <<= 1;
+    }
+    return N;
+}
+
+// ecfft_poly_pow_mod / ecfft_poly_mul_mod: synchronous (the chain reads back the device flag of a zero leading coefficient of the
+// modulus, reported as ECFFT_ERR_BAD_ARG)
+template <class F>
+int run_poly_pow_mod(ecfft_ctx* c, DeviceChain<F>& ch, const void* a, size_t na, const void* exp, size_t exp_bytes, const void* modulus,
+                     size_t nm, void* out, size_t count, int mem, void* stream) {
+    using E = typename F::elem;
+    if (!a || !modulus || !out || (!exp && exp_bytes)) return ECFFT_ERR_BAD_ARG;
+    const size_t lim = SIZE_MAX / (64 * sizeof(E));
+    if (na > lim || nm > lim) return ECFFT_ERR_BAD_ARG;
+    const size_t d = nm - 1;
+    size_t N = 1;
+    if (d > DeviceChain<F>::kPowSmall) {
+        while (N < 2 * d - 1) N <<= 1;
+        if (N > ch.size()) return ECFFT_ERR_TREE_TOO_SMALL;
+    }
+    const size_t Nd = divrem_leaves(na, nm);
+    if (Nd > ch.size()) return ECFFT_ERR_TREE_TOO_SMALL;
+    size_t per = N > Nd ? N : Nd;
+    if (per < na + nm) per = na + nm;
+    if (count > SIZE_MAX / (16 * per * sizeof(E))) return ECFFT_ERR_BAD_ARG; // byte counts of the temporaries must not wrap
+    const uint8_t* e = (const uint8_t*)exp;                                  // high zero bytes do not count
+    while (exp_bytes && e[exp_bytes - 1] == 0) --exp_bytes;
+    size_t nbits = 0;
+    if (exp_bytes) {
+        if (exp_bytes > UINT32_MAX / 8) return ECFFT_ERR_BAD_ARG;
+        nbits = 8 * exp_bytes;
+        while (!((e[(nbits - 1) >> 3] >> ((nbits - 1) & 7)) & 1)) --nbits;
+    }
+    const size_t eb = count * sizeof(E);
+    return staged(c, ch, mem, stream, {{a, na * eb}, {modulus, nm * eb}}, {{out, d * eb}}, [&](auto dv, auto o) -> int {
+        bool singular = false;
+        if (!ch.poly_pow_mod((const E*)dv[0], na, e, nbits, (const E*)dv[1], nm, (E*)o[0], count, &singular, (hipStream_t)stream)) return ECFFT_ERR_HIP;
+        return singular ? ECFFT_ERR_BAD_ARG : ECFFT_OK;                      // a zero leading coefficient of the modulus in some pair
+    });
+}
+
+template <class F>
+int run_poly_mul_mod(ecfft_ctx* c, DeviceChain<F>& ch, const void* a, size_t na, const void* b, size_t nb, const void* modulus, size_t nm,
+                     void* out, size_t count, int mem, void* stream) {
+    using E = typename F::elem;
+    if (!a || !b || !modulus || !out) return ECFFT_ERR_BAD_ARG;
+    const size_t lim = SIZE_MAX / (64 * sizeof(E));
+    if (na > lim || nb > lim || nm > lim) return ECFFT_ERR_BAD_ARG;
+    const size_t nc = na + nb - 1, d = nm - 1;
+    size_t N = 1; while (N < nc) N <<= 1;
+    if (N > ch.size()) return ECFFT_ERR_TREE_TOO_SMALL;
+    const size_t Nd = divrem_leaves(nc, nm);
+    if (Nd > ch.size()) return ECFFT_ERR_TREE_TOO_SMALL;
+    size_t per = N > Nd ? N : Nd;
+    if (per < nc + nm) per = nc + nm;
+    if (count > SIZE_MAX / (16 * per * sizeof(E))) return ECFFT_ERR_BAD_ARG; // byte counts of the temporaries must not wrap
+    const size_t eb = count * sizeof(E);
+    return staged(c, ch, mem, stream, {{a, na * eb}, {b, nb * eb}, {modulus, nm * eb}}, {{out, d * eb}}, [&](auto dv, auto o) -> int {
+        bool singular = false;
+        if (!ch.poly_mul_mod((const E*)dv[0], na, (const E*)dv[1], nb, (const E*)dv[2], nm, (E*)o[0], count, &singular, (hipStream_t)stream))
+            return ECFFT_ERR_HIP;
+        return singular ? ECFFT_ERR_BAD_ARG : ECFFT_OK;
+    });
+}
+
 // standard = true: plain standard-form residues (the FFTree wire format) instead of the crate's in-memory representation
 template <class F>
 int table_of(DeviceChain<F>& ch, size_t m, int which, void* host_out, size_t cap, size_t* count, bool standard = false) {
@@ -938,6 +1009,16 @@ int ecfft_poly_inv_series(ecfft_ctx* ctx, const void* f, size_t nf, void* out, s
 int ecfft_poly_divrem(ecfft_ctx* ctx, const void* a, size_t na, const void* b, size_t nb, void* q, void* r, size_t count, int mem, void* stream) {
     if (na == 0 || nb == 0 || count == 0) return ECFFT_ERR_BAD_ARG;
     return on_chain(ctx, [&](auto& ch) { return run_poly_divrem(ctx, ch, a, na, b, nb, q, r, count, mem, stream); });
+}
+int ecfft_poly_pow_mod(ecfft_ctx* ctx, const void* a, size_t na, const void* exp, size_t exp_bytes, const void* modulus, size_t nm,
+                       void* out, size_t count, int mem, void* stream) {
+    if (na == 0 || nm < 2 || count == 0) return ECFFT_ERR_BAD_ARG;
+    return on_chain(ctx, [&](auto& ch) { return run_poly_pow_mod(ctx, ch, a, na, exp, exp_bytes, modulus, nm, out, count, mem, stream); });
+}
+int ecfft_poly_mul_mod(ecfft_ctx* ctx, const void* a, size_t na, const void* b, size_t nb, const void* modulus, size_t nm, void* out,
+                       size_t count, int mem, void* stream) {
+    if (na == 0 || nb == 0 || nm < 2 || count == 0) return ECFFT_ERR_BAD_ARG;
+    return on_chain(ctx, [&](auto& ch) { return run_poly_mul_mod(ctx, ch, a, na, b, nb, modulus, nm, out, count, mem, stream); });
 }
 int ecfft_poly_eval_points(ecfft_ctx* ctx, const void* f, size_t nf, const void* points, size_t m, void* out, size_t count, int mem,
                            void* stream) {

@@ -2274,6 +2274,113 @@ __global__ __launch_bounds__(kBlock) void k_interp_combine(typename F::elem* __r
 }
 
 // ---------------------------------------------------------------------------------------------
+// ecfft_poly_pow_mod (utils::pow_mod, src/utils.rs:194-211: square-and-multiply with a div_rem per step).  Above K coefficients a
+// modular product is three products on T_N against operands whose evaluations are kept for the whole call (the base, the
+// reciprocal g of the reversed modulus, the modulus); up to K the whole exponentiation of a residue runs in one workgroup.
+// ---------------------------------------------------------------------------------------------
+// The pad load of a lift: count rows of n coefficients at a row stride of ld -> count rows of 2^log_m, zero-padded.  rev: the
+// row is read downwards from index `top` (dst[j] = src[top - j]), so rev(c) mod x^n and the reversal that turns the low half of
+// a product into the quotient need no pass of their own.
+template <class F>
+__global__ __launch_bounds__(kBlock) void k_powmod_pad(typename F::elem* __restrict__ dst, const typename F::elem* __restrict__ src, size_t n,
+                                                       size_t ld, uint32_t rev, size_t top, uint32_t log_m, size_t total) {
+    const size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= total) return;
+    const size_t b = i >> log_m, j = i & (((size_t)1 << log_m) - 1);
+    dst[i] = j < n ? src[b * ld + (rev ? top - j : j)] : F::zero();
+}
+// Pointwise product of a lifted operand (PolyEvals, as k_poly_pointwise reads it) with an operand cached for the call in the
+// natural leaf order EXIT reads (cached row r at cached + (r << log_n)); cached == nullptr squares the lifted operand.  Scaling
+// as k_poly_pointwise: both operands are user-form evaluations, the plain product carries R^2 and one table multiply by R^-1
+// puts it back in the crate's form (M31: R = 1).
+template <class F>
+__global__ __launch_bounds__(kBlock) void k_powmod_pointwise(typename F::elem* __restrict__ out, PolyEvals<F> a,
+                                                             const typename F::elem* __restrict__ cached, typename F::telem rinv,
+                                                             uint32_t log_n, size_t total) {
+    using E = typename F::elem;
+    const size_t g = (size_t)blockIdx.x * kBlock + threadIdx.x;
+    if (g >= total) return;
+    const size_t bi = g >> log_n, j = g & (((size_t)1 << log_n) - 1), k = j >> 1;
+    const E* pa = (j & 1) ? a.odd : a.even;
+    const E x = pa[bi * a.batch + k * a.stride];
+    E r = F::mul(x, cached ? cached[g] : x);
+    if constexpr (sizeof(E) == 32) r = F::tmul(rinv, r);
+    out[g] = F::canon(r);
+}
+// The end of a modular product: res[b*d + j] = c[b*ld + j] - t[b*ld + j] for j < d (c: the product x y, t: (f mod x^d) q)
+template <class F>
+__global__ __launch_bounds__(kBlock) void k_powmod_sub(typename F::elem* __restrict__ res, size_t d, const typename F::elem* __restrict__ c,
+                                                       const typename F::elem* __restrict__ t, size_t ld, size_t total) {
+    const size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= total) return;
+    const size_t b = i / d, j = i - b * d;
+    res[i] = F::canon(F::sub(F::canon(c[b * ld + j]), F::canon(t[b * ld + j])));
+}
+// a^exp mod f for residues of d <= K coefficients: one workgroup of K threads per pair, the whole left-to-right square-and-multiply
+// in LDS.  a: row b at a + b*lda, na <= d coefficients (crate form); f: row b at f + b*(d+1), d + 1 coefficients; exp: nbits bits,
+// little-endian bytes, bit nbits-1 set (nbits == 0: the result is 1); out: count x d.  f is made monic once (one Fermat inversion
+// of its leading coefficient; a zero one stores 1 to *flag) and kept as PLAIN residues: f_t / f_d is the same number in either
+// form.  A product brings its left operand to plain form (one table multiply by R^-1 per coefficient, M31: R = 1), so every inner
+// multiply is plain x crate: thread t sums the d terms of coefficients t and t + d of the schoolbook product (those with i <= t
+// belong to the first), then d - 1 elimination steps of the monic f fold coefficients 2d-2 .. d back.  r1 = R, the crate's 1.
+template <class F, int K>
+__global__ __launch_bounds__(K) void k_powmod_small(typename F::elem* __restrict__ out, const typename F::elem* __restrict__ a, size_t lda,
+                                                    uint32_t na, const typename F::elem* __restrict__ f, uint32_t d,
+                                                    const uint8_t* __restrict__ exp, uint32_t nbits, typename F::telem rinv,
+                                                    typename F::elem r1, int* __restrict__ flag) {
+    using E = typename F::elem;
+    __shared__ E sres[K], sbase[K], smod[K], sx[K], sprod[2 * K];
+    const uint32_t t = threadIdx.x;
+    const size_t b = blockIdx.x;
+    const E* fb = f + b * ((size_t)d + 1);
+    if (t == 0) {
+        const E lead = F::canon(fb[d]);
+        if (F::is_zero(lead)) *flag = 1;
+        sx[0] = F::canon(F::inv(lead));                  // inv(0) = 0: a flagged pair computes on a zero modulus, its row is not used
+    }
+    __syncthreads();
+    const E linv = sx[0];
+    __syncthreads();
+    smod[t] = t < d ? F::canon(F::mul(fb[t], linv)) : F::zero();
+    sbase[t] = t < na ? a[b * lda + t] : F::zero();
+    sres[t] = sbase[t];
+    __syncthreads();
+    if (nbits == 0) {
+        if (t < d) out[b * d + t] = t == 0 ? r1 : F::zero();
+        return;
+    }
+    for (uint32_t i = nbits - 1; i-- > 0;) {
+        const uint32_t passes = 1 + ((exp[i >> 3] >> (i & 7)) & 1);     // a squaring, then on a set bit a product with the base
+        for (uint32_t pass = 0; pass < passes; ++pass) {
+            const E* y = pass ? sbase : sres;                           // sres = sres * y mod f
+            E x = sres[t];
+            if constexpr (sizeof(E) == 32) x = F::tmul(rinv, x);
+            sx[t] = F::canon(x);
+            __syncthreads();
+            if (t < d) {
+                E acc = F::zero(), lo = F::zero();
+                for (uint32_t k = 0; k < d; ++k) {
+                    if (k == t + 1) { lo = acc; acc = F::zero(); }
+                    const uint32_t j = k <= t ? t - k : t + d - k;
+                    acc = F::canon(F::mul_add(sx[k], y[j], acc));
+                }
+                if (t + 1 == d) { lo = acc; acc = F::zero(); }          // the last thread never switched: coefficient 2d - 1 does not exist
+                sprod[t] = lo;
+                sprod[t + d] = acc;
+            }
+            __syncthreads();
+            for (uint32_t k = 2 * d - 2; k >= d; --k) {
+                if (t < d) sprod[k - d + t] = F::canon(F::sub(sprod[k - d + t], F::canon(F::mul(sprod[k], smod[t]))));
+                __syncthreads();
+            }
+            if (t < d) sres[t] = sprod[t];
+            __syncthreads();
+        }
+    }
+    if (t < d) out[b * d + t] = sres[t];
+}
+
+// ---------------------------------------------------------------------------------------------
 // generic element-wise helper for tree construction: functor(i) for i < n
 // ---------------------------------------------------------------------------------------------
 template <class Fn>

@@ -32,7 +32,8 @@ EXPORTS = ["ecfft_elem_size", "ecfft_build_fftree", "ecfft_fftree_new", "ecfft_c
            "ecfft_comm_get_unique_id", "ecfft_comm_init_rank", "ecfft_comm_init_callback", "ecfft_comm_destroy", "ecfft_comm_rank", "ecfft_comm_world",
            "ecfft_comm_stats_enable", "ecfft_comm_stats_read", "ecfft_extend_sharded", "ecfft_enter_sharded", "ecfft_exit_sharded", "ecfft_device_copy", "ecfft_shader_clock", "ecfft_device_alloc", "ecfft_device_free", "ecfft_device_sync", "ecfft_build_extend_shard", "ecfft_ctx_device_bytes", "ecfft_extend_sharded_layout", "ecfft_build_enter_shard", "ecfft_build_exit_shard", "ecfft_build_exit_shard_opts",
            "ecfft_fftree_serialize", "ecfft_fftree_deserialize", "ecfft_tree_rational_maps", "ecfft_ctx_trim", "ecfft_comm_abort", "ecfft_comm_set_rccl_library", "ecfft_comm_set_link_striping",
-           "ecfft_poly_mul", "ecfft_poly_inv_series", "ecfft_poly_divrem", "ecfft_poly_eval_points", "ecfft_poly_interpolate"]
+           "ecfft_poly_mul", "ecfft_poly_inv_series", "ecfft_poly_divrem", "ecfft_poly_eval_points", "ecfft_poly_interpolate",
+           "ecfft_poly_pow_mod", "ecfft_poly_mul_mod"]
 
 # include/ecfft_hip_hooks.h: only in a build with -DECFFT_TEST_HOOKS (tests/hooks/libecfft_hip_hooks.so), never in the shipped library
 HOOK_EXPORTS = ['ecfft_selftest_field', 'ecfft_selfcheck_pointwise_z', 'ecfft_test_fail_next_collective', 'ecfft_selftest_blk16', 'ecfft_selftest_blk16_small', 'ecfft_test_fail_build_rank', 'ecfft_comm_init_projection', 'ecfft_selftest_blk32', 'ecfft_ctx_low_map']
@@ -71,6 +72,8 @@ def _bind(L):
     L.ecfft_poly_divrem.restype, L.ecfft_poly_divrem.argtypes = ci, [vp, vp, sz, vp, sz, vp, vp, sz, ci, vp]
     L.ecfft_poly_eval_points.restype, L.ecfft_poly_eval_points.argtypes = ci, [vp, vp, sz, vp, sz, vp, sz, ci, vp]
     L.ecfft_poly_interpolate.restype, L.ecfft_poly_interpolate.argtypes = ci, [vp, vp, sz, vp, vp, sz, ci, vp]
+    L.ecfft_poly_pow_mod.restype, L.ecfft_poly_pow_mod.argtypes = ci, [vp, vp, sz, vp, sz, vp, sz, vp, sz, ci, vp]
+    L.ecfft_poly_mul_mod.restype, L.ecfft_poly_mul_mod.argtypes = ci, [vp, vp, sz, vp, sz, vp, sz, vp, sz, ci, vp]
     L.ecfft_tree_table.restype, L.ecfft_tree_table.argtypes = ci, [vp, sz, ci, vp, sz, ctypes.POINTER(sz)]
     L.ecfft_build_points.restype, L.ecfft_build_points.argtypes = ci, [ci, sz, vp, vp, vp]
     L.ecfft_device_info.restype, L.ecfft_device_info.argtypes = ci, [ci, ctypes.c_char_p, sz]
@@ -477,6 +480,47 @@ class FFTree:
         if rc == ERR_BAD_ARG:
             raise ValueError("poly_interpolate: a repeated point (the points must be pairwise distinct), no points, count = 0 or a "
                              "context that holds no full tree")
+        _check(rc)
+        return out
+
+    def poly_pow_mod(self, a, exp, modulus, count=1):
+        """a^exp mod modulus (ecfft_poly_pow_mod <-> utils::pow_mod, src/utils.rs:194-211): `count` pairs laid end to end, a of count *
+        na and modulus of count * nm coefficients, the modulus' leading coefficient nonzero in every pair; `exp` is one non-negative
+        Python int shared by all pairs (0 gives the polynomial 1).  Returns count * (nm - 1) coefficients, zero-padded above the
+        degree.  nm <= 65 works on any tree (the whole power runs in one workgroup per pair); a longer modulus needs a tree of
+        next_pow2(2 (nm - 1) - 1) leaves, and na >= nm what poly_divrem(na, nm) needs.  numpy arrays (host) or contiguous CUDA tensors
+        (device, on the current stream), both of the same kind.  Synchronous."""
+        exp = int(exp)
+        if exp < 0:
+            raise ValueError("poly_pow_mod: the exponent must be non-negative")
+        (a, modulus), (pa, pm), new, mem, stream = self._poly_io([a, modulus])
+        assert count > 0 and a.shape[0] % count == 0 and modulus.shape[0] % count == 0
+        na, nm = a.shape[0] // count, modulus.shape[0] // count
+        eb = exp.to_bytes((exp.bit_length() + 7) // 8, "little")
+        out = new(count * max(nm - 1, 0))
+        rc = self._L.ecfft_poly_pow_mod(self._h, pa, na, ctypes.c_char_p(eb) if eb else None, len(eb), pm, nm,
+                                        self._ptr(out) if out.shape[0] else None, count, mem, stream)
+        if rc == ERR_BAD_ARG:
+            raise ValueError("poly_pow_mod: empty operand, a modulus of fewer than 2 coefficients, a zero leading coefficient of the "
+                             "modulus, count = 0 or a context that holds no full tree")
+        _check(rc)
+        return out
+
+    def poly_mul_mod(self, a, b, modulus, count=1):
+        """a * b mod modulus (ecfft_poly_mul_mod <-> div_rem(&a.naive_mul(&b), modulus), the step of utils::pow_mod, src/utils.rs:205,
+        207): `count` triples laid end to end, a of count * na, b of count * nb and modulus of count * nm coefficients, the modulus'
+        leading coefficient nonzero in every pair.  Returns count * (nm - 1) coefficients.  Needs a tree of next_pow2(na + nb - 1)
+        leaves and what poly_divrem(na + nb - 1, nm) needs.  numpy arrays or contiguous CUDA tensors (current stream), all of the same
+        kind.  Synchronous."""
+        xs, ptrs, new, mem, stream = self._poly_io([a, modulus] if a is b else [a, b, modulus])
+        (a, b, modulus), (pa, pb, pm) = ((xs[0], xs[0], xs[1]), (ptrs[0], ptrs[0], ptrs[1])) if a is b else (xs, ptrs)
+        assert count > 0 and a.shape[0] % count == 0 and b.shape[0] % count == 0 and modulus.shape[0] % count == 0
+        na, nb, nm = a.shape[0] // count, b.shape[0] // count, modulus.shape[0] // count
+        out = new(count * max(nm - 1, 0))
+        rc = self._L.ecfft_poly_mul_mod(self._h, pa, na, pb, nb, pm, nm, self._ptr(out) if out.shape[0] else None, count, mem, stream)
+        if rc == ERR_BAD_ARG:
+            raise ValueError("poly_mul_mod: empty operand, a modulus of fewer than 2 coefficients, a zero leading coefficient of the "
+                             "modulus, count = 0 or a context that holds no full tree")
         _check(rc)
         return out
 

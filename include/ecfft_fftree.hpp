@@ -195,6 +195,23 @@ public:
         check(ecfft_poly_interpolate(ctx_, points.data(), points.size(), values.data(), out.data(), 1, ECFFT_MEM_HOST, nullptr));
         return out;
     }
+    // a^exp mod modulus (ecfft_poly_pow_mod <-> utils::pow_mod, src/utils.rs:194-211): modulus.size() - 1 coefficients (zero-padded);
+    // exp: little-endian bytes (BigUint::to_bytes_le; empty or all zero: the polynomial 1); modulus.size() >= 2, modulus.back() != 0
+    // (else std::runtime_error).  Up to 65 modulus coefficients on any tree; tree rule in ecfft_hip.h.  Synchronous.
+    std::vector<Elem> pow_mod(const std::vector<Elem>& a, const std::vector<uint8_t>& exp, const std::vector<Elem>& modulus) const {
+        require(!a.empty() && modulus.size() >= 2, "pow_mod: a must not be empty and the modulus needs at least 2 coefficients");
+        std::vector<Elem> out(modulus.size() - 1);
+        check(ecfft_poly_pow_mod(ctx_, a.data(), a.size(), exp.empty() ? nullptr : exp.data(), exp.size(), modulus.data(), modulus.size(),
+                                 out.data(), 1, ECFFT_MEM_HOST, nullptr));
+        return out;
+    }
+    // a*b mod modulus (ecfft_poly_mul_mod <-> div_rem(&a.naive_mul(&b), modulus), the step of utils::pow_mod, src/utils.rs:205, 207)
+    std::vector<Elem> mul_mod(const std::vector<Elem>& a, const std::vector<Elem>& b, const std::vector<Elem>& modulus) const {
+        require(!a.empty() && !b.empty() && modulus.size() >= 2, "mul_mod: operands must not be empty and the modulus needs at least 2 coefficients");
+        std::vector<Elem> out(modulus.size() - 1);
+        check(ecfft_poly_mul_mod(ctx_, a.data(), a.size(), b.data(), b.size(), modulus.data(), modulus.size(), out.data(), 1, ECFFT_MEM_HOST, nullptr));
+        return out;
+    }
     size_t device_bytes() const { return ecfft_ctx_device_bytes(ctx_); }     // HBM held between calls: tables + scratch
     // device-resident variants (pointers into HBM, caller's stream)
     void enter_device(const Elem* coeffs, Elem* evals, size_t n, void* stream) const { check(ecfft_enter(ctx_, coeffs, evals, n, ECFFT_MEM_DEVICE, stream)); }
@@ -219,6 +236,15 @@ public:
     // count value vectors (count x m) at m shared, pairwise distinct points, out count x m coefficients.  Synchronous.
     void interpolate_device(const Elem* points, size_t m, const Elem* values, Elem* out, size_t count, void* stream) const {
         check(ecfft_poly_interpolate(ctx_, points, m, values, out, count, ECFFT_MEM_DEVICE, stream));
+    }
+    // count pairs: a count x na, modulus count x nm, out count x (nm - 1); exp: HOST bytes, little-endian, shared by all pairs.  Synchronous.
+    void pow_mod_device(const Elem* a, size_t na, const uint8_t* exp, size_t exp_bytes, const Elem* modulus, size_t nm, Elem* out, size_t count,
+                        void* stream) const {
+        check(ecfft_poly_pow_mod(ctx_, a, na, exp, exp_bytes, modulus, nm, out, count, ECFFT_MEM_DEVICE, stream));
+    }
+    // count triples: a count x na, b count x nb, modulus count x nm, out count x (nm - 1).  Synchronous.
+    void mul_mod_device(const Elem* a, size_t na, const Elem* b, size_t nb, const Elem* modulus, size_t nm, Elem* out, size_t count, void* stream) const {
+        check(ecfft_poly_mul_mod(ctx_, a, na, b, nb, modulus, nm, out, count, ECFFT_MEM_DEVICE, stream));
     }
 
     // ONE transform split over the ranks of `comm` (device pointers: this rank's block shard of len / world elements)

@@ -157,6 +157,34 @@ int ecfft_poly_eval_points(ecfft_ctx* ctx, const void* f, size_t nf, const void*
 int ecfft_poly_interpolate(ecfft_ctx* ctx, const void* points, size_t m, const void* values, void* out, size_t count, int mem,
                            void* stream);
 
+/* Modular powers and products of polynomials.
+ *   ecfft_poly_pow_mod  <-> ecfft::utils::pow_mod(a, exp, modulus)                 src/utils.rs:194-211
+ *   ecfft_poly_mul_mod  <-> div_rem(&a.naive_mul(&b), modulus), pow_mod's step     src/utils.rs:205, 207
+ * Layout: `count` pairs laid end to end: a is count x na, b is count x nb, modulus is count x nm coefficients with
+ * modulus[nm-1] != 0 in every pair; out is count x (nm - 1) coefficients, zero-padded above the true degree, fully reduced, in the
+ * crate's form.  out must not overlap the inputs.
+ * Exponent: `exp` is a HOST pointer whatever `mem` is: exp_bytes little-endian bytes (the layout of BigUint::to_bytes_le), one
+ * exponent shared by all pairs.  High zero bytes are ignored; exp_bytes == 0 or an all-zero exponent gives the polynomial 1.
+ * Lengths: na and nb may be any value >= 1.  An operand of at least nm coefficients is reduced first (the division of
+ * ecfft_poly_divrem), a shorter one is zero-padded.
+ * Cost, with d = nm - 1: d <= 64 runs the whole square-and-multiply of a pair in one workgroup (one launch, no transform).
+ * Above that the reciprocal of the reversed modulus is computed ONCE per call and kept, with the modulus and the base, as
+ * evaluations on N = next_pow2(2d - 1) leaves (3 count N elements); every squaring or multiply of the left-to-right scan is then
+ * three forward lifts, three pointwise products and three batched EXITs of N, with no Newton step.  ecfft_poly_mul_mod is one
+ * ecfft_poly_mul and one division (a fresh modulus has nothing to keep).
+ * Tree: d <= 64 needs no transform for the power itself; otherwise next_pow2(2d - 1) leaves.  If na >= nm, also what
+ * ecfft_poly_divrem(na, nm) needs.  ecfft_poly_mul_mod needs next_pow2(na + nb - 1) leaves and what ecfft_poly_divrem(na + nb - 1,
+ * nm) needs.  Else ECFFT_ERR_TREE_TOO_SMALL.
+ * ECFFT_ERR_BAD_ARG: a NULL input or output, exp == NULL with exp_bytes > 0, na, nb or count 0, nm < 2 (the residue would have no
+ * coefficients), a context that holds no full tree, a byte count that would wrap — and a zero leading coefficient of the modulus
+ * in any pair, which is checked on the device.  Because of that check both calls are SYNCHRONOUS (like ecfft_poly_divrem); the
+ * context keeps working after the error.  Memory, stream and threading as for ecfft_poly_mul; temporaries are pooled
+ * (ecfft_ctx_trim) and do not grow with the number of exponent bits. */
+int ecfft_poly_pow_mod(ecfft_ctx* ctx, const void* a, size_t na, const void* exp, size_t exp_bytes, const void* modulus, size_t nm,
+                       void* out, size_t count, int mem, void* stream);
+int ecfft_poly_mul_mod(ecfft_ctx* ctx, const void* a, size_t na, const void* b, size_t nb, const void* modulus, size_t nm, void* out,
+                       size_t count, int mem, void* stream);
+
 /* The remaining FFTree algorithms, composed from the same GPU kernels.  Synchronous.
  *   ecfft_mextend         <-> FFTree::mextend(&self, &[F], Moiety)      src/fftree.rs:138-141
  *   ecfft_redc            <-> FFTree::redc_z0 / redc_z1(&self, evals, a)  src/fftree.rs:264-275  (moiety S0 / S1)
