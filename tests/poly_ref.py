@@ -10,6 +10,7 @@ m31 uint32[n]) or Python ints.  The test modules convert in-memory (Montgomery) 
   naming the first wrong coefficient.  Every output coefficient must also be canonical (< p).
 - sz_mul / sz_divrem / sz_inv_series: Schwartz-Zippel forms of the same identities at seeded points of [0, p), for sizes where the
   exact product is too slow.  `horner(coeffs, zs) -> values` may be passed (the oracle's); the default is horner() below.
+- sz_mul_mod: r == x y mod f proved by a witness quotient q: x(z) y(z) == f(z) q(z) + r(z) with len(r) = deg f.
 """
 import math
 
@@ -298,6 +299,28 @@ def sz_divrem(field, a, b, q, r, zs, horner_fn=None):
     for i, (x, y, u, v) in enumerate(zip(h(a, zs), h(b, zs), hq, hr)):
         if x % p != (y * u + v) % p:
             return f"a(z) != b(z) q(z) + r(z) at point {i}"
+    return ""
+
+
+def sz_mul_mod(field, x, y, f, q, r, zs, horner_fn=None):
+    """r == x y mod f, given a witness quotient q: x(z) y(z) == f(z) q(z) + r(z) at every point, with len(r) = len(f) - 1 and a
+    nonzero leading coefficient of f.  The identity is one of polynomials of degree < len(x) + len(y) - 1; once it holds, deg r <
+    deg f makes r THE remainder, wherever q came from (a wrong q cannot make a wrong r pass: f q + r determines r mod f)."""
+    h = horner_fn or (lambda c, z: horner(field, c, z))
+    p = P[field]
+    nc, nm = x.shape[0] + y.shape[0] - 1, f.shape[0]
+    if r.shape[0] != nm - 1 or q.shape[0] != max(nc - nm + 1, 0):
+        return f"lengths {q.shape[0]}, {r.shape[0]} for a product of {nc} and nm = {nm}"
+    if to_ints(field, f[nm - 1:])[0] == 0:
+        return "the leading coefficient of f is zero"
+    bad = _noncanonical(field, [("q", q), ("r", r)])
+    if bad:
+        return bad
+    hq = h(q, zs) if q.shape[0] else [0] * len(zs)
+    hr = h(r, zs) if r.shape[0] else [0] * len(zs)
+    for i, (u, v, w, s, t) in enumerate(zip(h(x, zs), h(y, zs), h(f, zs), hq, hr)):
+        if u * v % p != (w * s + t) % p:
+            return f"x(z) y(z) != f(z) q(z) + r(z) at point {i}"
     return ""
 
 

@@ -6,6 +6,7 @@ arrays in the element layout of the field, as poly_ref does.
 
 - Barrett: the reciprocal of the reversed modulus by Newton steps on Kronecker products, computed once per modulus; reduce() is then
   two products and a subtraction.  pow_mod / mul_mod are built on it (left-to-right square-and-multiply, utils::pow_mod).
+- check_pow_mod / check_mul_mod: the comparisons as jobs of a process pool ("" when the result is right, else a message).
 - from_roots: prod (x - r_i) by a product tree.
 - pow_repeated: a^e by e - 1 products, each reduced by schoolbook long division — shares nothing with Barrett but mul_exact.
 - exp_bits / exp_from_bytes: the exponent as the C ABI reads it (little-endian bytes, high zero bytes ignored).
@@ -114,6 +115,21 @@ def pow_mod(field, a, e, f, B=None):
         if bit == "1":
             res = B.mul(res, base)
     return res
+
+
+def check_pow_mod(field, a, f, exps, outs):
+    """outs[i] == a^exps[i] mod f for every exponent (one Barrett, so one reciprocal, for all of them)"""
+    B = Barrett(field, f)
+    for e, got in zip(exps, outs):
+        bad = R._noncanonical(field, [("a^e mod f", got)]) or R._first_diff(field, got, pow_mod(field, a, e, f, B), f"a^{e} mod f")
+        if bad:
+            return bad
+    return ""
+
+
+def check_mul_mod(field, a, b, f, out):
+    """out == a b mod f"""
+    return R._noncanonical(field, [("a b mod f", out)]) or R._first_diff(field, out, mul_mod(field, a, b, f), "a b mod f")
 
 
 def from_roots(field, roots):

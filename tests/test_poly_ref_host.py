@@ -178,3 +178,51 @@ def test_noncanonical_output_is_rejected():
     zc[0] = p
     assert R.check_mul("m31", z, z, zc) != ""
     assert R.sz_mul("m31", z, z, zc, R.sz_points("m31", 3, 1)) != ""
+
+
+# ---- the witness identity of a modular product ----------------------------------------------------------------------------------------
+MULMOD_SHAPES = [(30, 25, 20), (20, 20, 21), (7, 5, 11), (40, 3, 2), (5, 4, 30), (64, 64, 65)]      # (nx, ny, nm): long, one and no quotient
+
+
+@pytest.mark.parametrize("field", FIELDS)
+@pytest.mark.parametrize("nx,ny,nm", MULMOD_SHAPES)
+def test_sz_mul_mod_accepts_the_remainder_and_rejects_one_changed_coefficient(field, nx, ny, nm):
+    p = R.P[field]
+    x, y = R.rand_std(field, nx, nx + 3 * ny), R.rand_std(field, ny, ny + 5 * nm)
+    f = R.set_nonzero(field, R.rand_std(field, nm, nm + 7 * nx), nm - 1)
+    qi, ri = long_division(schoolbook(R.to_ints(field, x), R.to_ints(field, y), p), R.to_ints(field, f), p)
+    q, r = R.from_ints(field, qi), R.from_ints(field, ri)
+    assert q.shape[0] == max(nx + ny - nm, 0) and r.shape[0] == nm - 1
+    zs = R.sz_points(field, R.sz_count(field, nx + ny), 5)
+    assert R.sz_mul_mod(field, x, y, f, q, r, zs) == ""
+    for i in positions(r.shape[0]):
+        assert R.sz_mul_mod(field, x, y, f, q, bump(field, r, i), zs) != "", i
+    for i in positions(q.shape[0]) if q.shape[0] else []:
+        assert R.sz_mul_mod(field, x, y, f, bump(field, q, i), r, zs) != "", i
+    # shapes and canonical form are part of the check: a remainder one coefficient short or long, a zero leading coefficient of f
+    assert "lengths" in R.sz_mul_mod(field, x, y, f, q, r[:-1], zs)
+    assert "lengths" in R.sz_mul_mod(field, x, y, f, q[:-1] if q.shape[0] else R.from_ints(field, [0]), r, zs)
+    z = f.copy()
+    z[nm - 1] = 0
+    assert "leading" in R.sz_mul_mod(field, x, y, z, q, r, zs)
+    bad = r.copy()
+    bad[0] = R.from_ints(field, [p])[0]
+    assert "canonical" in R.sz_mul_mod(field, x, y, f, q, bad, zs)
+
+
+@pytest.mark.parametrize("field", FIELDS)
+def test_sz_mul_mod_with_a_passed_horner(field):
+    """the horner_fn interface (standard form in, Python ints out), as the GPU module passes the oracle's"""
+    p = R.P[field]
+    calls = []
+
+    def h(c, zs):
+        calls.append(c.shape[0])
+        return R.horner(field, c, zs)
+
+    x, y = R.rand_std(field, 50, 1), R.rand_std(field, 50, 2)
+    f = R.set_nonzero(field, R.rand_std(field, 41, 3), 40)
+    qi, ri = long_division(schoolbook(R.to_ints(field, x), R.to_ints(field, y), p), R.to_ints(field, f), p)
+    zs = R.sz_points(field, 3, 9)
+    assert R.sz_mul_mod(field, x, y, f, R.from_ints(field, qi), R.from_ints(field, ri), zs, h) == ""
+    assert sorted(calls) == [40, 41, 50, 50, 59]

@@ -82,3 +82,22 @@ def test_exponent_bytes():
     e = R.P["secp256k1"]
     ops = W.scan(e.to_bytes(32, "little"))
     assert ops.count("S") == 255 and ops.count("M") == bin(e).count("1") - 1
+
+
+@pytest.mark.parametrize("field", ["secp256k1", "m31"])
+def test_pool_checks_accept_and_reject(field):
+    """check_pow_mod / check_mul_mod (the pool jobs of the regime tests): "" for the right result, a message for one changed coefficient"""
+    a, b = R.rand_std(field, 70, 1), R.rand_std(field, 33, 2)
+    f = R.set_nonzero(field, R.rand_std(field, 31, 3), 30)
+    exps = [0, 1, 2, 3, 0b101101]
+    outs = [W.pow_repeated(field, a, e, f) for e in exps]
+    assert W.check_pow_mod(field, a, f, exps, outs) == ""
+    wrong = [o.copy() for o in outs]
+    wrong[4][29] = wrong[4][28]
+    assert "45" in W.check_pow_mod(field, a, f, exps, wrong)
+    m = W.mul_mod(field, a, b, f)
+    p = R.P[field]
+    assert R.to_ints(field, m) == W.long_division_rem(R.to_ints(field, R.mul_exact(field, a, b)), R.to_ints(field, f), p)
+    assert W.check_mul_mod(field, a, b, f, m) == ""
+    m[0] = m[1]
+    assert W.check_mul_mod(field, a, b, f, m) != ""
