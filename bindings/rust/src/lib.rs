@@ -58,6 +58,8 @@ pub mod ffi {
         pub fn ecfft_poly_interpolate(ctx: *mut EcfftCtx, points: *const c_void, m: usize, values: *const c_void, out: *mut c_void, count: usize, mem: i32, stream: *mut c_void) -> i32;
         pub fn ecfft_poly_pow_mod(ctx: *mut EcfftCtx, a: *const c_void, na: usize, exp: *const c_void, exp_bytes: usize, modulus: *const c_void, nm: usize, out: *mut c_void, count: usize, mem: i32, stream: *mut c_void) -> i32;
         pub fn ecfft_poly_mul_mod(ctx: *mut EcfftCtx, a: *const c_void, na: usize, b: *const c_void, nb: usize, modulus: *const c_void, nm: usize, out: *mut c_void, count: usize, mem: i32, stream: *mut c_void) -> i32;
+        pub fn ecfft_poly_gcd(ctx: *mut EcfftCtx, a: *const c_void, na: usize, b: *const c_void, nb: usize, g: *mut c_void, degrees: *mut i64, count: usize, mem: i32, stream: *mut c_void) -> i32;
+        pub fn ecfft_poly_xgcd(ctx: *mut EcfftCtx, a: *const c_void, na: usize, b: *const c_void, nb: usize, s: *mut c_void, t: *mut c_void, g: *mut c_void, degrees: *mut i64, count: usize, mem: i32, stream: *mut c_void) -> i32;
         pub fn ecfft_mextend(ctx: *mut EcfftCtx, inp: *const c_void, out: *mut c_void, e: usize, moiety: i32, count: usize, mem: i32, stream: *mut c_void) -> i32;
         pub fn ecfft_redc(ctx: *mut EcfftCtx, evals: *const c_void, a: *const c_void, out: *mut c_void, n: usize, moiety: i32, mem: i32, stream: *mut c_void) -> i32;
         pub fn ecfft_modular_reduce(ctx: *mut EcfftCtx, evals: *const c_void, a: *const c_void, c: *const c_void, out: *mut c_void, n: usize, mem: i32, stream: *mut c_void) -> i32;
@@ -308,6 +310,44 @@ impl<F: HipField> HipFFTree<F> {
         check(unsafe { ffi::ecfft_poly_mul_mod(self.ctx, a.as_ptr().cast(), a.len(), b.as_ptr().cast(), b.len(), modulus.as_ptr().cast(), modulus.len(), out.as_mut_ptr().cast(), 1, ffi::MEM_HOST, core::ptr::null_mut()) });
         unsafe { out.set_len(n) };
         out
+    }
+
+    /// `ecfft::utils::gcd` (src/utils.rs:132-141): the monic gcd, trimmed to its degree (empty for `a = b = 0`).  The operands need
+    /// not be trimmed and either may be zero; `gcd(0, b)` is monic `b`, as `utils::xgcd` has it (`utils::gcd` returns 0 there).  Up
+    /// to `ECFFT_GCD_SMALL_MAX` coefficients work on any tree; tree rule: include/ecfft_hip.h.
+    pub fn gcd(&self, a: &[F], b: &[F]) -> Vec<F> {
+        assert!(!a.is_empty() && !b.is_empty());
+        let n = a.len().max(b.len());
+        let mut g = Self::out_vec(n);
+        let mut deg: i64 = -1;
+        check(unsafe { ffi::ecfft_poly_gcd(self.ctx, a.as_ptr().cast(), a.len(), b.as_ptr().cast(), b.len(), g.as_mut_ptr().cast(), &mut deg, 1, ffi::MEM_HOST, core::ptr::null_mut()) });
+        unsafe { g.set_len((deg + 1) as usize) };
+        g
+    }
+
+    /// `ecfft::utils::xgcd` (src/utils.rs:147-182): `(s, t, gcd)` with `a*s + b*t = gcd`, the cofactors of the classical extended
+    /// Euclidean algorithm; all three are trimmed to their degrees like the reference's `DensePolynomial`s (a zero cofactor is
+    /// empty; `F::default()` is the field's zero), `gcd` is monic.
+    pub fn xgcd(&self, a: &[F], b: &[F]) -> (Vec<F>, Vec<F>, Vec<F>) {
+        assert!(!a.is_empty() && !b.is_empty());
+        let (ns, nt, n) = ((b.len() - 1).max(1), (a.len() - 1).max(1), a.len().max(b.len()));
+        let mut s = Self::out_vec(ns);
+        let mut t = Self::out_vec(nt);
+        let mut g = Self::out_vec(n);
+        let mut deg: i64 = -1;
+        check(unsafe { ffi::ecfft_poly_xgcd(self.ctx, a.as_ptr().cast(), a.len(), b.as_ptr().cast(), b.len(), s.as_mut_ptr().cast(), t.as_mut_ptr().cast(), g.as_mut_ptr().cast(), &mut deg, 1, ffi::MEM_HOST, core::ptr::null_mut()) });
+        unsafe {
+            s.set_len(ns);
+            t.set_len(nt);
+            g.set_len((deg + 1) as usize);
+        }
+        // trimmed like the DensePolynomials of the reference (and like HipFFTree::xgcd in include/ecfft_fftree.hpp)
+        for v in [&mut s, &mut t] {
+            while v.last().map_or(false, |c| *c == F::default()) {
+                v.pop();
+            }
+        }
+        (s, t, g)
     }
 
     /// `FFTree::mextend` (src/fftree.rs:138-141)

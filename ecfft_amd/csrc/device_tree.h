@@ -1830,6 +1830,341 @@ public:
         return ok;
     }
 
+    // ---- ecfft_poly_gcd / ecfft_poly_xgcd (utils::gcd / utils::xgcd, src/utils.rs:132-182) ----
+    // pairs of at most this many coefficients run their whole remainder sequence in k_gcd_small (one workgroup per pair, no transform)
+    static constexpr size_t kGcdSmall = 256;
+    // A half-GCD node, or what is left of a pair, of at most this many coefficients is one launch of k_gcd_small with as many
+    // threads: the kernel's time is linear in the size where a recursion node costs milliseconds whatever its size,
+    // so the leaf is as large as the hardware takes: 1024 threads per workgroup for M31 (24 KiB of LDS rows), 512 for secp256k1
+    // (96 KiB of the CU's 160 KiB; 1024 would need 192)
+    static constexpr size_t kGcdLeaf = sizeof(E) == 4 ? 1024 : 512;
+    static_assert(kGcdLeaf >= kGcdSmall, "the leaf kernel takes whatever the small regime takes");
+    // The leaves the large regime may need, checked before anything runs.  Degrees are only known on the device, so this is the
+    // worst case over every degree pattern of rows of nmax coefficients: the division step of gcd_pair with a short second operand
+    // (true lengths la <= nmax and lb >= 2) has a quotient of nq = la - lb + 1 < nmax coefficients, and its reciprocal's last Newton
+    // step and the product rev(a) g both take next_pow2(2 nq - 1) leaves, the rule of ecfft_poly_divrem.  Everything else is
+    // smaller: the top half-GCD's matrix (at most n - ceil(n/2) + 1 coefficients per entry, n = nmax - 1) times the operands is
+    // nmax + (nmax - 1) / 2 coefficients, matrix and cofactor products stay below nmax + 1 (cofactor degrees add up to at most
+    // deg a), and a division inside gcd_half has deg d >= m.
+    static size_t gcd_leaves(size_t nmax) {
+        if (nmax <= kGcdSmall) return 1;
+        size_t N = 1; while (N < 2 * nmax - 1) N <<= 1;
+        return N;
+    }
+    // gcd (and, with so / to, the cofactors of the classical extended Euclidean algorithm: a s + b t = g) of `count` pairs laid end
+    // to end (a: count x na, b: count x nb, g: count x max(na, nb), so: count x max(nb - 1, 1), to: count x max(na - 1, 1), all
+    // zero-padded; so / to may be null).  Rows need not be trimmed.  degrees (host, may be null): deg g per pair, -1 for a = b = 0.
+    //   max(na, nb) <= kGcdSmall: one launch of k_gcd_small for all pairs.
+    //   otherwise the pairs run one after another (their degree sequences differ): gcd_pair.
+    // Synchronous (degrees are read back per half-GCD node).  Caller holds lock() and checks the tree rule (gcd_leaves).
+    bool poly_gcd(const E* a, size_t na, const E* b, size_t nb, E* so, E* to, E* g, long long* degrees, size_t count, bool want_cof, hipStream_t s) {
+        const size_t ng = na > nb ? na : nb, ns = nb > 1 ? nb - 1 : 1, nt = na > 1 ? na - 1 : 1;
+        const E r1 = F::to_mont(F::one());
+        bool ok = true;
+        std::vector<long long> hdeg(count, -1);
+        if (ng <= kGcdSmall) {
+            long long* ddeg = reinterpret_cast<long long*>(temp((count * sizeof(long long) + sizeof(E) - 1) / sizeof(E)));
+            for (size_t c0 = 0; c0 < count; c0 += (size_t)1 << 16) {
+                const size_t c = count - c0 < ((size_t)1 << 16) ? count - c0 : (size_t)1 << 16;
+                ECFFT_LAUNCH(KC_POINTWISE, sizeof(E) * (double)c * (double)(na + nb + ng + ns + nt), (k_gcd_small<F, (int)kGcdSmall>), dim3((unsigned)c),
+                             dim3((unsigned)kGcdSmall), 0, s, a + c0 * na, na, (uint32_t)na, b + c0 * nb, nb, (uint32_t)nb, (int32_t)0, 0u, want_cof ? 1u : 0u,
+                             g + c0 * ng, (uint32_t)ng, so ? so + c0 * ns : nullptr, (uint32_t)ns, to ? to + c0 * nt : nullptr, (uint32_t)nt, ddeg + c0,
+                             (E*)nullptr, (size_t)0, 0u, (int32_t*)nullptr, r1);
+            }
+            ok = hipMemcpyAsync(hdeg.data(), ddeg, count * sizeof(long long), hipMemcpyDeviceToHost, s) == hipSuccess;
+        } else {
+            gcd_flag_ = new_flag(s);
+            for (size_t p = 0; p < count && ok; ++p) {
+                const TempMark mark = temps_mark();
+                ok = gcd_pair(a + p * na, na, b + p * nb, nb, so ? so + p * ns : nullptr, ns, to ? to + p * nt : nullptr, nt, g + p * ng, ng, &hdeg[p], want_cof, s);
+                temps_release(mark);
+            }
+        }
+        ok = finish_api(s) && ok;
+        if (degrees) for (size_t p = 0; p < count; ++p) degrees[p] = hdeg[p];
+        return ok;
+    }
+
+private:
+    // a 2x2 polynomial matrix of the half-GCD: rows 00, 01, 10, 11 at p + i*ld, each zero-padded to len <= ld coefficients
+    struct GcdMat {
+        E* p = nullptr; size_t ld = 0, len = 1; bool ident = true;
+        const E* at(int i) const { return p + (size_t)i * ld; }
+    };
+    int* gcd_flag_ = nullptr;
+    // true lengths (degree + 1; 0: the zero polynomial) of nrows <= 2 rows of n coefficients at a stride of ld.  Synchronous.
+    bool gcd_row_lens(const E* p, size_t ld, size_t n, int nrows, size_t* lens, hipStream_t s) {
+        int h[2] = {-1, -1};
+        if (n) {
+            int* d = reinterpret_cast<int*>(temp((2 * sizeof(int) + sizeof(E) - 1) / sizeof(E)));
+            if (hipMemsetAsync(d, 0xFF, 2 * sizeof(int), s) != hipSuccess) return false;
+            // from the top down, and only where the degree seen so far is lower: few lanes reach the atomic.  The look at d[r] is a
+            // relaxed atomic load that only prunes work: a stale value costs one more atomicMax, never a wrong degree
+            foreach_n(s, (size_t)nrows * n, [=] __device__(size_t i) {
+                const size_t r = i / n, j = n - 1 - (i - r * n);
+                if ((int)j > __hip_atomic_load(d + r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) && !F::is_zero(F::canon(p[r * ld + j])))
+                    atomicMax(d + r, (int)j);
+            });
+            if (hipMemcpyAsync(h, d, 2 * sizeof(int), hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) return false;
+        }
+        for (int r = 0; r < nrows; ++r) lens[r] = (size_t)(h[r] + 1);
+        return true;
+    }
+    void gcd_gather(E* dst, const GcdRows<F>& rows, int nrows, size_t n, hipStream_t s) {
+        if (!n) return;
+        ECFFT_LAUNCH(KC_POINTWISE, sizeof(E) * 2.0 * (double)nrows * (double)n, k_gcd_gather<F>, dim3(nblocks(n), (unsigned)nrows), dim3(kBlock), 0, s, dst, rows, n);
+    }
+    void gcd_combine(E* out, size_t ldo, int nrows, const E* P, size_t np, const GcdRows<F>* base, bool single, bool subtract, hipStream_t s) {
+        ECFFT_LAUNCH(KC_POINTWISE, sizeof(E) * 3.0 * (double)nrows * (double)ldo, k_gcd_combine<F>, dim3(nblocks(ldo), (unsigned)nrows), dim3(kBlock), 0, s,
+                     out, ldo, P, np, base ? *base : GcdRows<F>{}, base ? 1u : 0u, single ? 1u : 0u, subtract ? 1u : 0u);
+    }
+    // P (nprod x (nl + nr - 1)) = L_i R_i: the operand rows gathered into two zero-padded blocks, then ONE batched poly_mul_body
+    bool gcd_products(const GcdRows<F>& L, size_t nl, const GcdRows<F>& R, size_t nr, int nprod, E* P, hipStream_t s) {
+        E* lb = temp((size_t)nprod * nl); E* rb = temp((size_t)nprod * nr);
+        gcd_gather(lb, L, nprod, nl, s);
+        gcd_gather(rb, R, nprod, nr, s);
+        return poly_mul_body(lb, nl, nl, rb, nr, nr, P, (size_t)nprod, s);
+    }
+    // out = M (copy; out.p holds 4 rows of out.ld >= M.len)
+    bool gcd_mat_copy(const GcdMat& M, GcdMat& out, hipStream_t s) {
+        out.ident = M.ident; out.len = M.len;
+        if (M.ident) return true;
+        if (M.len > out.ld) return false;
+        GcdRows<F> rows{};
+        for (int i = 0; i < 4; ++i) { rows.p[i] = M.at(i); rows.len[i] = M.len; }
+        gcd_gather(out.p, rows, 4, out.ld, s);
+        return true;
+    }
+    // the identity written out (rows 1, 0, 0, 1 in crate form)
+    void gcd_mat_materialise(GcdMat& M, hipStream_t s) {
+        if (!M.ident) return;
+        E* p = M.p; const size_t ld = M.ld; const E r1 = F::to_mont(F::one());
+        foreach_n(s, 4 * ld, [=] __device__(size_t i) { E v = F::zero(); if (i == 0 || i == 3 * ld) v = r1; p[i] = v; });
+        M.ident = false; M.len = 1;
+    }
+    // (c, d) = M (a, b) as two rows of n coefficients at cd and cd + n (n >= la, lb: the coefficients of the products from n up cancel)
+    bool gcd_apply(const GcdMat& M, const E* a, size_t la, const E* b, size_t lb, E* cd, size_t n, hipStream_t s) {
+        GcdRows<F> ab{};
+        ab.p[0] = a; ab.len[0] = la; ab.p[1] = b; ab.len[1] = lb; ab.p[2] = a; ab.len[2] = la; ab.p[3] = b; ab.len[3] = lb;
+        if (M.ident) { gcd_gather(cd, ab, 2, n, s); return true; }
+        const size_t nr = la > lb ? la : lb, np = M.len + nr - 1;
+        GcdRows<F> L{};
+        for (int i = 0; i < 4; ++i) { L.p[i] = M.at(i); L.len[i] = M.len; }
+        E* P = temp(4 * np);
+        const bool ok = gcd_products(L, M.len, ab, nr, 4, P, s);
+        gcd_combine(cd, n, 2, P, np, nullptr, false, false, s);
+        return ok;
+    }
+    // out = S M (out.p holds 4 rows of out.ld coefficients)
+    bool gcd_matmul(const GcdMat& S, const GcdMat& M, GcdMat& out, hipStream_t s) {
+        if (S.ident) return gcd_mat_copy(M, out, s);
+        if (M.ident) return gcd_mat_copy(S, out, s);
+        const size_t np = S.len + M.len - 1;
+        if (np > out.ld) return false;
+        GcdRows<F> L{}, R{};
+        static constexpr int li[8] = {0, 1, 0, 1, 2, 3, 2, 3}, ri[8] = {0, 2, 1, 3, 0, 2, 1, 3};
+        for (int i = 0; i < 8; ++i) { L.p[i] = S.at(li[i]); L.len[i] = S.len; R.p[i] = M.at(ri[i]); R.len[i] = M.len; }
+        E* P = temp(8 * np);
+        const bool ok = gcd_products(L, S.len, R, M.len, 8, P, s);
+        gcd_combine(out.p, out.ld, 4, P, np, nullptr, false, false, s);
+        out.ident = false; out.len = np;
+        return ok;
+    }
+    // out = Q M for one division step, Q = (0 1; 1 -q): rows (M10, M11, M00 - q M10, M01 - q M11)
+    bool gcd_qstep(const E* q, size_t nq, const GcdMat& M0, GcdMat& out, hipStream_t s) {
+        GcdMat M = M0;
+        const TempMark mark = temps_mark();
+        if (M.ident) { M.ld = 1; M.p = temp(4); gcd_mat_materialise(M, s); }
+        const size_t np = nq + M.len - 1;
+        if (np > out.ld) { temps_release(mark); return false; }
+        GcdRows<F> L{}, R{}, base{};
+        L.p[0] = L.p[1] = q; L.len[0] = L.len[1] = nq;
+        R.p[0] = M.at(2); R.p[1] = M.at(3); R.len[0] = R.len[1] = M.len;
+        E* P = temp(2 * np);
+        const bool ok = gcd_products(L, nq, R, M.len, 2, P, s);
+        base.p[0] = M.at(0); base.p[1] = M.at(1); base.len[0] = base.len[1] = M.len;
+        gcd_combine(out.p + 2 * out.ld, out.ld, 2, P, np, &base, true, true, s);
+        base.p[0] = M.at(2); base.p[1] = M.at(3);
+        gcd_gather(out.p, base, 2, out.ld, s);
+        out.ident = false; out.len = np;
+        temps_release(mark);
+        return ok;
+    }
+    // (q, r) of one pair with la >= lb >= 1 and b[lb-1] != 0: q la - lb + 1 coefficients, r lb - 1.  The products of poly_divrem
+    // without its read-back; the temporaries stay with the caller's mark.
+    bool gcd_divrem(const E* a, size_t la, const E* b, size_t lb, E* q, E* r, hipStream_t s) {
+        const size_t nq = la - lb + 1, nr = lb - 1;
+        if (nr == 0) {
+            E* binv = temp(1);
+            series_base(b, 1, 1, binv, 1, 1, 1, gcd_flag_, s);
+            const E rinv = rinv_;
+            foreach_n(s, la, [=] __device__(size_t i) { q[i] = F::canon(F::mul(F::mul(a[i], binv[0]), rinv)); });
+            return true;
+        }
+        const size_t nf = nq < lb ? nq : lb, np = 2 * nq - 1;
+        E* fr = temp(nf); E* ar = temp(nq); E* g = temp(nq); E* pq = temp(np);
+        foreach_n(s, nf, [=] __device__(size_t i) { fr[i] = b[lb - 1 - i]; });
+        foreach_n(s, nq, [=] __device__(size_t i) { ar[i] = a[la - 1 - i]; });
+        bool ok = inv_series_body(fr, nf, nf, g, nq, 1, gcd_flag_, s);
+        ok = poly_mul_body(ar, nq, nq, g, nq, nq, pq, 1, s) && ok;
+        foreach_n(s, nq, [=] __device__(size_t i) { q[i] = pq[nq - 1 - i]; });
+        const size_t mq = nq < nr ? nq : nr, npr = nr + mq - 1;
+        E* pr = temp(npr);
+        ok = poly_mul_body(b, nr, lb, q, mq, nq, pr, 1, s) && ok;
+        ECFFT_LAUNCH(KC_POINTWISE, sizeof(E) * 3.0 * (double)nr, k_divrem_sub<F>, dim3(nblocks(nr)), dim3(kBlock), 0, s, r, nr, a, la, (const E*)pr, npr, nr);
+        return ok;
+    }
+    // k_gcd_small on ONE pair of at most kGcdLeaf coefficients, with kGcdSmall threads where those hold it
+    template <class... A>
+    void gcd_small_one(size_t la, double bytes, hipStream_t s, A... args) {
+        if (la <= kGcdSmall) ECFFT_LAUNCH(KC_POINTWISE, bytes, (k_gcd_small<F, (int)kGcdSmall>), dim3(1), dim3((unsigned)kGcdSmall), 0, s, args...);
+        else ECFFT_LAUNCH(KC_POINTWISE, bytes, (k_gcd_small<F, (int)kGcdLeaf>), dim3(1), dim3((unsigned)kGcdLeaf), 0, s, args...);
+    }
+    // The half-GCD of (a, b), deg a > deg b (la > lb true lengths), in the form of Thull and Yap, which is correct for abnormal
+    // remainder sequences: with n = deg a and m = ceil(n / 2), out = the matrix M_j of the Euclidean algorithm (rows scaled) with
+    // deg r_j >= m > deg r_{j+1}, where (r_j, r_{j+1}) = M_j (a, b).  out.p holds 4 rows of out.ld >= la coefficients.
+    //   deg b < m: the identity.  la <= kGcdLeaf (512 / 1024): one launch of k_gcd_small.  Otherwise R = hgcd(a div x^m, b div x^m), (c, d) =
+    //   R (a, b); if deg d >= m one division step (c, d) -> (d, e) and S = hgcd(d div x^k, e div x^k), k = 2m - deg d: out = S Q R.
+    // The degrees of (c, d) and of e are read back (two waits per inner node); the node's temporaries go back to the pool.
+    bool gcd_half(const E* a, size_t la, const E* b, size_t lb, GcdMat& out, hipStream_t s) {
+        const size_t n = la - 1, m = (n + 1) / 2;
+        out.ident = true; out.len = 1;
+        if (lb < m + 1) return true;
+        if (la <= kGcdLeaf) {
+            int32_t* info = reinterpret_cast<int32_t*>(temp((8 * sizeof(int32_t) + sizeof(E) - 1) / sizeof(E)));
+            gcd_small_one(la, sizeof(E) * (double)(la + lb + 4 * la), s,
+                          a, la, (uint32_t)la, b, lb, (uint32_t)lb, (int32_t)m, 1u, 1u, (E*)nullptr, 0u, (E*)nullptr, 0u, (E*)nullptr, 0u,
+                          (long long*)nullptr, out.p, out.ld, (uint32_t)la, info, F::to_mont(F::one()));
+            int32_t h[8];
+            if (hipMemcpyAsync(h, info, sizeof(h), hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) return false;
+            out.ident = h[4] == 0;
+            out.len = (size_t)(h[2] > h[3] ? h[2] : h[3]);
+            return out.len <= la;
+        }
+        const TempMark mark = temps_mark();
+        GcdMat R; R.ld = la - m; R.p = temp(4 * R.ld);
+        bool ok = gcd_half(a + m, la - m, b + m, lb - m, R, s);
+        E* cd = temp(2 * la);
+        size_t l2[2] = {0, 0};
+        ok = ok && gcd_apply(R, a, la, b, lb, cd, la, s) && gcd_row_lens(cd, la, la, 2, l2, s);
+        const E* c = cd; const E* d = cd + la;
+        const size_t lc = l2[0], ld = l2[1];
+        if (!ok || ld < m + 1 || lc <= ld) {                   // lc <= ld cannot happen (deg c > deg d in a remainder sequence)
+            ok = ok && ld < m + 1 && gcd_mat_copy(R, out, s);
+            temps_release(mark);
+            return ok;
+        }
+        const size_t nq = lc - ld + 1;
+        E* q = temp(nq); E* e = temp(ld);
+        size_t le = 0;
+        ok = gcd_divrem(c, lc, d, ld, q, e, s) && gcd_row_lens(e, ld, ld - 1, 1, &le, s);
+        GcdMat M1; M1.ld = la; M1.p = temp(4 * la);
+        ok = ok && gcd_qstep(q, nq, R, M1, s);
+        const size_t k = 2 * m - (ld - 1);
+        if (ok && le > k) {
+            GcdMat S; S.ld = ld - k; S.p = temp(4 * S.ld);
+            ok = gcd_half(d + k, ld - k, e + k, le - k, S, s) && gcd_matmul(S, M1, out, s);
+        } else {
+            ok = ok && gcd_mat_copy(M1, out, s);
+        }
+        temps_release(mark);
+        return ok;
+    }
+    // One pair above kGcdSmall: true lengths first, the longer operand first (the cofactor outputs swap with it, as the Euclidean
+    // algorithm's first step does), then { half-GCD; apply; one division step } on two alternating work buffers, the accumulated
+    // matrix alternating likewise (want_cof only), until the pair fits k_gcd_small, which finishes and normalises it; its cofactors
+    // (s', t') of the current pair become (s, t) = (s', t') M.  A second operand that reaches zero first (b | a) ends the loop
+    // with g = a / lc(a) and the first row of M.
+    bool gcd_pair(const E* a0, size_t na, const E* b0, size_t nb, E* so, size_t ns, E* to, size_t nt, E* g, size_t ng, long long* deg,
+                  bool want_cof, hipStream_t s) {
+        size_t la = 0, lb = 0;
+        if (!gcd_row_lens(a0, na, na, 1, &la, s) || !gcd_row_lens(b0, nb, nb, 1, &lb, s)) return false;
+        const E* a = a0; const E* b = b0;
+        if (la < lb) { std::swap(a, b); std::swap(la, lb); std::swap(so, to); std::swap(ns, nt); }
+        if (!want_cof) so = to = nullptr;
+        const size_t W = ng + 1;
+        E* work[2] = {temp(2 * W), temp(2 * W)};
+        GcdMat acc[2];
+        if (want_cof) for (auto& M : acc) { M.ld = W; M.p = temp(4 * W); }
+        int wi = 0, mi = 0;
+        bool ok = true;
+        const E r1 = F::to_mont(F::one());
+        while (ok && lb > 0 && la > kGcdLeaf) {
+            const TempMark lvl = temps_mark();
+            if (la > lb) {
+                GcdMat R; R.ld = la; R.p = temp(4 * la);
+                ok = gcd_half(a, la, b, lb, R, s);
+                if (ok && !R.ident) {
+                    E* cd = work[wi]; wi ^= 1;
+                    size_t l2[2] = {0, 0};
+                    ok = gcd_apply(R, a, la, b, lb, cd, W, s) && gcd_row_lens(cd, W, W, 2, l2, s);
+                    if (ok && want_cof) { ok = gcd_matmul(R, acc[mi], acc[mi ^ 1], s); mi ^= 1; }
+                    a = cd; b = cd + W; la = l2[0]; lb = l2[1];
+                }
+            }
+            if (ok && lb > 0 && la > kGcdLeaf) {
+                if (la < lb) { temps_release(lvl); return false; }       // cannot happen: the rows of a remainder sequence
+                const size_t nq = la - lb + 1;
+                E* q = temp(nq);
+                E* cd = work[wi]; wi ^= 1;
+                size_t le = 0;
+                GcdRows<F> rows{}; rows.p[0] = b; rows.len[0] = lb;
+                gcd_gather(cd, rows, 1, W, s);
+                if (lb > 1) (void)hipMemsetAsync(cd + W + lb - 1, 0, (W - (lb - 1)) * sizeof(E), s);
+                else (void)hipMemsetAsync(cd + W, 0, W * sizeof(E), s);
+                ok = gcd_divrem(a, la, b, lb, q, cd + W, s) && gcd_row_lens(cd + W, W, lb - 1, 1, &le, s);
+                if (ok && want_cof) { ok = gcd_qstep(q, nq, acc[mi], acc[mi ^ 1], s); mi ^= 1; }
+                a = cd; b = cd + W; la = lb; lb = le;
+            }
+            temps_release(lvl);
+        }
+        if (!ok) return false;
+        GcdMat& M = acc[mi];
+        if (lb == 0) {
+            // g = a / lc(a); (s, t) = the first row of M over lc(a)
+            *deg = (long long)la - 1;
+            E* c = temp(1);
+            const E* ap = a; const size_t lla = la;
+            foreach_n(s, 1, [=] __device__(size_t) { E v = F::zero(); if (lla) v = F::canon(F::mul(F::inv(F::canon(ap[lla - 1])), r1)); c[0] = v; });
+            foreach_n(s, ng, [=] __device__(size_t j) { E v = F::zero(); if (j < lla) v = F::canon(F::mul(ap[j], c[0])); g[j] = v; });
+            if (want_cof) {
+                if (M.ident) gcd_mat_materialise(M, s);
+                const E* m0 = M.at(0); const E* m1 = M.at(1); const size_t ml = M.len;
+                if (so) foreach_n(s, ns, [=] __device__(size_t j) { E v = F::zero(); if (j < ml) v = F::canon(F::mul(m0[j], c[0])); so[j] = v; });
+                if (to) foreach_n(s, nt, [=] __device__(size_t j) { E v = F::zero(); if (j < ml) v = F::canon(F::mul(m1[j], c[0])); to[j] = v; });
+            }
+            return hipGetLastError() == hipSuccess;
+        }
+        // the pair fits the kernel: finish there
+        const size_t fs = lb > 1 ? lb - 1 : 1, ft = la > 1 ? la - 1 : 1;
+        const bool direct = !want_cof || M.ident;              // no matrix to apply: the kernel writes the outputs themselves
+        E* gs = temp(la); E* ss = temp(fs); E* ts = temp(ft);
+        long long* ddeg = reinterpret_cast<long long*>(temp((sizeof(long long) + sizeof(E) - 1) / sizeof(E)));
+        gcd_small_one(la, sizeof(E) * 4.0 * (double)(la + lb), s,
+                     a, la, (uint32_t)la, b, lb, (uint32_t)lb, (int32_t)0, 0u, want_cof ? 1u : 0u, gs, (uint32_t)la, want_cof ? ss : (E*)nullptr, (uint32_t)fs,
+                     want_cof ? ts : (E*)nullptr, (uint32_t)ft, ddeg, (E*)nullptr, (size_t)0, 0u, (int32_t*)nullptr, r1);
+        GcdRows<F> rows{};
+        rows.p[0] = gs; rows.len[0] = la;
+        gcd_gather(g, rows, 1, ng, s);
+        if (want_cof && direct) {
+            rows.p[0] = ss; rows.len[0] = fs; if (so) gcd_gather(so, rows, 1, ns, s);
+            rows.p[0] = ts; rows.len[0] = ft; if (to) gcd_gather(to, rows, 1, nt, s);
+        } else if (want_cof) {
+            // (s, t) = (s' M00 + t' M10, s' M01 + t' M11)
+            const size_t nl = fs > ft ? fs : ft, np = nl + M.len - 1;
+            GcdRows<F> L{}, R{};
+            static constexpr int ri[4] = {0, 2, 1, 3};
+            for (int i = 0; i < 4; ++i) { L.p[i] = (i & 1) ? ts : ss; L.len[i] = (i & 1) ? ft : fs; R.p[i] = M.at(ri[i]); R.len[i] = M.len; }
+            E* P = temp(4 * np);
+            ok = gcd_products(L, nl, R, M.len, 4, P, s);
+            if (so) gcd_combine(so, ns, 1, P, np, nullptr, false, false, s);
+            if (to) gcd_combine(to, nt, 1, P + 2 * np, np, nullptr, false, false, s);
+        }
+        ok = ok && hipMemcpyAsync(deg, ddeg, sizeof(long long), hipMemcpyDeviceToHost, s) == hipSuccess && hipStreamSynchronize(s) == hipSuccess;
+        return ok;
+    }
+public:
+
     // coefficients of the reciprocal computed by k_series_base before the Newton steps take over (K0).  64 = one wave per pair: a
     // Newton step at p <= 64 costs a lift + EXIT in the latency regime, the recurrence's 63 tree sums a few us.
     static constexpr size_t kSeriesBase = 64;

@@ -445,6 +445,29 @@ int run_poly_mul_mod(ecfft_ctx* c, DeviceChain<F>& ch, const void* a, size_t na,
     });
 }
 
+// ecfft_poly_gcd / ecfft_poly_xgcd: synchronous (the half-GCD reads degrees back at every node, and `degrees` is a host array
+// whatever `mem` is).  Nothing fails on the data.
+template <class F>
+int run_poly_gcd(ecfft_ctx* c, DeviceChain<F>& ch, const void* a, size_t na, const void* b, size_t nb, void* so, void* to, void* g,
+                 int64_t* degrees, size_t count, bool want_cof, int mem, void* stream) {
+    using E = typename F::elem;
+    if (!a || !b || !g) return ECFFT_ERR_BAD_ARG;
+    const size_t lim = SIZE_MAX / (64 * sizeof(E));
+    if (na > lim || nb > lim) return ECFFT_ERR_BAD_ARG;
+    const size_t ng = na > nb ? na : nb, ns = nb > 1 ? nb - 1 : 1, nt = na > 1 ? na - 1 : 1;
+    const size_t N = DeviceChain<F>::gcd_leaves(ng);
+    if (N > 1 && N > ch.size()) return ECFFT_ERR_TREE_TOO_SMALL;
+    const size_t per = N > 4 * ng ? N : 4 * ng;
+    if (count > SIZE_MAX / (16 * per * sizeof(E))) return ECFFT_ERR_BAD_ARG;  // byte counts of the rows and temporaries must not wrap
+    static_assert(sizeof(long long) == sizeof(int64_t), "degrees are read back as long long");
+    static_assert(DeviceChain<F>::kGcdSmall == ECFFT_GCD_SMALL_MAX, "the header states the small regime's bound");
+    const size_t eb = count * sizeof(E);
+    return staged(c, ch, mem, stream, {{a, na * eb}, {b, nb * eb}}, {{so, ns * eb}, {to, nt * eb}, {g, ng * eb}}, [&](auto d, auto o) -> int {
+        return ch.poly_gcd((const E*)d[0], na, (const E*)d[1], nb, (E*)o[0], (E*)o[1], (E*)o[2], (long long*)degrees, count, want_cof, (hipStream_t)stream)
+                   ? ECFFT_OK : ECFFT_ERR_HIP;
+    });
+}
+
 // standard = true: plain standard-form residues (the FFTree wire format) instead of the crate's in-memory representation
 template <class F>
 int table_of(DeviceChain<F>& ch, size_t m, int which, void* host_out, size_t cap, size_t* count, bool standard = false) {
@@ -1019,6 +1042,16 @@ int ecfft_poly_mul_mod(ecfft_ctx* ctx, const void* a, size_t na, const void* b, 
                        size_t count, int mem, void* stream) {
     if (na == 0 || nb == 0 || nm < 2 || count == 0) return ECFFT_ERR_BAD_ARG;
     return on_chain(ctx, [&](auto& ch) { return run_poly_mul_mod(ctx, ch, a, na, b, nb, modulus, nm, out, count, mem, stream); });
+}
+int ecfft_poly_gcd(ecfft_ctx* ctx, const void* a, size_t na, const void* b, size_t nb, void* g, int64_t* degrees, size_t count, int mem,
+                   void* stream) {
+    if (na == 0 || nb == 0 || count == 0) return ECFFT_ERR_BAD_ARG;
+    return on_chain(ctx, [&](auto& ch) { return run_poly_gcd(ctx, ch, a, na, b, nb, nullptr, nullptr, g, degrees, count, false, mem, stream); });
+}
+int ecfft_poly_xgcd(ecfft_ctx* ctx, const void* a, size_t na, const void* b, size_t nb, void* s, void* t, void* g, int64_t* degrees,
+                    size_t count, int mem, void* stream) {
+    if (na == 0 || nb == 0 || count == 0) return ECFFT_ERR_BAD_ARG;
+    return on_chain(ctx, [&](auto& ch) { return run_poly_gcd(ctx, ch, a, na, b, nb, s, t, g, degrees, count, true, mem, stream); });
 }
 int ecfft_poly_eval_points(ecfft_ctx* ctx, const void* f, size_t nf, const void* points, size_t m, void* out, size_t count, int mem,
                            void* stream) {

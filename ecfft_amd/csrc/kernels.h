@@ -2381,6 +2381,149 @@ __global__ __launch_bounds__(K) void k_powmod_small(typename F::elem* __restrict
 }
 
 // ---------------------------------------------------------------------------------------------
+// ecfft_poly_gcd / ecfft_poly_xgcd (utils::gcd / utils::xgcd, src/utils.rs:132-182: one schoolbook div_rem per remainder on the
+// CPU).  Up to G coefficients the whole remainder sequence of a pair runs in one workgroup (k_gcd_small); above that the host
+// drives a half-GCD on the poly_mul and division bodies whose recursion ends in the same kernel.
+// ---------------------------------------------------------------------------------------------
+// The remainder sequence of one pair in one workgroup of G threads, entirely in LDS: thread t owns coefficient t of the two
+// remainders (R0, R1) and of the two cofactor rows (S0, T0), (S1, T1), with R_i = S_i a + T_i b throughout.  a: row p at
+// a + p*lda, na <= G coefficients; b likewise; high zero coefficients are allowed and either row may be zero — the true degrees
+// are found here.  No inversion per quotient: one elimination step is the cross-multiplied
+//     R0 <- lc(R1) R0 - lc(R0) x^k R1,   k = deg R0 - deg R1,
+// and the same combination of the cofactor rows, repeated until deg R0 < deg R1 (a quotient of degree q takes q + 1 steps), then
+// the rows swap.  Each row is therefore a non-zero scalar multiple of the Euclidean algorithm's row, which changes no degree.
+// The multiplies are plain products of stored numbers; with the cofactor rows started from the crate's 1 (r1 = R; M31: R = 1)
+// the relation R_i = S_i a + T_i b holds in the crate's arithmetic (x y / R) whatever the scalars are, so the Montgomery factor
+// needs no bookkeeping until the end.  The loop runs while deg R1 >= bound (and R1 != 0).
+//   leaf == 0 (bound = 0: to the end): R0 is a multiple of the gcd.  With c = R / lc(R0) — the one inversion of the pair —
+//     g = c R0 is the monic gcd in crate form and (s, t) = c (S0, T0) its cofactors: the scalars of the row cancel in c.  g: row p
+//     of ng coefficients, s: ns, t: nt (either may be null), zero-padded; deg_out[p] = deg g, -1 for a = b = 0 (all rows zero).
+//   leaf != 0 (the leaf of the half-GCD): mat + 4 p ldm receives the rows S0, T0, S1, T1 (nm coefficients each at a stride of
+//     ldm) and info + 8 p the numbers deg R0, deg R1, the lengths of the two cofactor rows and the count of row swaps (0: the
+//     matrix is the identity).
+// cof == 0 skips the cofactor rows (gcd only).  Cofactor row i is touched below its length only: deg S_i, T_i grow as deg R_i falls.
+template <class F, int G>
+__global__ __launch_bounds__(G) void k_gcd_small(const typename F::elem* __restrict__ a, size_t lda, uint32_t na,
+                                                 const typename F::elem* __restrict__ b, size_t ldb, uint32_t nb, int32_t bound,
+                                                 uint32_t leaf, uint32_t cof, typename F::elem* __restrict__ g, uint32_t ng,
+                                                 typename F::elem* __restrict__ s, uint32_t ns, typename F::elem* __restrict__ tt,
+                                                 uint32_t nt, long long* __restrict__ deg_out, typename F::elem* __restrict__ mat,
+                                                 size_t ldm, uint32_t nm, int32_t* __restrict__ info, typename F::elem r1) {
+    using E = typename F::elem;
+    __shared__ E buf[6 * G];
+    __shared__ E snorm;
+    __shared__ int sdeg[2];
+    const uint32_t t = threadIdx.x;
+    const size_t p = blockIdx.x;
+    E *R0 = buf, *R1 = buf + G, *S0 = buf + 2 * G, *S1 = buf + 3 * G, *T0 = buf + 4 * G, *T1 = buf + 5 * G;
+    if (t < 2) sdeg[t] = -1;
+    __syncthreads();
+    {
+        E va = F::zero(), vb = F::zero(), one = F::zero();
+        if (t < na) va = F::canon(a[p * lda + t]);
+        if (t < nb) vb = F::canon(b[p * ldb + t]);
+        if (t == 0) one = r1;
+        R0[t] = va; R1[t] = vb;
+        if (!F::is_zero(va)) atomicMax(&sdeg[0], (int)t);
+        if (!F::is_zero(vb)) atomicMax(&sdeg[1], (int)t);
+        S0[t] = one; T0[t] = F::zero(); S1[t] = F::zero(); T1[t] = one;
+    }
+    __syncthreads();
+    int d0 = sdeg[0], d1 = sdeg[1], c0 = 1, c1 = 1, swaps = 0;
+    __syncthreads();
+    if (t < 2) sdeg[t] = -1;
+    __syncthreads();
+    uint32_t par = 0;                                        // sdeg[par] == -1 receives the next step's degree
+    while (d1 >= 0 && d1 >= bound) {
+        while (d0 >= d1) {
+            const uint32_t k = (uint32_t)(d0 - d1);
+            const E lr = R0[d0], lb = R1[d1];
+            __syncthreads();                                 // everyone holds lr (thread d0 clears it) and the previous step's degree
+            if (t == 0) sdeg[par ^ 1] = -1;
+            if ((int)t < d0) {
+                E v = F::mul(lb, R0[t]);
+                if (t >= k) v = F::sub(v, F::mul(lr, R1[t - k]));
+                v = F::canon(v);
+                R0[t] = v;
+                if (!F::is_zero(v)) atomicMax(&sdeg[par], (int)t);
+            } else if ((int)t == d0) {
+                R0[t] = F::zero();
+            }
+            if (cof) {
+                const int cn = c0 > c1 + (int)k ? c0 : c1 + (int)k;
+                if ((int)t < cn) {
+                    E u = F::mul(lb, S0[t]), w = F::mul(lb, T0[t]);
+                    if (t >= k) { u = F::sub(u, F::mul(lr, S1[t - k])); w = F::sub(w, F::mul(lr, T1[t - k])); }
+                    S0[t] = F::canon(u); T0[t] = F::canon(w);
+                }
+                c0 = cn;
+            }
+            __syncthreads();
+            d0 = sdeg[par];
+            par ^= 1;
+        }
+        { E* x = R0; R0 = R1; R1 = x; x = S0; S0 = S1; S1 = x; x = T0; T0 = T1; T1 = x; }
+        { int x = d0; d0 = d1; d1 = x; x = c0; c0 = c1; c1 = x; }
+        ++swaps;
+    }
+    if (leaf) {
+        if (t < nm) {
+            E* m = mat + p * 4 * ldm;
+            m[t] = S0[t]; m[ldm + t] = T0[t]; m[2 * ldm + t] = S1[t]; m[3 * ldm + t] = T1[t];
+        }
+        if (t == 0) {
+            int32_t* o = info + p * 8;
+            o[0] = d0; o[1] = d1; o[2] = c0; o[3] = c1; o[4] = swaps;
+        }
+        return;
+    }
+    if (t == 0) {
+        E c = F::zero();
+        if (d0 >= 0) c = F::canon(F::mul(F::inv(R0[d0]), r1));
+        snorm = c;
+        if (deg_out) deg_out[p] = d0;
+    }
+    __syncthreads();
+    const E c = snorm;
+    if (t < ng) g[p * ng + t] = F::canon(F::mul(R0[t], c));
+    if (s && t < ns) s[p * ns + t] = F::canon(F::mul(S0[t], c));
+    if (tt && t < nt) tt[p * nt + t] = F::canon(F::mul(T0[t], c));
+}
+// Rows of different lengths gathered into one zero-padded block: dst row r (blockIdx.y) of n coefficients = rows.p[r] below
+// rows.len[r].  The operands of the batched products of the half-GCD (matrix entries, remainders) live in separate buffers.
+template <class F>
+struct GcdRows { const typename F::elem* p[8]; size_t len[8]; };
+template <class F>
+__global__ __launch_bounds__(kBlock) void k_gcd_gather(typename F::elem* __restrict__ dst, GcdRows<F> rows, size_t n) {
+    using E = typename F::elem;
+    const size_t j = (size_t)blockIdx.x * kBlock + threadIdx.x;
+    if (j >= n) return;
+    const uint32_t r = blockIdx.y;
+    E v = F::zero();
+    if (j < rows.len[r]) v = rows.p[r][j];
+    dst[(size_t)r * n + j] = v;
+}
+// Sums of pairs of product rows: out row r (blockIdx.y) of ldo coefficients = base_r + sign (P_{2r} [+ P_{2r+1}]) below np, zero
+// above — base == nullptr: none; single != 0: one product per row (P_r); sign != 0 subtracts.  The 2x2 matrix times vector, matrix
+// times matrix and quotient steps of the half-GCD after their batched products (rows of P: np coefficients).
+template <class F>
+__global__ __launch_bounds__(kBlock) void k_gcd_combine(typename F::elem* __restrict__ out, size_t ldo, const typename F::elem* __restrict__ P,
+                                                        size_t np, GcdRows<F> base, uint32_t has_base, uint32_t single, uint32_t sign) {
+    using E = typename F::elem;
+    const size_t j = (size_t)blockIdx.x * kBlock + threadIdx.x;
+    if (j >= ldo) return;
+    const uint32_t r = blockIdx.y;
+    E v = F::zero();
+    if (j < np) {
+        if (single) v = F::canon(P[(size_t)r * np + j]);
+        else v = F::canon(F::add(F::canon(P[(size_t)(2 * r) * np + j]), F::canon(P[(size_t)(2 * r + 1) * np + j])));
+    }
+    if (sign) v = F::canon(F::neg(v));
+    if (has_base && j < base.len[r]) v = F::canon(F::add(v, F::canon(base.p[r][j])));
+    out[(size_t)r * ldo + j] = v;
+}
+
+// ---------------------------------------------------------------------------------------------
 // generic element-wise helper for tree construction: functor(i) for i < n
 // ---------------------------------------------------------------------------------------------
 template <class Fn>

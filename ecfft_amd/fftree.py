@@ -33,7 +33,9 @@ EXPORTS = ["ecfft_elem_size", "ecfft_build_fftree", "ecfft_fftree_new", "ecfft_c
            "ecfft_comm_stats_enable", "ecfft_comm_stats_read", "ecfft_extend_sharded", "ecfft_enter_sharded", "ecfft_exit_sharded", "ecfft_device_copy", "ecfft_shader_clock", "ecfft_device_alloc", "ecfft_device_free", "ecfft_device_sync", "ecfft_build_extend_shard", "ecfft_ctx_device_bytes", "ecfft_extend_sharded_layout", "ecfft_build_enter_shard", "ecfft_build_exit_shard", "ecfft_build_exit_shard_opts",
            "ecfft_fftree_serialize", "ecfft_fftree_deserialize", "ecfft_tree_rational_maps", "ecfft_ctx_trim", "ecfft_comm_abort", "ecfft_comm_set_rccl_library", "ecfft_comm_set_link_striping",
            "ecfft_poly_mul", "ecfft_poly_inv_series", "ecfft_poly_divrem", "ecfft_poly_eval_points", "ecfft_poly_interpolate",
-           "ecfft_poly_pow_mod", "ecfft_poly_mul_mod"]
+           "ecfft_poly_pow_mod", "ecfft_poly_mul_mod", "ecfft_poly_gcd", "ecfft_poly_xgcd"]
+# include/ecfft_hip.h ECFFT_GCD_SMALL_MAX: max(na, nb) up to which a gcd runs in one workgroup per pair, on any tree
+GCD_SMALL_MAX = 256
 
 # include/ecfft_hip_hooks.h: only in a build with -DECFFT_TEST_HOOKS (tests/hooks/libecfft_hip_hooks.so), never in the shipped library
 HOOK_EXPORTS = ['ecfft_selftest_field', 'ecfft_selfcheck_pointwise_z', 'ecfft_test_fail_next_collective', 'ecfft_selftest_blk16', 'ecfft_selftest_blk16_small', 'ecfft_test_fail_build_rank', 'ecfft_comm_init_projection', 'ecfft_selftest_blk32', 'ecfft_ctx_low_map']
@@ -74,6 +76,8 @@ def _bind(L):
     L.ecfft_poly_interpolate.restype, L.ecfft_poly_interpolate.argtypes = ci, [vp, vp, sz, vp, vp, sz, ci, vp]
     L.ecfft_poly_pow_mod.restype, L.ecfft_poly_pow_mod.argtypes = ci, [vp, vp, sz, vp, sz, vp, sz, vp, sz, ci, vp]
     L.ecfft_poly_mul_mod.restype, L.ecfft_poly_mul_mod.argtypes = ci, [vp, vp, sz, vp, sz, vp, sz, vp, sz, ci, vp]
+    L.ecfft_poly_gcd.restype, L.ecfft_poly_gcd.argtypes = ci, [vp, vp, sz, vp, sz, vp, vp, sz, ci, vp]
+    L.ecfft_poly_xgcd.restype, L.ecfft_poly_xgcd.argtypes = ci, [vp, vp, sz, vp, sz, vp, vp, vp, vp, sz, ci, vp]
     L.ecfft_tree_table.restype, L.ecfft_tree_table.argtypes = ci, [vp, sz, ci, vp, sz, ctypes.POINTER(sz)]
     L.ecfft_build_points.restype, L.ecfft_build_points.argtypes = ci, [ci, sz, vp, vp, vp]
     L.ecfft_device_info.restype, L.ecfft_device_info.argtypes = ci, [ci, ctypes.c_char_p, sz]
@@ -523,6 +527,42 @@ class FFTree:
                              "modulus, count = 0 or a context that holds no full tree")
         _check(rc)
         return out
+
+    def poly_gcd(self, a, b, count=1):
+        """(g, degrees): the monic gcd (ecfft_poly_gcd <-> utils::gcd, src/utils.rs:132-141): `count` pairs laid end to end, a of
+        count * na and b of count * nb coefficients; rows need not be trimmed and either operand may be zero.  g has count *
+        max(na, nb) coefficients, zero-padded above its degree; degrees is a numpy int64 array of deg g per pair, -1 where a = b = 0
+        (then g = 0).  gcd(a, 0) = a / lc(a), gcd(0, b) = b / lc(b).  max(na, nb) <= GCD_SMALL_MAX works on any tree; otherwise a tree
+        of next_pow2(2 n - 1) leaves, n = max(na, nb) (the worst case over all degree patterns: a short b makes a long quotient).  numpy arrays (host) or contiguous
+        CUDA tensors (device, on the current stream), both of the same kind.  Synchronous."""
+        (a, b), (pa, pb), new, mem, stream = self._poly_io([a, b])
+        assert count > 0 and a.shape[0] % count == 0 and b.shape[0] % count == 0
+        na, nb = a.shape[0] // count, b.shape[0] // count
+        g = new(count * max(na, nb))
+        degrees = np.empty(count, np.int64)
+        rc = self._L.ecfft_poly_gcd(self._h, pa, na, pb, nb, self._ptr(g) if g.shape[0] else None, degrees.ctypes.data, count, mem, stream)
+        if rc == ERR_BAD_ARG:
+            raise ValueError("poly_gcd: empty operand, count = 0 or a context that holds no full tree")
+        _check(rc)
+        return g, degrees
+
+    def poly_xgcd(self, a, b, count=1):
+        """(s, t, g, degrees) with a*s + b*t = g, the monic gcd (ecfft_poly_xgcd <-> utils::xgcd, src/utils.rs:147-182): operands and
+        g as poly_gcd; s has count * max(nb - 1, 1) and t count * max(na - 1, 1) coefficients, zero-padded: the cofactors of the
+        classical extended Euclidean algorithm (deg s < deg b - deg g, deg t < deg a - deg g; b = 0: s = 1/lc(a), t = 0; a = 0 or
+        b | a: s = 0, t = 1/lc(b)).  Tree, memory kinds and synchronisation as poly_gcd."""
+        (a, b), (pa, pb), new, mem, stream = self._poly_io([a, b])
+        assert count > 0 and a.shape[0] % count == 0 and b.shape[0] % count == 0
+        na, nb = a.shape[0] // count, b.shape[0] // count
+        g = new(count * max(na, nb))
+        s, t = (new(count * max(nb - 1, 1)), new(count * max(na - 1, 1))) if na and nb else (new(0), new(0))
+        degrees = np.empty(count, np.int64)
+        rc = self._L.ecfft_poly_xgcd(self._h, pa, na, pb, nb, self._ptr(s) if s.shape[0] else None, self._ptr(t) if t.shape[0] else None,
+                                     self._ptr(g) if g.shape[0] else None, degrees.ctypes.data, count, mem, stream)
+        if rc == ERR_BAD_ARG:
+            raise ValueError("poly_xgcd: empty operand, count = 0 or a context that holds no full tree")
+        _check(rc)
+        return s, t, g, degrees
 
     # ---- the remaining FFTree algorithms (host numpy arrays; synchronous) ---------------------
     def _np(self, x):

@@ -4,8 +4,10 @@
 // behaviour: where the Rust code panics this throws (std::invalid_argument for non powers of two,
 // std::length_error("FFTree is too small")), `build_fftree` returns std::nullopt where Rust returns None.
 #pragma once
+#include <algorithm>
 #include <array>
 #include <cstdint>
+#include <cstring>
 #include <optional>
 #include <stdexcept>
 #include <string>
@@ -212,6 +214,32 @@ public:
         check(ecfft_poly_mul_mod(ctx_, a.data(), a.size(), b.data(), b.size(), modulus.data(), modulus.size(), out.data(), 1, ECFFT_MEM_HOST, nullptr));
         return out;
     }
+    // the monic gcd (ecfft_poly_gcd <-> utils::gcd, src/utils.rs:132-141), trimmed to its degree (empty for a = b = 0); the operands
+    // need not be trimmed and either may be zero; gcd(0, b) = b / lc(b) as utils::xgcd has it.  Up to ECFFT_GCD_SMALL_MAX coefficients
+    // on any tree; tree rule in ecfft_hip.h.  Synchronous.
+    std::vector<Elem> gcd(const std::vector<Elem>& a, const std::vector<Elem>& b) const {
+        require(!a.empty() && !b.empty(), "gcd: operands must not be empty");
+        std::vector<Elem> g(std::max(a.size(), b.size()));
+        int64_t deg = -1;
+        check(ecfft_poly_gcd(ctx_, a.data(), a.size(), b.data(), b.size(), g.data(), &deg, 1, ECFFT_MEM_HOST, nullptr));
+        g.resize((size_t)(deg + 1));
+        return g;
+    }
+    // {s, t, g} with a*s + b*t = g, the monic gcd (ecfft_poly_xgcd <-> utils::xgcd, src/utils.rs:147-182): the cofactors of the
+    // classical extended Euclidean algorithm, all three trimmed to their degrees.  Synchronous.
+    std::array<std::vector<Elem>, 3> xgcd(const std::vector<Elem>& a, const std::vector<Elem>& b) const {
+        require(!a.empty() && !b.empty(), "xgcd: operands must not be empty");
+        std::vector<Elem> s(std::max<size_t>(b.size() - 1, 1)), t(std::max<size_t>(a.size() - 1, 1)), g(std::max(a.size(), b.size()));
+        int64_t deg = -1;
+        check(ecfft_poly_xgcd(ctx_, a.data(), a.size(), b.data(), b.size(), s.data(), t.data(), g.data(), &deg, 1, ECFFT_MEM_HOST, nullptr));
+        g.resize((size_t)(deg + 1));
+        auto trim = [](std::vector<Elem>& v) {
+            static const Elem zero{};
+            while (!v.empty() && std::memcmp(&v.back(), &zero, sizeof(Elem)) == 0) v.pop_back();
+        };
+        trim(s); trim(t);
+        return {std::move(s), std::move(t), std::move(g)};
+    }
     size_t device_bytes() const { return ecfft_ctx_device_bytes(ctx_); }     // HBM held between calls: tables + scratch
     // device-resident variants (pointers into HBM, caller's stream)
     void enter_device(const Elem* coeffs, Elem* evals, size_t n, void* stream) const { check(ecfft_enter(ctx_, coeffs, evals, n, ECFFT_MEM_DEVICE, stream)); }
@@ -241,6 +269,14 @@ public:
     void pow_mod_device(const Elem* a, size_t na, const uint8_t* exp, size_t exp_bytes, const Elem* modulus, size_t nm, Elem* out, size_t count,
                         void* stream) const {
         check(ecfft_poly_pow_mod(ctx_, a, na, exp, exp_bytes, modulus, nm, out, count, ECFFT_MEM_DEVICE, stream));
+    }
+    // count pairs: a count x na, b count x nb (untrimmed), g count x max(na, nb); degrees: count HOST entries or null.  Synchronous.
+    void gcd_device(const Elem* a, size_t na, const Elem* b, size_t nb, Elem* g, int64_t* degrees, size_t count, void* stream) const {
+        check(ecfft_poly_gcd(ctx_, a, na, b, nb, g, degrees, count, ECFFT_MEM_DEVICE, stream));
+    }
+    // ... with the cofactors: s count x max(nb - 1, 1), t count x max(na - 1, 1); s or t may be null.  Synchronous.
+    void xgcd_device(const Elem* a, size_t na, const Elem* b, size_t nb, Elem* s, Elem* t, Elem* g, int64_t* degrees, size_t count, void* stream) const {
+        check(ecfft_poly_xgcd(ctx_, a, na, b, nb, s, t, g, degrees, count, ECFFT_MEM_DEVICE, stream));
     }
     // count triples: a count x na, b count x nb, modulus count x nm, out count x (nm - 1).  Synchronous.
     void mul_mod_device(const Elem* a, size_t na, const Elem* b, size_t nb, const Elem* modulus, size_t nm, Elem* out, size_t count, void* stream) const {

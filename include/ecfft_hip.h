@@ -185,6 +185,41 @@ int ecfft_poly_pow_mod(ecfft_ctx* ctx, const void* a, size_t na, const void* exp
 int ecfft_poly_mul_mod(ecfft_ctx* ctx, const void* a, size_t na, const void* b, size_t nb, const void* modulus, size_t nm, void* out,
                        size_t count, int mem, void* stream);
 
+/* Greatest common divisors of polynomials.
+ *   ecfft_poly_gcd   <-> ecfft::utils::gcd(a, b)                                    src/utils.rs:132-141
+ *   ecfft_poly_xgcd  <-> ecfft::utils::xgcd(a, b) -> (s, t, gcd), a s + b t = gcd    src/utils.rs:147-182
+ * Layout: `count` pairs laid end to end: a is count x na, b is count x nb coefficients in the crate's form.  Unlike
+ * ecfft_poly_divrem the rows NEED NOT BE TRIMMED: high zero coefficients are allowed and either operand may be the zero
+ * polynomial; the true degrees are found on the device (the natural inputs, x^p - x mod f or h^k - 1 mod f, have unknown degree).
+ * Outputs: g is count x max(na, nb): the MONIC gcd, zero-padded above its degree, fully reduced.  `degrees` is a HOST pointer
+ * whatever `mem` is, `count` entries, and may be NULL: deg g per pair, or -1 when a = b = 0 (then g = s = t = 0).
+ * Zero operands: gcd(a, 0) = a / lc(a) and gcd(0, b) = b / lc(b).  The reference's gcd(0, b) returns 0 (src/utils.rs:133-134)
+ * while its own xgcd(0, b) returns monic b (test_xgcd_with_zero_polynomial); both calls here follow xgcd and the textbook.
+ * ecfft_poly_xgcd: s is count x max(nb - 1, 1), t is count x max(na - 1, 1), zero-padded; either may be NULL, g may not.  They
+ * are the cofactors of the classical extended Euclidean algorithm, exactly what src/utils.rs:147-182 returns: when a/g or b/g is
+ * not constant, the unique pair with deg s < deg b - deg g and deg t < deg a - deg g.  The degenerate cases are the algorithm's:
+ *   b = 0:            s = 1/lc(a), t = 0
+ *   a = 0 or b | a:   s = 0, t = 1/lc(b)
+ * ECFFT_GCD_SMALL_MAX: max(na, nb) up to which a pair runs its whole remainder sequence in one workgroup (one launch for all
+ * pairs, no transform).  Above it every pair is a half-GCD (Thull-Yap form, correct for quotients of any degree) on the bodies of
+ * ecfft_poly_mul and ecfft_poly_divrem, O(M(n) log n), whose nodes of at most 512 (secp256k1) or 1024 (M31) coefficients are one
+ * launch of the same kernel; the pairs then run one after another, since their degree sequences differ.
+ * Tree: max(na, nb) <= ECFFT_GCD_SMALL_MAX needs no transform (any tree).  Otherwise, with n = max(na, nb), next_pow2(2 n - 1)
+ * leaves, which is what next_pow2(2 n) gives for every n >= 2.  The rule is checked before anything runs and true degrees are
+ * only known on the device, so it is the worst case over all inputs of that shape: a second operand of low degree makes the
+ * first division step a quotient of almost n coefficients, whose reciprocal and product take next_pow2(2 nq - 1) leaves as in
+ * ecfft_poly_divrem.  (The half-GCD matrix times the operands needs n + floor((n - 1) / 2) coefficients, every other product
+ * less.)  Else ECFFT_ERR_TREE_TOO_SMALL.
+ * ECFFT_ERR_BAD_ARG: a NULL input or g, na, nb or count 0, a context that holds no full tree, a byte count that would wrap.
+ * Nothing fails on the data.  Both calls are SYNCHRONOUS: the recursion reads degrees back, and `degrees` is returned to the
+ * host.  Outputs must not overlap the inputs.  Memory, stream and threading as for ecfft_poly_mul; temporaries are pooled
+ * (ecfft_ctx_trim) and are handed back level by level, so they grow neither with the depth nor with repeated calls. */
+#define ECFFT_GCD_SMALL_MAX 256
+int ecfft_poly_gcd(ecfft_ctx* ctx, const void* a, size_t na, const void* b, size_t nb, void* g, int64_t* degrees, size_t count, int mem,
+                   void* stream);
+int ecfft_poly_xgcd(ecfft_ctx* ctx, const void* a, size_t na, const void* b, size_t nb, void* s, void* t, void* g, int64_t* degrees,
+                    size_t count, int mem, void* stream);
+
 /* The remaining FFTree algorithms, composed from the same GPU kernels.  Synchronous.
  *   ecfft_mextend         <-> FFTree::mextend(&self, &[F], Moiety)      src/fftree.rs:138-141
  *   ecfft_redc            <-> FFTree::redc_z0 / redc_z1(&self, evals, a)  src/fftree.rs:264-275  (moiety S0 / S1)
