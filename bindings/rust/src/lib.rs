@@ -58,6 +58,7 @@ pub mod ffi {
         pub fn ecfft_poly_interpolate(ctx: *mut EcfftCtx, points: *const c_void, m: usize, values: *const c_void, out: *mut c_void, count: usize, mem: i32, stream: *mut c_void) -> i32;
         pub fn ecfft_poly_pow_mod(ctx: *mut EcfftCtx, a: *const c_void, na: usize, exp: *const c_void, exp_bytes: usize, modulus: *const c_void, nm: usize, out: *mut c_void, count: usize, mem: i32, stream: *mut c_void) -> i32;
         pub fn ecfft_poly_mul_mod(ctx: *mut EcfftCtx, a: *const c_void, na: usize, b: *const c_void, nb: usize, modulus: *const c_void, nm: usize, out: *mut c_void, count: usize, mem: i32, stream: *mut c_void) -> i32;
+        pub fn ecfft_poly_find_roots(ctx: *mut EcfftCtx, f: *const c_void, nf: usize, roots: *mut c_void, n_roots: *mut i64, count: usize, mem: i32, stream: *mut c_void) -> i32;
         pub fn ecfft_poly_gcd(ctx: *mut EcfftCtx, a: *const c_void, na: usize, b: *const c_void, nb: usize, g: *mut c_void, degrees: *mut i64, count: usize, mem: i32, stream: *mut c_void) -> i32;
         pub fn ecfft_poly_xgcd(ctx: *mut EcfftCtx, a: *const c_void, na: usize, b: *const c_void, nb: usize, s: *mut c_void, t: *mut c_void, g: *mut c_void, degrees: *mut i64, count: usize, mem: i32, stream: *mut c_void) -> i32;
         pub fn ecfft_mextend(ctx: *mut EcfftCtx, inp: *const c_void, out: *mut c_void, e: usize, moiety: i32, count: usize, mem: i32, stream: *mut c_void) -> i32;
@@ -348,6 +349,22 @@ impl<F: HipField> HipFFTree<F> {
             }
         }
         (s, t, g)
+    }
+
+    /// `ecfft::utils::find_roots` (src/utils.rs:25-44): the distinct roots of `f` in the field, in ascending order of their
+    /// standard form (the reference sorts its result the same way).  `f` need not be trimmed and multiplicities do not matter; a
+    /// non-zero constant has no roots.  Panics on the zero polynomial, as the reference does.  Deterministic: the splitting shifts
+    /// are 1, 2, 3, ...  Up to `ECFFT_ROOTS_SMALL_MAX` coefficients work on any tree; tree rule: include/ecfft_hip.h.
+    pub fn find_roots(&self, f: &[F]) -> Vec<F> {
+        assert!(!f.is_empty());
+        let n = f.len() - 1;
+        let mut roots = Self::out_vec(n);
+        let mut count: i64 = 0;
+        let p = if n == 0 { core::ptr::null_mut() } else { roots.as_mut_ptr().cast() };
+        check(unsafe { ffi::ecfft_poly_find_roots(self.ctx, f.as_ptr().cast(), f.len(), p, &mut count, 1, ffi::MEM_HOST, core::ptr::null_mut()) });
+        assert!(count >= 0, "find_roots: the zero polynomial");
+        unsafe { roots.set_len(count as usize) };
+        roots
     }
 
     /// `FFTree::mextend` (src/fftree.rs:138-141)

@@ -2163,7 +2163,265 @@ private:
         ok = ok && hipMemcpyAsync(deg, ddeg, sizeof(long long), hipMemcpyDeviceToHost, s) == hipSuccess && hipStreamSynchronize(s) == hipSuccess;
         return ok;
     }
+    // ---- ecfft_poly_find_roots (utils::find_roots, src/utils.rs:25-44) ----
+    // out (count x d, crate form) = (x + c)^exp mod f_b for `count` MONIC moduli of degree d > kRootsSmall laid end to end (f: count x
+    // (d + 1), f_b[d] = 1 in crate form).  The large regime of poly_pow_mod with another epilogue: the same kept evaluations of g =
+    // 1/rev(f) and f on T_N, N = next_pow2(2d - 1), and the same squaring (powmod_step); on a set bit the product with the base is
+    // not a second modular product but x r + c r - r_{d-1} f, one pass over the rows.  exp: host bytes, bit nbits - 1 set, nbits >= 1.
+    bool roots_pow_body(const E* f, size_t d, uint32_t c, const uint8_t* exp, size_t nbits, E* out, size_t count, int* flag, hipStream_t s) {
+        const size_t nm = d + 1;
+        size_t N = 1; while (N < 2 * d - 1) N <<= 1;
+        const size_t h = N / 2, total = count * N;
+        const unsigned lN = ilog2(N);
+        const E r1 = F::to_mont(F::one());
+        const TE rinv = F::to_table(rinv_);
+        bool ok = true;
+        E* kept = temp(2 * total);
+        E* next = temp(count * d);
+        {
+            const TempMark mark = temps_mark();
+            const size_t ng = d - 1;
+            E* fr = temp(count * ng); E* g = temp(count * ng); E* S = temp(2 * count * d);
+            foreach_n(s, count * ng, [=] __device__(size_t i) { const size_t b = i / ng, j = i - b * ng; fr[i] = f[b * nm + d - j]; });
+            ok = inv_series_body(fr, ng, ng, g, ng, count, flag, s) && ok;
+            const size_t cd = count * d;
+            foreach_n(s, 2 * cd, [=] __device__(size_t i) {
+                const size_t w = i / cd, k = i - w * cd, b = k / d, j = k - b * d;
+                E v = F::zero();
+                if (w == 0) { if (j < ng) v = g[b * ng + j]; } else v = f[b * nm + j];
+                S[i] = v;
+            });
+            E* U = temp(2 * count * h); E* V = temp(2 * count * h); E* X = temp(2 * count * h);
+            PolyEvals<F> ev;
+            ok = lift_one(S, d, d, false, 0, N, 2 * count, U, V, X, &ev, s) && ok;
+            foreach_n(s, 2 * total, [=] __device__(size_t i) {
+                const size_t r = i >> lN, k = (i & (N - 1)) >> 1;
+                kept[i] = ((i & 1) ? ev.odd : ev.even)[r * ev.batch + k * ev.stride];
+            });
+            temps_release(mark);
+        }
+        const E* kept_g = kept; const E* kept_f = kept + total;
+        const E cE = F::from_u32(c), ri = rinv_;
+        const E c_crate = F::canon(F::mul(cE, r1));
+        foreach_n(s, count * d, [=] __device__(size_t i) {
+            const size_t j = i % d;
+            E v = F::zero();
+            if (j == 0) v = c_crate;
+            if (j == 1) v = r1;
+            out[i] = v;
+        });
+        for (size_t i = nbits - 1; i-- > 0;) {
+            ok = powmod_step(out, nullptr, kept_g, kept_f, d, N, count, rinv, s) && ok;
+            if ((exp[i >> 3] >> (i & 7)) & 1) {
+                foreach_n(s, count * d, [=] __device__(size_t k) {
+                    const size_t b = k / d, j = k - b * d;
+                    E v = F::zero();
+                    if (j) v = out[k - 1];
+                    if (c) v = F::canon(F::add(v, F::canon(F::mul(cE, out[k]))));
+                    next[k] = F::canon(F::sub(v, F::canon(F::mul(F::mul(out[b * d + d - 1], f[b * nm + j]), ri))));
+                });
+                ok = hipMemcpyAsync(out, next, count * d * sizeof(E), hipMemcpyDeviceToDevice, s) == hipSuccess && ok;
+            }
+        }
+        return ok;
+    }
+    // p and (p - 1) / 2 of the field as little-endian bytes (p is odd: (p - 1) / 2 is p >> 1); returns their bit counts
+    static void roots_exponents(uint8_t* ep, uint32_t* nbits_p, uint8_t* eh, uint32_t* nbits_h) {
+        uint32_t w[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+        int nw = 1;
+        if constexpr (sizeof(E) == 4) w[0] = F::P;
+        else { nw = 8; for (int i = 0; i < 8; ++i) w[i] = F::p_limb(i); }
+        for (int i = 0; i < 32; ++i) { ep[i] = 0; eh[i] = 0; }
+        for (int i = 0; i < nw; ++i) {
+            const uint32_t hi = i + 1 < nw ? w[i + 1] : 0u, half = (w[i] >> 1) | (hi << 31);
+            for (int k = 0; k < 4; ++k) { ep[4 * i + k] = (uint8_t)(w[i] >> (8 * k)); eh[4 * i + k] = (uint8_t)(half >> (8 * k)); }
+        }
+        auto bits = [](const uint8_t* e) { uint32_t n = 256; while (n && !((e[(n - 1) >> 3] >> ((n - 1) & 7)) & 1)) --n; return n; };
+        *nbits_p = bits(ep); *nbits_h = bits(eh);
+    }
+    // what a call of poly_find_roots shares between its polynomials: the exponents on the device and the flag of the attempt cap
+    struct RootsCall { const uint8_t* dexp = nullptr; uint8_t ep[32], eh[32]; uint32_t nbits_p = 0, nbits_h = 0; int* flag = nullptr; };
+    // one launch of k_roots_small over nblk rows or descriptors
+    void roots_small_launch(const RootsCall& rc, const E* in, size_t ldin, size_t nin, E* out, size_t ldout, const uint32_t* desc, long long* n_out,
+                            bool frob, uint32_t c0, size_t nblk, double coeffs, hipStream_t s) {
+        const E r1 = F::to_mont(F::one());
+        const TE rinv = F::to_table(rinv_);
+        for (size_t b0 = 0; b0 < nblk; b0 += (size_t)1 << 16) {
+            const size_t nb = nblk - b0 < ((size_t)1 << 16) ? nblk - b0 : (size_t)1 << 16;
+            ECFFT_LAUNCH(KC_POINTWISE, sizeof(E) * coeffs * (double)nb / (double)nblk + 64.0, (k_roots_small<F, (int)kRootsSmall>), dim3((unsigned)nb),
+                         dim3((unsigned)kRootsSmall), 0, s, desc ? in : in + b0 * ldin, ldin, (uint32_t)nin, desc ? out : out + b0 * ldout, ldout,
+                         desc ? desc + 3 * b0 : (const uint32_t*)nullptr, n_out ? n_out + b0 : (long long*)nullptr, frob ? 1u : 0u, c0,
+                         rc.dexp, rc.nbits_p, rc.dexp + 32, rc.nbits_h, rinv, r1, rc.flag);
+        }
+    }
+    void roots_rank_launch(E* dst, size_t ldd, const E* src, size_t lds, const long long* n_dev, long long n_fixed, size_t rows, hipStream_t s) {
+        if (!ldd) return;
+        for (size_t r0 = 0; r0 < rows; r0 += 32768) {
+            const size_t nr = rows - r0 < 32768 ? rows - r0 : 32768;
+            ECFFT_LAUNCH(KC_POINTWISE, sizeof(E) * 2.0 * (double)nr * (double)ldd, k_roots_rank<F>, dim3(nblocks(ldd), (unsigned)nr), dim3(kBlock), 0, s,
+                         dst + r0 * ldd, ldd, src + r0 * lds, lds, n_dev ? n_dev + r0 : (const long long*)nullptr, n_fixed, F::to_table(rinv_));
+        }
+    }
+    // The roots of ONE polynomial of nf > kRootsSmall + 1 coefficients (untrimmed, crate form) into roots (nf - 1, sorted, zero-padded).
+    //   g = gcd(f, x^p - x mod f) on roots_pow_body (base x) and gcd_pair; then rounds with one shift c = 1, 2, ... for all pending
+    //   factors of degree > kRootsSmall: grouped by N = next_pow2(2e - 1), padded inside a group to its largest degree D as x^(D-e) h
+    //   (h divides it, so gcd(h, w - 1) is unchanged), ONE roots_pow_body per group, then per factor u = gcd_pair(h, w - 1) and
+    //   v = h / u (gcd_divrem).  Factors of degree <= kRootsSmall go to the leaf buffer, finished by ONE launch of k_roots_small.
+    bool roots_one_large(const RootsCall& rc, const E* f, size_t nf, E* roots, long long* n, hipStream_t s) {
+        const size_t K = kRootsSmall;
+        const E r1 = F::to_mont(F::one());
+        *n = 0;
+        size_t la = 0;
+        if (!gcd_row_lens(f, nf, nf, 1, &la, s)) return false;
+        E* uns = temp(nf - 1);                                // the roots before they are ordered
+        if (la <= K + 1) {                                    // a short polynomial in a long row: the small regime on its true length
+            long long* dn = reinterpret_cast<long long*>(temp((sizeof(long long) + sizeof(E) - 1) / sizeof(E)));
+            roots_small_launch(rc, f, nf, la ? la : 1, uns, nf - 1, nullptr, dn, true, 1u, 1, (double)(la + K), s);
+            roots_rank_launch(roots, nf - 1, uns, nf - 1, dn, 0, 1, s);
+            return hipMemcpyAsync(n, dn, sizeof(long long), hipMemcpyDeviceToHost, s) == hipSuccess && hipStreamSynchronize(s) == hipSuccess;
+        }
+        const size_t d = la - 1;
+        // ---- the linear part: fm = f / lc(f), w = x^p mod fm, g = gcd(fm, w - x) ----
+        E* fm = temp(la); E* w = temp(d); E* g = temp(la); E* lc = temp(1);
+        // lc = R / (stored leading coefficient) is the PLAIN inverse of the leading coefficient: plain x crate stays crate
+        foreach_n(s, 1, [=] __device__(size_t) { lc[0] = F::canon(F::mul(F::inv(F::canon(f[d])), r1)); });
+        foreach_n(s, la, [=] __device__(size_t j) { E v = r1; if (j < d) v = F::canon(F::mul(f[j], lc[0])); fm[j] = v; });
+        bool ok = roots_pow_body(fm, d, 0u, rc.ep, rc.nbits_p, w, 1, gcd_flag_, s);
+        foreach_n(s, 1, [=] __device__(size_t) { w[1] = F::canon(F::sub(F::canon(w[1]), r1)); });
+        long long dg = -1;
+        ok = ok && gcd_pair(fm, la, w, d, nullptr, 1, nullptr, 1, g, la, &dg, false, s);
+        if (!ok) return false;
+        if (dg <= 0) { roots_rank_launch(roots, nf - 1, uns, nf - 1, nullptr, 0, 1, s); return true; }
+        const size_t r = (size_t)dg;
+        // pending factors (degree > K) packed with their leading 1 in two alternating buffers, leaves packed likewise
+        struct Fac { size_t off, e; uint32_t fails; };
+        E* pend[2] = {temp(2 * r + 2), temp(2 * r + 2)};
+        E* leaf = temp(2 * r + 2);
+        std::vector<Fac> cur, nxt;
+        std::vector<uint32_t> ldesc;                          // (input offset, length, output offset) per leaf
+        size_t leaf_used = 0, roots_used = 0;
+        auto to_leaf = [&](const E* p, size_t e) {
+            ok = hipMemcpyAsync(leaf + leaf_used, p, (e + 1) * sizeof(E), hipMemcpyDeviceToDevice, s) == hipSuccess && ok;
+            ldesc.push_back((uint32_t)leaf_used); ldesc.push_back((uint32_t)(e + 1)); ldesc.push_back((uint32_t)roots_used);
+            leaf_used += e + 1; roots_used += e;
+        };
+        if (r <= K) to_leaf(g, r);
+        else {
+            ok = hipMemcpyAsync(pend[0], g, (r + 1) * sizeof(E), hipMemcpyDeviceToDevice, s) == hipSuccess && ok;
+            cur.push_back({0, r, 0});
+        }
+        int pi = 0;
+        uint32_t c = 1;
+        for (; ok && !cur.empty(); ++c) {
+            const TempMark round = temps_mark();
+            nxt.clear();
+            size_t nxt_used = 0;
+            const E* P = pend[pi]; E* Q = pend[pi ^ 1];
+            auto keep = [&](const E* p, size_t e, uint32_t fails) {
+                if (e <= K) { to_leaf(p, e); return; }
+                ok = hipMemcpyAsync(Q + nxt_used, p, (e + 1) * sizeof(E), hipMemcpyDeviceToDevice, s) == hipSuccess && ok;
+                nxt.push_back({nxt_used, e, fails});
+                nxt_used += e + 1;
+            };
+            std::vector<char> done(cur.size(), 0);
+            for (size_t i0 = 0; i0 < cur.size() && ok; ++i0) {
+                if (done[i0]) continue;
+                auto leaves_of = [](size_t e) { size_t N = 1; while (N < 2 * e - 1) N <<= 1; return N; };
+                const size_t N = leaves_of(cur[i0].e);
+                std::vector<size_t> grp;
+                size_t D = 0;
+                for (size_t i = i0; i < cur.size(); ++i)
+                    if (!done[i] && leaves_of(cur[i].e) == N) { grp.push_back(i); done[i] = 1; if (cur[i].e > D) D = cur[i].e; }
+                const size_t cnt = grp.size();
+                const TempMark gm = temps_mark();
+                // rows x^(D - e) h: row i reads P + off_i shifted up by D - e_i
+                std::vector<uint32_t> hd(2 * cnt);
+                for (size_t i = 0; i < cnt; ++i) { hd[2 * i] = (uint32_t)cur[grp[i]].off; hd[2 * i + 1] = (uint32_t)(D - cur[grp[i]].e); }
+                uint32_t* dd = reinterpret_cast<uint32_t*>(temp((2 * cnt * sizeof(uint32_t) + sizeof(E) - 1) / sizeof(E)));
+                ok = hipMemcpyAsync(dd, hd.data(), 2 * cnt * sizeof(uint32_t), hipMemcpyHostToDevice, s) == hipSuccess && hipStreamSynchronize(s) == hipSuccess && ok;
+                E* M = temp(cnt * (D + 1)); E* W = temp(cnt * D);
+                const size_t nm = D + 1;
+                foreach_n(s, cnt * nm, [=] __device__(size_t k) {
+                    const size_t b = k / nm, j = k - b * nm, sh = dd[2 * b + 1];
+                    E v = F::zero();
+                    if (j >= sh) v = P[dd[2 * b] + (j - sh)];
+                    M[k] = v;
+                });
+                ok = ok && roots_pow_body(M, D, c, rc.eh, rc.nbits_h, W, cnt, gcd_flag_, s);
+                foreach_n(s, cnt, [=] __device__(size_t b) { W[b * D] = F::canon(F::sub(F::canon(W[b * D]), r1)); });
+                E* u = temp(D + 1); E* v = temp(D + 1); E* rem = temp(D + 1);
+                for (size_t i = 0; i < cnt && ok; ++i) {
+                    const Fac& fc = cur[grp[i]];
+                    const E* hp = P + fc.off;
+                    long long du = -1;
+                    const TempMark fm2 = temps_mark();
+                    ok = gcd_pair(hp, fc.e + 1, W + i * D, D, nullptr, 1, nullptr, 1, u, D + 1, &du, false, s);
+                    if (ok && du > 0 && (size_t)du < fc.e) {
+                        ok = gcd_divrem(hp, fc.e + 1, u, (size_t)du + 1, v, rem, s);
+                        keep(u, (size_t)du, 0);
+                        keep(v, fc.e - (size_t)du, 0);         // copied on the stream before the next factor reuses u and v
+                    } else if (ok) {
+                        if (fc.fails + 1 >= 64) ok = false;                 // the attempt cap of k_roots_small, for the same reason
+                        keep(hp, fc.e, fc.fails + 1);
+                    }
+                    temps_release(fm2);
+                }
+                temps_release(gm);
+            }
+            cur.swap(nxt);
+            pi ^= 1;
+            temps_release(round);
+        }
+        if (!ok) return false;
+        // ---- the leaves: one launch, then the order ----
+        const size_t nleaf = ldesc.size() / 3;
+        uint32_t* ddesc = reinterpret_cast<uint32_t*>(temp((ldesc.size() * sizeof(uint32_t) + sizeof(E) - 1) / sizeof(E)));
+        ok = hipMemcpyAsync(ddesc, ldesc.data(), ldesc.size() * sizeof(uint32_t), hipMemcpyHostToDevice, s) == hipSuccess && hipStreamSynchronize(s) == hipSuccess;
+        roots_small_launch(rc, leaf, 0, 0, uns, 0, ddesc, nullptr, false, c, nleaf, (double)(leaf_used + roots_used), s);
+        roots_rank_launch(roots, nf - 1, uns, nf - 1, nullptr, (long long)r, 1, s);
+        *n = (long long)r;
+        return ok && hipGetLastError() == hipSuccess;
+    }
 public:
+    // a polynomial of at most kRootsSmall + 1 coefficients (degree <= kRootsSmall) is finished by k_roots_small, one workgroup each
+    static constexpr size_t kRootsSmall = 64;
+    // The leaves ecfft_poly_find_roots needs for rows of nf coefficients, checked before anything runs: poly_gcd's rule for rows of
+    // nf, which covers every later step
+    static size_t roots_leaves(size_t nf) {
+        if (nf <= kRootsSmall + 1) return 1;
+        size_t N = 1; while (N < 2 * nf - 1) N <<= 1;
+        return N;
+    }
+    // ecfft_poly_find_roots: roots (count x (nf - 1), crate form) = the distinct roots of f_b in ascending order of their standard
+    // form, zero-padded; n_roots (host): their number, -1 for the zero polynomial.  nf <= kRootsSmall + 1: ONE launch of k_roots_small
+    // (with its Frobenius flag) for all rows and one of k_roots_rank.  Otherwise the polynomials run one after another
+    // (roots_one_large).  *capped = a factor exhausted the attempt cap.  Synchronous.  Caller holds lock() and checks the tree rule.
+    bool poly_find_roots(const E* f, size_t nf, E* roots, long long* n_roots, size_t count, bool* capped, hipStream_t s) {
+        RootsCall rc;
+        roots_exponents(rc.ep, &rc.nbits_p, rc.eh, &rc.nbits_h);
+        uint8_t* dexp = reinterpret_cast<uint8_t*>(temp((64 + sizeof(E) - 1) / sizeof(E)));
+        uint8_t both[64];
+        for (int i = 0; i < 32; ++i) { both[i] = rc.ep[i]; both[32 + i] = rc.eh[i]; }
+        bool ok = hipMemcpyAsync(dexp, both, 64, hipMemcpyHostToDevice, s) == hipSuccess && hipStreamSynchronize(s) == hipSuccess;
+        rc.dexp = dexp;
+        rc.flag = new_flag(s);
+        const size_t nr = nf - 1;
+        if (nf <= kRootsSmall + 1) {
+            long long* dn = reinterpret_cast<long long*>(temp((count * sizeof(long long) + sizeof(E) - 1) / sizeof(E)));
+            E* uns = temp(count * nr);
+            roots_small_launch(rc, f, nf, nf, uns, nr, nullptr, dn, true, 1u, count, (double)count * (double)(nf + nr), s);
+            roots_rank_launch(roots, nr, uns, nr, dn, 0, count, s);
+            ok = hipMemcpyAsync(n_roots, dn, count * sizeof(long long), hipMemcpyDeviceToHost, s) == hipSuccess && ok;
+        } else {
+            gcd_flag_ = new_flag(s);
+            for (size_t p = 0; p < count && ok; ++p) {
+                const TempMark mark = temps_mark();
+                ok = roots_one_large(rc, f + p * nf, nf, roots + p * nr, &n_roots[p], s);
+                temps_release(mark);
+            }
+        }
+        return finish_flagged(ok, rc.flag, capped, s);
+    }
 
     // coefficients of the reciprocal computed by k_series_base before the Newton steps take over (K0).  64 = one wave per pair: a
     // Newton step at p <= 64 costs a lift + EXIT in the latency regime, the recurrence's 63 tree sums a few us.

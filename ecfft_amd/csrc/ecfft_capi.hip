@@ -468,6 +468,28 @@ int run_poly_gcd(ecfft_ctx* c, DeviceChain<F>& ch, const void* a, size_t na, con
     });
 }
 
+// ecfft_poly_find_roots: synchronous (degrees are read back between the rounds, and `n_roots` is a host array whatever `mem` is).
+// Nothing fails on the data; ECFFT_ERR_HIP also reports a factor that exhausted the attempt cap.
+template <class F>
+int run_poly_find_roots(ecfft_ctx* c, DeviceChain<F>& ch, const void* f, size_t nf, void* roots, int64_t* n_roots, size_t count, int mem,
+                        void* stream) {
+    using E = typename F::elem;
+    if (!f || !n_roots || (!roots && nf > 1)) return ECFFT_ERR_BAD_ARG;
+    if (nf > SIZE_MAX / (64 * sizeof(E))) return ECFFT_ERR_BAD_ARG;
+    static_assert(DeviceChain<F>::kRootsSmall + 1 == ECFFT_ROOTS_SMALL_MAX, "the header states the small regime's bound");
+    static_assert(sizeof(long long) == sizeof(int64_t), "root counts are read back as long long");
+    const size_t N = DeviceChain<F>::roots_leaves(nf);                        // checked on the row length, before anything runs
+    if (N > 1 && N > ch.size()) return ECFFT_ERR_TREE_TOO_SMALL;
+    const size_t per = N > 4 * nf ? N : 4 * nf;
+    if (count > SIZE_MAX / (16 * per * sizeof(E))) return ECFFT_ERR_BAD_ARG;  // byte counts of the rows and temporaries must not wrap
+    const size_t eb = count * sizeof(E);
+    return staged(c, ch, mem, stream, {{f, nf * eb}}, {{nf > 1 ? roots : nullptr, (nf - 1) * eb}}, [&](auto d, auto o) -> int {
+        bool capped = false;
+        if (!ch.poly_find_roots((const E*)d[0], nf, (E*)o[0], (long long*)n_roots, count, &capped, (hipStream_t)stream)) return ECFFT_ERR_HIP;
+        return capped ? ECFFT_ERR_HIP : ECFFT_OK;
+    });
+}
+
 // standard = true: plain standard-form residues (the FFTree wire format) instead of the crate's in-memory representation
 template <class F>
 int table_of(DeviceChain<F>& ch, size_t m, int which, void* host_out, size_t cap, size_t* count, bool standard = false) {
@@ -1052,6 +1074,10 @@ int ecfft_poly_xgcd(ecfft_ctx* ctx, const void* a, size_t na, const void* b, siz
                     size_t count, int mem, void* stream) {
     if (na == 0 || nb == 0 || count == 0) return ECFFT_ERR_BAD_ARG;
     return on_chain(ctx, [&](auto& ch) { return run_poly_gcd(ctx, ch, a, na, b, nb, s, t, g, degrees, count, true, mem, stream); });
+}
+int ecfft_poly_find_roots(ecfft_ctx* ctx, const void* f, size_t nf, void* roots, int64_t* n_roots, size_t count, int mem, void* stream) {
+    if (nf == 0 || count == 0) return ECFFT_ERR_BAD_ARG;
+    return on_chain(ctx, [&](auto& ch) { return run_poly_find_roots(ctx, ch, f, nf, roots, n_roots, count, mem, stream); });
 }
 int ecfft_poly_eval_points(ecfft_ctx* ctx, const void* f, size_t nf, const void* points, size_t m, void* out, size_t count, int mem,
                            void* stream) {

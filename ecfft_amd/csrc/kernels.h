@@ -2524,6 +2524,281 @@ __global__ __launch_bounds__(kBlock) void k_gcd_combine(typename F::elem* __rest
 }
 
 // ---------------------------------------------------------------------------------------------
+// ecfft_poly_find_roots (utils::find_roots, src/utils.rs:25-44).  A polynomial or factor of degree <= K is finished by ONE
+// workgroup (k_roots_small); above that the host drives rounds on the poly_pow_mod / gcd / division bodies that end in the same
+// kernel, and k_roots_rank puts the roots in ascending order of their standard form.
+// ---------------------------------------------------------------------------------------------
+// sres (e residues, crate form) = (x + c)^exp mod h for the monic h of degree e >= 2 whose low e coefficients smod holds as PLAIN
+// residues; exp: nbits >= 1 bits, bit nbits - 1 set.  k_powmod_small's scan: a squaring is its schoolbook product (thread t sums
+// coefficients t and t + e) and e - 1 elimination steps of the monic h; "multiply by the base" is a shift, a scale by the plain
+// integer c and ONE elimination step: x r + c r - r_{e-1} h.  plain x crate stays crate.
+template <class F, int K>
+__device__ __forceinline__ void roots_pow_scan(typename F::elem* sres, typename F::elem* sx, typename F::elem* sprod,
+                                               const typename F::elem* smod, uint32_t e, uint32_t c, const uint8_t* __restrict__ exp,
+                                               uint32_t nbits, const typename F::telem& rinv, const typename F::elem& r1, uint32_t t) {
+    using E = typename F::elem;
+    const E cE = F::from_u32(c);
+    {
+        E v = F::zero();
+        if (t == 1) v = r1;
+        if (t == 0 && c) v = F::canon(F::mul(cE, r1));
+        sres[t] = v;
+    }
+    __syncthreads();
+    for (uint32_t i = nbits - 1; i-- > 0;) {
+        E x = sres[t];
+        if constexpr (sizeof(E) == 32) x = F::tmul(rinv, x);
+        sx[t] = F::canon(x);
+        __syncthreads();
+        if (t < e) {
+            E acc = F::zero(), lo = F::zero();
+            for (uint32_t k = 0; k < e; ++k) {
+                if (k == t + 1) { lo = acc; acc = F::zero(); }
+                const uint32_t j = k <= t ? t - k : t + e - k;
+                acc = F::canon(F::mul_add(sx[k], sres[j], acc));
+            }
+            if (t + 1 == e) { lo = acc; acc = F::zero(); }
+            sprod[t] = lo;
+            sprod[t + e] = acc;
+        }
+        __syncthreads();
+        for (uint32_t k = 2 * e - 2; k >= e; --k) {
+            if (t < e) sprod[k - e + t] = F::canon(F::sub(sprod[k - e + t], F::canon(F::mul(sprod[k], smod[t]))));
+            __syncthreads();
+        }
+        if (t < e) sres[t] = sprod[t];
+        __syncthreads();
+        if ((exp[i >> 3] >> (i & 7)) & 1) {
+            E v = F::zero();
+            if (t < e) {
+                const E top = sres[e - 1];
+                if (t) v = sres[t - 1];
+                if (c) v = F::canon(F::add(v, F::canon(F::mul(cE, sres[t]))));
+                v = F::canon(F::sub(v, F::canon(F::mul(top, smod[t]))));
+            }
+            __syncthreads();
+            if (t < e) sres[t] = v;
+            __syncthreads();
+        }
+    }
+}
+// The remainder sequence of (R0, R1), deg R0 = d0 >= deg R1, to its end: k_gcd_small's cross-multiplied steps without cofactors.
+// Rows of K + 1 entries; nothing above a row's degree is read.  On return R0 is a non-zero multiple of the gcd and the result its
+// degree.  sdeg: two ints.  Every thread takes the same path (degrees come from LDS after a barrier).
+template <class F, int K>
+__device__ __forceinline__ int roots_gcd_rows(typename F::elem*& R0, typename F::elem*& R1, int d0, int* sdeg, uint32_t t) {
+    using E = typename F::elem;
+    if (t < 2) sdeg[t] = -1;
+    __syncthreads();
+    if ((int)t < d0 && !F::is_zero(R1[t])) atomicMax(&sdeg[1], (int)t);
+    __syncthreads();
+    int d1 = sdeg[1];
+    __syncthreads();
+    if (t < 2) sdeg[t] = -1;
+    __syncthreads();
+    uint32_t par = 0;
+    while (d1 >= 0) {
+        while (d0 >= d1) {
+            const uint32_t k = (uint32_t)(d0 - d1);
+            const E lr = R0[d0], lb = R1[d1];
+            __syncthreads();
+            if (t == 0) sdeg[par ^ 1] = -1;
+            if ((int)t < d0) {
+                E v = F::mul(lb, R0[t]);
+                if (t >= k) v = F::sub(F::canon(v), F::canon(F::mul(lr, R1[t - k])));
+                v = F::canon(v);
+                R0[t] = v;
+                if (!F::is_zero(v)) atomicMax(&sdeg[par], (int)t);
+            }
+            __syncthreads();
+            d0 = sdeg[par];
+            par ^= 1;
+        }
+        { E* x = R0; R0 = R1; R1 = x; }
+        { int x = d0; d0 = d1; d1 = x; }
+    }
+    return d0;
+}
+// All roots of one polynomial, or of one factor, of degree <= K in one workgroup of K threads, everything in LDS.  Block b reads
+// nin <= K + 1 coefficients (crate form, untrimmed, any non-zero leading coefficient) at in + b*ldin and writes its roots, in crate
+// form and in NO particular order, from out + b*ldout on; desc != nullptr gives block b the triple (input offset, input length,
+// output offset) instead.  n_out[b] (may be null) = the number of roots, -1 for the zero polynomial.
+//   frob != 0: the row is first replaced by g = gcd(f, x^p - x mod f), the product of its distinct linear factors (x^p - x is the
+//     squarefree product of ALL x - a).  Otherwise the row is taken to be such a product already.
+//   Then a stack of monic factors, kept as PLAIN residues without their leading 1 (at most K coefficients in all): a factor
+//   x + a yields the root -a; a factor h of degree e >= 2 is split by the next shift c = c0, c0 + 1, ... (one counter per
+//   workgroup, incremented after every attempt; p is odd): w = (x + c)^((p-1)/2) mod h, u = gcd(h, w - 1), v = h / u, a success
+//   when 0 < deg u < e.  u is made monic by the one inversion of the split; the exact division by the monic u needs none.
+// Loop bounds are fixed at launch: the exponents' bit counts, degrees <= K, and kCap consecutive failed shifts of one factor,
+// after which *flag = 1 and the workgroup stops (a bug must not spin it; for distinct roots the chance is below 2^-63).
+// exp_p / exp_h: p and (p-1)/2 as little-endian bytes with their top bits set.  rinv = R^-1 (table form), r1 = R (M31: both 1).
+template <class F, int K>
+__global__ __launch_bounds__(K) void k_roots_small(const typename F::elem* __restrict__ in, size_t ldin, uint32_t nin,
+                                                   typename F::elem* __restrict__ out, size_t ldout, const uint32_t* __restrict__ desc,
+                                                   long long* __restrict__ n_out, uint32_t frob, uint32_t c0,
+                                                   const uint8_t* __restrict__ exp_p, uint32_t nbits_p,
+                                                   const uint8_t* __restrict__ exp_h, uint32_t nbits_h, typename F::telem rinv,
+                                                   typename F::elem r1, int* __restrict__ flag) {
+    using E = typename F::elem;
+    constexpr uint32_t kCap = 64;
+    __shared__ E stack[K], smod[K], sres[K], sx[K], sprod[2 * K], rows[2 * (K + 1)];
+    __shared__ E snorm;
+    __shared__ int sdeg[2], stk_deg[K], stk_off[K];
+    const uint32_t t = threadIdx.x;
+    const size_t b = blockIdx.x;
+    const E* fb = in + b * ldin;
+    E* ob = out + b * ldout;
+    if (desc) { fb = in + desc[3 * b]; nin = desc[3 * b + 1]; ob = out + desc[3 * b + 2]; }
+    // ---- the true degree, and the row made monic (plain residues f_t / f_d) ----
+    if (t == 0) sdeg[0] = -1;
+    __syncthreads();
+    E mine = F::zero();
+    if (t < nin) mine = F::canon(fb[t]);
+    if (!F::is_zero(mine)) atomicMax(&sdeg[0], (int)t);
+    if (t == 0 && nin == K + 1 && !F::is_zero(F::canon(fb[K]))) atomicMax(&sdeg[0], K);
+    __syncthreads();
+    const int d = sdeg[0];
+    if (d <= 0) {
+        if (t == 0 && n_out) n_out[b] = d;                   // the zero polynomial: -1; a non-zero constant: no roots
+        return;
+    }
+    if (t == 0) snorm = F::canon(F::inv(F::canon(fb[d])));
+    __syncthreads();
+    {
+        E v = F::zero();
+        if ((int)t < d) v = F::canon(F::mul(mine, snorm));
+        stack[t] = v;
+        smod[t] = v;
+    }
+    if (t == 0) { stk_deg[0] = d; stk_off[0] = 0; }
+    __syncthreads();
+    E* R0 = rows;
+    E* R1 = rows + K + 1;
+    if (frob && d >= 2) {
+        // g = gcd(f, x^p - x mod f); the scan's base is x (c = 0)
+        roots_pow_scan<F, K>(sres, sx, sprod, smod, (uint32_t)d, 0u, exp_p, nbits_p, rinv, r1, t);
+        if ((int)t < d) {
+            E v = sres[t];
+            if (t == 1) v = F::canon(F::sub(v, r1));
+            R1[t] = v;
+            R0[t] = smod[t];
+        }
+        if (t == 0) R0[d] = F::one();
+        const int dg = roots_gcd_rows<F, K>(R0, R1, d, sdeg, t);
+        if (dg <= 0) {                                       // deg g = 0: no root in the field (g != 0: f != 0)
+            if (t == 0 && n_out) n_out[b] = 0;
+            return;
+        }
+        if (t == 0) { snorm = F::canon(F::inv(R0[dg])); stk_deg[0] = dg; }
+        __syncthreads();
+        if ((int)t < dg) stack[t] = F::canon(F::mul(R0[t], snorm));
+        __syncthreads();
+    }
+    // ---- the splitting recursion on the stack ----
+    int sp = 1;
+    uint32_t c = c0, fails = 0, nout = 0;
+    while (sp > 0) {
+        const int e = stk_deg[sp - 1], base = stk_off[sp - 1];
+        if (e == 1) {
+            if (t == 0) ob[nout] = F::canon(F::neg(F::canon(F::mul(stack[base], r1))));
+            ++nout; --sp;
+            continue;
+        }
+        {
+            E v = F::zero();
+            if ((int)t < e) v = stack[base + t];
+            smod[t] = v;
+        }
+        __syncthreads();
+        roots_pow_scan<F, K>(sres, sx, sprod, smod, (uint32_t)e, c, exp_h, nbits_h, rinv, r1, t);
+        R0 = rows; R1 = rows + K + 1;
+        if ((int)t < e) {
+            E v = sres[t];
+            if (t == 0) v = F::canon(F::sub(v, r1));
+            R1[t] = v;
+            R0[t] = smod[t];
+        }
+        if (t == 0) R0[e] = F::one();
+        const int du = roots_gcd_rows<F, K>(R0, R1, e, sdeg, t);
+        ++c;
+        if (du <= 0 || du >= e) {
+            if (++fails >= kCap) { if (t == 0) *flag = 1; break; }
+            continue;
+        }
+        fails = 0;
+        // u = R0 / lc(R0) (sx); v = h / u by synthetic division of A = h (sprod, with its leading 1) -> sres
+        if (t == 0) snorm = F::canon(F::inv(R0[du]));
+        __syncthreads();
+        if ((int)t < du) sx[t] = F::canon(F::mul(R0[t], snorm));
+        if ((int)t < e) sprod[t] = smod[t];
+        if (t == 0) sprod[e] = F::one();
+        __syncthreads();
+        for (int k = e - du; k >= 0; --k) {
+            const E qk = sprod[k + du];
+            if ((int)t < du) sprod[k + t] = F::canon(F::sub(sprod[k + t], F::canon(F::mul(qk, sx[t]))));
+            if (t == 0) sres[k] = qk;
+            __syncthreads();
+        }
+        if ((int)t < du) stack[base + t] = sx[t];
+        if ((int)t < e - du) stack[base + du + t] = sres[t];
+        if (t == 0) { stk_deg[sp - 1] = du; stk_deg[sp] = e - du; stk_off[sp] = base + du; }
+        ++sp;
+        __syncthreads();
+    }
+    if (t == 0 && n_out) n_out[b] = (long long)nout;
+}
+// a < b as standard-form integers (ark's Ord on Fp)
+template <class F>
+__device__ __forceinline__ bool roots_less(const typename F::elem& a, const typename F::elem& b) {
+    if constexpr (sizeof(typename F::elem) == 4) return a < b;
+    else {
+        bool lt = false;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) if (a.l[i] != b.l[i]) lt = a.l[i] < b.l[i];
+        return lt;
+    }
+}
+// Row r (blockIdx.y) of dst (ldd elements) = the n distinct roots of row r of src (lds apart, crate form, any order) in ascending
+// order of their standard form, zero above: rank(i) = the number of roots smaller than root i is a permutation, so each root is
+// scattered to its rank.  n = n_dev[r] (negative: 0) or n_fixed.  Standard form is one table multiply by R^-1 (M31: R = 1); the
+// others pass through LDS in tiles of kBlock.
+template <class F>
+__global__ __launch_bounds__(kBlock) void k_roots_rank(typename F::elem* __restrict__ dst, size_t ldd, const typename F::elem* __restrict__ src,
+                                                       size_t lds, const long long* __restrict__ n_dev, long long n_fixed,
+                                                       typename F::telem rinv) {
+    using E = typename F::elem;
+    __shared__ E tile[kBlock];
+    const uint32_t t = threadIdx.x;
+    const size_t r = blockIdx.y, i = (size_t)blockIdx.x * kBlock + t;
+    long long nn = n_dev ? n_dev[r] : n_fixed;
+    if (nn < 0) nn = 0;
+    const size_t n = (size_t)nn < ldd ? (size_t)nn : ldd;
+    const E* sr = src + r * lds;
+    E mine = F::zero(), ms = F::zero();
+    if (i < n) {
+        mine = F::canon(sr[i]);
+        ms = mine;
+        if constexpr (sizeof(E) == 32) ms = F::tmul(rinv, ms);
+        ms = F::canon(ms);
+    }
+    size_t rank = 0;
+    for (size_t j0 = 0; j0 < n; j0 += kBlock) {
+        __syncthreads();
+        if (j0 + t < n) {
+            E v = F::canon(sr[j0 + t]);
+            if constexpr (sizeof(E) == 32) v = F::tmul(rinv, v);
+            tile[t] = F::canon(v);
+        }
+        __syncthreads();
+        const uint32_t m = n - j0 < (size_t)kBlock ? (uint32_t)(n - j0) : (uint32_t)kBlock;
+        if (i < n)
+            for (uint32_t j = 0; j < m; ++j) rank += roots_less<F>(tile[j], ms) ? 1u : 0u;
+    }
+    if (i < n) dst[r * ldd + rank] = mine;
+    else if (i < ldd) dst[r * ldd + i] = F::zero();
+}
+
+// ---------------------------------------------------------------------------------------------
 // generic element-wise helper for tree construction: functor(i) for i < n
 // ---------------------------------------------------------------------------------------------
 template <class Fn>

@@ -33,9 +33,11 @@ EXPORTS = ["ecfft_elem_size", "ecfft_build_fftree", "ecfft_fftree_new", "ecfft_c
            "ecfft_comm_stats_enable", "ecfft_comm_stats_read", "ecfft_extend_sharded", "ecfft_enter_sharded", "ecfft_exit_sharded", "ecfft_device_copy", "ecfft_shader_clock", "ecfft_device_alloc", "ecfft_device_free", "ecfft_device_sync", "ecfft_build_extend_shard", "ecfft_ctx_device_bytes", "ecfft_extend_sharded_layout", "ecfft_build_enter_shard", "ecfft_build_exit_shard", "ecfft_build_exit_shard_opts",
            "ecfft_fftree_serialize", "ecfft_fftree_deserialize", "ecfft_tree_rational_maps", "ecfft_ctx_trim", "ecfft_comm_abort", "ecfft_comm_set_rccl_library", "ecfft_comm_set_link_striping",
            "ecfft_poly_mul", "ecfft_poly_inv_series", "ecfft_poly_divrem", "ecfft_poly_eval_points", "ecfft_poly_interpolate",
-           "ecfft_poly_pow_mod", "ecfft_poly_mul_mod", "ecfft_poly_gcd", "ecfft_poly_xgcd"]
+           "ecfft_poly_pow_mod", "ecfft_poly_mul_mod", "ecfft_poly_gcd", "ecfft_poly_xgcd", "ecfft_poly_find_roots"]
 # include/ecfft_hip.h ECFFT_GCD_SMALL_MAX: max(na, nb) up to which a gcd runs in one workgroup per pair, on any tree
 GCD_SMALL_MAX = 256
+# include/ecfft_hip.h ECFFT_ROOTS_SMALL_MAX: nf up to which poly_find_roots finishes a polynomial in one workgroup, on any tree
+ROOTS_SMALL_MAX = 65
 
 # include/ecfft_hip_hooks.h: only in a build with -DECFFT_TEST_HOOKS (tests/hooks/libecfft_hip_hooks.so), never in the shipped library
 HOOK_EXPORTS = ['ecfft_selftest_field', 'ecfft_selfcheck_pointwise_z', 'ecfft_test_fail_next_collective', 'ecfft_selftest_blk16', 'ecfft_selftest_blk16_small', 'ecfft_test_fail_build_rank', 'ecfft_comm_init_projection', 'ecfft_selftest_blk32', 'ecfft_ctx_low_map']
@@ -78,6 +80,7 @@ def _bind(L):
     L.ecfft_poly_mul_mod.restype, L.ecfft_poly_mul_mod.argtypes = ci, [vp, vp, sz, vp, sz, vp, sz, vp, sz, ci, vp]
     L.ecfft_poly_gcd.restype, L.ecfft_poly_gcd.argtypes = ci, [vp, vp, sz, vp, sz, vp, vp, sz, ci, vp]
     L.ecfft_poly_xgcd.restype, L.ecfft_poly_xgcd.argtypes = ci, [vp, vp, sz, vp, sz, vp, vp, vp, vp, sz, ci, vp]
+    L.ecfft_poly_find_roots.restype, L.ecfft_poly_find_roots.argtypes = ci, [vp, vp, sz, vp, vp, sz, ci, vp]
     L.ecfft_tree_table.restype, L.ecfft_tree_table.argtypes = ci, [vp, sz, ci, vp, sz, ctypes.POINTER(sz)]
     L.ecfft_build_points.restype, L.ecfft_build_points.argtypes = ci, [ci, sz, vp, vp, vp]
     L.ecfft_device_info.restype, L.ecfft_device_info.argtypes = ci, [ci, ctypes.c_char_p, sz]
@@ -563,6 +566,25 @@ class FFTree:
             raise ValueError("poly_xgcd: empty operand, count = 0 or a context that holds no full tree")
         _check(rc)
         return s, t, g, degrees
+
+    def poly_find_roots(self, f, count=1):
+        """(roots, n_roots): the distinct roots in the field (ecfft_poly_find_roots <-> utils::find_roots, src/utils.rs:25-44) of
+        `count` polynomials laid end to end, f of count * nf coefficients; rows need not be trimmed.  roots has count * (nf - 1)
+        elements: row b holds its n_roots[b] roots in ascending order of their standard form, then zeros; n_roots is a numpy int64
+        array, 0 for a non-zero constant and -1 for the zero polynomial (every element is a root; the row is zero).  Multiplicities
+        do not matter.  Deterministic: the splitting shifts are 1, 2, 3, ...  nf <= ROOTS_SMALL_MAX works on any tree (one launch
+        for all rows); otherwise a tree of next_pow2(2 nf - 1) leaves.  numpy arrays (host) or contiguous CUDA tensors (device, on
+        the current stream).  Synchronous."""
+        (f,), (pf,), new, mem, stream = self._poly_io([f])
+        assert count > 0 and f.shape[0] % count == 0
+        nf = f.shape[0] // count
+        roots = new(count * max(nf - 1, 0))
+        n_roots = np.empty(count, np.int64)
+        rc = self._L.ecfft_poly_find_roots(self._h, pf, nf, self._ptr(roots) if roots.shape[0] else None, n_roots.ctypes.data, count, mem, stream)
+        if rc == ERR_BAD_ARG:
+            raise ValueError("poly_find_roots: empty operand, count = 0 or a context that holds no full tree")
+        _check(rc)
+        return roots, n_roots
 
     # ---- the remaining FFTree algorithms (host numpy arrays; synchronous) ---------------------
     def _np(self, x):

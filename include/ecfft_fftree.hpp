@@ -240,6 +240,19 @@ public:
         trim(s); trim(t);
         return {std::move(s), std::move(t), std::move(g)};
     }
+    // the distinct roots of f in the field in ascending order of their standard form (ecfft_poly_find_roots <-> utils::find_roots,
+    // src/utils.rs:25-44, whose result is sorted the same way).  f need not be trimmed; multiplicities do not matter; a non-zero
+    // constant has none.  The zero polynomial, on which the reference panics, throws.  Up to ECFFT_ROOTS_SMALL_MAX coefficients on
+    // any tree; tree rule in ecfft_hip.h.  Deterministic (the splitting shifts are 1, 2, 3, ...).  Synchronous.
+    std::vector<Elem> find_roots(const std::vector<Elem>& f) const {
+        require(!f.empty(), "find_roots: the polynomial must not be empty");
+        std::vector<Elem> roots(f.size() - 1);
+        int64_t n = 0;
+        check(ecfft_poly_find_roots(ctx_, f.data(), f.size(), roots.empty() ? nullptr : roots.data(), &n, 1, ECFFT_MEM_HOST, nullptr));
+        require(n >= 0, "find_roots: the zero polynomial (every element is a root)");
+        roots.resize((size_t)n);
+        return roots;
+    }
     size_t device_bytes() const { return ecfft_ctx_device_bytes(ctx_); }     // HBM held between calls: tables + scratch
     // device-resident variants (pointers into HBM, caller's stream)
     void enter_device(const Elem* coeffs, Elem* evals, size_t n, void* stream) const { check(ecfft_enter(ctx_, coeffs, evals, n, ECFFT_MEM_DEVICE, stream)); }
@@ -277,6 +290,11 @@ public:
     // ... with the cofactors: s count x max(nb - 1, 1), t count x max(na - 1, 1); s or t may be null.  Synchronous.
     void xgcd_device(const Elem* a, size_t na, const Elem* b, size_t nb, Elem* s, Elem* t, Elem* g, int64_t* degrees, size_t count, void* stream) const {
         check(ecfft_poly_xgcd(ctx_, a, na, b, nb, s, t, g, degrees, count, ECFFT_MEM_DEVICE, stream));
+    }
+    // count polynomials f count x nf (untrimmed), roots count x (nf - 1) sorted and zero-padded; n_roots: count HOST entries (-1: the
+    // zero polynomial).  Synchronous.
+    void find_roots_device(const Elem* f, size_t nf, Elem* roots, int64_t* n_roots, size_t count, void* stream) const {
+        check(ecfft_poly_find_roots(ctx_, f, nf, roots, n_roots, count, ECFFT_MEM_DEVICE, stream));
     }
     // count triples: a count x na, b count x nb, modulus count x nm, out count x (nm - 1).  Synchronous.
     void mul_mod_device(const Elem* a, size_t na, const Elem* b, size_t nb, const Elem* modulus, size_t nm, Elem* out, size_t count, void* stream) const {

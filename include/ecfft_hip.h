@@ -220,6 +220,36 @@ int ecfft_poly_gcd(ecfft_ctx* ctx, const void* a, size_t na, const void* b, size
 int ecfft_poly_xgcd(ecfft_ctx* ctx, const void* a, size_t na, const void* b, size_t nb, void* s, void* t, void* g, int64_t* degrees,
                     size_t count, int mem, void* stream);
 
+/* Roots of polynomials in the field.
+ *   ecfft_poly_find_roots <-> ecfft::utils::find_roots(poly)                        src/utils.rs:25-44
+ * Layout: f is count x nf coefficients in the crate's form; as in ecfft_poly_gcd the rows NEED NOT BE TRIMMED.  roots is
+ * count x (nf - 1) elements: row b holds the n_roots[b] DISTINCT roots of f_b in the field in ascending order of their
+ * standard-form integer (ark's Ord on Fp, what roots.sort() in the reference produces), fully reduced, in the crate's form, the
+ * rest of the row zero.  roots may be NULL only when nf == 1 and must not overlap f.  `n_roots` is a HOST pointer whatever `mem`
+ * is, `count` entries, required: a non-zero constant gives 0; the zero polynomial gives -1 and a zero row (every element is a
+ * root; the reference panics there, at assert_eq!(1, factor.degree())).
+ * Method (both fields have odd p, which the exponent (p - 1) / 2 below relies on):
+ *   g = gcd(f, x^p - x mod f) is the product of the distinct linear factors of f WHATEVER the multiplicities are, because
+ *   x^p - x is the squarefree product of all x - a.  The reference's square_free_factors and the higher degrees of its
+ *   distinct_degree_factors are therefore not needed to find roots.  A monic product h of e >= 2 distinct linear factors is split
+ *   by a shift c: w = (x + c)^((p-1)/2) mod h, u = gcd(h, w - 1), v = h / u, a success when 0 < deg u < e; x + a yields -a.  The
+ *   shifts are the plain integers 1, 2, 3, ... from an attempt counter incremented after every attempt: no randomness, and since
+ *   the set of roots does not depend on the shifts the result is deterministic and bit-exact.
+ * ECFFT_ROOTS_SMALL_MAX: nf up to which a polynomial is finished by one workgroup, everything in LDS; all `count` rows are ONE
+ * launch (plus the ordering).  Above it the polynomials run one after another: g on the bodies of ecfft_poly_pow_mod and
+ * ecfft_poly_gcd, then rounds in which all pending factors of more than 64 roots share the launches of one modular power, until
+ * every factor has at most 64 roots; those are finished by one launch of the same workgroup kernel.
+ * A factor that fails 64 shifts in a row (chance below 2^-63 for distinct roots; the bound keeps a defect from spinning) ends the
+ * call with ECFFT_ERR_HIP.
+ * Tree: nf <= ECFFT_ROOTS_SMALL_MAX needs no transform (any tree).  Otherwise next_pow2(2 nf - 1) leaves, ecfft_poly_gcd's rule for
+ * rows of nf, which covers the modular power (next_pow2(2d - 1), d <= nf - 1) and every later, smaller step; it is checked on the
+ * row length before anything runs.  Else ECFFT_ERR_TREE_TOO_SMALL.
+ * ECFFT_ERR_BAD_ARG: NULL f or n_roots, NULL roots with nf > 1, nf or count 0, a context that holds no full tree, a byte count
+ * that would wrap.  Nothing fails on the data.  The call is SYNCHRONOUS.  Memory, stream, threading and pooled temporaries as
+ * for ecfft_poly_gcd. */
+#define ECFFT_ROOTS_SMALL_MAX 65     /* nf up to which a polynomial is finished in one workgroup, on any tree */
+int ecfft_poly_find_roots(ecfft_ctx* ctx, const void* f, size_t nf, void* roots, int64_t* n_roots, size_t count, int mem, void* stream);
+
 /* The remaining FFTree algorithms, composed from the same GPU kernels.  Synchronous.
  *   ecfft_mextend         <-> FFTree::mextend(&self, &[F], Moiety)      src/fftree.rs:138-141
  *   ecfft_redc            <-> FFTree::redc_z0 / redc_z1(&self, evals, a)  src/fftree.rs:264-275  (moiety S0 / S1)
