@@ -52,6 +52,7 @@ struct DeviceAllocError : std::bad_alloc {
 };
 
 static inline unsigned ilog2(size_t n) { unsigned l = 0; while (n > 1) { n >>= 1; ++l; } return l; }
+static inline size_t next_pow2(size_t n) { size_t m = 1; while (m < n) m <<= 1; return m; }
 static inline unsigned nblocks(size_t n) { return (unsigned)((n + kBlock - 1) / kBlock); }
 
 template <class Fn>
@@ -1619,6 +1620,19 @@ public:
         temps_done();
         return ok && hipGetLastError() == hipSuccess;
     }
+    // The leaves an operation needs, checked by the C ABI before anything runs and used by the drivers below (1: no transform)
+    static size_t mul_leaves(size_t na, size_t nb) { return next_pow2(na + nb - 1); }
+    // the last Newton step: p = ceil(k / 2), p' = k on next_pow2(2p + k - 2) leaves (k <= kSeriesBase runs none; the rule is the same)
+    static size_t inv_series_leaves(size_t k) { return next_pow2(2 * k - 1); }
+    // the two products of divrem_body: rev(a) g (2 nq - 1 coefficients) and (b mod x^nr)(q mod x^nr)
+    static size_t divrem_leaves(size_t na, size_t nb) {
+        const size_t nq = na >= nb ? na - nb + 1 : 0, nr = nb - 1;
+        if (nq == 0 || nr == 0) return 1;
+        const size_t mq = nq < nr ? nq : nr;
+        return next_pow2(2 * nq - 1 > nr + mq - 1 ? 2 * nq - 1 : nr + mq - 1);
+    }
+    // the modular products of a power on residues of d = nm - 1 coefficients (powmod_step); the reduction of the base is divrem_leaves
+    static size_t powmod_leaves(size_t nm) { return nm - 1 <= kPowSmall ? 1 : next_pow2(2 * (nm - 1) - 1); }
 
     // ecfft_poly_inv_series (no reference counterpart): out_b = 1/f_b mod x^k for `count` series laid end to end (f: count x nf,
     // out: count x k, crate representation).  The first p0 = ceil(k / 2^t) <= kSeriesBase coefficients come from the schoolbook
@@ -1638,60 +1652,8 @@ public:
     // divisor's leading coefficient on the device.  Synchronous; *singular = some b_b[nb-1] == 0.  Caller holds lock().
     bool poly_divrem(const E* a, size_t na, const E* b, size_t nb, E* q, E* r, size_t count, bool* singular, hipStream_t s) {
         int* flag = new_flag(s);
-        const size_t nq = na >= nb ? na - nb + 1 : 0, nr = nb - 1;
-        bool ok = true;
-        if (nq == 0 || nb == 1) {
-            E* binv = temp(count);                                // 1/b_{nb-1} of every pair, crate form
-            series_base(b + nb - 1, nb, 1, binv, 1, 1, count, flag, s);
-            if (nq == 0 && r) {
-                foreach_n(s, count * nr, [=] __device__(size_t i) { const size_t bi = i / nr, j = i - bi * nr; r[i] = j < na ? a[bi * na + j] : F::zero(); });
-            } else if (nq && q) {
-                const E rinv = rinv_;
-                foreach_n(s, count * na, [=] __device__(size_t i) { q[i] = F::canon(F::mul(F::mul(a[i], binv[i / na]), rinv)); });
-            }
-            return finish_flagged(ok, flag, singular, s);
-        }
-        const size_t nf = nq < nb ? nq : nb, np = 2 * nq - 1;    // rev(b) mod x^nq; rev(a) mod x^nq times g
-        E* fr = temp(count * nf); E* ar = temp(count * nq); E* g = temp(count * nq); E* pq = temp(count * np);
-        E* qq = q ? q : temp(count * nq);
-        foreach_n(s, count * nf, [=] __device__(size_t i) { const size_t bi = i / nf, j = i - bi * nf; fr[i] = b[bi * nb + nb - 1 - j]; });
-        foreach_n(s, count * nq, [=] __device__(size_t i) { const size_t bi = i / nq, j = i - bi * nq; ar[i] = a[bi * na + na - 1 - j]; });
-        ok = inv_series_body(fr, nf, nf, g, nq, count, flag, s) && ok;
-        ok = poly_mul_body(ar, nq, nq, g, nq, nq, pq, count, s) && ok;
-        foreach_n(s, count * nq, [=] __device__(size_t i) { const size_t bi = i / nq, j = i - bi * nq; qq[i] = pq[bi * np + nq - 1 - j]; });
-        if (r) {
-            const size_t mq = nq < nr ? nq : nr, npr = nr + mq - 1, total = count * nr;
-            E* pr = temp(count * npr);
-            ok = poly_mul_body(b, nr, nb, qq, mq, nq, pr, count, s) && ok;    // (b mod x^nr)(q mod x^nr): rows read in place
-            ECFFT_LAUNCH(KC_POINTWISE, sizeof(E) * 3.0 * (double)total, k_divrem_sub<F>, dim3(nblocks(total)), dim3(kBlock), 0, s,
-                         r, nr, a, na, (const E*)pr, npr, total);
-        }
+        const bool ok = divrem_body(a, na, b, nb, q, r, count, flag, s);
         return finish_flagged(ok, flag, singular, s);
-    }
-    // The remainder half of poly_divrem inside a longer call (poly_pow_mod and poly_mul_mod reduce their operands with it): r_b =
-    // a_b mod f_b for nm >= 2 (r: count x (nm - 1)), the same reciprocal, products and subtraction, without the quotient's output,
-    // the read-back of the flag and the release of the temporaries.  na < nm copies a into r and checks the leading coefficient.
-    bool rem_body(const E* a, size_t na, const E* f, size_t nm, E* r, size_t count, int* flag, hipStream_t s) {
-        const size_t nq = na >= nm ? na - nm + 1 : 0, nr = nm - 1;
-        if (nq == 0) {
-            E* finv = temp(count);
-            series_base(f + nm - 1, nm, 1, finv, 1, 1, count, flag, s);
-            foreach_n(s, count * nr, [=] __device__(size_t i) { const size_t bi = i / nr, j = i - bi * nr; r[i] = j < na ? a[bi * na + j] : F::zero(); });
-            return true;
-        }
-        const size_t nf = nq < nm ? nq : nm, np = 2 * nq - 1;
-        E* fr = temp(count * nf); E* ar = temp(count * nq); E* g = temp(count * nq); E* pq = temp(count * np); E* qq = temp(count * nq);
-        foreach_n(s, count * nf, [=] __device__(size_t i) { const size_t bi = i / nf, j = i - bi * nf; fr[i] = f[bi * nm + nm - 1 - j]; });
-        foreach_n(s, count * nq, [=] __device__(size_t i) { const size_t bi = i / nq, j = i - bi * nq; ar[i] = a[bi * na + na - 1 - j]; });
-        bool ok = inv_series_body(fr, nf, nf, g, nq, count, flag, s);
-        ok = poly_mul_body(ar, nq, nq, g, nq, nq, pq, count, s) && ok;
-        foreach_n(s, count * nq, [=] __device__(size_t i) { const size_t bi = i / nq, j = i - bi * nq; qq[i] = pq[bi * np + nq - 1 - j]; });
-        const size_t mq = nq < nr ? nq : nr, npr = nr + mq - 1, total = count * nr;
-        E* pr = temp(count * npr);
-        ok = poly_mul_body(f, nr, nm, qq, mq, nq, pr, count, s) && ok;
-        ECFFT_LAUNCH(KC_POINTWISE, sizeof(E) * 3.0 * (double)total, k_divrem_sub<F>, dim3(nblocks(total)), dim3(kBlock), 0, s,
-                     r, nr, a, na, (const E*)pr, npr, total);
-        return ok;
     }
 
     // ecfft_poly_mul_mod (the step of utils::pow_mod, src/utils.rs:205, 207: div_rem(&a.naive_mul(&b), modulus)): out_b =
@@ -1702,7 +1664,7 @@ public:
         const size_t nc = na + nb - 1;
         E* c = temp(count * nc);
         bool ok = poly_mul_body(a, na, na, b, nb, nb, c, count, s);
-        ok = rem_body(c, nc, f, nm, out, count, flag, s) && ok;
+        ok = divrem_body(c, nc, f, nm, nullptr, out, count, flag, s) && ok;
         return finish_flagged(ok, flag, singular, s);
     }
 
@@ -1710,11 +1672,11 @@ public:
     static constexpr size_t kPowSmall = 64;
     // ecfft_poly_pow_mod (utils::pow_mod, src/utils.rs:194-211): out_b = a_b^e mod f_b for `count` pairs laid end to end (a: count x
     // na, f: count x nm, out: count x d, d = nm - 1, zero-padded above its degree); e: `nbits` bits in little-endian HOST bytes with
-    // bit nbits - 1 set (nbits == 0: out_b = 1), shared by all pairs.  a is reduced below nm coefficients first (rem_body).
+    // bit nbits - 1 set (nbits == 0: out_b = 1), shared by all pairs.  a is reduced below nm coefficients first (divrem_body).
     //   d <= kPowSmall: k_powmod_small, the whole scan in one launch.
     //   otherwise, on T_N, N = next_pow2(2d - 1): g = 1/rev(f) mod x^(d-1) once (inv_series_body), then g, f mod x^d and the base
-    //   lifted ONCE to evaluations kept for the call (3 count N elements); res = a, then per bit below the top one a squaring and,
-    //   on a set bit, a product with the kept base.  A modular product (powmod_step) is three lifts and three batched EXIT_N:
+    //   lifted ONCE to evaluations kept for the call (keep_modulus: 3 count N elements); res = a, then per bit below the top one a
+    //   squaring and, on a set bit, a product with the kept base.  A modular product (powmod_step) is three lifts and three batched EXIT_N:
     //     c = x y                                  (2d - 1 coefficients; y is x itself or the kept base)
     //     q = rev(rev(c) mod x^(d-1) g mod x^(d-1))   against the kept g   (2d - 3 coefficients before the cut)
     //     res = (c mod x^d) - (f mod x^d) q mod x^d   against the kept f   (2d - 2 coefficients before the cut)
@@ -1730,60 +1692,95 @@ public:
         size_t lda = na, la = na;
         if (na >= nm) {
             E* r = temp(count * d);
-            ok = rem_body(a, na, f, nm, r, count, flag, s) && ok;
+            ok = divrem_body(a, na, f, nm, nullptr, r, count, flag, s) && ok;
             ar = r; lda = la = d;
         }
         const E r1 = F::to_mont(F::one());
         const TE rinv = F::to_table(rinv_);
         if (d <= kPowSmall) {
             const size_t nbytes = (nbits + 7) / 8;
-            uint8_t* dexp = reinterpret_cast<uint8_t*>(temp((nbytes + sizeof(E) - 1) / sizeof(E)));
+            uint8_t* dexp = temp_as<uint8_t>(nbytes);
             if (nbytes) ok = hipMemcpyAsync(dexp, exp, nbytes, hipMemcpyHostToDevice, s) == hipSuccess && ok;
-            for (size_t c0 = 0; c0 < count; c0 += (size_t)1 << 16) {
-                const size_t c = count - c0 < ((size_t)1 << 16) ? count - c0 : (size_t)1 << 16;
+            for_chunks(count, [&](size_t c0, size_t c) {
                 ECFFT_LAUNCH(KC_POINTWISE, sizeof(E) * (double)c * (double)(la + nm + d) + (double)nbytes,
                              (k_powmod_small<F, (int)kPowSmall>), dim3((unsigned)c), dim3((unsigned)kPowSmall), 0, s, out + c0 * d,
                              ar + c0 * lda, lda, (uint32_t)la, f + c0 * nm, (uint32_t)d, (const uint8_t*)dexp, (uint32_t)nbits, rinv, r1, flag);
-            }
+            });
             return finish_flagged(ok, flag, singular, s);
         }
-        size_t N = 1; while (N < 2 * d - 1) N <<= 1;
-        const size_t h = N / 2, total = count * N;
-        const unsigned lN = ilog2(N);
-        // ---- once per call: g, then the evaluations of g | f mod x^d | base on T_N in the natural leaf order ----
-        E* kept = temp(3 * total);
-        {
-            const TempMark mark = temps_mark();
-            const size_t ng = d - 1;
-            E* fr = temp(count * ng); E* g = temp(count * ng); E* S = temp(3 * count * d);
-            foreach_n(s, count * ng, [=] __device__(size_t i) { const size_t b = i / ng, j = i - b * ng; fr[i] = f[b * nm + d - j]; });
-            ok = inv_series_body(fr, ng, ng, g, ng, count, flag, s) && ok;
-            const size_t cd = count * d;
-            foreach_n(s, 3 * cd, [=] __device__(size_t i) {
-                const size_t w = i / cd, k = i - w * cd, b = k / d, j = k - b * d;
-                S[i] = w == 0 ? (j < ng ? g[b * ng + j] : F::zero()) : w == 1 ? f[b * nm + j] : (j < la ? ar[b * lda + j] : F::zero());
-            });
-            E* U = temp(3 * count * h); E* V = temp(3 * count * h); E* X = temp(3 * count * h);
-            PolyEvals<F> ev;
-            ok = lift_one(S, d, d, false, 0, N, 3 * count, U, V, X, &ev, s) && ok;
-            foreach_n(s, 3 * total, [=] __device__(size_t i) {
-                const size_t r = i >> lN, k = (i & (N - 1)) >> 1;
-                kept[i] = ((i & 1) ? ev.odd : ev.even)[r * ev.batch + k * ev.stride];
-            });
-            temps_release(mark);
-        }
-        const E* kept_g = kept; const E* kept_f = kept + total; const E* kept_a = kept + 2 * total;
+        E* kept = temp(3 * count * powmod_leaves(nm));
+        KeptModulus km;
+        ok = keep_modulus(f, d, ar, la, lda, count, kept, flag, &km, s) && ok;
         if (nbits == 0) foreach_n(s, count * d, [=] __device__(size_t i) { out[i] = i % d == 0 ? r1 : F::zero(); });
         else foreach_n(s, count * d, [=] __device__(size_t i) { const size_t b = i / d, j = i - b * d; out[i] = j < la ? ar[b * lda + j] : F::zero(); });
         for (size_t i = nbits > 0 ? nbits - 1 : 0; i-- > 0;) {
-            ok = powmod_step(out, nullptr, kept_g, kept_f, d, N, count, rinv, s) && ok;
-            if ((exp[i >> 3] >> (i & 7)) & 1) ok = powmod_step(out, kept_a, kept_g, kept_f, d, N, count, rinv, s) && ok;
+            ok = powmod_step(out, nullptr, km, count, rinv, s) && ok;
+            if ((exp[i >> 3] >> (i & 7)) & 1) ok = powmod_step(out, km.base, km, count, rinv, s) && ok;
         }
         return finish_flagged(ok, flag, singular, s);
     }
-    // One modular product of poly_pow_mod in place: res (count x d) = res y mod f, y = res itself (kept_y == nullptr) or the kept base
-    bool powmod_step(E* res, const E* kept_y, const E* kept_g, const E* kept_f, size_t d, size_t N, size_t count, TE rinv, hipStream_t s) {
-        const size_t h = N / 2, total = count * N;
+
+private:
+    // poly_divrem without the read-back of the flag and the release of the temporaries, which stay with the caller: the one
+    // division of this layer.  poly_mul_mod and poly_pow_mod reduce with it (q == nullptr); gcd_pair, gcd_half and roots_one_large
+    // divide one pair under gcd_flag_.  q or r may be null; a zero leading coefficient of some b_b raises *flag on every path.
+    bool divrem_body(const E* a, size_t na, const E* b, size_t nb, E* q, E* r, size_t count, int* flag, hipStream_t s) {
+        const size_t nq = na >= nb ? na - nb + 1 : 0, nr = nb - 1;
+        if (nq == 0 || nb == 1) {
+            E* binv = temp(count);                                // 1/b_{nb-1} of every pair, crate form
+            series_base(b + nb - 1, nb, 1, binv, 1, 1, count, flag, s);
+            if (nq == 0 && r) {
+                foreach_n(s, count * nr, [=] __device__(size_t i) { const size_t bi = i / nr, j = i - bi * nr; r[i] = j < na ? a[bi * na + j] : F::zero(); });
+            } else if (nq && q) {
+                const E rinv = rinv_;
+                foreach_n(s, count * na, [=] __device__(size_t i) { q[i] = F::canon(F::mul(F::mul(a[i], binv[i / na]), rinv)); });
+            }
+            return true;
+        }
+        const size_t nf = nq < nb ? nq : nb, np = 2 * nq - 1;    // rev(b) mod x^nq; rev(a) mod x^nq times g
+        E* fr = temp(count * nf); E* ar = temp(count * nq); E* g = temp(count * nq); E* pq = temp(count * np);
+        E* qq = q ? q : temp(count * nq);
+        foreach_n(s, count * nf, [=] __device__(size_t i) { const size_t bi = i / nf, j = i - bi * nf; fr[i] = b[bi * nb + nb - 1 - j]; });
+        foreach_n(s, count * nq, [=] __device__(size_t i) { const size_t bi = i / nq, j = i - bi * nq; ar[i] = a[bi * na + na - 1 - j]; });
+        bool ok = inv_series_body(fr, nf, nf, g, nq, count, flag, s);
+        ok = poly_mul_body(ar, nq, nq, g, nq, nq, pq, count, s) && ok;
+        foreach_n(s, count * nq, [=] __device__(size_t i) { const size_t bi = i / nq, j = i - bi * nq; qq[i] = pq[bi * np + nq - 1 - j]; });
+        if (r) {
+            const size_t mq = nq < nr ? nq : nr, npr = nr + mq - 1, total = count * nr;
+            E* pr = temp(count * npr);
+            ok = poly_mul_body(b, nr, nb, qq, mq, nq, pr, count, s) && ok;    // (b mod x^nr)(q mod x^nr): rows read in place
+            ECFFT_LAUNCH(KC_POINTWISE, sizeof(E) * 3.0 * (double)total, k_divrem_sub<F>, dim3(nblocks(total)), dim3(kBlock), 0, s,
+                         r, nr, a, na, (const E*)pr, npr, total);
+        }
+        return ok;
+    }
+    // What the large regime of a modular power keeps for the call: the evaluations on T_N, N = powmod_leaves(d + 1), in the natural
+    // leaf order EXIT reads, of g = 1/rev(f) mod x^(d-1), f mod x^d and, where there is one, the base (count x N each)
+    struct KeptModulus { const E* g; const E* f; const E* base; size_t d, N; };
+    // Once per call, for `count` moduli f (count x (d + 1)) and, unless null, bases of lb coefficients at a row stride of ldb: g by
+    // inv_series_body, then g | f mod x^d [| base] stacked and lifted in ONE pass and written into `kept` (3 count N elements, 2 count
+    // N without a base), which the caller takes before its own later temporaries; everything taken here goes back to the pool.
+    bool keep_modulus(const E* f, size_t d, const E* base, size_t lb, size_t ldb, size_t count, E* kept, int* flag, KeptModulus* km, hipStream_t s) {
+        const size_t nm = d + 1, ng = d - 1, cd = count * d, rows = base ? 3 : 2, N = powmod_leaves(nm), h = N / 2;
+        const TempMark mark = temps_mark();
+        E* fr = temp(count * ng); E* g = temp(count * ng); E* S = temp(rows * cd);
+        foreach_n(s, count * ng, [=] __device__(size_t i) { const size_t b = i / ng, j = i - b * ng; fr[i] = f[b * nm + d - j]; });
+        bool ok = inv_series_body(fr, ng, ng, g, ng, count, flag, s);
+        foreach_n(s, rows * cd, [=] __device__(size_t i) {
+            const size_t w = i / cd, k = i - w * cd, b = k / d, j = k - b * d;
+            S[i] = w == 0 ? (j < ng ? g[b * ng + j] : F::zero()) : w == 1 ? f[b * nm + j] : (j < lb ? base[b * ldb + j] : F::zero());
+        });
+        E* U = temp(rows * count * h); E* V = temp(rows * count * h); E* X = temp(rows * count * h);
+        PolyEvals<F> ev;
+        ok = lift_one(S, d, d, false, 0, N, rows * count, U, V, X, &ev, s) && ok;
+        materialise(ev, N, rows * count, kept, s);
+        temps_release(mark);
+        *km = KeptModulus{kept, kept + count * N, base ? kept + 2 * count * N : nullptr, d, N};
+        return ok;
+    }
+    // One modular product in place: res (count x d) = res y mod f, y = res itself (kept_y == nullptr) or the kept base
+    bool powmod_step(E* res, const E* kept_y, const KeptModulus& km, size_t count, TE rinv, hipStream_t s) {
+        const size_t d = km.d, N = km.N, h = N / 2, total = count * N;
         const unsigned lN = ilog2(N);
         const TempMark mark = temps_mark();
         E* U = temp(count * h); E* V = temp(count * h); E* X = temp(count * h); E* C = temp(total); E* T = temp(total);
@@ -1794,11 +1791,11 @@ public:
         ok = exit(C, C, N, count, s) && ok;                      // c = res y: 2d - 1 coefficients
         ok = lift_one(C, d - 1, N, true, 2 * d - 2, N, count, U, V, X, &ev, s) && ok;
         ECFFT_LAUNCH(KC_POINTWISE, sizeof(E) * 3.0 * (double)total, k_powmod_pointwise<F>, dim3(nblocks(total)), dim3(kBlock), 0, s,
-                     T, ev, kept_g, rinv, lN, total);
+                     T, ev, km.g, rinv, lN, total);
         ok = exit(T, T, N, count, s) && ok;                      // rev(c) g: its first d - 1 coefficients are rev(q)
         ok = lift_one(T, d - 1, N, true, d - 2, N, count, U, V, X, &ev, s) && ok;
         ECFFT_LAUNCH(KC_POINTWISE, sizeof(E) * 3.0 * (double)total, k_powmod_pointwise<F>, dim3(nblocks(total)), dim3(kBlock), 0, s,
-                     T, ev, kept_f, rinv, lN, total);
+                     T, ev, km.f, rinv, lN, total);
         ok = exit(T, T, N, count, s) && ok;                      // (f mod x^d) q
         const size_t nres = count * d;
         ECFFT_LAUNCH(KC_POINTWISE, sizeof(E) * 3.0 * (double)nres, k_powmod_sub<F>, dim3(nblocks(nres)), dim3(kBlock), 0, s,
@@ -1806,30 +1803,38 @@ public:
         temps_release(mark);
         return ok;
     }
+    // One lift: cnt vectors of mm evaluations on T_mm (cur) -> 2mm evaluations on T_2mm (dst): interleave(cur, EXTEND_S1(cur)); ext: work
+    bool lift_step(const E* cur, E* dst, E* ext, size_t mm, size_t cnt, hipStream_t s) {
+        if (!extend_api(cur, ext, mm, cnt, 1, s)) return false;
+        foreach_n(s, 2 * mm * cnt, [=] __device__(size_t i) { dst[i] = (i & 1) ? ext[i >> 1] : cur[i >> 1]; });
+        return true;
+    }
     // lift_operands for ONE operand of at most N/2 coefficients with the reversal folded into its pad load: count rows of len
     // coefficients at a row stride of ld (rev: read downwards from index top) entered at m = next_pow2(len) and lifted to N; *ev
     // reads the evaluations on the leaves of T_N (the last lift's interleave).  U, V, X: count x N/2 elements of work each.
     bool lift_one(const E* src, size_t len, size_t ld, bool rev, size_t top, size_t N, size_t count, E* U, E* V, E* X, PolyEvals<F>* ev,
                   hipStream_t s) {
-        const size_t h = N / 2;
-        size_t m = 1; while (m < len) m <<= 1;
-        const size_t padded = count * m;
+        const size_t h = N / 2, m = next_pow2(len), padded = count * m;
         ECFFT_LAUNCH(KC_POINTWISE, sizeof(E) * ((double)count * (double)len + (double)padded), k_powmod_pad<F>, dim3(nblocks(padded)), dim3(kBlock),
                      0, s, U, src, len, ld, rev ? 1u : 0u, top, ilog2(m), padded);
         bool ok = enter(U, U, m, count, s);
         E* c = U;
-        for (size_t mm = m; mm < h; mm *= 2) {
-            E* dst = c == U ? V : U;
-            const E* cur = c;
-            ok = extend_api(cur, X, mm, count, 1, s) && ok;
-            foreach_n(s, 2 * mm * count, [=] __device__(size_t i) { dst[i] = (i & 1) ? X[i >> 1] : cur[i >> 1]; });
-            c = dst;
-        }
+        for (size_t mm = m; mm < h; mm *= 2) { E* dst = c == U ? V : U; ok = lift_step(c, dst, X, mm, count, s) && ok; c = dst; }
         ok = extend_api(c, X, h, count, 1, s) && ok;              // the last lift's EXTEND; its interleave is the pointwise load
         *ev = PolyEvals<F>{c, X, h, 1u};
         return ok;
     }
+    // count rows of evaluations on the leaves of T_N as a last lift leaves them (even / odd halves) -> dst (count x N), natural leaf order
+    void materialise(const PolyEvals<F>& ev, size_t N, size_t count, E* dst, hipStream_t s) {
+        const PolyEvals<F> e = ev;
+        const unsigned lN = ilog2(N);
+        foreach_n(s, count * N, [=] __device__(size_t i) {
+            const size_t r = i >> lN, k = (i & (N - 1)) >> 1;
+            dst[i] = ((i & 1) ? e.odd : e.even)[r * e.batch + k * e.stride];
+        });
+    }
 
+public:
     // ---- ecfft_poly_gcd / ecfft_poly_xgcd (utils::gcd / utils::xgcd, src/utils.rs:132-182) ----
     // pairs of at most this many coefficients run their whole remainder sequence in k_gcd_small (one workgroup per pair, no transform)
     static constexpr size_t kGcdSmall = 256;
@@ -1847,9 +1852,7 @@ public:
     // nmax + (nmax - 1) / 2 coefficients, matrix and cofactor products stay below nmax + 1 (cofactor degrees add up to at most
     // deg a), and a division inside gcd_half has deg d >= m.
     static size_t gcd_leaves(size_t nmax) {
-        if (nmax <= kGcdSmall) return 1;
-        size_t N = 1; while (N < 2 * nmax - 1) N <<= 1;
-        return N;
+        return nmax <= kGcdSmall ? 1 : next_pow2(2 * nmax - 1);
     }
     // gcd (and, with so / to, the cofactors of the classical extended Euclidean algorithm: a s + b t = g) of `count` pairs laid end
     // to end (a: count x na, b: count x nb, g: count x max(na, nb), so: count x max(nb - 1, 1), to: count x max(na - 1, 1), all
@@ -1863,14 +1866,13 @@ public:
         bool ok = true;
         std::vector<long long> hdeg(count, -1);
         if (ng <= kGcdSmall) {
-            long long* ddeg = reinterpret_cast<long long*>(temp((count * sizeof(long long) + sizeof(E) - 1) / sizeof(E)));
-            for (size_t c0 = 0; c0 < count; c0 += (size_t)1 << 16) {
-                const size_t c = count - c0 < ((size_t)1 << 16) ? count - c0 : (size_t)1 << 16;
+            long long* ddeg = temp_as<long long>(count);
+            for_chunks(count, [&](size_t c0, size_t c) {
                 ECFFT_LAUNCH(KC_POINTWISE, sizeof(E) * (double)c * (double)(na + nb + ng + ns + nt), (k_gcd_small<F, (int)kGcdSmall>), dim3((unsigned)c),
                              dim3((unsigned)kGcdSmall), 0, s, a + c0 * na, na, (uint32_t)na, b + c0 * nb, nb, (uint32_t)nb, (int32_t)0, 0u, want_cof ? 1u : 0u,
                              g + c0 * ng, (uint32_t)ng, so ? so + c0 * ns : nullptr, (uint32_t)ns, to ? to + c0 * nt : nullptr, (uint32_t)nt, ddeg + c0,
                              (E*)nullptr, (size_t)0, 0u, (int32_t*)nullptr, r1);
-            }
+            });
             ok = hipMemcpyAsync(hdeg.data(), ddeg, count * sizeof(long long), hipMemcpyDeviceToHost, s) == hipSuccess;
         } else {
             gcd_flag_ = new_flag(s);
@@ -1896,7 +1898,7 @@ private:
     bool gcd_row_lens(const E* p, size_t ld, size_t n, int nrows, size_t* lens, hipStream_t s) {
         int h[2] = {-1, -1};
         if (n) {
-            int* d = reinterpret_cast<int*>(temp((2 * sizeof(int) + sizeof(E) - 1) / sizeof(E)));
+            int* d = temp_as<int>(2);
             if (hipMemsetAsync(d, 0xFF, 2 * sizeof(int), s) != hipSuccess) return false;
             // from the top down, and only where the degree seen so far is lower: few lanes reach the atomic.  The look at d[r] is a
             // relaxed atomic load that only prunes work: a stale value costs one more atomicMax, never a wrong degree
@@ -1990,30 +1992,6 @@ private:
         temps_release(mark);
         return ok;
     }
-    // (q, r) of one pair with la >= lb >= 1 and b[lb-1] != 0: q la - lb + 1 coefficients, r lb - 1.  The products of poly_divrem
-    // without its read-back; the temporaries stay with the caller's mark.
-    bool gcd_divrem(const E* a, size_t la, const E* b, size_t lb, E* q, E* r, hipStream_t s) {
-        const size_t nq = la - lb + 1, nr = lb - 1;
-        if (nr == 0) {
-            E* binv = temp(1);
-            series_base(b, 1, 1, binv, 1, 1, 1, gcd_flag_, s);
-            const E rinv = rinv_;
-            foreach_n(s, la, [=] __device__(size_t i) { q[i] = F::canon(F::mul(F::mul(a[i], binv[0]), rinv)); });
-            return true;
-        }
-        const size_t nf = nq < lb ? nq : lb, np = 2 * nq - 1;
-        E* fr = temp(nf); E* ar = temp(nq); E* g = temp(nq); E* pq = temp(np);
-        foreach_n(s, nf, [=] __device__(size_t i) { fr[i] = b[lb - 1 - i]; });
-        foreach_n(s, nq, [=] __device__(size_t i) { ar[i] = a[la - 1 - i]; });
-        bool ok = inv_series_body(fr, nf, nf, g, nq, 1, gcd_flag_, s);
-        ok = poly_mul_body(ar, nq, nq, g, nq, nq, pq, 1, s) && ok;
-        foreach_n(s, nq, [=] __device__(size_t i) { q[i] = pq[nq - 1 - i]; });
-        const size_t mq = nq < nr ? nq : nr, npr = nr + mq - 1;
-        E* pr = temp(npr);
-        ok = poly_mul_body(b, nr, lb, q, mq, nq, pr, 1, s) && ok;
-        ECFFT_LAUNCH(KC_POINTWISE, sizeof(E) * 3.0 * (double)nr, k_divrem_sub<F>, dim3(nblocks(nr)), dim3(kBlock), 0, s, r, nr, a, la, (const E*)pr, npr, nr);
-        return ok;
-    }
     // k_gcd_small on ONE pair of at most kGcdLeaf coefficients, with kGcdSmall threads where those hold it
     template <class... A>
     void gcd_small_one(size_t la, double bytes, hipStream_t s, A... args) {
@@ -2031,7 +2009,7 @@ private:
         out.ident = true; out.len = 1;
         if (lb < m + 1) return true;
         if (la <= kGcdLeaf) {
-            int32_t* info = reinterpret_cast<int32_t*>(temp((8 * sizeof(int32_t) + sizeof(E) - 1) / sizeof(E)));
+            int32_t* info = temp_as<int32_t>(8);
             gcd_small_one(la, sizeof(E) * (double)(la + lb + 4 * la), s,
                           a, la, (uint32_t)la, b, lb, (uint32_t)lb, (int32_t)m, 1u, 1u, (E*)nullptr, 0u, (E*)nullptr, 0u, (E*)nullptr, 0u,
                           (long long*)nullptr, out.p, out.ld, (uint32_t)la, info, F::to_mont(F::one()));
@@ -2057,7 +2035,7 @@ private:
         const size_t nq = lc - ld + 1;
         E* q = temp(nq); E* e = temp(ld);
         size_t le = 0;
-        ok = gcd_divrem(c, lc, d, ld, q, e, s) && gcd_row_lens(e, ld, ld - 1, 1, &le, s);
+        ok = divrem_body(c, lc, d, ld, q, e, 1, gcd_flag_, s) && gcd_row_lens(e, ld, ld - 1, 1, &le, s);
         GcdMat M1; M1.ld = la; M1.p = temp(4 * la);
         ok = ok && gcd_qstep(q, nq, R, M1, s);
         const size_t k = 2 * m - (ld - 1);
@@ -2112,7 +2090,7 @@ private:
                 gcd_gather(cd, rows, 1, W, s);
                 if (lb > 1) (void)hipMemsetAsync(cd + W + lb - 1, 0, (W - (lb - 1)) * sizeof(E), s);
                 else (void)hipMemsetAsync(cd + W, 0, W * sizeof(E), s);
-                ok = gcd_divrem(a, la, b, lb, q, cd + W, s) && gcd_row_lens(cd + W, W, lb - 1, 1, &le, s);
+                ok = divrem_body(a, la, b, lb, q, cd + W, 1, gcd_flag_, s) && gcd_row_lens(cd + W, W, lb - 1, 1, &le, s);
                 if (ok && want_cof) { ok = gcd_qstep(q, nq, acc[mi], acc[mi ^ 1], s); mi ^= 1; }
                 a = cd; b = cd + W; la = lb; lb = le;
             }
@@ -2139,7 +2117,7 @@ private:
         const size_t fs = lb > 1 ? lb - 1 : 1, ft = la > 1 ? la - 1 : 1;
         const bool direct = !want_cof || M.ident;              // no matrix to apply: the kernel writes the outputs themselves
         E* gs = temp(la); E* ss = temp(fs); E* ts = temp(ft);
-        long long* ddeg = reinterpret_cast<long long*>(temp((sizeof(long long) + sizeof(E) - 1) / sizeof(E)));
+        long long* ddeg = temp_as<long long>(1);
         gcd_small_one(la, sizeof(E) * 4.0 * (double)(la + lb), s,
                      a, la, (uint32_t)la, b, lb, (uint32_t)lb, (int32_t)0, 0u, want_cof ? 1u : 0u, gs, (uint32_t)la, want_cof ? ss : (E*)nullptr, (uint32_t)fs,
                      want_cof ? ts : (E*)nullptr, (uint32_t)ft, ddeg, (E*)nullptr, (size_t)0, 0u, (int32_t*)nullptr, r1);
@@ -2166,41 +2144,17 @@ private:
     // ---- ecfft_poly_find_roots (utils::find_roots, src/utils.rs:25-44) ----
     // out (count x d, crate form) = (x + c)^exp mod f_b for `count` MONIC moduli of degree d > kRootsSmall laid end to end (f: count x
     // (d + 1), f_b[d] = 1 in crate form).  The large regime of poly_pow_mod with another epilogue: the same kept evaluations of g =
-    // 1/rev(f) and f on T_N, N = next_pow2(2d - 1), and the same squaring (powmod_step); on a set bit the product with the base is
+    // 1/rev(f) and f on T_N (keep_modulus without a base), and the same squaring (powmod_step); on a set bit the product with the base is
     // not a second modular product but x r + c r - r_{d-1} f, one pass over the rows.  exp: host bytes, bit nbits - 1 set, nbits >= 1.
     bool roots_pow_body(const E* f, size_t d, uint32_t c, const uint8_t* exp, size_t nbits, E* out, size_t count, int* flag, hipStream_t s) {
+        static_assert(kRootsSmall >= kPowSmall, "d > kRootsSmall is the large regime of powmod_leaves");
         const size_t nm = d + 1;
-        size_t N = 1; while (N < 2 * d - 1) N <<= 1;
-        const size_t h = N / 2, total = count * N;
-        const unsigned lN = ilog2(N);
         const E r1 = F::to_mont(F::one());
         const TE rinv = F::to_table(rinv_);
-        bool ok = true;
-        E* kept = temp(2 * total);
+        E* kept = temp(2 * count * powmod_leaves(nm));
         E* next = temp(count * d);
-        {
-            const TempMark mark = temps_mark();
-            const size_t ng = d - 1;
-            E* fr = temp(count * ng); E* g = temp(count * ng); E* S = temp(2 * count * d);
-            foreach_n(s, count * ng, [=] __device__(size_t i) { const size_t b = i / ng, j = i - b * ng; fr[i] = f[b * nm + d - j]; });
-            ok = inv_series_body(fr, ng, ng, g, ng, count, flag, s) && ok;
-            const size_t cd = count * d;
-            foreach_n(s, 2 * cd, [=] __device__(size_t i) {
-                const size_t w = i / cd, k = i - w * cd, b = k / d, j = k - b * d;
-                E v = F::zero();
-                if (w == 0) { if (j < ng) v = g[b * ng + j]; } else v = f[b * nm + j];
-                S[i] = v;
-            });
-            E* U = temp(2 * count * h); E* V = temp(2 * count * h); E* X = temp(2 * count * h);
-            PolyEvals<F> ev;
-            ok = lift_one(S, d, d, false, 0, N, 2 * count, U, V, X, &ev, s) && ok;
-            foreach_n(s, 2 * total, [=] __device__(size_t i) {
-                const size_t r = i >> lN, k = (i & (N - 1)) >> 1;
-                kept[i] = ((i & 1) ? ev.odd : ev.even)[r * ev.batch + k * ev.stride];
-            });
-            temps_release(mark);
-        }
-        const E* kept_g = kept; const E* kept_f = kept + total;
+        KeptModulus km;
+        bool ok = keep_modulus(f, d, nullptr, 0, 0, count, kept, flag, &km, s);
         const E cE = F::from_u32(c), ri = rinv_;
         const E c_crate = F::canon(F::mul(cE, r1));
         foreach_n(s, count * d, [=] __device__(size_t i) {
@@ -2211,7 +2165,7 @@ private:
             out[i] = v;
         });
         for (size_t i = nbits - 1; i-- > 0;) {
-            ok = powmod_step(out, nullptr, kept_g, kept_f, d, N, count, rinv, s) && ok;
+            ok = powmod_step(out, nullptr, km, count, rinv, s) && ok;
             if ((exp[i >> 3] >> (i & 7)) & 1) {
                 foreach_n(s, count * d, [=] __device__(size_t k) {
                     const size_t b = k / d, j = k - b * d;
@@ -2246,13 +2200,12 @@ private:
                             bool frob, uint32_t c0, size_t nblk, double coeffs, hipStream_t s) {
         const E r1 = F::to_mont(F::one());
         const TE rinv = F::to_table(rinv_);
-        for (size_t b0 = 0; b0 < nblk; b0 += (size_t)1 << 16) {
-            const size_t nb = nblk - b0 < ((size_t)1 << 16) ? nblk - b0 : (size_t)1 << 16;
+        for_chunks(nblk, [&](size_t b0, size_t nb) {
             ECFFT_LAUNCH(KC_POINTWISE, sizeof(E) * coeffs * (double)nb / (double)nblk + 64.0, (k_roots_small<F, (int)kRootsSmall>), dim3((unsigned)nb),
                          dim3((unsigned)kRootsSmall), 0, s, desc ? in : in + b0 * ldin, ldin, (uint32_t)nin, desc ? out : out + b0 * ldout, ldout,
                          desc ? desc + 3 * b0 : (const uint32_t*)nullptr, n_out ? n_out + b0 : (long long*)nullptr, frob ? 1u : 0u, c0,
                          rc.dexp, rc.nbits_p, rc.dexp + 32, rc.nbits_h, rinv, r1, rc.flag);
-        }
+        });
     }
     void roots_rank_launch(E* dst, size_t ldd, const E* src, size_t lds, const long long* n_dev, long long n_fixed, size_t rows, hipStream_t s) {
         if (!ldd) return;
@@ -2266,7 +2219,7 @@ private:
     //   g = gcd(f, x^p - x mod f) on roots_pow_body (base x) and gcd_pair; then rounds with one shift c = 1, 2, ... for all pending
     //   factors of degree > kRootsSmall: grouped by N = next_pow2(2e - 1), padded inside a group to its largest degree D as x^(D-e) h
     //   (h divides it, so gcd(h, w - 1) is unchanged), ONE roots_pow_body per group, then per factor u = gcd_pair(h, w - 1) and
-    //   v = h / u (gcd_divrem).  Factors of degree <= kRootsSmall go to the leaf buffer, finished by ONE launch of k_roots_small.
+    //   v = h / u (divrem_body).  Factors of degree <= kRootsSmall go to the leaf buffer, finished by ONE launch of k_roots_small.
     bool roots_one_large(const RootsCall& rc, const E* f, size_t nf, E* roots, long long* n, hipStream_t s) {
         const size_t K = kRootsSmall;
         const E r1 = F::to_mont(F::one());
@@ -2275,7 +2228,7 @@ private:
         if (!gcd_row_lens(f, nf, nf, 1, &la, s)) return false;
         E* uns = temp(nf - 1);                                // the roots before they are ordered
         if (la <= K + 1) {                                    // a short polynomial in a long row: the small regime on its true length
-            long long* dn = reinterpret_cast<long long*>(temp((sizeof(long long) + sizeof(E) - 1) / sizeof(E)));
+            long long* dn = temp_as<long long>(1);
             roots_small_launch(rc, f, nf, la ? la : 1, uns, nf - 1, nullptr, dn, true, 1u, 1, (double)(la + K), s);
             roots_rank_launch(roots, nf - 1, uns, nf - 1, dn, 0, 1, s);
             return hipMemcpyAsync(n, dn, sizeof(long long), hipMemcpyDeviceToHost, s) == hipSuccess && hipStreamSynchronize(s) == hipSuccess;
@@ -2326,18 +2279,17 @@ private:
             std::vector<char> done(cur.size(), 0);
             for (size_t i0 = 0; i0 < cur.size() && ok; ++i0) {
                 if (done[i0]) continue;
-                auto leaves_of = [](size_t e) { size_t N = 1; while (N < 2 * e - 1) N <<= 1; return N; };
-                const size_t N = leaves_of(cur[i0].e);
+                const size_t N = powmod_leaves(cur[i0].e + 1);
                 std::vector<size_t> grp;
                 size_t D = 0;
                 for (size_t i = i0; i < cur.size(); ++i)
-                    if (!done[i] && leaves_of(cur[i].e) == N) { grp.push_back(i); done[i] = 1; if (cur[i].e > D) D = cur[i].e; }
+                    if (!done[i] && powmod_leaves(cur[i].e + 1) == N) { grp.push_back(i); done[i] = 1; if (cur[i].e > D) D = cur[i].e; }
                 const size_t cnt = grp.size();
                 const TempMark gm = temps_mark();
                 // rows x^(D - e) h: row i reads P + off_i shifted up by D - e_i
                 std::vector<uint32_t> hd(2 * cnt);
                 for (size_t i = 0; i < cnt; ++i) { hd[2 * i] = (uint32_t)cur[grp[i]].off; hd[2 * i + 1] = (uint32_t)(D - cur[grp[i]].e); }
-                uint32_t* dd = reinterpret_cast<uint32_t*>(temp((2 * cnt * sizeof(uint32_t) + sizeof(E) - 1) / sizeof(E)));
+                uint32_t* dd = temp_as<uint32_t>(2 * cnt);
                 ok = hipMemcpyAsync(dd, hd.data(), 2 * cnt * sizeof(uint32_t), hipMemcpyHostToDevice, s) == hipSuccess && hipStreamSynchronize(s) == hipSuccess && ok;
                 E* M = temp(cnt * (D + 1)); E* W = temp(cnt * D);
                 const size_t nm = D + 1;
@@ -2357,7 +2309,7 @@ private:
                     const TempMark fm2 = temps_mark();
                     ok = gcd_pair(hp, fc.e + 1, W + i * D, D, nullptr, 1, nullptr, 1, u, D + 1, &du, false, s);
                     if (ok && du > 0 && (size_t)du < fc.e) {
-                        ok = gcd_divrem(hp, fc.e + 1, u, (size_t)du + 1, v, rem, s);
+                        ok = divrem_body(hp, fc.e + 1, u, (size_t)du + 1, v, rem, 1, gcd_flag_, s);
                         keep(u, (size_t)du, 0);
                         keep(v, fc.e - (size_t)du, 0);         // copied on the stream before the next factor reuses u and v
                     } else if (ok) {
@@ -2375,7 +2327,7 @@ private:
         if (!ok) return false;
         // ---- the leaves: one launch, then the order ----
         const size_t nleaf = ldesc.size() / 3;
-        uint32_t* ddesc = reinterpret_cast<uint32_t*>(temp((ldesc.size() * sizeof(uint32_t) + sizeof(E) - 1) / sizeof(E)));
+        uint32_t* ddesc = temp_as<uint32_t>(ldesc.size());
         ok = hipMemcpyAsync(ddesc, ldesc.data(), ldesc.size() * sizeof(uint32_t), hipMemcpyHostToDevice, s) == hipSuccess && hipStreamSynchronize(s) == hipSuccess;
         roots_small_launch(rc, leaf, 0, 0, uns, 0, ddesc, nullptr, false, c, nleaf, (double)(leaf_used + roots_used), s);
         roots_rank_launch(roots, nf - 1, uns, nf - 1, nullptr, (long long)r, 1, s);
@@ -2388,9 +2340,7 @@ public:
     // The leaves ecfft_poly_find_roots needs for rows of nf coefficients, checked before anything runs: poly_gcd's rule for rows of
     // nf, which covers every later step
     static size_t roots_leaves(size_t nf) {
-        if (nf <= kRootsSmall + 1) return 1;
-        size_t N = 1; while (N < 2 * nf - 1) N <<= 1;
-        return N;
+        return nf <= kRootsSmall + 1 ? 1 : next_pow2(2 * nf - 1);
     }
     // ecfft_poly_find_roots: roots (count x (nf - 1), crate form) = the distinct roots of f_b in ascending order of their standard
     // form, zero-padded; n_roots (host): their number, -1 for the zero polynomial.  nf <= kRootsSmall + 1: ONE launch of k_roots_small
@@ -2399,7 +2349,7 @@ public:
     bool poly_find_roots(const E* f, size_t nf, E* roots, long long* n_roots, size_t count, bool* capped, hipStream_t s) {
         RootsCall rc;
         roots_exponents(rc.ep, &rc.nbits_p, rc.eh, &rc.nbits_h);
-        uint8_t* dexp = reinterpret_cast<uint8_t*>(temp((64 + sizeof(E) - 1) / sizeof(E)));
+        uint8_t* dexp = temp_as<uint8_t>(64);
         uint8_t both[64];
         for (int i = 0; i < 32; ++i) { both[i] = rc.ep[i]; both[32 + i] = rc.eh[i]; }
         bool ok = hipMemcpyAsync(dexp, both, 64, hipMemcpyHostToDevice, s) == hipSuccess && hipStreamSynchronize(s) == hipSuccess;
@@ -2407,7 +2357,7 @@ public:
         rc.flag = new_flag(s);
         const size_t nr = nf - 1;
         if (nf <= kRootsSmall + 1) {
-            long long* dn = reinterpret_cast<long long*>(temp((count * sizeof(long long) + sizeof(E) - 1) / sizeof(E)));
+            long long* dn = temp_as<long long>(count);
             E* uns = temp(count * nr);
             roots_small_launch(rc, f, nf, nf, uns, nr, nullptr, dn, true, 1u, count, (double)count * (double)(nf + nr), s);
             roots_rank_launch(roots, nr, uns, nr, dn, 0, count, s);
@@ -2430,7 +2380,7 @@ public:
     // coefficients at a row stride of ld (>= len) elements
     bool poly_mul_body(const E* a, size_t na, size_t lda, const E* b, size_t nb, size_t ldb, E* out, size_t count, hipStream_t s) {
         const size_t nc = na + nb - 1;
-        size_t N = 1; while (N < nc) N <<= 1;
+        const size_t N = mul_leaves(na, nb);
         const int nops = (a == b && na == nb && lda == ldb) ? 1 : 2;
         const E* src[2] = {a, b};
         const size_t len[2] = {na, nb}, ld[2] = {lda, ldb};
@@ -2454,11 +2404,10 @@ public:
     // k_series_base on count rows (grid chunks of at most 2^16 pairs)
     void series_base(const E* f, size_t ldf, size_t nf, E* out, size_t ldo, size_t p0, size_t count, int* flag, hipStream_t s) {
         const E r1 = F::to_mont(F::one());
-        for (size_t c0 = 0; c0 < count; c0 += (size_t)1 << 16) {
-            const size_t c = count - c0 < ((size_t)1 << 16) ? count - c0 : (size_t)1 << 16;
+        for_chunks(count, [&](size_t c0, size_t c) {
             ECFFT_LAUNCH(KC_POINTWISE, sizeof(E) * 2.0 * (double)(c * p0), (k_series_base<F, (int)kSeriesBase>), dim3((unsigned)c),
                          dim3((unsigned)kSeriesBase), 0, s, out + c0 * ldo, ldo, f + c0 * ldf, ldf, nf, (uint32_t)p0, rinv_, r1, flag);
-        }
+        });
     }
     // 1/f mod x^k (f: count rows of nf coefficients at a stride of ldf) into out (count x k); raises *flag on a zero f[0]
     bool inv_series_body(const E* f, size_t nf, size_t ldf, E* out, size_t k, size_t count, int* flag, hipStream_t s) {
@@ -2481,7 +2430,7 @@ public:
     // and lifted to N = next_pow2(2p + p2 - 2) on the joint launches of poly_mul, k_newton_pointwise, one batched EXIT_N.
     // deg(g^2 f) < N, so nothing wraps.
     bool newton_step(const E* f, size_t nf, size_t ldf, const E* g, size_t p, E* out, size_t p2, size_t count, hipStream_t s) {
-        size_t N = 1; while (N < 2 * p + p2 - 2) N <<= 1;
+        const size_t N = next_pow2(2 * p + p2 - 2);
         const E* src[2] = {f, g};
         const size_t len[2] = {nf < p2 ? nf : p2, p}, ld[2] = {ldf, p};
         PolyEvals<F> ev[2];
@@ -2494,7 +2443,7 @@ public:
         return exit_rows(Y, out, p2, N, count, ok, s);
     }
     int* new_flag(hipStream_t s) {
-        int* flag = reinterpret_cast<int*>(temp((sizeof(int) + sizeof(E) - 1) / sizeof(E)));
+        int* flag = temp_as<int>(1);
         (void)hipMemsetAsync(flag, 0, sizeof(int), s);
         return flag;
     }
@@ -2511,18 +2460,11 @@ public:
     bool lift_operands(const E* const* src, const size_t* len, const size_t* ld, int nops, size_t N, size_t count, PolyEvals<F>* ev, E*& Y,
                        hipStream_t s) {
         const size_t h = N / 2;
-        auto pow2_ceil = [](size_t n) { size_t m = 1; while (m < n) m <<= 1; return m; };
-        const size_t m[2] = {pow2_ceil(len[0]), pow2_ceil(len[1])};
+        const size_t m[2] = {next_pow2(len[0]), next_pow2(len[1])};
         // count rows of n coefficients (row stride ldp) -> count rows of mm, zero-padded
         auto pad = [&](E* dst, const E* p, size_t n, size_t ldp, size_t mm) {
             const size_t mask = mm - 1; const unsigned lm = ilog2(mm);
             foreach_n(s, count * mm, [=] __device__(size_t i) { const size_t j = i & mask; dst[i] = j < n ? p[(i >> lm) * ldp + j] : F::zero(); });
-        };
-        // cnt vectors of mm evaluations on T_mm (cur) -> 2mm evaluations on T_2mm (dst): interleave(cur, EXTEND_S1(cur)); ext: work
-        auto lift = [&](const E* cur, E* dst, E* ext, size_t mm, size_t cnt) -> bool {
-            if (!extend_api(cur, ext, mm, cnt, 1, s)) return false;
-            foreach_n(s, 2 * mm * cnt, [=] __device__(size_t i) { dst[i] = (i & 1) ? ext[i >> 1] : cur[i >> 1]; });
-            return true;
         };
         bool ok = true;
         int slot[2] = {-1, -1}, nl = 0;                           // lifted operands: slot q of the joint buffer
@@ -2553,12 +2495,12 @@ public:
                 ok = enter(V, V, m[i], count, s) && ok;
                 for (size_t mm = m[i]; mm < hi; mm *= 2) {
                     E* dst = 2 * mm == hi ? U + slot[i] * count * hi : (c == V ? V + count * h : V);
-                    ok = lift(c, dst, X, mm, count) && ok;
+                    ok = lift_step(c, dst, X, mm, count, s) && ok;
                     c = dst;
                 }
             }
             E* c = U;
-            for (size_t mm = hi; mm < h; mm *= 2) { E* dst = c == U ? V : U; ok = lift(c, dst, X, mm, nl * count) && ok; c = dst; }
+            for (size_t mm = hi; mm < h; mm *= 2) { E* dst = c == U ? V : U; ok = lift_step(c, dst, X, mm, nl * count, s) && ok; c = dst; }
             ok = extend_api(c, X, h, nl * count, 1, s) && ok;      // the last lift's EXTEND; its interleave is k_poly_pointwise's load
             cur = c;
             for (int i = 0; i < nops; ++i)
@@ -2595,7 +2537,7 @@ public:
     }
     // leaf size B of the remainder tree: a node of B points is evaluated by Horner (B multiplies per point) instead of descending
     static constexpr size_t kEvalLeaf = 64;
-    static size_t eval_group(size_t nf) { size_t G = kEvalLeaf; while (G < nf) G <<= 1; return G; }
+    static size_t eval_group(size_t nf) { return nf <= kEvalLeaf ? kEvalLeaf : next_pow2(nf); }
     // Per-level node data of the subproduct tree of npts points (a multiple of G, in groups of G): level k holds the npts / d nodes
     // of d = B << k points (d = B .. G/2) laid end to end, each as M^ (its monic node polynomial M on the 2d leaves of T_2d, from the
     // vanish recursion) and G^ (g = 1/rev(M) mod x^d, lifted to T_2d): 2 npts elements each per level.  Temporaries of the call.
@@ -2688,12 +2630,7 @@ public:
     bool lift_rows(const E* src, size_t d, size_t count, E* dst, hipStream_t s) {
         PolyEvals<F> ev[2];
         const bool ok = lift_evals(src, d, count, ev, s);
-        const PolyEvals<F> e = ev[0];
-        const unsigned ld = ilog2(d);
-        foreach_n(s, count * 2 * d, [=] __device__(size_t i) {
-            const size_t r = i >> (ld + 1), k = (i & (2 * d - 1)) >> 1;
-            dst[i] = ((i & 1) ? e.odd : e.even)[r * e.batch + k * e.stride];
-        });
+        materialise(ev[0], 2 * d, count, dst, s);
         return ok;
     }
 
@@ -2834,7 +2771,7 @@ public:
         unsigned long long hdeg = 0;
         if (n > 1) {
             E* cur = temp(n); E* e0 = temp(n / 2); E* e1 = temp(n / 2); E* g1 = temp(n / 2);
-            unsigned long long* acc = reinterpret_cast<unsigned long long*>(temp((2 * sizeof(unsigned long long) + sizeof(E) - 1) / sizeof(E)));   // {degree, flag}
+            unsigned long long* acc = temp_as<unsigned long long>(2);   // {degree, flag}
             (void)hipMemsetAsync(acc, 0, 2 * sizeof(unsigned long long), s);
             (void)hipMemcpyAsync(cur, evals, n * sizeof(E), hipMemcpyDeviceToDevice, s);
             for (size_t m = n; m >= 2; m >>= 1) {
@@ -2978,6 +2915,12 @@ private:
         }
         pool_.push_back({p, bytes, true, false, 0});
         return (E*)p;
+    }
+    // n objects of T in a temporary (rounded up to whole elements)
+    template <class T> T* temp_as(size_t n) { return reinterpret_cast<T*>(temp((n * sizeof(T) + sizeof(E) - 1) / sizeof(E))); }
+    // one workgroup per row of `count` rows: fn(first row, rows) per launch of at most 2^16 workgroups
+    template <class Fn> static void for_chunks(size_t count, Fn&& fn) {
+        for (size_t c0 = 0; c0 < count; c0 += (size_t)1 << 16) fn(c0, count - c0 < ((size_t)1 << 16) ? count - c0 : (size_t)1 << 16);
     }
     // End of a call: every pooled temporary becomes reusable.  The pool is bounded: idle blocks beyond `keep` bytes in total
     // (twice the transform scratch, at least 256 MiB) are returned to the device, largest first — one large ecfft_vanish /

@@ -280,8 +280,7 @@ int run_poly_mul(ecfft_ctx* c, DeviceChain<F>& ch, const void* a, size_t na, con
     using E = typename F::elem;
     if (!a || !b || !out) return ECFFT_ERR_BAD_ARG;
     if (na > ch.size() || nb > ch.size()) return ECFFT_ERR_TREE_TOO_SMALL;
-    const size_t nc = na + nb - 1;
-    size_t N = 1; while (N < nc) N <<= 1;
+    const size_t nc = na + nb - 1, N = DeviceChain<F>::mul_leaves(na, nb);
     if (N > ch.size()) return ECFFT_ERR_TREE_TOO_SMALL;                   // "FFTree is too small"
     if (count > SIZE_MAX / (8 * N * sizeof(E))) return ECFFT_ERR_BAD_ARG;  // byte counts of the temporaries must not wrap
     const size_t eb = count * sizeof(E);
@@ -300,12 +299,8 @@ int run_poly_divrem(ecfft_ctx* c, DeviceChain<F>& ch, const void* a, size_t na, 
     const size_t lim = SIZE_MAX / (64 * sizeof(E));
     if (na > lim || nb > lim) return ECFFT_ERR_BAD_ARG;
     const size_t nq = na >= nb ? na - nb + 1 : 0, nr = nb - 1;
-    size_t N = 1;
-    if (nq && nr) {                                                         // nb == 1 (scaling) and na < nb (copy): no transform
-        const size_t mq = nq < nr ? nq : nr, need = 2 * nq - 1 > nr + mq - 1 ? 2 * nq - 1 : nr + mq - 1;
-        while (N < need) N <<= 1;
-        if (N > ch.size()) return ECFFT_ERR_TREE_TOO_SMALL;
-    }
+    const size_t N = DeviceChain<F>::divrem_leaves(na, nb);                 // 1 for nb == 1 (scaling) and na < nb (copy): no transform
+    if (N > 1 && N > ch.size()) return ECFFT_ERR_TREE_TOO_SMALL;
     const size_t per = N > na + nb ? N : na + nb;
     if (count > SIZE_MAX / (8 * per * sizeof(E))) return ECFFT_ERR_BAD_ARG; // byte counts of the temporaries must not wrap
     const size_t eb = count * sizeof(E);
@@ -322,8 +317,7 @@ int run_inv_series(ecfft_ctx* c, DeviceChain<F>& ch, const void* f, size_t nf, v
     if (!f || !out) return ECFFT_ERR_BAD_ARG;
     const size_t lim = SIZE_MAX / (64 * sizeof(E));
     if (nf > lim || k > lim) return ECFFT_ERR_BAD_ARG;
-    size_t N = 1;
-    while (N < 2 * k - 1) N <<= 1;
+    const size_t N = DeviceChain<F>::inv_series_leaves(k);
     if (N > ch.size()) return ECFFT_ERR_TREE_TOO_SMALL;                     // k = 1: N = 1, any tree
     const size_t per = N > nf + k ? N : nf + k;
     if (count > SIZE_MAX / (8 * per * sizeof(E))) return ECFFT_ERR_BAD_ARG;
@@ -374,17 +368,6 @@ int run_poly_interpolate(ecfft_ctx* c, DeviceChain<F>& ch, const void* points, s
     });
 }
 
-// the leaves ecfft_poly_divrem(na, nb) needs (run_poly_divrem's rule; 1 = no transform)
-inline size_t divrem_leaves(size_t na, size_t nb) {
-    const size_t nq = na >= nb ? na - nb + 1 : 0, nr = nb - 1;
-    size_t N = 1;
-    if (nq && nr) {
-        const size_t mq = nq < nr ? nq : nr, need = 2 * nq - 1 > nr + mq - 1 ? 2 * nq - 1 : nr + mq - 1;
-        while (N < need) N <<= 1;
-    }
-    return N;
-}
-
 // ecfft_poly_pow_mod / ecfft_poly_mul_mod: synchronous (the chain reads back the device flag of a zero leading coefficient of the
 // modulus, reported as ECFFT_ERR_BAD_ARG)
 template <class F>
@@ -395,12 +378,9 @@ int run_poly_pow_mod(ecfft_ctx* c, DeviceChain<F>& ch, const void* a, size_t na,
     const size_t lim = SIZE_MAX / (64 * sizeof(E));
     if (na > lim || nm > lim) return ECFFT_ERR_BAD_ARG;
     const size_t d = nm - 1;
-    size_t N = 1;
-    if (d > DeviceChain<F>::kPowSmall) {
-        while (N < 2 * d - 1) N <<= 1;
-        if (N > ch.size()) return ECFFT_ERR_TREE_TOO_SMALL;
-    }
-    const size_t Nd = divrem_leaves(na, nm);
+    const size_t N = DeviceChain<F>::powmod_leaves(nm);                      // 1 for d <= kPowSmall: no transform for the power itself
+    if (N > 1 && N > ch.size()) return ECFFT_ERR_TREE_TOO_SMALL;
+    const size_t Nd = DeviceChain<F>::divrem_leaves(na, nm);
     if (Nd > ch.size()) return ECFFT_ERR_TREE_TOO_SMALL;
     size_t per = N > Nd ? N : Nd;
     if (per < na + nm) per = na + nm;
@@ -428,10 +408,9 @@ int run_poly_mul_mod(ecfft_ctx* c, DeviceChain<F>& ch, const void* a, size_t na,
     if (!a || !b || !modulus || !out) return ECFFT_ERR_BAD_ARG;
     const size_t lim = SIZE_MAX / (64 * sizeof(E));
     if (na > lim || nb > lim || nm > lim) return ECFFT_ERR_BAD_ARG;
-    const size_t nc = na + nb - 1, d = nm - 1;
-    size_t N = 1; while (N < nc) N <<= 1;
+    const size_t nc = na + nb - 1, d = nm - 1, N = DeviceChain<F>::mul_leaves(na, nb);
     if (N > ch.size()) return ECFFT_ERR_TREE_TOO_SMALL;
-    const size_t Nd = divrem_leaves(nc, nm);
+    const size_t Nd = DeviceChain<F>::divrem_leaves(nc, nm);
     if (Nd > ch.size()) return ECFFT_ERR_TREE_TOO_SMALL;
     size_t per = N > Nd ? N : Nd;
     if (per < nc + nm) per = nc + nm;

@@ -152,6 +152,38 @@ def test_batch_equals_separate_calls(field, na, nb, count):
 
 
 @pytest.mark.parametrize("field", FIELDS)
+@pytest.mark.parametrize("na,nb", [(200, 70), (134, 70), (200, 1), (70, 200)])
+def test_outputs_do_not_depend_on_which_are_asked_for(oracle_mod, field, na, nb):
+    """q of a q-only call and r of an r-only call are byte for byte those of the call that asks for both, and that call matches
+    long division: 3 pairs on a 512-leaf tree with nq = 131 > K0 (a Newton step) > nr, nq = 65 (the first size past the base
+    case) < nr, nb = 1 (scaling) and na < nb (copy)"""
+    from ecfft_amd import fftree as FT
+    F, p, t, count = oracle_mod.field(field), P[field], tree(field, 512), 3
+    rng = np.random.default_rng(na * 31 + nb)
+    ai = [rand_ints(field, na, rng) for _ in range(count)]
+    bi = [rand_divisor(field, nb, rng) for _ in range(count)]
+    a, b = F.from_ints(sum(ai, [])), F.from_ints(sum(bi, []))
+    nq, nr = max(na - nb + 1, 0), nb - 1
+
+    def call(want_q, want_r):
+        # one element more than the output, so that an empty output still has an address; all-ones bytes are no field element
+        q = np.full((count * nq + 1,) + a.shape[1:], np.iinfo(a.dtype).max, a.dtype)
+        r = np.full((count * nr + 1,) + a.shape[1:], np.iinfo(a.dtype).max, a.dtype)
+        rc = t._L.ecfft_poly_divrem(t._h, a.ctypes.data, na, b.ctypes.data, nb, q.ctypes.data if want_q else None,
+                                    r.ctypes.data if want_r else None, count, FT.MEM_HOST, None)
+        assert rc == FT.OK, (want_q, want_r)
+        return q[:count * nq], r[:count * nr]
+
+    q, r = call(True, True)
+    for i in range(count):
+        wq, wr = long_division(ai[i], bi[i], p)
+        assert (F.to_ints(q[i * nq:(i + 1) * nq]) if nq else []) == wq, i
+        assert (F.to_ints(r[i * nr:(i + 1) * nr]) if nr else []) == wr, i
+    assert np.array_equal(call(True, False)[0], q)
+    assert np.array_equal(call(False, True)[1], r)
+
+
+@pytest.mark.parametrize("field", FIELDS)
 def test_device_tensors_match_host(field):
     import torch
     t = tree(field, 4096)
