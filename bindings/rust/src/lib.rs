@@ -90,6 +90,11 @@ pub mod ffi {
         pub fn ecfft_extend_sharded_layout(ctx: *mut EcfftCtx, comm: *mut EcfftComm, input: *const c_void, out: *mut c_void, e: usize, moiety: i32, in_layout: i32, out_layout: i32, stream: *mut c_void) -> i32; // 0 block, 1 cyclic
         pub fn ecfft_enter_sharded(ctx: *mut EcfftCtx, comm: *mut EcfftComm, coeffs: *const c_void, evals: *mut c_void, n: usize, stream: *mut c_void) -> i32;
         pub fn ecfft_exit_sharded(ctx: *mut EcfftCtx, comm: *mut EcfftComm, evals: *const c_void, coeffs: *mut c_void, n: usize, stream: *mut c_void) -> i32;
+        // curves of the caller's own: the search (src/find_curve.rs:190-246) and build_fftree on a good curve; host pointers, synchronous
+        pub fn ecfft_find_curve_candidate(field: i32, seed: u64, index: u64, a_out: *mut c_void, bb_out: *mut c_void) -> i32;
+        pub fn ecfft_curve_two_sylow(field: i32, device: i32, a: *const c_void, bb: *const c_void, count: usize, n_out: *mut u32, x_out: *mut c_void) -> i32;
+        pub fn ecfft_find_curve(field: i32, device: i32, k: u32, seed: u64, start: u64, max_candidates: u64, index_out: *mut u64, n_out: *mut u32, a_out: *mut c_void, bb_out: *mut c_void, gen_xy_out: *mut c_void, offset_xy_out: *mut c_void) -> i32;
+        pub fn ecfft_build_fftree_on_curve(field: i32, n: usize, a: *const c_void, bb: *const c_void, gen_xy: *const c_void, gen_log_order: u32, offset_xy: *const c_void, device: i32, out: *mut *mut EcfftCtx) -> i32;
         pub fn ecfft_device_alloc(device: i32, bytes: usize, out: *mut *mut c_void) -> i32;
         pub fn ecfft_device_free(ptr: *mut c_void) -> i32;
         pub fn ecfft_device_copy(dst: *mut c_void, src: *const c_void, bytes: usize, kind: i32) -> i32; // 0 D2H, 1 H2D, 2 D2D
@@ -138,6 +143,17 @@ impl<F: HipField> Drop for HipFFTree<F> {
     }
 }
 
+/// What `HipFFTree::find_curve` returns: the curve y^2 = x(x^2 + a x + bb), a generator (x, y) of order 2^n and a coset offset
+#[derive(Clone, Copy, Debug)]
+pub struct FoundCurve<F: HipField> {
+    pub index: u64,
+    pub n: u32,
+    pub a: F,
+    pub bb: F,
+    pub gen: [F; 2],
+    pub offset: [F; 2],
+}
+
 fn check(rc: i32) {
     match rc {
         ffi::OK => {}
@@ -164,6 +180,36 @@ impl<F: HipField> HipFFTree<F> {
         assert_eq!(core::mem::size_of::<F>(), F::ELEM_BYTES, "unexpected in-memory size of the field element");
         let mut ctx = core::ptr::null_mut();
         match unsafe { ffi::ecfft_build_fftree(F::FIELD_ID, n, device, &mut ctx) } {
+            ffi::ERR_TREE_TOO_LARGE => None,
+            rc => {
+                check(rc);
+                Some(Self { ctx, _f: PhantomData })
+            }
+        }
+    }
+
+    /// `find_curve(rng, k)` (src/find_curve.rs:224-246) on the GPU, over candidates `start .. start + max_candidates` of the
+    /// reproducible stream `seed` (ecfft_hip.h): the candidate of smallest index whose 2-Sylow subgroup is cyclic of order
+    /// 2^n, n >= max(k, 2).  `None` when the window holds none.
+    pub fn find_curve(k: u32, seed: u64, start: u64, max_candidates: u64, device: i32) -> Option<FoundCurve<F>> {
+        assert_eq!(core::mem::size_of::<F>(), F::ELEM_BYTES, "unexpected in-memory size of the field element");
+        let (mut index, mut n) = (0u64, 0u32);
+        let (mut a, mut bb) = (F::zero(), F::zero());
+        let (mut gen, mut offset) = ([F::zero(); 2], [F::zero(); 2]);
+        check(unsafe {
+            ffi::ecfft_find_curve(F::FIELD_ID, device, k, seed, start, max_candidates, &mut index, &mut n, (&mut a as *mut F).cast(),
+                (&mut bb as *mut F).cast(), gen.as_mut_ptr().cast(), offset.as_mut_ptr().cast())
+        });
+        (n != 0).then_some(FoundCurve { index, n, a, bb, gen, offset })
+    }
+
+    /// `build_fftree(n)` on a found curve (ecfft_build_fftree_on_curve): `None` when log2 n >= the generator's log order
+    pub fn build_on_curve(n: usize, c: &FoundCurve<F>, device: i32) -> Option<Self> {
+        let mut ctx = core::ptr::null_mut();
+        match unsafe {
+            ffi::ecfft_build_fftree_on_curve(F::FIELD_ID, n, (&c.a as *const F).cast(), (&c.bb as *const F).cast(), c.gen.as_ptr().cast(), c.n,
+                c.offset.as_ptr().cast(), device, &mut ctx)
+        } {
             ffi::ERR_TREE_TOO_LARGE => None,
             rc => {
                 check(rc);

@@ -1348,3 +1348,260 @@ int ecfft_device_info(int device, char* buf, size_t cap) {
 }
 
 }  // extern "C"
+
+// ---- curve search: ecfft_find_curve_candidate / ecfft_curve_two_sylow / ecfft_find_curve / ecfft_build_fftree_on_curve ------------------
+#include "curve_search.h"
+#ifdef ECFFT_TEST_HOOKS
+#include <chrono>
+#endif
+
+namespace {
+using curve::Cand;
+using curve::StageArgs;
+
+template <class F>
+typename F::elem half_of_one() { return F::inv(F::from_u32(2)); }
+
+// candidates per batch: both queues hold a whole batch (a stage never makes candidates), 2 x 112 MiB / 2 x 384 MiB
+template <class F> constexpr unsigned kSearchBatch = std::is_same<F, Secp256k1>::value ? (1u << 20) : (1u << 24);
+
+#ifdef ECFFT_TEST_HOOKS
+// entries each stage read, summed over the batches since the last ecfft_curve_search_stats: [0] bb, [1] discriminant, [2] order 4,
+// [3 + r] halving round r (measurement only: tools/findcurve_time.py)
+uint64_t g_stage_len[3 + 8 * 32 + 2 + 1];
+double g_stage_s[3 + 8 * 32 + 2 + 1];        // host seconds around each stage's launch and the read of its queue length (which waits for it)
+#endif
+
+// The device side of one search: two queues, the length counters of every stage and the flags.
+template <class F>
+struct SearchWork {
+    unsigned cap;
+    DeviceBuffer qa, qb, lens, flags;
+    explicit SearchWork(unsigned cap_) : cap(cap_), qa((size_t)cap_ * sizeof(Cand<F>)), qb((size_t)cap_ * sizeof(Cand<F>)),
+                                         lens((4 + curve::kMaxRounds<F>) * sizeof(unsigned)), flags(sizeof(unsigned)) {}
+    bool ok() const { return qa.ok && qb.ok && lens.ok && flags.ok; }
+};
+
+template <class F, int STAGE>
+bool launch_stage(StageArgs<F>& g, unsigned* out_len_dev, unsigned* len_host) {
+    g.out_len = out_len_dev;
+#ifdef ECFFT_TEST_HOOKS
+    const size_t slot = STAGE == curve::STAGE_HALVE ? 3 + (g.n_now - 2) : STAGE;
+    g_stage_len[slot] += g.in_len;
+    const auto t0 = std::chrono::steady_clock::now();
+#endif
+    hipLaunchKernelGGL((curve::k_stage<F, STAGE>), dim3((g.in_len + 255) / 256), dim3(256), 0, nullptr, g);
+    const bool ok = hipMemcpy(len_host, out_len_dev, sizeof(unsigned), hipMemcpyDeviceToHost) == hipSuccess;   // waits for the stage
+#ifdef ECFFT_TEST_HOOKS
+    g_stage_s[slot] += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+#endif
+    return ok;
+}
+
+// `count` <= w.cap candidates through every stage.  g names the source and where results go (StageArgs); the queue fields are set here.
+template <class F>
+int run_search_batch(SearchWork<F>& w, StageArgs<F> g, unsigned count) {
+    Cand<F>*qa = w.qa.template as<Cand<F>>(), *qb = w.qb.template as<Cand<F>>();
+    unsigned* lens = w.lens.template as<unsigned>();
+    if (hipMemset(lens, 0, (4 + curve::kMaxRounds<F>) * sizeof(unsigned)) != hipSuccess || hipMemset(w.flags.p, 0, sizeof(unsigned)) != hipSuccess)
+        return ECFFT_ERR_HIP;
+    g.flags = w.flags.template as<unsigned>(); g.cap = w.cap; g.half = half_of_one<F>();
+    unsigned len = 0;
+    g.in = nullptr; g.out = qa; g.in_len = count; g.n_now = 0;
+    if (!launch_stage<F, curve::STAGE_BB>(g, lens + 0, &len)) return ECFFT_ERR_HIP;
+    g.in = qa; g.out = qb; g.in_len = len;
+    if (len && !launch_stage<F, curve::STAGE_DISC>(g, lens + 1, &len)) return ECFFT_ERR_HIP;
+    g.in = qb; g.out = qa; g.in_len = len; g.n_now = 1;
+    if (len && !launch_stage<F, curve::STAGE_ORDER4>(g, lens + 2, &len)) return ECFFT_ERR_HIP;
+    bool bound_hit = false;
+    for (unsigned r = 0; len; ++r) {                         // halving rounds: a candidate that fails round r has n = 2 + r
+        if (r == curve::kMaxRounds<F>) { bound_hit = true; break; }
+        g.in = (r & 1) ? qb : qa; g.out = (r & 1) ? qa : qb; g.in_len = len; g.n_now = 2 + r;
+        if (!launch_stage<F, curve::STAGE_HALVE>(g, lens + 3 + r, &len)) return ECFFT_ERR_HIP;
+    }
+    unsigned flags = 0;
+    if (hipMemcpy(&flags, w.flags.p, sizeof(unsigned), hipMemcpyDeviceToHost) != hipSuccess || hipGetLastError() != hipSuccess) return ECFFT_ERR_HIP;
+    if (flags || bound_hit) { fprintf(stderr, "ecfft: curve search: %s\n", bound_hit ? "a candidate survived every halving round" : "a queue overflowed"); return ECFFT_ERR_HIP; }
+    return ECFFT_OK;
+}
+
+// cyclic_two_sylow_subgroup of `count` curves given in PLAIN form on the host; n and x (plain) back to the host
+template <class F>
+int two_sylow_device(int device, const typename F::elem* a, const typename F::elem* bb, size_t count, uint32_t* n_out, typename F::elem* x_out) {
+    using E = typename F::elem;
+    if (!have_device(device)) return ECFFT_ERR_HIP;
+    DeviceGuard dev(device);
+    if (!dev.ok) return ECFFT_ERR_HIP;
+    const unsigned cap = (unsigned)std::min<size_t>(count, kSearchBatch<F>);
+    SearchWork<F> w(cap);
+    DeviceBuffer da((size_t)cap * sizeof(E)), db((size_t)cap * sizeof(E)), dn((size_t)cap * sizeof(uint32_t)), dx((size_t)cap * sizeof(E));
+    if (!w.ok() || !da.ok || !db.ok || !dn.ok || !dx.ok) return ECFFT_ERR_HIP;
+    for (size_t at = 0; at < count; at += cap) {
+        const unsigned cnt = (unsigned)std::min<size_t>(cap, count - at);
+        if (hipMemcpy(da.p, a + at, cnt * sizeof(E), hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(db.p, bb + at, cnt * sizeof(E), hipMemcpyHostToDevice) != hipSuccess ||
+            hipMemset(dn.p, 0, cnt * sizeof(uint32_t)) != hipSuccess || hipMemset(dx.p, 0, cnt * sizeof(E)) != hipSuccess) return ECFFT_ERR_HIP;
+        StageArgs<F> g{};
+        g.a_in = da.template as<const E>(); g.bb_in = db.template as<const E>(); g.base = 0;
+        g.n_out = dn.template as<uint32_t>(); g.x_out = dx.template as<E>(); g.best = nullptr;
+        const int rc = run_search_batch<F>(w, g, cnt);
+        if (rc != ECFFT_OK) return rc;
+        if (hipMemcpy(n_out + at, dn.p, cnt * sizeof(uint32_t), hipMemcpyDeviceToHost) != hipSuccess ||
+            hipMemcpy(x_out + at, dx.p, cnt * sizeof(E), hipMemcpyDeviceToHost) != hipSuccess) return ECFFT_ERR_HIP;
+    }
+    return ECFFT_OK;
+}
+
+// the smallest index in [start, start + max) of stream `seed` whose n >= k_min (UINT64_MAX: none), scanned batch by batch in order;
+// the scan ends after the first batch that holds a hit
+template <class F>
+int scan_stream(int device, uint32_t k_min, uint64_t seed, uint64_t start, uint64_t max, uint64_t* index) {
+    *index = UINT64_MAX;
+    if (!have_device(device)) return ECFFT_ERR_HIP;
+    DeviceGuard dev(device);
+    if (!dev.ok) return ECFFT_ERR_HIP;
+    const unsigned cap = (unsigned)std::min<uint64_t>(max, kSearchBatch<F>);
+    SearchWork<F> w(cap);
+    DeviceBuffer best(sizeof(unsigned long long));
+    if (!w.ok() || !best.ok || hipMemset(best.p, 0xFF, sizeof(unsigned long long)) != hipSuccess) return ECFFT_ERR_HIP;
+    for (uint64_t at = 0; at < max; at += cap) {
+        const unsigned cnt = (unsigned)std::min<uint64_t>(cap, max - at);
+        StageArgs<F> g{};
+        g.seed = seed; g.base = start + at; g.best = best.template as<unsigned long long>(); g.k_min = k_min;
+        const int rc = run_search_batch<F>(w, g, cnt);
+        if (rc != ECFFT_OK) return rc;
+        unsigned long long h = 0;
+        if (hipMemcpy(&h, best.p, sizeof(h), hipMemcpyDeviceToHost) != hipSuccess) return ECFFT_ERR_HIP;
+        if (h != ~0ull) { *index = h; break; }
+    }
+    return ECFFT_OK;
+}
+
+template <class F>
+bool on_curve(const Curve<F>& c, const Pt<F>& p) { return F::eq(F::sqr(p.y), curve::rhs<F>(p.x, c.a2, c.a4)); }
+template <class F>
+Pt<F> pt_double_n(const Curve<F>& c, Pt<F> p, unsigned times) { for (unsigned i = 0; i < times; ++i) p = pt_add(c, p, p); return p; }
+template <class F>
+Pt<F> load_point(const void* xy) {
+    Pt<F> p; p.inf = false;
+    memcpy(&p.x, xy, sizeof(p.x)); memcpy(&p.y, (const char*)xy + sizeof(p.x), sizeof(p.y));
+    from_crate_host<F>(&p.x, 1); from_crate_host<F>(&p.y, 1);
+    return p;
+}
+template <class F>
+void store_elems(void* out, const typename F::elem* v, size_t n) {       // plain -> the crate's form, into a caller buffer that may be NULL
+    if (!out) return;
+    std::vector<typename F::elem> t(v, v + n);
+    to_crate_host<F>(t.data(), n);
+    memcpy(out, t.data(), n * sizeof(typename F::elem));
+}
+}  // namespace
+
+extern "C" {
+
+int ecfft_find_curve_candidate(int field, uint64_t seed, uint64_t index, void* a_out, void* bb_out) {
+    if (!a_out || !bb_out || index >= curve::kMaxIndex) return ECFFT_ERR_BAD_ARG;
+    return with_field(field, [&](auto tag) -> int {
+        using F = typename decltype(tag)::type;
+        const typename F::elem a = curve::stream_elem<F>(seed, 8 * index), bb = curve::stream_elem<F>(seed, 8 * index + 4);
+        store_elems<F>(a_out, &a, 1); store_elems<F>(bb_out, &bb, 1);
+        return ECFFT_OK;
+    });
+}
+
+int ecfft_curve_two_sylow(int field, int device, const void* a, const void* bb, size_t count, uint32_t* n_out, void* x_out) {
+    if (!known_field(field) || !a || !bb || !n_out || !x_out || count == 0 || count > SIZE_MAX / 64) return ECFFT_ERR_BAD_ARG;
+    return guarded([&] {
+        return with_field(field, [&](auto tag) -> int {
+            using F = typename decltype(tag)::type;
+            using E = typename F::elem;
+            std::vector<E> pa((const E*)a, (const E*)a + count), pb((const E*)bb, (const E*)bb + count), px(count);
+            from_crate_host<F>(pa.data(), count); from_crate_host<F>(pb.data(), count);
+            const int rc = two_sylow_device<F>(device, pa.data(), pb.data(), count, n_out, px.data());
+            if (rc == ECFFT_OK) store_elems<F>(x_out, px.data(), count);
+            return rc;
+        });
+    });
+}
+
+int ecfft_find_curve(int field, int device, unsigned k, uint64_t seed, uint64_t start, uint64_t max_candidates, uint64_t* index_out,
+                     uint32_t* n_out, void* a_out, void* bb_out, void* gen_xy_out, void* offset_xy_out) {
+    if (!known_field(field) || !index_out || !n_out || max_candidates == 0 || start > curve::kMaxIndex ||
+        max_candidates > curve::kMaxIndex - start || k > 8 * ecfft_elem_size(field)) return ECFFT_ERR_BAD_ARG;
+    *index_out = UINT64_MAX; *n_out = 0;
+    return guarded([&] {
+        return with_field(field, [&](auto tag) -> int {
+            using F = typename decltype(tag)::type;
+            using E = typename F::elem;
+            uint64_t idx = UINT64_MAX;
+            int rc = scan_stream<F>(device, k < 2 ? 2u : k, seed, start, max_candidates, &idx);      // k.max(2), find_curve.rs:225
+            if (rc != ECFFT_OK || idx == UINT64_MAX) return rc;
+            const E a = curve::stream_elem<F>(seed, 8 * idx), bb = curve::stream_elem<F>(seed, 8 * idx + 4);
+            uint32_t n = 0; E x;
+            rc = two_sylow_device<F>(device, &a, &bb, 1, &n, &x);                                // its n and generator, from the same stages
+            if (rc != ECFFT_OK) return rc;
+            const Curve<F> c{a, bb, F::zero()};
+            Pt<F> gen{x, F::zero(), false}, off{F::zero(), F::zero(), false};
+            if (n < 2 || !curve::is_square<F>(curve::rhs<F>(x, a, bb), &gen.y)) return ECFFT_ERR_HIP;
+            // coset offset: the point of smallest integer x >= 1 whose y^2 is a non-zero square and whose order does not divide 2^n
+            // (none exists when the whole group is the cyclic group of order 2^n.  By the Hasse bound that is exactly n = the bit
+            // length of p, M31's supersingular curves of p + 1 = 2^31 points for one: the offset is then returned as 0, 0)
+            const unsigned p_bits = 8 * F::kBytes - (F::kBytes == 4 ? 1 : 0);
+            bool found = n == p_bits;
+            if (found) off.y = F::zero();
+            for (uint32_t xi = 1; xi < (1u << 20) && !found; ++xi) {
+                off.x = F::from_u32(xi);
+                const E yy = curve::rhs<F>(off.x, a, bb);
+                if (F::is_zero(yy) || !curve::is_square<F>(yy, &off.y)) continue;
+                found = !pt_double_n<F>(c, off, n).inf;
+            }
+            if (!found) return ECFFT_ERR_HIP;
+            *index_out = idx; *n_out = n;
+            store_elems<F>(a_out, &a, 1); store_elems<F>(bb_out, &bb, 1);
+            const E g2[2] = {gen.x, gen.y}, o2[2] = {off.x, off.y};
+            store_elems<F>(gen_xy_out, g2, 2); store_elems<F>(offset_xy_out, o2, 2);
+            return ECFFT_OK;
+        });
+    });
+}
+
+int ecfft_build_fftree_on_curve(int field, size_t n, const void* a, const void* bb, const void* gen_xy, unsigned gen_log_order,
+                                const void* offset_xy, int device, ecfft_ctx** out) {
+    if (!out) return ECFFT_ERR_BAD_ARG;
+    *out = nullptr;
+    if (!a || !bb || !gen_xy || !offset_xy) return ECFFT_ERR_BAD_ARG;
+    if (!is_pow2(n)) return ECFFT_ERR_NOT_POW2;
+    if (!known_field(field) || gen_log_order == 0 || gen_log_order > 8 * ecfft_elem_size(field)) return ECFFT_ERR_BAD_ARG;
+    if (ilog2(n) >= gen_log_order) return ECFFT_ERR_TREE_TOO_LARGE;                                  // src/lib.rs:62-64
+    return guarded([&] {
+        return with_field(field, [&](auto tag) -> int {
+            using F = typename decltype(tag)::type;
+            using E = typename F::elem;
+            E ca, cbb, b;
+            memcpy(&ca, a, sizeof(E)); memcpy(&cbb, bb, sizeof(E));
+            from_crate_host<F>(&ca, 1); from_crate_host<F>(&cbb, 1);
+            if (F::is_zero(cbb) || !F::sqrt(cbb, &b)) return ECFFT_ERR_BAD_ARG;
+            const Curve<F> c{ca, cbb, F::zero()};
+            const Pt<F> gen = load_point<F>(gen_xy), off = load_point<F>(offset_xy);
+            if (!on_curve<F>(c, gen) || !on_curve<F>(c, off)) return ECFFT_ERR_BAD_ARG;
+            const Pt<F> g2 = pt_double_n<F>(c, gen, gen_log_order - 1);                              // exact order 2^m: 2^(m-1) gen = (0, 0)
+            if (g2.inf || !F::is_zero(g2.x) || !F::is_zero(g2.y)) return ECFFT_ERR_BAD_ARG;
+            if (pt_double_n<F>(c, off, gen_log_order).inf) return ECFFT_ERR_BAD_ARG;                 // off + <gen> must miss the identity and pair up no +-P
+            HostTree<F> ht;
+            const int r = build_good_curve<F>(ca, cbb, gen, gen_log_order, off, ilog2(n), ht, /*points=*/false);
+            if (r) return r == 1 ? ECFFT_ERR_TREE_TOO_LARGE : ECFFT_ERR_BAD_ARG;
+            if (!have_device(device)) return ECFFT_ERR_HIP;
+            return new_ctx<F>(field, device, out, [&](DeviceChain<F>& ch) -> int { return build_chain(ch, std::move(ht), device); });
+        });
+    });
+}
+
+#ifdef ECFFT_TEST_HOOKS
+int ecfft_curve_search_stats(uint64_t* lens, double* seconds, size_t cap, int reset) {
+    const size_t n = sizeof(g_stage_len) / sizeof(g_stage_len[0]);
+    for (size_t i = 0; i < cap && i < n; ++i) { if (lens) lens[i] = g_stage_len[i]; if (seconds) seconds[i] = g_stage_s[i]; }
+    if (reset) { memset(g_stage_len, 0, sizeof(g_stage_len)); memset(g_stage_s, 0, sizeof(g_stage_s)); }
+    return (int)n;
+}
+#endif
+
+}  // extern "C"

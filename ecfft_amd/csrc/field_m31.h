@@ -56,6 +56,12 @@ struct M31 {
         return r;
     }
     __host__ __device__ static inline elem inv(elem a) { return pow_u64(a, P - 2); }
+    // a^((p+1)/4) = a^(2^29): THE square root of a when a is a square (p = 3 mod 4); the caller squares it to find out
+    __host__ __device__ static inline elem sqrt_canon(elem a) {
+#pragma unroll 1
+        for (int i = 0; i < 29; ++i) a = sqr(a);
+        return a;
+    }
     __host__ static inline bool sqrt(elem a, elem* out) {
         elem r = pow_u64(a, ((uint64_t)P + 1) / 4);
         if (sqr(r) != a) return false;

@@ -143,22 +143,18 @@ static void compute_leaves(const Curve<F>& c, const Pt<F>& offset, const Pt<F>& 
     }
 }
 
-// ---- secp256k1: good curve + good isogeny chain (src/ec.rs:38-45, 61-90, 177-189) ----
-// returns 0 ok, 1 = n too large for the curve's 2-adicity (build_fftree -> None), 2 = internal error
+// ---- good curve y^2 = x(x^2 + a x + bb) + good isogeny chain (src/ec.rs:38-45, 61-90, 177-189) ----
+// The build_fftree front end (src/lib.rs:39-85) for ANY good curve: `gen` of order 2^log_order, leaves x(off + i * 2^(log_order - log_n) gen).
+// returns 0 ok, 1 = n too large for the generator's order (build_fftree -> None), 2 = bb or a later B is no square (not a good curve)
 // points = false: only the maps and the generator data (the GPU computes leaves and layers)
-static inline int build_secp256k1(unsigned log_n, HostTree<Secp256k1>& t, bool points = true) {
-    using F = Secp256k1; using E = F::elem;
-    const unsigned two_adicity = 36;
-    if (log_n >= two_adicity) return 1;                         // src/lib.rs:62-64
-    E a = F::from_dec("31172306031375832341232376275243462303334845584808513005362718476441963632613");
-    E bb = F::from_dec("45508371059383884471556188660911097844526467659576498497548207627741160623272");
+template <class F>
+static inline int build_good_curve(typename F::elem a, const typename F::elem& bb, Pt<F> gen, unsigned log_order, const Pt<F>& off,
+                                   unsigned log_n, HostTree<F>& t, bool points = true) {
+    using E = typename F::elem;
+    if (log_n >= log_order) return 1;                           // src/lib.rs:62-64
     E b; if (!F::sqrt(bb, &b)) return 2;                        // GoodCurve::new_odd
     Curve<F> c{a, bb, F::zero()};
-    Pt<F> off{F::from_dec("105623886150579165427389078198493427091405550492761682382732004625374789850161"),
-              F::from_dec("7709812624542158994629670452026922591039826164720902911013234773380889499231"), false};
-    Pt<F> gen{F::from_dec("41293412487153066667050767300223451435019201659857889215769525847559135483332"),
-              F::from_dec("73754924733368840065089190002333366411120578552679996887076912271884749237510"), false};
-    for (unsigned i = 0; i < two_adicity - log_n; ++i) gen = pt_add(c, gen, gen);   // src/lib.rs:67-70
+    for (unsigned i = 0; i < log_order - log_n; ++i) gen = pt_add(c, gen, gen);     // src/lib.rs:67-70
     size_t n = (size_t)1 << log_n;
     t.n = n; t.maps.resize(log_n);
     t.have_gen = true; t.curve = c; t.off = off; t.gen = gen;
@@ -176,6 +172,17 @@ static inline int build_secp256k1(unsigned log_n, HostTree<Secp256k1>& t, bool p
     }
     if (!points) return 0;
     return fill_layers<F>(t) ? 0 : 2;
+}
+
+// secp256k1: the crate's curve, coset offset and generator of order 2^36 (src/lib.rs:45-59)
+static inline int build_secp256k1(unsigned log_n, HostTree<Secp256k1>& t, bool points = true) {
+    using F = Secp256k1;
+    const Pt<F> off{F::from_dec("105623886150579165427389078198493427091405550492761682382732004625374789850161"),
+                    F::from_dec("7709812624542158994629670452026922591039826164720902911013234773380889499231"), false};
+    const Pt<F> gen{F::from_dec("41293412487153066667050767300223451435019201659857889215769525847559135483332"),
+                    F::from_dec("73754924733368840065089190002333366411120578552679996887076912271884749237510"), false};
+    return build_good_curve<F>(F::from_dec("31172306031375832341232376275243462303334845584808513005362718476441963632613"),
+                               F::from_dec("45508371059383884471556188660911097844526467659576498497548207627741160623272"), gen, 36, off, log_n, t, points);
 }
 
 // ---- Mersenne-31: Velu 2-isogenies of short Weierstrass curves (src/ec.rs:209-259, 498-554) ----

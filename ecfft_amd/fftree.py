@@ -33,14 +33,15 @@ EXPORTS = ["ecfft_elem_size", "ecfft_build_fftree", "ecfft_fftree_new", "ecfft_c
            "ecfft_comm_stats_enable", "ecfft_comm_stats_read", "ecfft_extend_sharded", "ecfft_enter_sharded", "ecfft_exit_sharded", "ecfft_device_copy", "ecfft_shader_clock", "ecfft_device_alloc", "ecfft_device_free", "ecfft_device_sync", "ecfft_build_extend_shard", "ecfft_ctx_device_bytes", "ecfft_extend_sharded_layout", "ecfft_build_enter_shard", "ecfft_build_exit_shard", "ecfft_build_exit_shard_opts",
            "ecfft_fftree_serialize", "ecfft_fftree_deserialize", "ecfft_tree_rational_maps", "ecfft_ctx_trim", "ecfft_comm_abort", "ecfft_comm_set_rccl_library", "ecfft_comm_set_link_striping",
            "ecfft_poly_mul", "ecfft_poly_inv_series", "ecfft_poly_divrem", "ecfft_poly_eval_points", "ecfft_poly_interpolate",
-           "ecfft_poly_pow_mod", "ecfft_poly_mul_mod", "ecfft_poly_gcd", "ecfft_poly_xgcd", "ecfft_poly_find_roots"]
+           "ecfft_poly_pow_mod", "ecfft_poly_mul_mod", "ecfft_poly_gcd", "ecfft_poly_xgcd", "ecfft_poly_find_roots",
+           "ecfft_find_curve_candidate", "ecfft_curve_two_sylow", "ecfft_find_curve", "ecfft_build_fftree_on_curve"]
 # include/ecfft_hip.h ECFFT_GCD_SMALL_MAX: max(na, nb) up to which a gcd runs in one workgroup per pair, on any tree
 GCD_SMALL_MAX = 256
 # include/ecfft_hip.h ECFFT_ROOTS_SMALL_MAX: nf up to which poly_find_roots finishes a polynomial in one workgroup, on any tree
 ROOTS_SMALL_MAX = 65
 
 # include/ecfft_hip_hooks.h: only in a build with -DECFFT_TEST_HOOKS (tests/hooks/libecfft_hip_hooks.so), never in the shipped library
-HOOK_EXPORTS = ['ecfft_selftest_field', 'ecfft_selfcheck_pointwise_z', 'ecfft_test_fail_next_collective', 'ecfft_selftest_blk16', 'ecfft_selftest_blk16_small', 'ecfft_test_fail_build_rank', 'ecfft_comm_init_projection', 'ecfft_selftest_blk32', 'ecfft_ctx_low_map']
+HOOK_EXPORTS = ['ecfft_selftest_field', 'ecfft_selfcheck_pointwise_z', 'ecfft_test_fail_next_collective', 'ecfft_selftest_blk16', 'ecfft_selftest_blk16_small', 'ecfft_test_fail_build_rank', 'ecfft_comm_init_projection', 'ecfft_selftest_blk32', 'ecfft_ctx_low_map', 'ecfft_curve_search_stats']
 
 EXCHANGE_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_void_p),
                                ctypes.POINTER(ctypes.c_size_t), ctypes.c_int, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_void_p),
@@ -124,6 +125,12 @@ def _bind(L):
     L.ecfft_profile_classes.restype, L.ecfft_profile_classes.argtypes = ci, []
     L.ecfft_profile_read.restype, L.ecfft_profile_read.argtypes = ci, [vp, ci, ctypes.c_char_p, sz, ctypes.POINTER(ctypes.c_uint64),
                                                                            ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]
+    u32, u64 = ctypes.c_uint32, ctypes.c_uint64
+    L.ecfft_find_curve_candidate.restype, L.ecfft_find_curve_candidate.argtypes = ci, [ci, u64, u64, vp, vp]
+    L.ecfft_curve_two_sylow.restype, L.ecfft_curve_two_sylow.argtypes = ci, [ci, ci, vp, vp, sz, vp, vp]
+    L.ecfft_find_curve.restype, L.ecfft_find_curve.argtypes = ci, [ci, ci, ctypes.c_uint, u64, u64, u64, ctypes.POINTER(u64), ctypes.POINTER(u32),
+                                                                   vp, vp, vp, vp]
+    L.ecfft_build_fftree_on_curve.restype, L.ecfft_build_fftree_on_curve.argtypes = ci, [ci, sz, vp, vp, vp, ctypes.c_uint, vp, ci, ctypes.POINTER(vp)]
     L.ecfft_comm_set_rccl_library.restype, L.ecfft_comm_set_rccl_library.argtypes = ci, [ctypes.c_char_p]
     L.ecfft_comm_set_link_striping.restype, L.ecfft_comm_set_link_striping.argtypes = ci, [vp, sz]
     L.has_hooks = hasattr(L, "ecfft_selftest_field")
@@ -136,6 +143,7 @@ def _bind(L):
         L.ecfft_selftest_blk16_small.restype, L.ecfft_selftest_blk16_small.argtypes = ci, [vp, vp, vp, sz, ci, ci]
         L.ecfft_selftest_blk32.restype, L.ecfft_selftest_blk32.argtypes = ci, [vp, vp, vp, sz, ci]
         L.ecfft_ctx_low_map.restype, L.ecfft_ctx_low_map.argtypes = ci, [vp, ci]
+        L.ecfft_curve_search_stats.restype, L.ecfft_curve_search_stats.argtypes = ci, [ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_double), sz, ci]
         L.ecfft_comm_init_projection.restype = ci
         L.ecfft_comm_init_projection.argtypes = [ci, ci, ci, ctypes.c_double, ctypes.c_double, ctypes.POINTER(vp)]
     return L
@@ -299,6 +307,64 @@ class Field:
         h = ctypes.c_void_p()
         _check(lib().ecfft_fftree_new(self.id, leaves.ctypes.data, n, map_num.ctypes.data, map_den.ctypes.data, device, ctypes.byref(h)))
         return FFTree(self, h, device, maps=(map_num, map_den))
+
+    # ---- curves of the caller's own (include/ecfft_hip.h: curve search) ----------------------------------------------
+    FIND_CURVE_DEFAULT_MAX = 1 << 26
+
+    def find_curve_candidate(self, seed, index):
+        """(a, bb) of candidate `index` of the stream `seed` (ecfft_find_curve_candidate), one element each; host only"""
+        a, bb = np.zeros(self.shape(1), self.dtype), np.zeros(self.shape(1), self.dtype)
+        rc = lib().ecfft_find_curve_candidate(self.id, seed, index, a.ctypes.data, bb.ctypes.data)
+        if rc == ERR_BAD_ARG:
+            raise ValueError("find_curve_candidate: the index must be below 2^60")
+        _check(rc)
+        return a, bb
+
+    def curve_two_sylow(self, a, bb, device=0):
+        """(n, x) of `cyclic_two_sylow_subgroup` (src/find_curve.rs:190-218) for the curves y^2 = x(x^2 + a[i] x + bb[i]): n a numpy
+        uint32 array (0: not cyclic, bb no square or a singular curve), x the x-coordinates of points of order 2^n (0 where n is 0)"""
+        a = np.ascontiguousarray(a, self.dtype); bb = np.ascontiguousarray(bb, self.dtype)
+        assert a.shape == bb.shape
+        count = a.shape[0]
+        n, x = np.zeros(count, np.uint32), np.zeros_like(a)
+        rc = lib().ecfft_curve_two_sylow(self.id, device, a.ctypes.data, bb.ctypes.data, count, n.ctypes.data, x.ctypes.data)
+        if rc == ERR_BAD_ARG:
+            raise ValueError("curve_two_sylow: no curves")
+        _check(rc)
+        return n, x
+
+    def find_curve(self, k, seed, start=0, max_candidates=None, device=0):
+        """`find_curve(rng, k)` (src/find_curve.rs:224-246) over candidates start .. start + max_candidates - 1 of the stream `seed`:
+        the candidate of smallest index with n >= max(k, 2), as a dict index, n, a, bb, gen (x, y of a point of order 2^n) and offset
+        (x, y of a coset offset) in the crate's form, the arguments of build_fftree_on_curve; None when the window holds none."""
+        if max_candidates is None:
+            max_candidates = self.FIND_CURVE_DEFAULT_MAX
+        idx, n = ctypes.c_uint64(), ctypes.c_uint32()
+        a, bb = np.zeros(self.shape(1), self.dtype), np.zeros(self.shape(1), self.dtype)
+        gen, off = np.zeros(self.shape(2), self.dtype), np.zeros(self.shape(2), self.dtype)
+        rc = lib().ecfft_find_curve(self.id, device, k, seed, start, max_candidates, ctypes.byref(idx), ctypes.byref(n),
+                                    a.ctypes.data, bb.ctypes.data, gen.ctypes.data, off.ctypes.data)
+        if rc == ERR_BAD_ARG:
+            raise ValueError("find_curve: an empty window, a window that ends above 2^60 or k above the field's bit length")
+        _check(rc)
+        if n.value == 0:
+            return None
+        return {"index": idx.value, "n": n.value, "a": a, "bb": bb, "gen": gen, "offset": off}
+
+    def build_fftree_on_curve(self, n, a, bb, gen, gen_log_order, offset, device=0):
+        """`build_fftree(n)` on the good curve y^2 = x(x^2 + a x + bb) (ecfft_build_fftree_on_curve): gen = (x, y) of order
+        2^gen_log_order, offset = (x, y) of a coset offset; None if log2 n >= gen_log_order.  ValueError for what is no good curve,
+        no point of it, a generator of another order or an offset inside the subgroup."""
+        a = np.ascontiguousarray(a, self.dtype); bb = np.ascontiguousarray(bb, self.dtype)
+        gen = np.ascontiguousarray(gen, self.dtype); offset = np.ascontiguousarray(offset, self.dtype)
+        assert a.size == bb.size == self.limbs and gen.size == offset.size == 2 * self.limbs
+
+        def make(out):
+            rc = lib().ecfft_build_fftree_on_curve(self.id, n, a.ctypes.data, bb.ctypes.data, gen.ctypes.data, gen_log_order, offset.ctypes.data, device, out)
+            if rc == ERR_BAD_ARG:
+                raise ValueError("build_fftree_on_curve: not a good curve, a point off the curve, a generator of another order or an offset inside its subgroup")
+            return rc
+        return self._new_tree(make, device)
 
 
 def deserialize_fftree(field, data, compress, device=0, verify=True):

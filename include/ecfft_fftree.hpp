@@ -115,6 +115,31 @@ public:
         check(ecfft_fftree_new(F::id, leaves.data(), leaves.size(), num3.data(), den3.data(), device, &c));
         return FFTree(c);
     }
+    // find_curve (src/find_curve.rs:224-246) over candidates start .. start + max_candidates - 1 of the stream `seed`
+    // (ecfft_find_curve): the candidate of smallest index whose 2-Sylow subgroup is cyclic of order 2^n, n >= max(k, 2), with a
+    // generator of that order and a coset offset; nullopt when the window holds none.  Synchronous.
+    struct FoundCurve {
+        uint64_t index; uint32_t n;
+        Elem a, bb;
+        std::array<Elem, 2> gen, offset;       // x, y
+    };
+    static std::optional<FoundCurve> find_curve(unsigned k, uint64_t seed, uint64_t start = 0, uint64_t max_candidates = uint64_t(1) << 26, int device = 0) {
+        FoundCurve f{};
+        check(ecfft_find_curve(F::id, device, k, seed, start, max_candidates, &f.index, &f.n, &f.a, &f.bb, f.gen.data(), f.offset.data()));
+        if (f.n == 0) return std::nullopt;
+        return f;
+    }
+    // build_fftree on a good curve of the caller's (ecfft_build_fftree_on_curve): gen of order 2^gen_log_order; nullopt when
+    // log2 n >= gen_log_order.  What is no good curve, no point of it, or a generator of another order throws.
+    static std::optional<FFTree> build_on_curve(size_t n, const Elem& a, const Elem& bb, const std::array<Elem, 2>& gen, unsigned gen_log_order,
+                                                const std::array<Elem, 2>& offset, int device = 0) {
+        ecfft_ctx* c = nullptr;
+        int rc = ecfft_build_fftree_on_curve(F::id, n, &a, &bb, gen.data(), gen_log_order, offset.data(), device, &c);
+        if (rc == ECFFT_ERR_TREE_TOO_LARGE) return std::nullopt;
+        check(rc);
+        return FFTree(c);
+    }
+    static std::optional<FFTree> build_on_curve(size_t n, const FoundCurve& f, int device = 0) { return build_on_curve(n, f.a, f.bb, f.gen, f.n, f.offset, device); }
     size_t size() const { return ecfft_tree_size(ctx_); }
 
     std::vector<Elem> enter(const std::vector<Elem>& coeffs) const {            // src/fftree.rs:164-167

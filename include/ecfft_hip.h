@@ -408,6 +408,56 @@ int ecfft_fftree_deserialize(int field, const void* bytes, size_t len, int compr
  * construction against an ark-built tree. */
 int ecfft_build_points(int field, size_t n, void* f_out, void* map_num3_out, void* map_den3_out);
 
+/* Curves of the caller's own: search for a good curve on the GPU and build a tree on it.
+ *   ecfft_find_curve            <-> ecfft::find_curve::find_curve(rng, k)                 src/find_curve.rs:224-246
+ *   ecfft_curve_two_sylow       <-> cyclic_two_sylow_subgroup, for many curves            src/find_curve.rs:190-218
+ *   ecfft_build_fftree_on_curve <-> the body of build_fftree for a GoodCurve              src/lib.rs:39-85, src/ec.rs:38-45, 61-90
+ * The curve is y^2 = x (x^2 + a x + bb).  All four calls take `field` and `device` like ecfft_mul_ceiling, need no context, take
+ * HOST pointers and are SYNCHRONOUS; elements are in the crate's in-memory form, points are the pair x, y laid end to end.
+ *
+ * ecfft_find_curve_candidate: candidate `index` of the stream `seed`, which replaces the reference's rng so that a search can be
+ * reproduced.  Host only, needs no GPU.  With mix = the splitmix64 finaliser (z ^= z >> 30, z *= 0xBF58476D1CE4E5B9, z ^= z >> 27,
+ * z *= 0x94D049BB133111EB, z ^= z >> 31) and word number c = mix of seed + (c + 1) * 0x9E3779B97F4A7C15 mod 2^64:
+ *   secp256k1: a = the 256-bit integer made of words 8 index .. 8 index + 3, low word first, mod p; bb from words 8 index + 4 .. + 7;
+ *   M31:       a = the low 31 bits of word 8 index, mod p; bb from word 8 index + 4.
+ * ECFFT_ERR_BAD_ARG: a NULL output, an unknown field, index >= 2^60.
+ *
+ * ecfft_curve_two_sylow: for `count` curves a[i], bb[i]: n_out[i] = n when the 2-Sylow subgroup of the curve's group is cyclic of
+ * order 2^n and bb is a square, else 0; a zero bb or a zero discriminant a^2 - 4 bb, where the reference asserts, gives 0 too.
+ * x_out[i] = the x-coordinate of a point of order 2^n, 0 when n_out[i] is 0.  Bit-exact by one convention: every square root is
+ * v^((p+1)/4), accepted when its square is v (both fields have p = 3 mod 4; 0 counts as a square, as sqrt().is_some() does), and the
+ * two roots of a quadratic are tried in the reference's order, (-b + s)/2 then (-b - s)/2.
+ * Method: stages over device-resident queues (bb square, discriminant no square, point of order 4, then one halving round per
+ * launch); each stage appends its survivors densely to the next queue, so every launch runs full waves although half the curves
+ * die at each test.  A curve that survives 8 * element bytes + 2 halving rounds (impossible: the group is too small) ends the call
+ * with ECFFT_ERR_HIP.  ECFFT_ERR_BAD_ARG: a NULL pointer, count 0, an unknown field.
+ *
+ * ecfft_find_curve: scans candidates start .. start + max_candidates - 1 of stream `seed` and returns the one with the SMALLEST
+ * index whose n >= max of k and 2: the answer does not depend on how the scan is cut into batches.  It stops after the first batch
+ * that holds a hit.  Outputs, when found: *index_out, *n_out, a and bb, the generator gen_xy of order 2^n (the x that
+ * ecfft_curve_two_sylow gives, y = the canonical root of x (x^2 + a x + bb)), and a coset offset offset_xy: the point with the smallest
+ * integer x >= 1 for which x (x^2 + a x + bb) is a non-zero square and 2^n times the point is not the identity, y canonical.  These
+ * are the arguments of ecfft_build_fftree_on_curve with gen_log_order = n.  One kind of curve has no such point: when n is the bit
+ * length of p the Hasse bound leaves 2^n as the only group order, the whole group is the cyclic one (M31: the supersingular curves
+ * of p + 1 = 2^31 points, which a deep search meets first), and offset_xy is returned as 0, 0; a tree on such a curve takes twice the
+ * generator, gen_log_order = n - 1 and the generator itself as the offset.  Nothing found: ECFFT_OK with *n_out = 0 and
+ * *index_out = UINT64_MAX, the other outputs untouched.  ECFFT_ERR_BAD_ARG: NULL index_out or n_out (a_out, bb_out, gen_xy_out and
+ * offset_xy_out may be NULL), max_candidates 0, start + max_candidates > 2^60, k > 8 * element bytes, an unknown field.
+ *
+ * ecfft_build_fftree_on_curve: ecfft_build_fftree on the good curve a, bb: leaf i = x of offset + i * 2^(gen_log_order - log2 n) gen,
+ * the isogenies x -> (x - b)^2 / x.  Checked on the host before any device work, in this order:
+ *   n not a power of two                                          ECFFT_ERR_NOT_POW2
+ *   log2 n >= gen_log_order (the reference's rule, src/lib.rs:62-64)   ECFFT_ERR_TREE_TOO_LARGE
+ *   bb zero or no square; a point not on the curve; gen not of order exactly 2^gen_log_order (2^(gen_log_order - 1) gen must be the
+ *   point 0, 0); 2^gen_log_order offset the identity; a NULL pointer; gen_log_order 0 or above 8 * element bytes   ECFFT_ERR_BAD_ARG
+ * With n < 2^gen_log_order the last check makes the leaves distinct and keeps every layer away from the pole of its map. */
+int ecfft_find_curve_candidate(int field, uint64_t seed, uint64_t index, void* a_out, void* bb_out);
+int ecfft_curve_two_sylow(int field, int device, const void* a, const void* bb, size_t count, uint32_t* n_out, void* x_out);
+int ecfft_find_curve(int field, int device, unsigned k, uint64_t seed, uint64_t start, uint64_t max_candidates, uint64_t* index_out,
+                     uint32_t* n_out, void* a_out, void* bb_out, void* gen_xy_out, void* offset_xy_out);
+int ecfft_build_fftree_on_curve(int field, size_t n, const void* a, const void* bb, const void* gen_xy, unsigned gen_log_order,
+                                const void* offset_xy, int device, ecfft_ctx** out);
+
 /* Per-launch timing for benchmarks (no reference counterpart): while enabled, every hot-path kernel
  * launch is bracketed by HIP events on its stream.  ecfft_profile_read synchronises the device and
  * returns, for kernel class `cls` (0 <= cls < ecfft_profile_classes()), its name, number of launches,

@@ -53,6 +53,11 @@ int ecfft_selftest_blk32(const void* matrix1024, const void* x, void* out, size_
 /* measurement / test hook: which composite map the context's 1024-element low-level kernels run for the lowest levels of ENTER
  * (dir 0) / EXIT (dir 1): 32 = levels 1..5, 16 = levels 1..4, 0 = level code (secp256k1 only; A/B: ECFFT_LOW32, ECFFT_NO_LOW16) */
 int ecfft_ctx_low_map(const ecfft_ctx* ctx, int dir);
+/* measurement hook (tools/findcurve_time.py): the number of queue entries every stage of the curve search has read since the last
+ * reset, summed over batches: [0] bb square, [1] discriminant, [2] point of order 4, [3 + r] halving round r; and the host seconds
+ * spent around each stage's launch and the read of its queue length, which waits for it.  Copies up to `cap` entries into each
+ * array that is not NULL, clears the counters when `reset` is set, returns how many entries there are.  Not thread safe. */
+int ecfft_curve_search_stats(uint64_t* lens, double* seconds, size_t cap, int reset);
 
 #ifdef __cplusplus
 }
