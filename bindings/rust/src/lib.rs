@@ -58,6 +58,7 @@ pub mod ffi {
         pub fn ecfft_poly_interpolate(ctx: *mut EcfftCtx, points: *const c_void, m: usize, values: *const c_void, out: *mut c_void, count: usize, mem: i32, stream: *mut c_void) -> i32;
         pub fn ecfft_poly_pow_mod(ctx: *mut EcfftCtx, a: *const c_void, na: usize, exp: *const c_void, exp_bytes: usize, modulus: *const c_void, nm: usize, out: *mut c_void, count: usize, mem: i32, stream: *mut c_void) -> i32;
         pub fn ecfft_poly_mul_mod(ctx: *mut EcfftCtx, a: *const c_void, na: usize, b: *const c_void, nb: usize, modulus: *const c_void, nm: usize, out: *mut c_void, count: usize, mem: i32, stream: *mut c_void) -> i32;
+        pub fn ecfft_poly_compose_mod(ctx: *mut EcfftCtx, f: *const c_void, nf: usize, g: *const c_void, ng: usize, modulus: *const c_void, nm: usize, out: *mut c_void, count: usize, mem: i32, stream: *mut c_void) -> i32;
         pub fn ecfft_poly_find_roots(ctx: *mut EcfftCtx, f: *const c_void, nf: usize, roots: *mut c_void, n_roots: *mut i64, count: usize, mem: i32, stream: *mut c_void) -> i32;
         pub fn ecfft_poly_gcd(ctx: *mut EcfftCtx, a: *const c_void, na: usize, b: *const c_void, nb: usize, g: *mut c_void, degrees: *mut i64, count: usize, mem: i32, stream: *mut c_void) -> i32;
         pub fn ecfft_poly_xgcd(ctx: *mut EcfftCtx, a: *const c_void, na: usize, b: *const c_void, nb: usize, s: *mut c_void, t: *mut c_void, g: *mut c_void, degrees: *mut i64, count: usize, mem: i32, stream: *mut c_void) -> i32;
@@ -355,6 +356,19 @@ impl<F: HipField> HipFFTree<F> {
         let n = modulus.len() - 1;
         let mut out = Self::out_vec(n);
         check(unsafe { ffi::ecfft_poly_mul_mod(self.ctx, a.as_ptr().cast(), a.len(), b.as_ptr().cast(), b.len(), modulus.as_ptr().cast(), modulus.len(), out.as_mut_ptr().cast(), 1, ffi::MEM_HOST, core::ptr::null_mut()) });
+        unsafe { out.set_len(n) };
+        out
+    }
+
+    /// `f(g) mod modulus` (ecfft_poly_compose_mod): the step of distinct-degree factorisation (src/utils.rs:52-78) and the product
+    /// of two endomorphisms in examples/schoofs.rs:197-235, as `modulus.len() - 1` coefficients, zero-padded above the degree.  `f`
+    /// may be longer than the modulus.  Up to `ECFFT_COMPOSE_SMALL_MAX` modulus coefficients work on any tree; above that the call
+    /// runs about `2 sqrt(f.len())` modular products on the tree rule of `pow_mod` (include/ecfft_hip.h).
+    pub fn compose_mod(&self, f: &[F], g: &[F], modulus: &[F]) -> Vec<F> {
+        assert!(!f.is_empty() && !g.is_empty() && modulus.len() >= 2);
+        let n = modulus.len() - 1;
+        let mut out = Self::out_vec(n);
+        check(unsafe { ffi::ecfft_poly_compose_mod(self.ctx, f.as_ptr().cast(), f.len(), g.as_ptr().cast(), g.len(), modulus.as_ptr().cast(), modulus.len(), out.as_mut_ptr().cast(), 1, ffi::MEM_HOST, core::ptr::null_mut()) });
         unsafe { out.set_len(n) };
         out
     }

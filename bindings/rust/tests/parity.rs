@@ -106,6 +106,34 @@ fn pow_mod_matches<F: HipField>(log_tree: u32) {
     assert_eq!(gpu.pow_mod(&a, &p.to_bytes_le(), &m), want);
 }
 
+/// `compose_mod` against Horner on the crate's own `naive_mul` and `div_rem`, the loop of examples/schoofs.rs:197-235
+fn compose_mod_matches<F: HipField>(log_tree: u32) {
+    use ark_poly::univariate::DensePolynomial;
+    use ark_poly::DenseUVPolynomial;
+    let gpu: HipFFTree<F> = HipFFTree::build_fftree(1usize << log_tree).unwrap();
+    for (nf, ng, nm) in [(1usize, 1usize, 2usize), (2, 3, 2), (5, 10, 4), (64, 64, 65), (130, 20, 65), (17, 66, 67), (101, 300, 130), (145, 129, 130)] {
+        let (f, g) = (rand_vec::<F>(nf, 5), rand_vec::<F>(ng, 6));
+        let mut m: Vec<F> = rand_vec(nm, 8);
+        if m[nm - 1] == F::zero() {
+            m[nm - 1] = F::one();
+        }
+        let (pg, pm) = (DensePolynomial::from_coefficients_slice(&g), DensePolynomial::from_coefficients_slice(&m));
+        let mut res = DensePolynomial::from_coefficients_slice(&f[nf - 1..]);
+        for c in f[..nf - 1].iter().rev() {
+            res = &ecfft::utils::div_rem(&res.naive_mul(&pg), &pm) + &DensePolynomial::from_coefficients_slice(&[*c]);
+        }
+        let mut want = ecfft::utils::div_rem(&res, &pm).coeffs;
+        want.resize(nm - 1, F::zero());
+        assert_eq!(gpu.compose_mod(&f, &g, &m), want, "COMPOSE_MOD nf={nf} ng={ng} nm={nm}");
+    }
+}
+
+#[test]
+fn compose_mod_matches_the_crate() {
+    compose_mod_matches::<ecfft::secp256k1::Fp>(12);
+    compose_mod_matches::<ecfft::m31::Fp>(12);
+}
+
 #[test]
 fn pow_mod_matches_the_crate() {
     pow_mod_matches::<ecfft::secp256k1::Fp>(12);

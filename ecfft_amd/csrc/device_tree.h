@@ -1720,6 +1720,86 @@ public:
         return finish_flagged(ok, flag, singular, s);
     }
 
+    // residues of at most this many coefficients are composed by k_compose_small (one workgroup per triple, no transform)
+    static constexpr size_t kComposeSmall = kPowSmall;
+    // the chunking of Brent-Kung: k = ceil(sqrt(nf)) baby steps, k' = ceil(nf / k) chunks of k coefficients
+    static size_t compose_chunk(size_t nf) { size_t k = 1; while (k * k < nf) ++k; return k; }
+    // ecfft_poly_compose_mod: out_b = f_b(g_b) mod h_b for `count` triples laid end to end (f: count x nf, g: count x ng, h: count x
+    // nm, out: count x d, d = nm - 1, zero-padded above its degree).  g is reduced below nm coefficients first (divrem_body).
+    //   d <= kComposeSmall: k_compose_small, Horner in one launch.
+    //   otherwise Brent-Kung on the kept-modulus products of poly_pow_mod, with k = ceil(sqrt(nf)), k' = ceil(nf / k):
+    //     keep_modulus(h, g) once, g the kept base;
+    //     baby steps B_t = g^t mod h, t = 0 .. k ((k + 1) x count x d): B_0 = 1, B_1 = g, B_(t+1) = one copy and one powmod_step
+    //       against the kept base; B_k is the giant step, so it is only taken when there is a second chunk;
+    //     C_i = sum_{t<k} f[i k + t] B_t for i < k' (k_compose_rows: k' x count x d);
+    //     giant steps: G = B_k lifted once and kept (count x N), res = C_(k'-1), then res = res G + C_i for i = k' - 2 .. 0.
+    //   (k - 1) + (k' - 1) modular products where Horner takes nf - 1; nf <= 2 runs none.
+    // Temporaries beyond a product's own: (k + 1 + k') count d + 4 count N elements (B and C; the three kept operands and G).
+    // Synchronous; *singular = some h_b[nm-1] == 0.  Caller holds lock() and checks the tree rule (powmod_leaves(nm), and
+    // divrem_leaves(ng, nm) when ng >= nm: independent of nf).
+    bool poly_compose_mod(const E* f, size_t nf, const E* g, size_t ng, const E* h, size_t nm, E* out, size_t count, bool* singular,
+                          hipStream_t s) {
+        int* flag = new_flag(s);
+        const size_t d = nm - 1, cd = count * d;
+        bool ok = true;
+        const E* gr = g;                                         // g below nm coefficients: count rows of lg at a stride of ldg
+        size_t ldg = ng, lg = ng;
+        if (ng >= nm) {
+            E* r = temp(cd);
+            ok = divrem_body(g, ng, h, nm, nullptr, r, count, flag, s) && ok;
+            gr = r; ldg = lg = d;
+        }
+        const E r1 = F::to_mont(F::one());
+        const TE rinv = F::to_table(rinv_);
+        if (d <= kComposeSmall) {
+            for_chunks(count, [&](size_t c0, size_t c) {
+                ECFFT_LAUNCH(KC_POINTWISE, sizeof(E) * (double)c * (double)(nf + lg + nm + d), (k_compose_small<F, (int)kComposeSmall>),
+                             dim3((unsigned)c), dim3((unsigned)kComposeSmall), 0, s, out + c0 * d, f + c0 * nf, (uint32_t)nf, gr + c0 * ldg, ldg,
+                             (uint32_t)lg, h + c0 * nm, (uint32_t)d, rinv, flag);
+            });
+            return finish_flagged(ok, flag, singular, s);
+        }
+        const size_t k = compose_chunk(nf), kp = (nf + k - 1) / k, N = powmod_leaves(nm);
+        E* kept = temp(3 * count * N);
+        KeptModulus km;
+        ok = keep_modulus(h, d, gr, lg, ldg, count, kept, flag, &km, s) && ok;
+        E* B = temp((k + 1) * cd); E* C = temp(kp * cd);
+        foreach_n(s, 2 * cd, [=] __device__(size_t i) {
+            const size_t w = i / cd, q = i - w * cd, b = q / d, j = q - b * d;
+            B[i] = w == 0 ? (j == 0 ? r1 : F::zero()) : (j < lg ? F::canon(gr[b * ldg + j]) : F::zero());
+        });
+        const size_t nb = kp > 1 ? k : k - 1;                    // the highest baby step anything reads
+        for (size_t t = 1; t < nb; ++t) {
+            ok = hipMemcpyAsync(B + (t + 1) * cd, B + t * cd, cd * sizeof(E), hipMemcpyDeviceToDevice, s) == hipSuccess && ok;
+            ok = powmod_step(B + (t + 1) * cd, km.base, km, count, rinv, s) && ok;
+        }
+        constexpr size_t TR = ComposeTile<F>::TR;
+        for_chunks(count, [&](size_t c0, size_t c) {
+            ECFFT_LAUNCH(KC_POINTWISE, sizeof(E) * (double)c * ((double)nf + (double)(k + kp) * (double)d), k_compose_rows<F>,
+                         dim3(nblocks(d), (unsigned)((kp + TR - 1) / TR), (unsigned)c), dim3(kBlock), 0, s, C + c0 * d, (const E*)B + c0 * d,
+                         f + c0 * nf, nf, k, kp, d, count, rinv);
+        });
+        ok = hipMemcpyAsync(out, C + (kp - 1) * cd, cd * sizeof(E), hipMemcpyDeviceToDevice, s) == hipSuccess && ok;
+        if (kp > 1) {
+            E* G = temp(count * N);
+            {
+                const TempMark mark = temps_mark();
+                const size_t hN = N / 2;
+                E* U = temp(count * hN); E* V = temp(count * hN); E* X = temp(count * hN);
+                PolyEvals<F> ev;
+                ok = lift_one(B + k * cd, d, d, false, 0, N, count, U, V, X, &ev, s) && ok;
+                materialise(ev, N, count, G, s);
+                temps_release(mark);
+            }
+            for (size_t i = kp - 1; i-- > 0;) {
+                ok = powmod_step(out, G, km, count, rinv, s) && ok;
+                const E* Ci = C + i * cd;
+                foreach_n(s, cd, [=] __device__(size_t q) { out[q] = F::canon(F::add(out[q], Ci[q])); });
+            }
+        }
+        return finish_flagged(ok, flag, singular, s);
+    }
+
 private:
     // poly_divrem without the read-back of the flag and the release of the temporaries, which stay with the caller: the one
     // division of this layer.  poly_mul_mod and poly_pow_mod reduce with it (q == nullptr); gcd_pair, gcd_half and roots_one_large

@@ -424,6 +424,37 @@ int run_poly_mul_mod(ecfft_ctx* c, DeviceChain<F>& ch, const void* a, size_t na,
     });
 }
 
+// ecfft_poly_compose_mod: synchronous like ecfft_poly_pow_mod, whose tree rule it shares (independent of nf)
+template <class F>
+int run_poly_compose_mod(ecfft_ctx* c, DeviceChain<F>& ch, const void* f, size_t nf, const void* g, size_t ng, const void* modulus, size_t nm,
+                         void* out, size_t count, int mem, void* stream) {
+    using E = typename F::elem;
+    const size_t lim = SIZE_MAX / (64 * sizeof(E));
+    if (nf > lim || ng > lim || nm > lim) return ECFFT_ERR_BAD_ARG;
+    static_assert(DeviceChain<F>::kComposeSmall + 1 == ECFFT_COMPOSE_SMALL_MAX, "the header states the small regime's bound");
+    const size_t d = nm - 1;
+    const size_t N = DeviceChain<F>::powmod_leaves(nm);                      // 1 for d <= kComposeSmall: Horner in one workgroup
+    if (N > 1 && N > ch.size()) return ECFFT_ERR_TREE_TOO_SMALL;
+    const size_t Nd = DeviceChain<F>::divrem_leaves(ng, nm);
+    if (Nd > ch.size()) return ECFFT_ERR_TREE_TOO_SMALL;
+    const size_t k = DeviceChain<F>::compose_chunk(nf), kp = (nf + k - 1) / k;
+    size_t per = N > Nd ? N : Nd;
+    if (per < ng + nm) per = ng + nm;
+    if (per < nf) per = nf;
+    if (N > 1) {                                                             // the baby-step table and the chunk sums
+        if (k + 1 + kp > SIZE_MAX / (16 * sizeof(E)) / d) return ECFFT_ERR_BAD_ARG;
+        if (per < (k + 1 + kp) * d) per = (k + 1 + kp) * d;
+    }
+    if (count > SIZE_MAX / (16 * per * sizeof(E))) return ECFFT_ERR_BAD_ARG; // byte counts of the temporaries must not wrap
+    const size_t eb = count * sizeof(E);
+    return staged(c, ch, mem, stream, {{f, nf * eb}, {g, ng * eb}, {modulus, nm * eb}}, {{out, d * eb}}, [&](auto dv, auto o) -> int {
+        bool singular = false;
+        if (!ch.poly_compose_mod((const E*)dv[0], nf, (const E*)dv[1], ng, (const E*)dv[2], nm, (E*)o[0], count, &singular, (hipStream_t)stream))
+            return ECFFT_ERR_HIP;
+        return singular ? ECFFT_ERR_BAD_ARG : ECFFT_OK;                      // a zero leading coefficient of the modulus in some triple
+    });
+}
+
 // ecfft_poly_gcd / ecfft_poly_xgcd: synchronous (the half-GCD reads degrees back at every node, and `degrees` is a host array
 // whatever `mem` is).  Nothing fails on the data.
 template <class F>
@@ -1043,6 +1074,11 @@ int ecfft_poly_mul_mod(ecfft_ctx* ctx, const void* a, size_t na, const void* b, 
                        size_t count, int mem, void* stream) {
     if (na == 0 || nb == 0 || nm < 2 || count == 0) return ECFFT_ERR_BAD_ARG;
     return on_chain(ctx, [&](auto& ch) { return run_poly_mul_mod(ctx, ch, a, na, b, nb, modulus, nm, out, count, mem, stream); });
+}
+int ecfft_poly_compose_mod(ecfft_ctx* ctx, const void* f, size_t nf, const void* g, size_t ng, const void* modulus, size_t nm, void* out,
+                           size_t count, int mem, void* stream) {
+    if (!f || !g || !modulus || !out || nf == 0 || ng == 0 || nm < 2 || count == 0) return ECFFT_ERR_BAD_ARG;
+    return on_chain(ctx, [&](auto& ch) { return run_poly_compose_mod(ctx, ch, f, nf, g, ng, modulus, nm, out, count, mem, stream); });
 }
 int ecfft_poly_gcd(ecfft_ctx* ctx, const void* a, size_t na, const void* b, size_t nb, void* g, int64_t* degrees, size_t count, int mem,
                    void* stream) {

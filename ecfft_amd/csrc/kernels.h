@@ -2381,6 +2381,121 @@ __global__ __launch_bounds__(K) void k_powmod_small(typename F::elem* __restrict
 }
 
 // ---------------------------------------------------------------------------------------------
+// ecfft_poly_compose_mod (no single reference counterpart: the composition of two residues, the Horner-like loop of
+// examples/schoofs.rs:197-235 and the step x^(p^i) -> x^(p^(i+1)) of distinct-degree factorisation, utils.rs:52-78).  Up to K
+// residue coefficients one workgroup runs the whole Horner scheme (k_compose_small); above that the host drives Brent-Kung baby
+// and giant steps on the kept-modulus products of poly_pow_mod, and k_compose_rows is the dense matrix product between them
+// (DESIGN.md 5.10).
+// ---------------------------------------------------------------------------------------------
+// f(g) mod h for residues of d <= K coefficients: one workgroup of K threads per triple, Horner in LDS: res = f[nf-1], then for
+// i = nf - 2 .. 0 res = res g mod h and res[0] += f[i]; nf is the only loop bound.  f: row b at f + b*nf; g: row b at g + b*ldg,
+// ng <= d coefficients; h: row b at h + b*(d+1); out: count x d.  The product is k_powmod_small's, written out as a sibling (as
+// roots_pow_scan is) so that the kernels that were there keep their code: h made monic by one Fermat inversion (a zero leading
+// coefficient stores 1 to *flag) and kept as PLAIN residues, the left operand brought to plain form by one table multiply by R^-1,
+// thread t summing coefficients t and t + d of the schoolbook product, then d - 1 elimination steps.
+template <class F, int K>
+__global__ __launch_bounds__(K) void k_compose_small(typename F::elem* __restrict__ out, const typename F::elem* __restrict__ f, uint32_t nf,
+                                                     const typename F::elem* __restrict__ g, size_t ldg, uint32_t ng,
+                                                     const typename F::elem* __restrict__ h, uint32_t d, typename F::telem rinv,
+                                                     int* __restrict__ flag) {
+    using E = typename F::elem;
+    __shared__ E sres[K], sg[K], smod[K], sx[K], sprod[2 * K];
+    const uint32_t t = threadIdx.x;
+    const size_t b = blockIdx.x;
+    const E* hb = h + b * ((size_t)d + 1);
+    const E* fb = f + b * (size_t)nf;
+    if (t == 0) {
+        const E lead = F::canon(hb[d]);
+        if (F::is_zero(lead)) *flag = 1;
+        sx[0] = F::canon(F::inv(lead));                  // inv(0) = 0: a flagged triple computes on a zero modulus, its row is not used
+    }
+    __syncthreads();
+    const E linv = sx[0];
+    __syncthreads();
+    smod[t] = t < d ? F::canon(F::mul(hb[t], linv)) : F::zero();
+    sg[t] = t < ng ? F::canon(g[b * ldg + t]) : F::zero();
+    {
+        E v = F::zero();
+        if (t == 0) v = F::canon(fb[nf - 1]);
+        sres[t] = v;
+    }
+    __syncthreads();
+    for (uint32_t i = nf - 1; i-- > 0;) {
+        E x = sres[t];
+        if constexpr (sizeof(E) == 32) x = F::tmul(rinv, x);
+        sx[t] = F::canon(x);
+        __syncthreads();
+        if (t < d) {
+            E acc = F::zero(), lo = F::zero();
+            for (uint32_t k = 0; k < d; ++k) {
+                if (k == t + 1) { lo = acc; acc = F::zero(); }
+                const uint32_t j = k <= t ? t - k : t + d - k;
+                acc = F::canon(F::mul_add(sx[k], sg[j], acc));
+            }
+            if (t + 1 == d) { lo = acc; acc = F::zero(); }              // the last thread never switched: coefficient 2d - 1 does not exist
+            sprod[t] = lo;
+            sprod[t + d] = acc;
+        }
+        __syncthreads();
+        for (uint32_t k = 2 * d - 2; k >= d; --k) {
+            if (t < d) sprod[k - d + t] = F::canon(F::sub(sprod[k - d + t], F::canon(F::mul(sprod[k], smod[t]))));
+            __syncthreads();
+        }
+        if (t < d) {
+            E v = sprod[t];
+            if (t == 0) v = F::canon(F::add(v, F::canon(fb[i])));
+            sres[t] = v;
+        }
+        __syncthreads();
+    }
+    if (t < d) out[b * d + t] = sres[t];
+}
+// The matrix product between the baby and the giant steps: C[i][b][j] = R^-1 sum_{t < k} f_b[i k + t] B[t][b][j] for i < kp, j < d
+// (B: (k + 1) x count x d, the powers g^t mod h; C: kp x count x d; f: row b at f + b*nf; a term with i k + t >= nf is absent).
+// Both factors are crate form, so the plain sum carries R^2 and one table multiply by R^-1 per output restores crate form (M31:
+// R = 1).  A thread owns column j and TR rows i; the f-coefficients of the tile go through LDS TC columns of t at a time, so the
+// inner loop is one coalesced load of B[t][b][j], reused by every row of the tile, and one F::mul_add per row.  Grid: (column
+// blocks, row tiles, count).
+template <class F> struct ComposeTile { static constexpr int TR = sizeof(typename F::elem) == 4 ? 8 : 4, TC = 32; };
+template <class F>
+__global__ __launch_bounds__(kBlock) void k_compose_rows(typename F::elem* __restrict__ C, const typename F::elem* __restrict__ B,
+                                                         const typename F::elem* __restrict__ f, size_t nf, size_t k, size_t kp,
+                                                         size_t d, size_t count, typename F::telem rinv) {
+    using E = typename F::elem;
+    constexpr int TR = ComposeTile<F>::TR, TC = ComposeTile<F>::TC;
+    static_assert(TR * TC <= (int)kBlock, "one thread stages one coefficient");
+    __shared__ E sf[TR * TC];
+    const size_t j = (size_t)blockIdx.x * kBlock + threadIdx.x, i0 = (size_t)blockIdx.y * TR, b = blockIdx.z;
+    const E* fb = f + b * nf;
+    E acc[TR];
+#pragma unroll
+    for (int r = 0; r < TR; ++r) acc[r] = F::zero();
+    for (size_t t0 = 0; t0 < k; t0 += TC) {
+        if (threadIdx.x < (unsigned)(TR * TC)) {
+            const size_t r = threadIdx.x / TC, t = t0 + threadIdx.x % TC, idx = (i0 + r) * k + t;
+            sf[threadIdx.x] = (t < k && i0 + r < kp && idx < nf) ? F::canon(fb[idx]) : F::zero();
+        }
+        __syncthreads();
+        if (j < d) {
+            const size_t tn = k - t0 < (size_t)TC ? k - t0 : (size_t)TC;
+            for (size_t tt = 0; tt < tn; ++tt) {
+                const E bv = B[((t0 + tt) * count + b) * d + j];
+#pragma unroll
+                for (int r = 0; r < TR; ++r) acc[r] = F::canon(F::mul_add(sf[r * TC + tt], bv, acc[r]));
+            }
+        }
+        __syncthreads();
+    }
+    if (j >= d) return;
+#pragma unroll
+    for (int r = 0; r < TR; ++r) {
+        E v = acc[r];
+        if constexpr (sizeof(E) == 32) v = F::tmul(rinv, v);
+        if (i0 + r < kp) C[((i0 + r) * count + b) * d + j] = F::canon(v);
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
 // ecfft_poly_gcd / ecfft_poly_xgcd (utils::gcd / utils::xgcd, src/utils.rs:132-182: one schoolbook div_rem per remainder on the
 // CPU).  Up to G coefficients the whole remainder sequence of a pair runs in one workgroup (k_gcd_small); above that the host
 // drives a half-GCD on the poly_mul and division bodies whose recursion ends in the same kernel.

@@ -34,11 +34,14 @@ EXPORTS = ["ecfft_elem_size", "ecfft_build_fftree", "ecfft_fftree_new", "ecfft_c
            "ecfft_fftree_serialize", "ecfft_fftree_deserialize", "ecfft_tree_rational_maps", "ecfft_ctx_trim", "ecfft_comm_abort", "ecfft_comm_set_rccl_library", "ecfft_comm_set_link_striping",
            "ecfft_poly_mul", "ecfft_poly_inv_series", "ecfft_poly_divrem", "ecfft_poly_eval_points", "ecfft_poly_interpolate",
            "ecfft_poly_pow_mod", "ecfft_poly_mul_mod", "ecfft_poly_gcd", "ecfft_poly_xgcd", "ecfft_poly_find_roots",
+           "ecfft_poly_compose_mod",
            "ecfft_find_curve_candidate", "ecfft_curve_two_sylow", "ecfft_find_curve", "ecfft_build_fftree_on_curve"]
 # include/ecfft_hip.h ECFFT_GCD_SMALL_MAX: max(na, nb) up to which a gcd runs in one workgroup per pair, on any tree
 GCD_SMALL_MAX = 256
 # include/ecfft_hip.h ECFFT_ROOTS_SMALL_MAX: nf up to which poly_find_roots finishes a polynomial in one workgroup, on any tree
 ROOTS_SMALL_MAX = 65
+# include/ecfft_hip.h ECFFT_COMPOSE_SMALL_MAX: nm up to which poly_compose_mod runs Horner for a triple in one workgroup, on any tree
+COMPOSE_SMALL_MAX = 65
 
 # include/ecfft_hip_hooks.h: only in a build with -DECFFT_TEST_HOOKS (tests/hooks/libecfft_hip_hooks.so), never in the shipped library
 HOOK_EXPORTS = ['ecfft_selftest_field', 'ecfft_selfcheck_pointwise_z', 'ecfft_test_fail_next_collective', 'ecfft_selftest_blk16', 'ecfft_selftest_blk16_small', 'ecfft_test_fail_build_rank', 'ecfft_comm_init_projection', 'ecfft_selftest_blk32', 'ecfft_ctx_low_map', 'ecfft_curve_search_stats']
@@ -79,6 +82,7 @@ def _bind(L):
     L.ecfft_poly_interpolate.restype, L.ecfft_poly_interpolate.argtypes = ci, [vp, vp, sz, vp, vp, sz, ci, vp]
     L.ecfft_poly_pow_mod.restype, L.ecfft_poly_pow_mod.argtypes = ci, [vp, vp, sz, vp, sz, vp, sz, vp, sz, ci, vp]
     L.ecfft_poly_mul_mod.restype, L.ecfft_poly_mul_mod.argtypes = ci, [vp, vp, sz, vp, sz, vp, sz, vp, sz, ci, vp]
+    L.ecfft_poly_compose_mod.restype, L.ecfft_poly_compose_mod.argtypes = ci, [vp, vp, sz, vp, sz, vp, sz, vp, sz, ci, vp]
     L.ecfft_poly_gcd.restype, L.ecfft_poly_gcd.argtypes = ci, [vp, vp, sz, vp, sz, vp, vp, sz, ci, vp]
     L.ecfft_poly_xgcd.restype, L.ecfft_poly_xgcd.argtypes = ci, [vp, vp, sz, vp, sz, vp, vp, vp, vp, sz, ci, vp]
     L.ecfft_poly_find_roots.restype, L.ecfft_poly_find_roots.argtypes = ci, [vp, vp, sz, vp, vp, sz, ci, vp]
@@ -593,6 +597,27 @@ class FFTree:
         rc = self._L.ecfft_poly_mul_mod(self._h, pa, na, pb, nb, pm, nm, self._ptr(out) if out.shape[0] else None, count, mem, stream)
         if rc == ERR_BAD_ARG:
             raise ValueError("poly_mul_mod: empty operand, a modulus of fewer than 2 coefficients, a zero leading coefficient of the "
+                             "modulus, count = 0 or a context that holds no full tree")
+        _check(rc)
+        return out
+
+    def poly_compose_mod(self, f, g, modulus, count=1):
+        """f(g) mod modulus (ecfft_poly_compose_mod; the step x^(p^i) -> x^(p^(i+1)) of distinct-degree factorisation, src/utils.rs:52-78,
+        and the product of two endomorphisms in examples/schoofs.rs:197-235): `count` triples laid end to end, f of count * nf (it may
+        be longer than the modulus), g of count * ng and modulus of count * nm coefficients, the modulus' leading coefficient nonzero
+        in every triple.  Returns count * (nm - 1) coefficients, zero-padded above the degree.  nm <= COMPOSE_SMALL_MAX works on any
+        tree (Horner in one workgroup per triple); a longer modulus needs a tree of next_pow2(2 (nm - 1) - 1) leaves, whatever nf is,
+        and runs about 2 sqrt(nf) modular products (Brent-Kung baby and giant steps) instead of nf - 1; ng >= nm also needs what
+        poly_divrem(ng, nm) needs.  numpy arrays (host) or contiguous CUDA tensors (device, on the current stream), all of the same
+        kind.  Synchronous."""
+        xs, ptrs, new, mem, stream = self._poly_io([f, modulus] if f is g else [f, g, modulus])
+        (f, g, modulus), (pf, pg, pm) = ((xs[0], xs[0], xs[1]), (ptrs[0], ptrs[0], ptrs[1])) if f is g else (xs, ptrs)
+        assert count > 0 and f.shape[0] % count == 0 and g.shape[0] % count == 0 and modulus.shape[0] % count == 0
+        nf, ng, nm = f.shape[0] // count, g.shape[0] // count, modulus.shape[0] // count
+        out = new(count * max(nm - 1, 0))
+        rc = self._L.ecfft_poly_compose_mod(self._h, pf, nf, pg, ng, pm, nm, self._ptr(out) if out.shape[0] else None, count, mem, stream)
+        if rc == ERR_BAD_ARG:
+            raise ValueError("poly_compose_mod: empty operand, a modulus of fewer than 2 coefficients, a zero leading coefficient of the "
                              "modulus, count = 0 or a context that holds no full tree")
         _check(rc)
         return out

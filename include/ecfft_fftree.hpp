@@ -239,6 +239,16 @@ public:
         check(ecfft_poly_mul_mod(ctx_, a.data(), a.size(), b.data(), b.size(), modulus.data(), modulus.size(), out.data(), 1, ECFFT_MEM_HOST, nullptr));
         return out;
     }
+    // f(g) mod modulus (ecfft_poly_compose_mod; the step of distinct-degree factorisation, src/utils.rs:52-78, and the product of two
+    // endomorphisms in examples/schoofs.rs:197-235): modulus.size() - 1 coefficients (zero-padded); f may be longer than the modulus;
+    // modulus.size() >= 2, modulus.back() != 0 (else std::runtime_error).  Up to ECFFT_COMPOSE_SMALL_MAX modulus coefficients on any
+    // tree; above that about 2 sqrt(f.size()) modular products on the tree rule of pow_mod (ecfft_hip.h).  Synchronous.
+    std::vector<Elem> compose_mod(const std::vector<Elem>& f, const std::vector<Elem>& g, const std::vector<Elem>& modulus) const {
+        require(!f.empty() && !g.empty() && modulus.size() >= 2, "compose_mod: operands must not be empty and the modulus needs at least 2 coefficients");
+        std::vector<Elem> out(modulus.size() - 1);
+        check(ecfft_poly_compose_mod(ctx_, f.data(), f.size(), g.data(), g.size(), modulus.data(), modulus.size(), out.data(), 1, ECFFT_MEM_HOST, nullptr));
+        return out;
+    }
     // the monic gcd (ecfft_poly_gcd <-> utils::gcd, src/utils.rs:132-141), trimmed to its degree (empty for a = b = 0); the operands
     // need not be trimmed and either may be zero; gcd(0, b) = b / lc(b) as utils::xgcd has it.  Up to ECFFT_GCD_SMALL_MAX coefficients
     // on any tree; tree rule in ecfft_hip.h.  Synchronous.
@@ -307,6 +317,11 @@ public:
     void pow_mod_device(const Elem* a, size_t na, const uint8_t* exp, size_t exp_bytes, const Elem* modulus, size_t nm, Elem* out, size_t count,
                         void* stream) const {
         check(ecfft_poly_pow_mod(ctx_, a, na, exp, exp_bytes, modulus, nm, out, count, ECFFT_MEM_DEVICE, stream));
+    }
+    // count triples: f count x nf, g count x ng, modulus count x nm, out count x (nm - 1).  Synchronous.
+    void compose_mod_device(const Elem* f, size_t nf, const Elem* g, size_t ng, const Elem* modulus, size_t nm, Elem* out, size_t count,
+                            void* stream) const {
+        check(ecfft_poly_compose_mod(ctx_, f, nf, g, ng, modulus, nm, out, count, ECFFT_MEM_DEVICE, stream));
     }
     // count pairs: a count x na, b count x nb (untrimmed), g count x max(na, nb); degrees: count HOST entries or null.  Synchronous.
     void gcd_device(const Elem* a, size_t na, const Elem* b, size_t nb, Elem* g, int64_t* degrees, size_t count, void* stream) const {

@@ -185,6 +185,32 @@ int ecfft_poly_pow_mod(ecfft_ctx* ctx, const void* a, size_t na, const void* exp
 int ecfft_poly_mul_mod(ecfft_ctx* ctx, const void* a, size_t na, const void* b, size_t nb, const void* modulus, size_t nm, void* out,
                        size_t count, int mem, void* stream);
 
+/* Modular composition of polynomials: out_b = f_b(g_b) mod modulus_b.
+ *   ecfft_poly_compose_mod <-> the step of distinct-degree factorisation, x^(p^(i+1)) = x^(p^i) composed with x^p mod f
+ *                              (src/utils.rs:52-78), and Endomorphism * Endomorphism of examples/schoofs.rs:197-235
+ * Layout: `count` triples laid end to end: f is count x nf (nf >= 1, possibly longer than the modulus), g is count x ng (ng >= 1),
+ * modulus is count x nm (nm >= 2) with modulus[nm-1] != 0 in every triple; out is count x (nm - 1) coefficients, zero-padded
+ * above the true degree, fully reduced, in the crate's form.  out must not overlap the inputs.  g of at least nm coefficients is
+ * reduced first (the division of ecfft_poly_divrem).
+ * ECFFT_COMPOSE_SMALL_MAX: nm up to which one workgroup runs Horner's scheme for a triple in LDS (nf - 1 schoolbook products; one
+ * launch for all triples, no transform).
+ * Above it, with d = nm - 1, k = ceil(sqrt(nf)) and k' = ceil(nf / k) (Brent-Kung): the reciprocal of the reversed modulus, the
+ * modulus and g are kept as evaluations on N = next_pow2(2d - 1) leaves as in ecfft_poly_pow_mod; the baby steps g^t mod modulus,
+ * t = 0 .. k, take k - 1 of its modular products; the k' chunk sums C_i = sum_t f[i k + t] g^t are one dense field matrix product of
+ * nf d multiply-adds; the giant steps res = res g^k + C_i take k' - 1 products against the kept evaluations of g^k.  That is
+ * (k - 1) + (k' - 1) modular products where Horner on ecfft_poly_mul_mod takes nf - 1; nf <= 2 runs none.
+ * Memory: (k + 1 + k') count d + 4 count N elements of pooled temporaries beyond those of one modular product.
+ * Tree: the rule of ecfft_poly_pow_mod, independent of nf: nm <= ECFFT_COMPOSE_SMALL_MAX needs no transform for the composition
+ * itself; otherwise next_pow2(2d - 1) leaves.  If ng >= nm, also what ecfft_poly_divrem(ng, nm) needs.  Else
+ * ECFFT_ERR_TREE_TOO_SMALL, checked before anything runs.
+ * ECFFT_ERR_BAD_ARG: a NULL input or output, nf, ng or count 0, nm < 2, a context that holds no full tree, a byte count that would
+ * wrap — and a zero leading coefficient of the modulus in any triple, which is checked on the device.  Because of that check the
+ * call is SYNCHRONOUS (like ecfft_poly_pow_mod); the context keeps working after the error.  Memory, stream and threading as for
+ * ecfft_poly_mul; temporaries are pooled (ecfft_ctx_trim). */
+#define ECFFT_COMPOSE_SMALL_MAX 65   /* nm up to which a row is finished in one workgroup, on any tree */
+int ecfft_poly_compose_mod(ecfft_ctx* ctx, const void* f, size_t nf, const void* g, size_t ng, const void* modulus, size_t nm, void* out,
+                           size_t count, int mem, void* stream);
+
 /* Greatest common divisors of polynomials.
  *   ecfft_poly_gcd   <-> ecfft::utils::gcd(a, b)                                    src/utils.rs:132-141
  *   ecfft_poly_xgcd  <-> ecfft::utils::xgcd(a, b) -> (s, t, gcd), a s + b t = gcd    src/utils.rs:147-182
