@@ -1688,15 +1688,11 @@ public:
         int* flag = new_flag(s);
         const size_t d = nm - 1;
         bool ok = true;
-        const E* ar = a;                                         // the base below nm coefficients: count rows of la at a stride of lda
-        size_t lda = na, la = na;
-        if (na >= nm) {
-            E* r = temp(count * d);
-            ok = divrem_body(a, na, f, nm, nullptr, r, count, flag, s) && ok;
-            ar = r; lda = la = d;
-        }
-        const E r1 = F::to_mont(F::one());
-        const TE rinv = F::to_table(rinv_);
+        const RowsRef base = reduced_below(a, na, f, nm, count, flag, &ok, s);           // the base below nm coefficients
+        const E* ar = base.p;
+        const size_t lda = base.ld, la = base.len;
+        const E r1 = crate_one();
+        const TE rinv = rinv_table();
         if (d <= kPowSmall) {
             const size_t nbytes = (nbits + 7) / 8;
             uint8_t* dexp = temp_as<uint8_t>(nbytes);
@@ -1742,15 +1738,11 @@ public:
         int* flag = new_flag(s);
         const size_t d = nm - 1, cd = count * d;
         bool ok = true;
-        const E* gr = g;                                         // g below nm coefficients: count rows of lg at a stride of ldg
-        size_t ldg = ng, lg = ng;
-        if (ng >= nm) {
-            E* r = temp(cd);
-            ok = divrem_body(g, ng, h, nm, nullptr, r, count, flag, s) && ok;
-            gr = r; ldg = lg = d;
-        }
-        const E r1 = F::to_mont(F::one());
-        const TE rinv = F::to_table(rinv_);
+        const RowsRef gred = reduced_below(g, ng, h, nm, count, flag, &ok, s);           // g below nm coefficients
+        const E* gr = gred.p;
+        const size_t ldg = gred.ld, lg = gred.len;
+        const E r1 = crate_one();
+        const TE rinv = rinv_table();
         if (d <= kComposeSmall) {
             for_chunks(count, [&](size_t c0, size_t c) {
                 ECFFT_LAUNCH(KC_POINTWISE, sizeof(E) * (double)c * (double)(nf + lg + nm + d), (k_compose_small<F, (int)kComposeSmall>),
@@ -1782,15 +1774,7 @@ public:
         ok = hipMemcpyAsync(out, C + (kp - 1) * cd, cd * sizeof(E), hipMemcpyDeviceToDevice, s) == hipSuccess && ok;
         if (kp > 1) {
             E* G = temp(count * N);
-            {
-                const TempMark mark = temps_mark();
-                const size_t hN = N / 2;
-                E* U = temp(count * hN); E* V = temp(count * hN); E* X = temp(count * hN);
-                PolyEvals<F> ev;
-                ok = lift_one(B + k * cd, d, d, false, 0, N, count, U, V, X, &ev, s) && ok;
-                materialise(ev, N, count, G, s);
-                temps_release(mark);
-            }
+            ok = lift_and_keep(B + k * cd, d, N, count, G, s) && ok;
             for (size_t i = kp - 1; i-- > 0;) {
                 ok = powmod_step(out, G, km, count, rinv, s) && ok;
                 const E* Ci = C + i * cd;
@@ -1834,6 +1818,27 @@ private:
         }
         return ok;
     }
+    // An operand of a modular power or composition below the modulus: a itself, or a mod f in a temporary when na >= nm
+    // (divrem_body).  Returns count rows as (pointer, row stride, length).
+    struct RowsRef { const E* p; size_t ld, len; };
+    RowsRef reduced_below(const E* a, size_t na, const E* f, size_t nm, size_t count, int* flag, bool* ok, hipStream_t s) {
+        if (na < nm) return {a, na, na};
+        E* r = temp(count * (nm - 1));
+        *ok = divrem_body(a, na, f, nm, nullptr, r, count, flag, s) && *ok;
+        return {r, nm - 1, nm - 1};
+    }
+    // rows x d coefficients lifted to T_N and written to dst (rows x N) in the natural leaf order EXIT reads; the work goes back
+    // to the pool
+    bool lift_and_keep(const E* src, size_t d, size_t N, size_t rows, E* dst, hipStream_t s) {
+        const TempMark mark = temps_mark();
+        const size_t h = N / 2;
+        E* U = temp(rows * h); E* V = temp(rows * h); E* X = temp(rows * h);
+        PolyEvals<F> ev;
+        const bool ok = lift_one(src, d, d, false, 0, N, rows, U, V, X, &ev, s);
+        materialise(ev, N, rows, dst, s);
+        temps_release(mark);
+        return ok;
+    }
     // What the large regime of a modular power keeps for the call: the evaluations on T_N, N = powmod_leaves(d + 1), in the natural
     // leaf order EXIT reads, of g = 1/rev(f) mod x^(d-1), f mod x^d and, where there is one, the base (count x N each)
     struct KeptModulus { const E* g; const E* f; const E* base; size_t d, N; };
@@ -1841,7 +1846,7 @@ private:
     // inv_series_body, then g | f mod x^d [| base] stacked and lifted in ONE pass and written into `kept` (3 count N elements, 2 count
     // N without a base), which the caller takes before its own later temporaries; everything taken here goes back to the pool.
     bool keep_modulus(const E* f, size_t d, const E* base, size_t lb, size_t ldb, size_t count, E* kept, int* flag, KeptModulus* km, hipStream_t s) {
-        const size_t nm = d + 1, ng = d - 1, cd = count * d, rows = base ? 3 : 2, N = powmod_leaves(nm), h = N / 2;
+        const size_t nm = d + 1, ng = d - 1, cd = count * d, rows = base ? 3 : 2, N = powmod_leaves(nm);
         const TempMark mark = temps_mark();
         E* fr = temp(count * ng); E* g = temp(count * ng); E* S = temp(rows * cd);
         foreach_n(s, count * ng, [=] __device__(size_t i) { const size_t b = i / ng, j = i - b * ng; fr[i] = f[b * nm + d - j]; });
@@ -1850,10 +1855,7 @@ private:
             const size_t w = i / cd, k = i - w * cd, b = k / d, j = k - b * d;
             S[i] = w == 0 ? (j < ng ? g[b * ng + j] : F::zero()) : w == 1 ? f[b * nm + j] : (j < lb ? base[b * ldb + j] : F::zero());
         });
-        E* U = temp(rows * count * h); E* V = temp(rows * count * h); E* X = temp(rows * count * h);
-        PolyEvals<F> ev;
-        ok = lift_one(S, d, d, false, 0, N, rows * count, U, V, X, &ev, s) && ok;
-        materialise(ev, N, rows * count, kept, s);
+        ok = lift_and_keep(S, d, N, rows * count, kept, s) && ok;
         temps_release(mark);
         *km = KeptModulus{kept, kept + count * N, base ? kept + 2 * count * N : nullptr, d, N};
         return ok;
@@ -1942,7 +1944,7 @@ public:
     // Synchronous (degrees are read back per half-GCD node).  Caller holds lock() and checks the tree rule (gcd_leaves).
     bool poly_gcd(const E* a, size_t na, const E* b, size_t nb, E* so, E* to, E* g, long long* degrees, size_t count, bool want_cof, hipStream_t s) {
         const size_t ng = na > nb ? na : nb, ns = nb > 1 ? nb - 1 : 1, nt = na > 1 ? na - 1 : 1;
-        const E r1 = F::to_mont(F::one());
+        const E r1 = crate_one();
         bool ok = true;
         std::vector<long long> hdeg(count, -1);
         if (ng <= kGcdSmall) {
@@ -2020,7 +2022,7 @@ private:
     // the identity written out (rows 1, 0, 0, 1 in crate form)
     void gcd_mat_materialise(GcdMat& M, hipStream_t s) {
         if (!M.ident) return;
-        E* p = M.p; const size_t ld = M.ld; const E r1 = F::to_mont(F::one());
+        E* p = M.p; const size_t ld = M.ld; const E r1 = crate_one();
         foreach_n(s, 4 * ld, [=] __device__(size_t i) { E v = F::zero(); if (i == 0 || i == 3 * ld) v = r1; p[i] = v; });
         M.ident = false; M.len = 1;
     }
@@ -2092,7 +2094,7 @@ private:
             int32_t* info = temp_as<int32_t>(8);
             gcd_small_one(la, sizeof(E) * (double)(la + lb + 4 * la), s,
                           a, la, (uint32_t)la, b, lb, (uint32_t)lb, (int32_t)m, 1u, 1u, (E*)nullptr, 0u, (E*)nullptr, 0u, (E*)nullptr, 0u,
-                          (long long*)nullptr, out.p, out.ld, (uint32_t)la, info, F::to_mont(F::one()));
+                          (long long*)nullptr, out.p, out.ld, (uint32_t)la, info, crate_one());
             int32_t h[8];
             if (hipMemcpyAsync(h, info, sizeof(h), hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) return false;
             out.ident = h[4] == 0;
@@ -2146,7 +2148,7 @@ private:
         if (want_cof) for (auto& M : acc) { M.ld = W; M.p = temp(4 * W); }
         int wi = 0, mi = 0;
         bool ok = true;
-        const E r1 = F::to_mont(F::one());
+        const E r1 = crate_one();
         while (ok && lb > 0 && la > kGcdLeaf) {
             const TempMark lvl = temps_mark();
             if (la > lb) {
@@ -2229,8 +2231,8 @@ private:
     bool roots_pow_body(const E* f, size_t d, uint32_t c, const uint8_t* exp, size_t nbits, E* out, size_t count, int* flag, hipStream_t s) {
         static_assert(kRootsSmall >= kPowSmall, "d > kRootsSmall is the large regime of powmod_leaves");
         const size_t nm = d + 1;
-        const E r1 = F::to_mont(F::one());
-        const TE rinv = F::to_table(rinv_);
+        const E r1 = crate_one();
+        const TE rinv = rinv_table();
         E* kept = temp(2 * count * powmod_leaves(nm));
         E* next = temp(count * d);
         KeptModulus km;
@@ -2278,8 +2280,8 @@ private:
     // one launch of k_roots_small over nblk rows or descriptors
     void roots_small_launch(const RootsCall& rc, const E* in, size_t ldin, size_t nin, E* out, size_t ldout, const uint32_t* desc, long long* n_out,
                             bool frob, uint32_t c0, size_t nblk, double coeffs, hipStream_t s) {
-        const E r1 = F::to_mont(F::one());
-        const TE rinv = F::to_table(rinv_);
+        const E r1 = crate_one();
+        const TE rinv = rinv_table();
         for_chunks(nblk, [&](size_t b0, size_t nb) {
             ECFFT_LAUNCH(KC_POINTWISE, sizeof(E) * coeffs * (double)nb / (double)nblk + 64.0, (k_roots_small<F, (int)kRootsSmall>), dim3((unsigned)nb),
                          dim3((unsigned)kRootsSmall), 0, s, desc ? in : in + b0 * ldin, ldin, (uint32_t)nin, desc ? out : out + b0 * ldout, ldout,
@@ -2292,7 +2294,7 @@ private:
         for (size_t r0 = 0; r0 < rows; r0 += 32768) {
             const size_t nr = rows - r0 < 32768 ? rows - r0 : 32768;
             ECFFT_LAUNCH(KC_POINTWISE, sizeof(E) * 2.0 * (double)nr * (double)ldd, k_roots_rank<F>, dim3(nblocks(ldd), (unsigned)nr), dim3(kBlock), 0, s,
-                         dst + r0 * ldd, ldd, src + r0 * lds, lds, n_dev ? n_dev + r0 : (const long long*)nullptr, n_fixed, F::to_table(rinv_));
+                         dst + r0 * ldd, ldd, src + r0 * lds, lds, n_dev ? n_dev + r0 : (const long long*)nullptr, n_fixed, rinv_table());
         }
     }
     // The roots of ONE polynomial of nf > kRootsSmall + 1 coefficients (untrimmed, crate form) into roots (nf - 1, sorted, zero-padded).
@@ -2302,7 +2304,7 @@ private:
     //   v = h / u (divrem_body).  Factors of degree <= kRootsSmall go to the leaf buffer, finished by ONE launch of k_roots_small.
     bool roots_one_large(const RootsCall& rc, const E* f, size_t nf, E* roots, long long* n, hipStream_t s) {
         const size_t K = kRootsSmall;
-        const E r1 = F::to_mont(F::one());
+        const E r1 = crate_one();
         *n = 0;
         size_t la = 0;
         if (!gcd_row_lens(f, nf, nf, 1, &la, s)) return false;
@@ -2469,7 +2471,7 @@ public:
         bool ok = lift_operands(src, len, ld, nops, N, count, ev, Y, s);
         const size_t total = count * N;
         ECFFT_LAUNCH(KC_POINTWISE, sizeof(E) * (nops + 1.0) * (double)total, k_poly_pointwise<F>, dim3(nblocks(total)), dim3(kBlock), 0, s,
-                     Y, ev[0], ev[1], F::to_table(rinv_), ilog2(N), total);
+                     Y, ev[0], ev[1], rinv_table(), ilog2(N), total);
         return exit_rows(Y, out, nc, N, count, ok, s);
     }
     // EXIT_N of count rows of Y, keeping the first nc coefficients of each (the others are zero) in out (count x nc)
@@ -2483,7 +2485,7 @@ public:
     }
     // k_series_base on count rows (grid chunks of at most 2^16 pairs)
     void series_base(const E* f, size_t ldf, size_t nf, E* out, size_t ldo, size_t p0, size_t count, int* flag, hipStream_t s) {
-        const E r1 = F::to_mont(F::one());
+        const E r1 = crate_one();
         for_chunks(count, [&](size_t c0, size_t c) {
             ECFFT_LAUNCH(KC_POINTWISE, sizeof(E) * 2.0 * (double)(c * p0), (k_series_base<F, (int)kSeriesBase>), dim3((unsigned)c),
                          dim3((unsigned)kSeriesBase), 0, s, out + c0 * ldo, ldo, f + c0 * ldf, ldf, nf, (uint32_t)p0, rinv_, r1, flag);
@@ -2516,7 +2518,7 @@ public:
         PolyEvals<F> ev[2];
         E* Y = nullptr;
         bool ok = lift_operands(src, len, ld, 2, N, count, ev, Y, s);
-        const E R = F::to_mont(F::one()), r2 = F::mul(R, R);
+        const E R = crate_one(), r2 = F::mul(R, R);
         const size_t total = count * N;
         ECFFT_LAUNCH(KC_POINTWISE, sizeof(E) * 3.0 * (double)total, k_newton_pointwise<F>, dim3(nblocks(total)), dim3(kBlock), 0, s,
                      Y, ev[0], ev[1], F::add(r2, r2), F::to_table(F::mul(rinv_, rinv_)), ilog2(N), total);
@@ -2611,7 +2613,7 @@ public:
         const size_t rows = count * (P / B);
         ECFFT_LAUNCH(KC_POINTWISE, sizeof(E) * ((double)rows * nc + (double)count * m + (double)m), (k_eval_leaves<F, (int)kEvalLeaf>),
                      dim3(nblocks(rows * B)), dim3(kBlock), 0, s, out, rem, ld_poly, ld_row, (uint32_t)nc, points, m, P / B, rows,
-                     F::to_table(rinv_));
+                     rinv_table());
         temps_done();
         return ok && hipGetLastError() == hipSuccess;
     }
@@ -2664,7 +2666,7 @@ public:
     bool remainder_descent(const E* f, size_t nf, const SubproductTree& st, size_t count, E* rem, hipStream_t s) {
         const size_t P = st.npts;
         E* A = temp(count * P); E* C = temp(count * P); E* t = temp(count * P / 2); E* q = temp(count * P); E* Y = temp(2 * count * P);
-        const TE rinv = F::to_table(rinv_);
+        const TE rinv = rinv_table();
         const E* par = f;
         size_t ldb = nf, ldr = 0, plen = nf;                     // parent row (b, p) at par + b*ldb + p*ldr, plen coefficients
         bool ok = true;
@@ -2726,7 +2728,7 @@ public:
     // denominator is read back: *repeated = two equal points).  Caller holds lock() and checks the tree rule (P <= size() if P > B).
     bool poly_interpolate(const E* points, size_t m, const E* values, E* out, size_t count, bool* repeated, hipStream_t s) {
         const size_t B = kEvalLeaf, P = eval_group(m), k = P - m, rpv = P / B, rows = count * rpv;
-        const TE rinv = F::to_table(rinv_);
+        const TE rinv = rinv_table();
         int* flag = new_flag(s);
         bool ok = true;
         SubproductTree st;
@@ -2787,7 +2789,7 @@ public:
         E* Mc = temp(2 * P); E* AB = temp(P); E* dM = temp(m); E* rem = temp(P);
         bool ok = exit(st.lv.back().Mh, Mc, P, 2, s);
         ok = poly_mul_body(Mc, h, P, Mc + P, h, P, AB, 1, s) && ok;              // P - 1 coefficients
-        const E r1 = F::to_mont(F::one());
+        const E r1 = crate_one();
         foreach_n(s, m, [=] __device__(size_t j) {
             const size_t c = k + j + 1;                                          // coefficient of Mp
             E v = r1;
@@ -2799,7 +2801,7 @@ public:
         });
         ok = remainder_descent(dM, m, st, 1, rem, s) && ok;
         ECFFT_LAUNCH(KC_POINTWISE, sizeof(E) * ((double)P + 2.0 * (double)m), (k_eval_leaves<F, (int)kEvalLeaf>), dim3(nblocks(P)),
-                     dim3(kBlock), 0, s, w, (const E*)rem, P, B, (uint32_t)B, points, m, P / B, P / B, F::to_table(rinv_));
+                     dim3(kBlock), 0, s, w, (const E*)rem, P, B, (uint32_t)B, points, m, P / B, P / B, rinv_table());
         const E ri = rinv_;
         foreach_n(s, m, [=] __device__(size_t i) {
             const E v = F::canon(F::mul(w[i], ri));
@@ -3425,6 +3427,8 @@ private:
 
     HostTree<F> host_;
     E rinv_ = F::inv(F::to_mont(F::one()));   // R^-1 as a plain residue (1 for M31)
+    static E crate_one() { return F::to_mont(F::one()); }   // R, the crate's 1
+    TE rinv_table() const { return F::to_table(rinv_); }    // R^-1 in the form the table multiply takes
     size_t N_ = 0; unsigned L_ = 0; int device_ = 0;
     E* arena_ = nullptr; size_t arena_cap_ = 0, arena_used_ = 0;
     E* f_ = nullptr; E* den_ = nullptr; E* scratch_ = nullptr; size_t scratch_cap_ = 0;

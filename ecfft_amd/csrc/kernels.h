@@ -2316,13 +2316,67 @@ __global__ __launch_bounds__(kBlock) void k_powmod_sub(typename F::elem* __restr
     const size_t b = i / d, j = i - b * d;
     res[i] = F::canon(F::sub(F::canon(c[b * ld + j]), F::canon(t[b * ld + j])));
 }
+// The modular product of the small regimes (k_powmod_small, k_compose_small, roots_pow_scan): one workgroup of K threads per row,
+// residues of d <= K coefficients in LDS rows of K, thread t owning coefficient t.  The modulus is made monic once (one Fermat
+// inversion of its leading coefficient) and kept as PLAIN residues: f_t / f_d is the same number in either form.  A product brings
+// its left operand to plain form (one table multiply by R^-1 per coefficient, M31: R = 1), so every inner multiply is plain x crate
+// and stays crate: thread t sums the d terms of coefficients t and t + d of the schoolbook product (those with k <= t belong to the
+// first; it switches accumulators at k = t + 1), then d - 1 elimination steps of the monic modulus fold coefficients 2d-2 .. d
+// back.  The last thread never switches, because coefficient 2d - 1 does not exist: its sum is the low one.
+//
+// smod[t] = f[t] / f[d] as plain residues (zero from d on); a zero leading coefficient stores 1 to *flag.  The inverse passes
+// through sx[0].  No barrier after the store: the caller loads its own rows first.
+template <class F>
+__device__ __forceinline__ void modmul_monic(typename F::elem* smod, typename F::elem* sx, const typename F::elem* __restrict__ f, uint32_t d,
+                                             int* __restrict__ flag, uint32_t t) {
+    using E = typename F::elem;
+    if (t == 0) {
+        const E lead = F::canon(f[d]);
+        if (F::is_zero(lead)) *flag = 1;
+        sx[0] = F::canon(F::inv(lead));                  // inv(0) = 0: a flagged row computes on a zero modulus, its result is not used
+    }
+    __syncthreads();
+    const E linv = sx[0];
+    __syncthreads();
+    smod[t] = t < d ? F::canon(F::mul(f[t], linv)) : F::zero();
+}
+// sx = the left operand sres in plain form
+template <class F>
+__device__ __forceinline__ void modmul_plain(typename F::elem* sx, const typename F::elem* sres, const typename F::telem& rinv, uint32_t t) {
+    using E = typename F::elem;
+    E x = sres[t];
+    if constexpr (sizeof(E) == 32) x = F::tmul(rinv, x);
+    sx[t] = F::canon(x);
+    __syncthreads();
+}
+// sprod[0 .. d) = sx y mod (x^d + smod) for the plain sx and any LDS row y of d crate-form coefficients (sprod: 2K entries)
+template <class F>
+__device__ __forceinline__ void modmul_reduce(typename F::elem* sprod, const typename F::elem* sx, const typename F::elem* y,
+                                              const typename F::elem* smod, uint32_t d, uint32_t t) {
+    using E = typename F::elem;
+    if (t < d) {
+        uint32_t k = 0;                                  // declared ahead of the sums: in the for statement, hipcc 7 counts the
+                                                         // loop of k_powmod_small<M31> in a vector register (+4.5 % on a full GPU)
+        E acc = F::zero(), lo = F::zero();
+        for (; k < d; ++k) {
+            if (k == t + 1) { lo = acc; acc = F::zero(); }
+            const uint32_t j = k <= t ? t - k : t + d - k;
+            acc = F::canon(F::mul_add(sx[k], y[j], acc));
+        }
+        if (t + 1 == d) { lo = acc; acc = F::zero(); }
+        sprod[t] = lo;
+        sprod[t + d] = acc;
+    }
+    __syncthreads();
+    for (uint32_t k = 2 * d - 2; k >= d; --k) {
+        if (t < d) sprod[k - d + t] = F::canon(F::sub(sprod[k - d + t], F::canon(F::mul(sprod[k], smod[t]))));
+        __syncthreads();
+    }
+}
 // a^exp mod f for residues of d <= K coefficients: one workgroup of K threads per pair, the whole left-to-right square-and-multiply
-// in LDS.  a: row b at a + b*lda, na <= d coefficients (crate form); f: row b at f + b*(d+1), d + 1 coefficients; exp: nbits bits,
-// little-endian bytes, bit nbits-1 set (nbits == 0: the result is 1); out: count x d.  f is made monic once (one Fermat inversion
-// of its leading coefficient; a zero one stores 1 to *flag) and kept as PLAIN residues: f_t / f_d is the same number in either
-// form.  A product brings its left operand to plain form (one table multiply by R^-1 per coefficient, M31: R = 1), so every inner
-// multiply is plain x crate: thread t sums the d terms of coefficients t and t + d of the schoolbook product (those with i <= t
-// belong to the first), then d - 1 elimination steps of the monic f fold coefficients 2d-2 .. d back.  r1 = R, the crate's 1.
+// in LDS on the product above.  a: row b at a + b*lda, na <= d coefficients (crate form); f: row b at f + b*(d+1), d + 1
+// coefficients; exp: nbits bits, little-endian bytes, bit nbits-1 set (nbits == 0: the result is 1); out: count x d.  r1 = R, the
+// crate's 1.
 template <class F, int K>
 __global__ __launch_bounds__(K) void k_powmod_small(typename F::elem* __restrict__ out, const typename F::elem* __restrict__ a, size_t lda,
                                                     uint32_t na, const typename F::elem* __restrict__ f, uint32_t d,
@@ -2332,16 +2386,7 @@ __global__ __launch_bounds__(K) void k_powmod_small(typename F::elem* __restrict
     __shared__ E sres[K], sbase[K], smod[K], sx[K], sprod[2 * K];
     const uint32_t t = threadIdx.x;
     const size_t b = blockIdx.x;
-    const E* fb = f + b * ((size_t)d + 1);
-    if (t == 0) {
-        const E lead = F::canon(fb[d]);
-        if (F::is_zero(lead)) *flag = 1;
-        sx[0] = F::canon(F::inv(lead));                  // inv(0) = 0: a flagged pair computes on a zero modulus, its row is not used
-    }
-    __syncthreads();
-    const E linv = sx[0];
-    __syncthreads();
-    smod[t] = t < d ? F::canon(F::mul(fb[t], linv)) : F::zero();
+    modmul_monic<F>(smod, sx, f + b * ((size_t)d + 1), d, flag, t);
     sbase[t] = t < na ? a[b * lda + t] : F::zero();
     sres[t] = sbase[t];
     __syncthreads();
@@ -2352,27 +2397,8 @@ __global__ __launch_bounds__(K) void k_powmod_small(typename F::elem* __restrict
     for (uint32_t i = nbits - 1; i-- > 0;) {
         const uint32_t passes = 1 + ((exp[i >> 3] >> (i & 7)) & 1);     // a squaring, then on a set bit a product with the base
         for (uint32_t pass = 0; pass < passes; ++pass) {
-            const E* y = pass ? sbase : sres;                           // sres = sres * y mod f
-            E x = sres[t];
-            if constexpr (sizeof(E) == 32) x = F::tmul(rinv, x);
-            sx[t] = F::canon(x);
-            __syncthreads();
-            if (t < d) {
-                E acc = F::zero(), lo = F::zero();
-                for (uint32_t k = 0; k < d; ++k) {
-                    if (k == t + 1) { lo = acc; acc = F::zero(); }
-                    const uint32_t j = k <= t ? t - k : t + d - k;
-                    acc = F::canon(F::mul_add(sx[k], y[j], acc));
-                }
-                if (t + 1 == d) { lo = acc; acc = F::zero(); }          // the last thread never switched: coefficient 2d - 1 does not exist
-                sprod[t] = lo;
-                sprod[t + d] = acc;
-            }
-            __syncthreads();
-            for (uint32_t k = 2 * d - 2; k >= d; --k) {
-                if (t < d) sprod[k - d + t] = F::canon(F::sub(sprod[k - d + t], F::canon(F::mul(sprod[k], smod[t]))));
-                __syncthreads();
-            }
+            modmul_plain<F>(sx, sres, rinv, t);
+            modmul_reduce<F>(sprod, sx, pass ? sbase : sres, smod, d, t);   // sres = sres * y mod f
             if (t < d) sres[t] = sprod[t];
             __syncthreads();
         }
@@ -2387,12 +2413,9 @@ __global__ __launch_bounds__(K) void k_powmod_small(typename F::elem* __restrict
 // and giant steps on the kept-modulus products of poly_pow_mod, and k_compose_rows is the dense matrix product between them
 // (DESIGN.md 5.10).
 // ---------------------------------------------------------------------------------------------
-// f(g) mod h for residues of d <= K coefficients: one workgroup of K threads per triple, Horner in LDS: res = f[nf-1], then for
-// i = nf - 2 .. 0 res = res g mod h and res[0] += f[i]; nf is the only loop bound.  f: row b at f + b*nf; g: row b at g + b*ldg,
-// ng <= d coefficients; h: row b at h + b*(d+1); out: count x d.  The product is k_powmod_small's, written out as a sibling (as
-// roots_pow_scan is) so that the kernels that were there keep their code: h made monic by one Fermat inversion (a zero leading
-// coefficient stores 1 to *flag) and kept as PLAIN residues, the left operand brought to plain form by one table multiply by R^-1,
-// thread t summing coefficients t and t + d of the schoolbook product, then d - 1 elimination steps.
+// f(g) mod h for residues of d <= K coefficients: one workgroup of K threads per triple, Horner in LDS on the product of
+// k_powmod_small (modmul_*): res = f[nf-1], then for i = nf - 2 .. 0 res = res g mod h and res[0] += f[i]; nf is the only loop
+// bound.  f: row b at f + b*nf; g: row b at g + b*ldg, ng <= d coefficients; h: row b at h + b*(d+1); out: count x d.
 template <class F, int K>
 __global__ __launch_bounds__(K) void k_compose_small(typename F::elem* __restrict__ out, const typename F::elem* __restrict__ f, uint32_t nf,
                                                      const typename F::elem* __restrict__ g, size_t ldg, uint32_t ng,
@@ -2402,17 +2425,8 @@ __global__ __launch_bounds__(K) void k_compose_small(typename F::elem* __restric
     __shared__ E sres[K], sg[K], smod[K], sx[K], sprod[2 * K];
     const uint32_t t = threadIdx.x;
     const size_t b = blockIdx.x;
-    const E* hb = h + b * ((size_t)d + 1);
     const E* fb = f + b * (size_t)nf;
-    if (t == 0) {
-        const E lead = F::canon(hb[d]);
-        if (F::is_zero(lead)) *flag = 1;
-        sx[0] = F::canon(F::inv(lead));                  // inv(0) = 0: a flagged triple computes on a zero modulus, its row is not used
-    }
-    __syncthreads();
-    const E linv = sx[0];
-    __syncthreads();
-    smod[t] = t < d ? F::canon(F::mul(hb[t], linv)) : F::zero();
+    modmul_monic<F>(smod, sx, h + b * ((size_t)d + 1), d, flag, t);
     sg[t] = t < ng ? F::canon(g[b * ldg + t]) : F::zero();
     {
         E v = F::zero();
@@ -2421,26 +2435,8 @@ __global__ __launch_bounds__(K) void k_compose_small(typename F::elem* __restric
     }
     __syncthreads();
     for (uint32_t i = nf - 1; i-- > 0;) {
-        E x = sres[t];
-        if constexpr (sizeof(E) == 32) x = F::tmul(rinv, x);
-        sx[t] = F::canon(x);
-        __syncthreads();
-        if (t < d) {
-            E acc = F::zero(), lo = F::zero();
-            for (uint32_t k = 0; k < d; ++k) {
-                if (k == t + 1) { lo = acc; acc = F::zero(); }
-                const uint32_t j = k <= t ? t - k : t + d - k;
-                acc = F::canon(F::mul_add(sx[k], sg[j], acc));
-            }
-            if (t + 1 == d) { lo = acc; acc = F::zero(); }              // the last thread never switched: coefficient 2d - 1 does not exist
-            sprod[t] = lo;
-            sprod[t + d] = acc;
-        }
-        __syncthreads();
-        for (uint32_t k = 2 * d - 2; k >= d; --k) {
-            if (t < d) sprod[k - d + t] = F::canon(F::sub(sprod[k - d + t], F::canon(F::mul(sprod[k], smod[t]))));
-            __syncthreads();
-        }
+        modmul_plain<F>(sx, sres, rinv, t);
+        modmul_reduce<F>(sprod, sx, sg, smod, d, t);
         if (t < d) {
             E v = sprod[t];
             if (t == 0) v = F::canon(F::add(v, F::canon(fb[i])));
@@ -2500,13 +2496,60 @@ __global__ __launch_bounds__(kBlock) void k_compose_rows(typename F::elem* __res
 // CPU).  Up to G coefficients the whole remainder sequence of a pair runs in one workgroup (k_gcd_small); above that the host
 // drives a half-GCD on the poly_mul and division bodies whose recursion ends in the same kernel.
 // ---------------------------------------------------------------------------------------------
+// The cross-multiplied remainder loop of k_gcd_small and k_roots_small on LDS rows, thread t owning coefficient t of every row:
+// while deg R1 >= bound (and R1 != 0), steps
+//     R0 <- lc(R1) R0 - lc(R0) x^k R1,   k = deg R0 - deg R1,
+// until deg R0 < deg R1, then the rows swap.  The new degree is an atomicMax into sdeg[par], which the step before left at -1;
+// the step resets the other entry, so the two alternate.  On entry d0 = deg R0, d1 = deg R1 (-1: zero) and both sdeg are -1 behind
+// a barrier.  cof != 0 applies the same combination to the cofactor rows (S0, T0), (S1, T1), touched below their lengths c0, c1
+// only; cof == 0 ignores them.  Returns the number of swaps.  Every thread takes the same path through every barrier: d0, d1 come
+// from LDS after a barrier, bound and cof are the same for the workgroup.
+template <class F>
+__device__ __forceinline__ int gcd_remainder_loop(typename F::elem*& R0, typename F::elem*& R1, int& d0, int& d1, typename F::elem*& S0,
+                                                  typename F::elem*& S1, typename F::elem*& T0, typename F::elem*& T1, int& c0, int& c1,
+                                                  uint32_t cof, int bound, int* sdeg, uint32_t t) {
+    using E = typename F::elem;
+    int swaps = 0;
+    uint32_t par = 0;                                        // sdeg[par] == -1 receives the next step's degree
+    while (d1 >= 0 && d1 >= bound) {
+        while (d0 >= d1) {
+            const uint32_t k = (uint32_t)(d0 - d1);
+            const E lr = R0[d0], lb = R1[d1];
+            __syncthreads();                                 // everyone holds lr (thread d0 clears it) and the previous step's degree
+            if (t == 0) sdeg[par ^ 1] = -1;
+            if ((int)t < d0) {
+                E v = F::mul(lb, R0[t]);
+                if (t >= k) v = F::sub(v, F::mul(lr, R1[t - k]));
+                v = F::canon(v);
+                R0[t] = v;
+                if (!F::is_zero(v)) atomicMax(&sdeg[par], (int)t);
+            } else if ((int)t == d0) {
+                R0[t] = F::zero();
+            }
+            if (cof) {
+                const int cn = c0 > c1 + (int)k ? c0 : c1 + (int)k;
+                if ((int)t < cn) {
+                    E u = F::mul(lb, S0[t]), w = F::mul(lb, T0[t]);
+                    if (t >= k) { u = F::sub(u, F::mul(lr, S1[t - k])); w = F::sub(w, F::mul(lr, T1[t - k])); }
+                    S0[t] = F::canon(u); T0[t] = F::canon(w);
+                }
+                c0 = cn;
+            }
+            __syncthreads();
+            d0 = sdeg[par];
+            par ^= 1;
+        }
+        { E* x = R0; R0 = R1; R1 = x; x = S0; S0 = S1; S1 = x; x = T0; T0 = T1; T1 = x; }
+        { int x = d0; d0 = d1; d1 = x; x = c0; c0 = c1; c1 = x; }
+        ++swaps;
+    }
+    return swaps;
+}
 // The remainder sequence of one pair in one workgroup of G threads, entirely in LDS: thread t owns coefficient t of the two
 // remainders (R0, R1) and of the two cofactor rows (S0, T0), (S1, T1), with R_i = S_i a + T_i b throughout.  a: row p at
 // a + p*lda, na <= G coefficients; b likewise; high zero coefficients are allowed and either row may be zero — the true degrees
-// are found here.  No inversion per quotient: one elimination step is the cross-multiplied
-//     R0 <- lc(R1) R0 - lc(R0) x^k R1,   k = deg R0 - deg R1,
-// and the same combination of the cofactor rows, repeated until deg R0 < deg R1 (a quotient of degree q takes q + 1 steps), then
-// the rows swap.  Each row is therefore a non-zero scalar multiple of the Euclidean algorithm's row, which changes no degree.
+// are found here.  No inversion per quotient: gcd_remainder_loop's steps are cross-multiplied (a quotient of degree q takes q + 1
+// of them), so each row is a non-zero scalar multiple of the Euclidean algorithm's row, which changes no degree.
 // The multiplies are plain products of stored numbers; with the cofactor rows started from the crate's 1 (r1 = R; M31: R = 1)
 // the relation R_i = S_i a + T_i b holds in the crate's arithmetic (x y / R) whatever the scalars are, so the Montgomery factor
 // needs no bookkeeping until the end.  The loop runs while deg R1 >= bound (and R1 != 0).
@@ -2544,43 +2587,11 @@ __global__ __launch_bounds__(G) void k_gcd_small(const typename F::elem* __restr
         S0[t] = one; T0[t] = F::zero(); S1[t] = F::zero(); T1[t] = one;
     }
     __syncthreads();
-    int d0 = sdeg[0], d1 = sdeg[1], c0 = 1, c1 = 1, swaps = 0;
+    int d0 = sdeg[0], d1 = sdeg[1], c0 = 1, c1 = 1;
     __syncthreads();
     if (t < 2) sdeg[t] = -1;
     __syncthreads();
-    uint32_t par = 0;                                        // sdeg[par] == -1 receives the next step's degree
-    while (d1 >= 0 && d1 >= bound) {
-        while (d0 >= d1) {
-            const uint32_t k = (uint32_t)(d0 - d1);
-            const E lr = R0[d0], lb = R1[d1];
-            __syncthreads();                                 // everyone holds lr (thread d0 clears it) and the previous step's degree
-            if (t == 0) sdeg[par ^ 1] = -1;
-            if ((int)t < d0) {
-                E v = F::mul(lb, R0[t]);
-                if (t >= k) v = F::sub(v, F::mul(lr, R1[t - k]));
-                v = F::canon(v);
-                R0[t] = v;
-                if (!F::is_zero(v)) atomicMax(&sdeg[par], (int)t);
-            } else if ((int)t == d0) {
-                R0[t] = F::zero();
-            }
-            if (cof) {
-                const int cn = c0 > c1 + (int)k ? c0 : c1 + (int)k;
-                if ((int)t < cn) {
-                    E u = F::mul(lb, S0[t]), w = F::mul(lb, T0[t]);
-                    if (t >= k) { u = F::sub(u, F::mul(lr, S1[t - k])); w = F::sub(w, F::mul(lr, T1[t - k])); }
-                    S0[t] = F::canon(u); T0[t] = F::canon(w);
-                }
-                c0 = cn;
-            }
-            __syncthreads();
-            d0 = sdeg[par];
-            par ^= 1;
-        }
-        { E* x = R0; R0 = R1; R1 = x; x = S0; S0 = S1; S1 = x; x = T0; T0 = T1; T1 = x; }
-        { int x = d0; d0 = d1; d1 = x; x = c0; c0 = c1; c1 = x; }
-        ++swaps;
-    }
+    const int swaps = gcd_remainder_loop<F>(R0, R1, d0, d1, S0, S1, T0, T1, c0, c1, cof, bound, sdeg, t);
     if (leaf) {
         if (t < nm) {
             E* m = mat + p * 4 * ldm;
@@ -2644,9 +2655,8 @@ __global__ __launch_bounds__(kBlock) void k_gcd_combine(typename F::elem* __rest
 // kernel, and k_roots_rank puts the roots in ascending order of their standard form.
 // ---------------------------------------------------------------------------------------------
 // sres (e residues, crate form) = (x + c)^exp mod h for the monic h of degree e >= 2 whose low e coefficients smod holds as PLAIN
-// residues; exp: nbits >= 1 bits, bit nbits - 1 set.  k_powmod_small's scan: a squaring is its schoolbook product (thread t sums
-// coefficients t and t + e) and e - 1 elimination steps of the monic h; "multiply by the base" is a shift, a scale by the plain
-// integer c and ONE elimination step: x r + c r - r_{e-1} h.  plain x crate stays crate.
+// residues; exp: nbits >= 1 bits, bit nbits - 1 set.  k_powmod_small's scan: a squaring is its product (modmul_*); "multiply by
+// the base" is a shift, a scale by the plain integer c and ONE elimination step: x r + c r - r_{e-1} h.
 template <class F, int K>
 __device__ __forceinline__ void roots_pow_scan(typename F::elem* sres, typename F::elem* sx, typename F::elem* sprod,
                                                const typename F::elem* smod, uint32_t e, uint32_t c, const uint8_t* __restrict__ exp,
@@ -2661,26 +2671,8 @@ __device__ __forceinline__ void roots_pow_scan(typename F::elem* sres, typename 
     }
     __syncthreads();
     for (uint32_t i = nbits - 1; i-- > 0;) {
-        E x = sres[t];
-        if constexpr (sizeof(E) == 32) x = F::tmul(rinv, x);
-        sx[t] = F::canon(x);
-        __syncthreads();
-        if (t < e) {
-            E acc = F::zero(), lo = F::zero();
-            for (uint32_t k = 0; k < e; ++k) {
-                if (k == t + 1) { lo = acc; acc = F::zero(); }
-                const uint32_t j = k <= t ? t - k : t + e - k;
-                acc = F::canon(F::mul_add(sx[k], sres[j], acc));
-            }
-            if (t + 1 == e) { lo = acc; acc = F::zero(); }
-            sprod[t] = lo;
-            sprod[t + e] = acc;
-        }
-        __syncthreads();
-        for (uint32_t k = 2 * e - 2; k >= e; --k) {
-            if (t < e) sprod[k - e + t] = F::canon(F::sub(sprod[k - e + t], F::canon(F::mul(sprod[k], smod[t]))));
-            __syncthreads();
-        }
+        modmul_plain<F>(sx, sres, rinv, t);
+        modmul_reduce<F>(sprod, sx, sres, smod, e, t);
         if (t < e) sres[t] = sprod[t];
         __syncthreads();
         if ((exp[i >> 3] >> (i & 7)) & 1) {
@@ -2697,9 +2689,9 @@ __device__ __forceinline__ void roots_pow_scan(typename F::elem* sres, typename 
         }
     }
 }
-// The remainder sequence of (R0, R1), deg R0 = d0 >= deg R1, to its end: k_gcd_small's cross-multiplied steps without cofactors.
-// Rows of K + 1 entries; nothing above a row's degree is read.  On return R0 is a non-zero multiple of the gcd and the result its
-// degree.  sdeg: two ints.  Every thread takes the same path (degrees come from LDS after a barrier).
+// The remainder sequence of (R0, R1), deg R0 = d0 >= deg R1, to its end: gcd_remainder_loop without cofactors, after the degree
+// of R1 is found below d0.  Rows of K + 1 entries; nothing above a row's degree is read.  On return R0 is a non-zero multiple of
+// the gcd and the result its degree.  sdeg: two ints.
 template <class F, int K>
 __device__ __forceinline__ int roots_gcd_rows(typename F::elem*& R0, typename F::elem*& R1, int d0, int* sdeg, uint32_t t) {
     using E = typename F::elem;
@@ -2711,27 +2703,9 @@ __device__ __forceinline__ int roots_gcd_rows(typename F::elem*& R0, typename F:
     __syncthreads();
     if (t < 2) sdeg[t] = -1;
     __syncthreads();
-    uint32_t par = 0;
-    while (d1 >= 0) {
-        while (d0 >= d1) {
-            const uint32_t k = (uint32_t)(d0 - d1);
-            const E lr = R0[d0], lb = R1[d1];
-            __syncthreads();
-            if (t == 0) sdeg[par ^ 1] = -1;
-            if ((int)t < d0) {
-                E v = F::mul(lb, R0[t]);
-                if (t >= k) v = F::sub(F::canon(v), F::canon(F::mul(lr, R1[t - k])));
-                v = F::canon(v);
-                R0[t] = v;
-                if (!F::is_zero(v)) atomicMax(&sdeg[par], (int)t);
-            }
-            __syncthreads();
-            d0 = sdeg[par];
-            par ^= 1;
-        }
-        { E* x = R0; R0 = R1; R1 = x; }
-        { int x = d0; d0 = d1; d1 = x; }
-    }
+    E* none = nullptr;
+    int c = 0;
+    gcd_remainder_loop<F>(R0, R1, d0, d1, none, none, none, none, c, c, 0u, 0, sdeg, t);
     return d0;
 }
 // All roots of one polynomial, or of one factor, of degree <= K in one workgroup of K threads, everything in LDS.  Block b reads
