@@ -59,6 +59,8 @@ pub mod ffi {
         pub fn ecfft_poly_pow_mod(ctx: *mut EcfftCtx, a: *const c_void, na: usize, exp: *const c_void, exp_bytes: usize, modulus: *const c_void, nm: usize, out: *mut c_void, count: usize, mem: i32, stream: *mut c_void) -> i32;
         pub fn ecfft_poly_mul_mod(ctx: *mut EcfftCtx, a: *const c_void, na: usize, b: *const c_void, nb: usize, modulus: *const c_void, nm: usize, out: *mut c_void, count: usize, mem: i32, stream: *mut c_void) -> i32;
         pub fn ecfft_poly_compose_mod(ctx: *mut EcfftCtx, f: *const c_void, nf: usize, g: *const c_void, ng: usize, modulus: *const c_void, nm: usize, out: *mut c_void, count: usize, mem: i32, stream: *mut c_void) -> i32;
+        pub fn ecfft_poly_squarefree(ctx: *mut EcfftCtx, f: *const c_void, nf: usize, out: *mut c_void, degrees: *mut i64, count: usize, mem: i32, stream: *mut c_void) -> i32;
+        pub fn ecfft_poly_distinct_degree(ctx: *mut EcfftCtx, f: *const c_void, nf: usize, factors: *mut c_void, degrees: *mut i64, count: usize, mem: i32, stream: *mut c_void) -> i32;
         pub fn ecfft_poly_find_roots(ctx: *mut EcfftCtx, f: *const c_void, nf: usize, roots: *mut c_void, n_roots: *mut i64, count: usize, mem: i32, stream: *mut c_void) -> i32;
         pub fn ecfft_poly_gcd(ctx: *mut EcfftCtx, a: *const c_void, na: usize, b: *const c_void, nb: usize, g: *mut c_void, degrees: *mut i64, count: usize, mem: i32, stream: *mut c_void) -> i32;
         pub fn ecfft_poly_xgcd(ctx: *mut EcfftCtx, a: *const c_void, na: usize, b: *const c_void, nb: usize, s: *mut c_void, t: *mut c_void, g: *mut c_void, degrees: *mut i64, count: usize, mem: i32, stream: *mut c_void) -> i32;
@@ -425,6 +427,32 @@ impl<F: HipField> HipFFTree<F> {
         assert!(count >= 0, "find_roots: the zero polynomial");
         unsafe { roots.set_len(count as usize) };
         roots
+    }
+
+    /// `ecfft::utils::distinct_degree_factors` (src/utils.rs:52-78) by its definition: degree `d` -> the monic product of the
+    /// irreducible factors of degree `d` of `f`, with its leading 1.  (The reference takes `x^(p i)` for `x^(p^i)`, so it agrees at
+    /// `d = 1` only, the degree its own `find_roots` uses.)  `f` need not be trimmed or squarefree; a non-zero constant gives an empty
+    /// map.  Panics on the zero polynomial.  Up to `ECFFT_DDF_SMALL_MAX` coefficients work on any tree; tree rule:
+    /// include/ecfft_hip.h.
+    pub fn distinct_degree_factors(&self, f: &[F]) -> std::collections::BTreeMap<usize, Vec<F>> {
+        assert!(!f.is_empty());
+        let nd = core::cmp::max(f.len() - 1, 1);
+        let mut fac = Self::out_vec(nd);
+        let mut deg = vec![0i64; nd];
+        check(unsafe { ffi::ecfft_poly_distinct_degree(self.ctx, f.as_ptr().cast(), f.len(), fac.as_mut_ptr().cast(), deg.as_mut_ptr(), 1, ffi::MEM_HOST, core::ptr::null_mut()) });
+        assert!(deg[0] >= 0, "distinct_degree_factors: the zero polynomial");
+        unsafe { fac.set_len(nd) };
+        let mut out = std::collections::BTreeMap::new();
+        let mut pos = 0usize;
+        for (i, &n) in deg.iter().enumerate() {
+            if n > 0 {
+                let mut g = fac[pos..pos + n as usize].to_vec();
+                g.push(F::one());
+                out.insert(i + 1, g);
+                pos += n as usize;
+            }
+        }
+        out
     }
 
     /// `FFTree::mextend` (src/fftree.rs:138-141)

@@ -1729,7 +1729,8 @@ public:
     //       against the kept base; B_k is the giant step, so it is only taken when there is a second chunk;
     //     C_i = sum_{t<k} f[i k + t] B_t for i < k' (k_compose_rows: k' x count x d);
     //     giant steps: G = B_k lifted once and kept (count x N), res = C_(k'-1), then res = res G + C_i for i = k' - 2 .. 0.
-    //   (k - 1) + (k' - 1) modular products where Horner takes nf - 1; nf <= 2 runs none.
+    //   (k - 1) + (k' - 1) modular products where Horner takes nf - 1; nf <= 2 runs none.  compose_prepare takes the baby steps and
+    //   compose_apply the rest: the kept composition of the distinct-degree driver, applied once here.
     // Temporaries beyond a product's own: (k + 1 + k') count d + 4 count N elements (B and C; the three kept operands and G).
     // Synchronous; *singular = some h_b[nm-1] == 0.  Caller holds lock() and checks the tree rule (powmod_leaves(nm), and
     // divrem_leaves(ng, nm) when ng >= nm: independent of nf).
@@ -1741,9 +1742,8 @@ public:
         const RowsRef gred = reduced_below(g, ng, h, nm, count, flag, &ok, s);           // g below nm coefficients
         const E* gr = gred.p;
         const size_t ldg = gred.ld, lg = gred.len;
-        const E r1 = crate_one();
-        const TE rinv = rinv_table();
         if (d <= kComposeSmall) {
+            const TE rinv = rinv_table();
             for_chunks(count, [&](size_t c0, size_t c) {
                 ECFFT_LAUNCH(KC_POINTWISE, sizeof(E) * (double)c * (double)(nf + lg + nm + d), (k_compose_small<F, (int)kComposeSmall>),
                              dim3((unsigned)c), dim3((unsigned)kComposeSmall), 0, s, out + c0 * d, f + c0 * nf, (uint32_t)nf, gr + c0 * ldg, ldg,
@@ -1751,36 +1751,14 @@ public:
             });
             return finish_flagged(ok, flag, singular, s);
         }
-        const size_t k = compose_chunk(nf), kp = (nf + k - 1) / k, N = powmod_leaves(nm);
-        E* kept = temp(3 * count * N);
+        E* kept = temp(3 * count * powmod_leaves(nm));
         KeptModulus km;
         ok = keep_modulus(h, d, gr, lg, ldg, count, kept, flag, &km, s) && ok;
-        E* B = temp((k + 1) * cd); E* C = temp(kp * cd);
-        foreach_n(s, 2 * cd, [=] __device__(size_t i) {
-            const size_t w = i / cd, q = i - w * cd, b = q / d, j = q - b * d;
-            B[i] = w == 0 ? (j == 0 ? r1 : F::zero()) : (j < lg ? F::canon(gr[b * ldg + j]) : F::zero());
-        });
-        const size_t nb = kp > 1 ? k : k - 1;                    // the highest baby step anything reads
-        for (size_t t = 1; t < nb; ++t) {
-            ok = hipMemcpyAsync(B + (t + 1) * cd, B + t * cd, cd * sizeof(E), hipMemcpyDeviceToDevice, s) == hipSuccess && ok;
-            ok = powmod_step(B + (t + 1) * cd, km.base, km, count, rinv, s) && ok;
-        }
-        constexpr size_t TR = ComposeTile<F>::TR;
-        for_chunks(count, [&](size_t c0, size_t c) {
-            ECFFT_LAUNCH(KC_POINTWISE, sizeof(E) * (double)c * ((double)nf + (double)(k + kp) * (double)d), k_compose_rows<F>,
-                         dim3(nblocks(d), (unsigned)((kp + TR - 1) / TR), (unsigned)c), dim3(kBlock), 0, s, C + c0 * d, (const E*)B + c0 * d,
-                         f + c0 * nf, nf, k, kp, d, count, rinv);
-        });
-        ok = hipMemcpyAsync(out, C + (kp - 1) * cd, cd * sizeof(E), hipMemcpyDeviceToDevice, s) == hipSuccess && ok;
-        if (kp > 1) {
-            E* G = temp(count * N);
-            ok = lift_and_keep(B + k * cd, d, N, count, G, s) && ok;
-            for (size_t i = kp - 1; i-- > 0;) {
-                ok = powmod_step(out, G, km, count, rinv, s) && ok;
-                const E* Ci = C + i * cd;
-                foreach_n(s, cd, [=] __device__(size_t q) { out[q] = F::canon(F::add(out[q], Ci[q])); });
-            }
-        }
+        const size_t k = compose_chunk(nf), kp = (nf + k - 1) / k;
+        KeptCompose kc;
+        kc.B = temp((k + 1) * cd); kc.C = temp(kp * cd);
+        ok = compose_prepare(km, gr, lg, ldg, nf, count, &kc, s) && ok;
+        ok = compose_apply(kc, f, out, s) && ok;
         return finish_flagged(ok, flag, singular, s);
     }
 
@@ -1883,6 +1861,57 @@ private:
         ECFFT_LAUNCH(KC_POINTWISE, sizeof(E) * 3.0 * (double)nres, k_powmod_sub<F>, dim3(nblocks(nres)), dim3(kBlock), 0, s,
                      res, d, (const E*)C, (const E*)T, N, nres);
         temps_release(mark);
+        return ok;
+    }
+    // A kept composition: what the large regime of poly_compose_mod computes from the inner polynomial g and the modulus alone, so
+    // that several outer polynomials of nf coefficients share it (the Frobenius iterates of ddf_one_large all compose with x^p).
+    //   prepare: on a kept modulus whose base is g, the baby steps B_t = g^t mod h, t = 0 .. k (B: (k + 1) x count x d, taken by the
+    //     caller like C: k' x count x d).
+    //   apply: C_i = sum_t f[i k + t] B_t (k_compose_rows), res = C_(k'-1), then res = res G + C_i against G = B_k lifted and kept
+    //     (count x N, made by the first apply that has a second chunk; G == nullptr: taken here): k' - 1 modular products.
+    // prepare then one apply are the launches of poly_compose_mod in their order.
+    struct KeptCompose { KeptModulus km; E* B = nullptr; E* C = nullptr; E* G = nullptr; size_t nf = 0, k = 0, kp = 0, count = 0; bool lifted = false; };
+    bool compose_prepare(const KeptModulus& km, const E* gr, size_t lg, size_t ldg, size_t nf, size_t count, KeptCompose* kc, hipStream_t s) {
+        const size_t d = km.d, cd = count * d, k = compose_chunk(nf), kp = (nf + k - 1) / k;
+        const E r1 = crate_one();
+        const TE rinv = rinv_table();
+        E* B = kc->B;
+        kc->km = km; kc->nf = nf; kc->k = k; kc->kp = kp; kc->count = count; kc->lifted = false;
+        bool ok = true;
+        foreach_n(s, 2 * cd, [=] __device__(size_t i) {
+            const size_t w = i / cd, q = i - w * cd, b = q / d, j = q - b * d;
+            B[i] = w == 0 ? (j == 0 ? r1 : F::zero()) : (j < lg ? F::canon(gr[b * ldg + j]) : F::zero());
+        });
+        const size_t nb = kp > 1 ? k : k - 1;                    // the highest baby step anything reads
+        for (size_t t = 1; t < nb; ++t) {
+            ok = hipMemcpyAsync(B + (t + 1) * cd, B + t * cd, cd * sizeof(E), hipMemcpyDeviceToDevice, s) == hipSuccess && ok;
+            ok = powmod_step(B + (t + 1) * cd, km.base, km, count, rinv, s) && ok;
+        }
+        return ok;
+    }
+    bool compose_apply(KeptCompose& kc, const E* f, E* out, hipStream_t s) {
+        const KeptModulus& km = kc.km;
+        const size_t d = km.d, count = kc.count, cd = count * d, nf = kc.nf, k = kc.k, kp = kc.kp;
+        const TE rinv = rinv_table();
+        const E* B = kc.B; E* C = kc.C;
+        bool ok = true;
+        constexpr size_t TR = ComposeTile<F>::TR;
+        for_chunks(count, [&](size_t c0, size_t c) {
+            ECFFT_LAUNCH(KC_POINTWISE, sizeof(E) * (double)c * ((double)nf + (double)(k + kp) * (double)d), k_compose_rows<F>,
+                         dim3(nblocks(d), (unsigned)((kp + TR - 1) / TR), (unsigned)c), dim3(kBlock), 0, s, C + c0 * d, B + c0 * d,
+                         f + c0 * nf, nf, k, kp, d, count, rinv);
+        });
+        ok = hipMemcpyAsync(out, C + (kp - 1) * cd, cd * sizeof(E), hipMemcpyDeviceToDevice, s) == hipSuccess && ok;
+        if (kp > 1) {
+            if (!kc.G) kc.G = temp(count * km.N);
+            if (!kc.lifted) { ok = lift_and_keep(B + k * cd, d, km.N, count, kc.G, s) && ok; kc.lifted = true; }
+            const E* G = kc.G;
+            for (size_t i = kp - 1; i-- > 0;) {
+                ok = powmod_step(out, G, km, count, rinv, s) && ok;
+                const E* Ci = C + i * cd;
+                foreach_n(s, cd, [=] __device__(size_t q) { out[q] = F::canon(F::add(out[q], Ci[q])); });
+            }
+        }
         return ok;
     }
     // One lift: cnt vectors of mm evaluations on T_mm (cur) -> 2mm evaluations on T_2mm (dst): interleave(cur, EXTEND_S1(cur)); ext: work
@@ -2230,13 +2259,19 @@ private:
     // not a second modular product but x r + c r - r_{d-1} f, one pass over the rows.  exp: host bytes, bit nbits - 1 set, nbits >= 1.
     bool roots_pow_body(const E* f, size_t d, uint32_t c, const uint8_t* exp, size_t nbits, E* out, size_t count, int* flag, hipStream_t s) {
         static_assert(kRootsSmall >= kPowSmall, "d > kRootsSmall is the large regime of powmod_leaves");
-        const size_t nm = d + 1;
-        const E r1 = crate_one();
-        const TE rinv = rinv_table();
-        E* kept = temp(2 * count * powmod_leaves(nm));
+        E* kept = temp(2 * count * powmod_leaves(d + 1));
         E* next = temp(count * d);
         KeptModulus km;
-        bool ok = keep_modulus(f, d, nullptr, 0, 0, count, kept, flag, &km, s);
+        const bool ok = keep_modulus(f, d, nullptr, 0, 0, count, kept, flag, &km, s);
+        return roots_pow_kept(f, km, c, exp, nbits, out, next, count, s) && ok;
+    }
+    // the scan of roots_pow_body on a modulus that is already kept (next: count x d elements of work)
+    bool roots_pow_kept(const E* f, const KeptModulus& km, uint32_t c, const uint8_t* exp, size_t nbits, E* out, E* next, size_t count,
+                        hipStream_t s) {
+        const size_t d = km.d, nm = d + 1;
+        const E r1 = crate_one();
+        const TE rinv = rinv_table();
+        bool ok = true;
         const E cE = F::from_u32(c), ri = rinv_;
         const E c_crate = F::canon(F::mul(cE, r1));
         foreach_n(s, count * d, [=] __device__(size_t i) {
@@ -2453,6 +2488,221 @@ public:
             }
         }
         return finish_flagged(ok, rc.flag, capped, s);
+    }
+
+    // ---- ecfft_poly_squarefree / ecfft_poly_distinct_degree (utils::square_free_factors / distinct_degree_factors, src/utils.rs:46-78) ----
+    // a polynomial of at most kDdfSmall + 1 coefficients is finished by k_ddf_small, one workgroup each
+    static constexpr size_t kDdfSmall = kRootsSmall;
+    // The leaves both calls need for rows of nf coefficients, checked before anything runs: the rule of ecfft_poly_find_roots (the
+    // gcds with f' and with h_i - x are pairs of at most nf coefficients; the kept modulus s has at most nf)
+    static size_t ddf_leaves(size_t nf) { return roots_leaves(nf); }
+    // How the large regime takes the Frobenius iterate h_(i+1) from h_i on a kept modulus of degree ds: true = the kept composition
+    // h_i(h_1) (k' - 1 modular products and one k_compose_rows), false = the fresh power h_i^p (bits + popcount(p) - 2 products).
+    // The rule is the count of modular products; profiles/polyddf/polyddf_time.json is the measurement behind it.
+    static bool ddf_iterate_composes(size_t ds) {
+#ifdef ECFFT_TEST_HOOKS
+        if (ddf_iterate_force() == 1) return true;
+        if (ddf_iterate_force() == 2) return false;
+#endif
+        uint8_t ep[32], eh[32];
+        uint32_t nbits_p = 0, nbits_h = 0, pop = 0;
+        roots_exponents(ep, &nbits_p, eh, &nbits_h);
+        for (int i = 0; i < 32; ++i) pop += (uint32_t)__builtin_popcount(ep[i]);
+        const size_t k = compose_chunk(ds), kp = (ds + k - 1) / k;
+        return kp - 1 <= (size_t)nbits_p + pop - 2;
+    }
+#ifdef ECFFT_TEST_HOOKS
+    // ecfft_test_ddf_iterate (include/ecfft_hip_hooks.h): 0 = the rule, 1 = always the kept composition, 2 = always the fresh power
+    static int& ddf_iterate_force() { static int v = 0; return v; }
+#endif
+private:
+    // what a call shares between its polynomials: p as host and device bytes
+    struct DdfCall { const uint8_t* dexp = nullptr; uint8_t ep[32], eh[32]; uint32_t nbits_p = 0, nbits_h = 0; };
+    bool ddf_call_init(DdfCall* dc, hipStream_t s) {
+        roots_exponents(dc->ep, &dc->nbits_p, dc->eh, &dc->nbits_h);
+        uint8_t* dexp = temp_as<uint8_t>(32);
+        dc->dexp = dexp;
+        return hipMemcpyAsync(dexp, dc->ep, 32, hipMemcpyHostToDevice, s) == hipSuccess && hipStreamSynchronize(s) == hipSuccess;
+    }
+    // one launch of k_ddf_small over nblk rows: nin coefficients read and nw entries written per row
+    void ddf_small_launch(const DdfCall& dc, const E* in, size_t ldin, size_t nin, E* out, size_t ldout, size_t nw, long long* deg, size_t lddeg,
+                          bool squarefree, size_t nblk, hipStream_t s) {
+        const E r1 = crate_one();
+        const TE rinv = rinv_table();
+        for_chunks(nblk, [&](size_t b0, size_t nb) {
+            ECFFT_LAUNCH(KC_POINTWISE, sizeof(E) * (double)nb * (double)(nin + nw) + 32.0, (k_ddf_small<F, (int)kDdfSmall>), dim3((unsigned)nb),
+                         dim3((unsigned)kDdfSmall), 0, s, in + b0 * ldin, ldin, (uint32_t)nin, out + b0 * ldout, ldout, (uint32_t)nw, deg + b0 * lddeg, lddeg,
+                         squarefree ? 1u : 0u, dc.dexp, dc.nbits_p, rinv, r1);
+        });
+    }
+    // The monic squarefree part of ONE polynomial of true length la > kDdfSmall + 1 (f: untrimmed, crate form) into sq (la elements):
+    // fm = f / lc(f), g = gcd_pair(fm, fm'), s = fm / g (divrem_body) where deg g > 0.  *ls = deg s + 1.  p exceeds every degree a
+    // tree holds (the C ABI asserts it), so f' = 0 only for constants and there is no p-th-power case.
+    bool squarefree_one_large(const E* f, size_t la, E* sq, size_t* ls, hipStream_t s) {
+        const size_t d = la - 1;
+        const E r1 = crate_one();
+        E* fm = temp(la); E* fd = temp(d); E* g = temp(la); E* lc = temp(1);
+        foreach_n(s, 1, [=] __device__(size_t) { lc[0] = F::canon(F::mul(F::inv(F::canon(f[d])), r1)); });
+        foreach_n(s, la, [=] __device__(size_t j) { E v = r1; if (j < d) v = F::canon(F::mul(f[j], lc[0])); fm[j] = v; });
+        foreach_n(s, d, [=] __device__(size_t j) { fd[j] = F::canon(F::mul(F::from_u32((uint32_t)(j + 1)), fm[j + 1])); });   // the plain integer j + 1 times a crate coefficient
+        long long dg = -1;
+        bool ok = gcd_pair(fm, la, fd, d, nullptr, 1, nullptr, 1, g, la, &dg, false, s);
+        if (!ok || dg < 0) return false;
+        *ls = la - (size_t)dg;
+        if (dg == 0) return hipMemcpyAsync(sq, fm, la * sizeof(E), hipMemcpyDeviceToDevice, s) == hipSuccess;
+        ok = divrem_body(fm, la, g, (size_t)dg + 1, sq, nullptr, 1, gcd_flag_, s);
+        return ok;
+    }
+    // The distinct-degree factors of ONE polynomial of nf > kDdfSmall + 1 coefficients: fac (device, nd = nf - 1 elements) and hdeg
+    // (host, nd entries), both zero on entry.  ddeg: nd device entries of work.
+    //   true length la <= kDdfSmall + 1, or deg s <= kDdfSmall after the squarefree part: k_ddf_small on that length.
+    //   otherwise the modulus s is kept ONCE for the row (keep_modulus: g = 1/rev(s) and s on T_N, N = powmod_leaves(deg s + 1));
+    //   h_1 = x^p mod s (roots_pow_kept); for i = 1, 2, ... while deg f* >= 2i: g = gcd_pair(f*, h_i - x), appended and divided out
+    //   (divrem_body) where its degree is positive; then, unless the loop is about to end, h_(i+1) by ddf_iterate_composes:
+    //     the kept composition h_i(h_1): h_1 lifted as the kept base and the baby steps taken before the first iterate that needs
+    //       them (compose_prepare), then compose_apply per iterate;
+    //     or the fresh power h_i^p: h_i lifted once (lift_and_keep), then poly_pow_mod's scan on the kept modulus.
+    //   What is left of f* is irreducible of its own degree.  The modulus stays s for the whole row.
+    // Temporaries beyond a step's own: 4 N elements (the kept g, s, h_1 and G or the lifted h_i), (k + 1 + k') deg s for the baby
+    // steps and chunk sums, and eight rows of at most nf.  Synchronous (gcd_pair reads degrees back).
+    bool ddf_one_large(const DdfCall& dc, const E* f, size_t nf, E* fac, long long* ddeg, long long* hdeg, hipStream_t s) {
+        const size_t K = kDdfSmall, nd = nf - 1;
+        const E r1 = crate_one();
+        const TE rinv = rinv_table();
+        size_t la = 0;
+        if (!gcd_row_lens(f, nf, nf, 1, &la, s)) return false;
+        auto small = [&](const E* p, size_t ld, size_t len) {     // the small regime on `len` coefficients: len - 1 entries (at least one)
+            const size_t nw = len > 1 ? len - 1 : 1;
+            ddf_small_launch(dc, p, ld, len ? len : 1, fac, nd, nw, ddeg, nd, false, 1, s);
+            return hipMemcpyAsync(hdeg, ddeg, nw * sizeof(long long), hipMemcpyDeviceToHost, s) == hipSuccess && hipStreamSynchronize(s) == hipSuccess;
+        };
+        if (la <= K + 1) return small(f, nf, la);
+        E* sq = temp(la);
+        size_t ls = 0;
+        if (!squarefree_one_large(f, la, sq, &ls, s)) return false;
+        if (ls <= K + 1) return small(sq, la, ls);
+        const size_t ds = ls - 1, N = powmod_leaves(ls);
+        E* kept = temp(4 * N); E* next = temp(ds);
+        E* h1 = temp(ds); E* hb[2] = {temp(ds), temp(ds)}; E* w = temp(ds);
+        E* fs[2] = {temp(ls), temp(ls)}; E* g = temp(ls);
+        KeptModulus km;
+        bool ok = keep_modulus(sq, ds, nullptr, 0, 0, 1, kept, gcd_flag_, &km, s);
+        ok = roots_pow_kept(sq, km, 0u, dc.ep, dc.nbits_p, h1, next, 1, s) && ok;
+        ok = hipMemcpyAsync(hb[0], h1, ds * sizeof(E), hipMemcpyDeviceToDevice, s) == hipSuccess && ok;
+        E* lifted = kept + 3 * N;                             // G of the kept composition, or the lifted h_i of a fresh power
+        KeptCompose kc;
+        const size_t k = compose_chunk(ds), kp = (ds + k - 1) / k;
+        const bool composes = ddf_iterate_composes(ds);
+        bool prepared = false;
+        if (composes) { kc.B = temp((k + 1) * ds); kc.C = temp(kp * ds); kc.G = lifted; }
+        const E* fcur = sq;
+        size_t e = ds, pos = 0;
+        int hi = 0, fi = 0;
+        for (size_t i = 1; ok && e >= 2 * i; ++i) {
+            const E* h = hb[hi];
+            {
+                const TempMark mark = temps_mark();
+                foreach_n(s, ds, [=] __device__(size_t j) { E v = F::canon(h[j]); if (j == 1) v = F::canon(F::sub(v, r1)); w[j] = v; });
+                long long dg = -1;
+                ok = gcd_pair(fcur, e + 1, w, ds, nullptr, 1, nullptr, 1, g, ls, &dg, false, s);
+                if (ok && dg > 0) {
+                    const size_t du = (size_t)dg;
+                    hdeg[i - 1] = dg;
+                    ok = hipMemcpyAsync(fac + pos, g, du * sizeof(E), hipMemcpyDeviceToDevice, s) == hipSuccess;
+                    if (ok && du < e) {
+                        ok = divrem_body(fcur, e + 1, g, du + 1, fs[fi], nullptr, 1, gcd_flag_, s);
+                        fcur = fs[fi]; fi ^= 1;
+                    }
+                    pos += du; e -= du;
+                }
+                temps_release(mark);
+            }
+            if (!ok || e < 2 * (i + 1)) break;
+            E* hn = hb[hi ^ 1];
+            const TempMark mark = temps_mark();
+            if (composes) {
+                if (!prepared) {
+                    ok = lift_and_keep(h1, ds, N, 1, kept + 2 * N, s) && ok;
+                    km.base = kept + 2 * N;
+                    ok = compose_prepare(km, h1, ds, ds, ds, 1, &kc, s) && ok;
+                    prepared = true;
+                }
+                ok = compose_apply(kc, h, hn, s) && ok;
+            } else {
+                ok = lift_and_keep(h, ds, N, 1, lifted, s) && ok;
+                ok = hipMemcpyAsync(hn, h, ds * sizeof(E), hipMemcpyDeviceToDevice, s) == hipSuccess && ok;
+                for (size_t bit = dc.nbits_p - 1; bit-- > 0;) {
+                    ok = powmod_step(hn, nullptr, km, 1, rinv, s) && ok;
+                    if ((dc.ep[bit >> 3] >> (bit & 7)) & 1) ok = powmod_step(hn, lifted, km, 1, rinv, s) && ok;
+                }
+            }
+            temps_release(mark);
+            hi ^= 1;
+        }
+        if (ok && e > 0) {
+            hdeg[e - 1] = (long long)e;
+            ok = hipMemcpyAsync(fac + pos, fcur, e * sizeof(E), hipMemcpyDeviceToDevice, s) == hipSuccess;
+        }
+        return ok && hipGetLastError() == hipSuccess;
+    }
+public:
+    // ecfft_poly_squarefree: out (count x nf, crate form) = the monic s_b = f_b / gcd(f_b, f_b'), zero-padded; degrees (host) = deg
+    // s_b, 0 for a non-zero constant (s = 1), -1 for the zero polynomial (a zero row).  nf <= kDdfSmall + 1: ONE launch of
+    // k_ddf_small in its squarefree mode for all rows.  Otherwise the rows run one after another: a short polynomial in a long row
+    // goes to the same kernel on its true length, the others to squarefree_one_large.  Synchronous.  Caller holds lock() and checks
+    // the tree rule (ddf_leaves).
+    bool poly_squarefree(const E* f, size_t nf, E* out, long long* degrees, size_t count, hipStream_t s) {
+        DdfCall dc;
+        bool ok = ddf_call_init(&dc, s);
+        long long* ddeg = temp_as<long long>(count);
+        if (nf <= kDdfSmall + 1) {
+            ddf_small_launch(dc, f, nf, nf, out, nf, nf, ddeg, 1, true, count, s);
+            ok = hipMemcpyAsync(degrees, ddeg, count * sizeof(long long), hipMemcpyDeviceToHost, s) == hipSuccess && ok;
+            return finish_api(s) && ok;
+        }
+        gcd_flag_ = new_flag(s);
+        ok = hipMemsetAsync(out, 0, count * nf * sizeof(E), s) == hipSuccess && ok;
+        for (size_t p = 0; p < count && ok; ++p) {
+            const TempMark mark = temps_mark();
+            const E* fp = f + p * nf;
+            size_t la = 0;
+            ok = gcd_row_lens(fp, nf, nf, 1, &la, s);
+            if (ok && la <= kDdfSmall + 1) {
+                ddf_small_launch(dc, fp, nf, la ? la : 1, out + p * nf, nf, la ? la : 1, ddeg + p, 1, true, 1, s);
+                ok = hipMemcpyAsync(&degrees[p], ddeg + p, sizeof(long long), hipMemcpyDeviceToHost, s) == hipSuccess && hipStreamSynchronize(s) == hipSuccess;
+            } else if (ok) {
+                size_t ls = 0;
+                ok = squarefree_one_large(fp, la, out + p * nf, &ls, s);
+                degrees[p] = (long long)ls - 1;
+            }
+            temps_release(mark);
+        }
+        return finish_api(s) && ok;
+    }
+    // ecfft_poly_distinct_degree: with nd = max(nf - 1, 1), degrees (host, count x nd): degrees[b][d-1] = deg g_d, the product of the
+    // monic irreducible factors of degree d of f_b (zero polynomial: -1, 0, 0, ...); factors (count x nd, crate form): the g_d of
+    // positive degree in ascending d, each as its low deg g_d coefficients, then zeros.  nf <= kDdfSmall + 1: ONE launch of
+    // k_ddf_small for all rows.  Otherwise the rows run one after another (their degree sequences differ): ddf_one_large.
+    // Synchronous.  Caller holds lock() and checks the tree rule (ddf_leaves).
+    bool poly_distinct_degree(const E* f, size_t nf, E* factors, long long* degrees, size_t count, hipStream_t s) {
+        DdfCall dc;
+        bool ok = ddf_call_init(&dc, s);
+        const size_t nd = nf > 1 ? nf - 1 : 1;
+        long long* ddeg = temp_as<long long>(count * nd);
+        if (nf <= kDdfSmall + 1) {
+            ddf_small_launch(dc, f, nf, nf, factors, nd, nd, ddeg, nd, false, count, s);
+            ok = hipMemcpyAsync(degrees, ddeg, count * nd * sizeof(long long), hipMemcpyDeviceToHost, s) == hipSuccess && ok;
+            return finish_api(s) && ok;
+        }
+        gcd_flag_ = new_flag(s);
+        ok = hipMemsetAsync(factors, 0, count * nd * sizeof(E), s) == hipSuccess && ok;
+        for (size_t i = 0; i < count * nd; ++i) degrees[i] = 0;
+        for (size_t p = 0; p < count && ok; ++p) {
+            const TempMark mark = temps_mark();
+            ok = ddf_one_large(dc, f + p * nf, nf, factors + p * nd, ddeg + p * nd, degrees + p * nd, s);
+            temps_release(mark);
+        }
+        return finish_api(s) && ok;
     }
 
     // coefficients of the reciprocal computed by k_series_base before the Newton steps take over (K0).  64 = one wave per pair: a

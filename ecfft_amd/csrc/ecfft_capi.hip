@@ -500,6 +500,46 @@ int run_poly_find_roots(ecfft_ctx* c, DeviceChain<F>& ch, const void* f, size_t 
     });
 }
 
+// ecfft_poly_squarefree / ecfft_poly_distinct_degree: synchronous (degrees are read back between the steps, and `degrees` is a
+// host array whatever `mem` is).  Nothing fails on the data.  Both share the tree rule of ecfft_poly_find_roots.
+template <class F>
+int ddf_check(DeviceChain<F>& ch, size_t nf, size_t count) {
+    using E = typename F::elem;
+    // square_free_factors (src/utils.rs:46-50) divides by gcd(f, f') and is right only while f' = 0 means "constant": the degree must
+    // stay below p.  No tree holds more than 2^kMaxLogN coefficients and both fields have p > 2^kMaxLogN, so there is no p-th-power case.
+    static_assert(kMaxLogN<F> < (sizeof(E) == 4 ? 31 : 255), "p exceeds the degree of every polynomial a tree holds");
+    static_assert(DeviceChain<F>::kDdfSmall + 1 == ECFFT_DDF_SMALL_MAX, "the header states the small regime's bound");
+    static_assert(sizeof(long long) == sizeof(int64_t), "degrees are read back as long long");
+    if (nf > SIZE_MAX / (64 * sizeof(E))) return ECFFT_ERR_BAD_ARG;
+    const size_t N = DeviceChain<F>::ddf_leaves(nf);                          // checked on the row length, before anything runs
+    if (N > 1 && N > ch.size()) return ECFFT_ERR_TREE_TOO_SMALL;
+    const size_t per = N > 4 * nf ? N : 4 * nf;
+    if (count > SIZE_MAX / (16 * per * sizeof(E))) return ECFFT_ERR_BAD_ARG;  // byte counts of the rows and temporaries must not wrap
+    return ECFFT_OK;
+}
+template <class F>
+int run_poly_squarefree(ecfft_ctx* c, DeviceChain<F>& ch, const void* f, size_t nf, void* out, int64_t* degrees, size_t count, int mem,
+                        void* stream) {
+    using E = typename F::elem;
+    if (!f || !out || !degrees) return ECFFT_ERR_BAD_ARG;
+    if (const int rc = ddf_check(ch, nf, count); rc != ECFFT_OK) return rc;
+    const size_t eb = count * sizeof(E);
+    return staged(c, ch, mem, stream, {{f, nf * eb}}, {{out, nf * eb}}, [&](auto d, auto o) -> int {
+        return ch.poly_squarefree((const E*)d[0], nf, (E*)o[0], (long long*)degrees, count, (hipStream_t)stream) ? ECFFT_OK : ECFFT_ERR_HIP;
+    });
+}
+template <class F>
+int run_poly_distinct_degree(ecfft_ctx* c, DeviceChain<F>& ch, const void* f, size_t nf, void* factors, int64_t* degrees, size_t count,
+                             int mem, void* stream) {
+    using E = typename F::elem;
+    if (!f || !factors || !degrees) return ECFFT_ERR_BAD_ARG;
+    if (const int rc = ddf_check(ch, nf, count); rc != ECFFT_OK) return rc;
+    const size_t eb = count * sizeof(E), nd = nf > 1 ? nf - 1 : 1;
+    return staged(c, ch, mem, stream, {{f, nf * eb}}, {{factors, nd * eb}}, [&](auto d, auto o) -> int {
+        return ch.poly_distinct_degree((const E*)d[0], nf, (E*)o[0], (long long*)degrees, count, (hipStream_t)stream) ? ECFFT_OK : ECFFT_ERR_HIP;
+    });
+}
+
 // standard = true: plain standard-form residues (the FFTree wire format) instead of the crate's in-memory representation
 template <class F>
 int table_of(DeviceChain<F>& ch, size_t m, int which, void* host_out, size_t cap, size_t* count, bool standard = false) {
@@ -1094,6 +1134,22 @@ int ecfft_poly_find_roots(ecfft_ctx* ctx, const void* f, size_t nf, void* roots,
     if (nf == 0 || count == 0) return ECFFT_ERR_BAD_ARG;
     return on_chain(ctx, [&](auto& ch) { return run_poly_find_roots(ctx, ch, f, nf, roots, n_roots, count, mem, stream); });
 }
+int ecfft_poly_squarefree(ecfft_ctx* ctx, const void* f, size_t nf, void* out, int64_t* degrees, size_t count, int mem, void* stream) {
+    if (nf == 0 || count == 0) return ECFFT_ERR_BAD_ARG;
+    return on_chain(ctx, [&](auto& ch) { return run_poly_squarefree(ctx, ch, f, nf, out, degrees, count, mem, stream); });
+}
+int ecfft_poly_distinct_degree(ecfft_ctx* ctx, const void* f, size_t nf, void* factors, int64_t* degrees, size_t count, int mem, void* stream) {
+    if (nf == 0 || count == 0) return ECFFT_ERR_BAD_ARG;
+    return on_chain(ctx, [&](auto& ch) { return run_poly_distinct_degree(ctx, ch, f, nf, factors, degrees, count, mem, stream); });
+}
+#ifdef ECFFT_TEST_HOOKS
+int ecfft_test_ddf_iterate(int mode) {
+    if (mode < 0 || mode > 2) return ECFFT_ERR_BAD_ARG;
+    DeviceChain<Secp256k1>::ddf_iterate_force() = mode;
+    DeviceChain<M31>::ddf_iterate_force() = mode;
+    return ECFFT_OK;
+}
+#endif  // ECFFT_TEST_HOOKS
 int ecfft_poly_eval_points(ecfft_ctx* ctx, const void* f, size_t nf, const void* points, size_t m, void* out, size_t count, int mem,
                            void* stream) {
     if (nf == 0 || m == 0 || count == 0) return ECFFT_ERR_BAD_ARG;

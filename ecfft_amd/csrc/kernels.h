@@ -2888,6 +2888,214 @@ __global__ __launch_bounds__(kBlock) void k_roots_rank(typename F::elem* __restr
 }
 
 // ---------------------------------------------------------------------------------------------
+// ecfft_poly_squarefree / ecfft_poly_distinct_degree (utils::square_free_factors and utils::distinct_degree_factors,
+// src/utils.rs:46-78, the latter with x^(p^i) where the reference takes x^(p i)).  A polynomial of degree <= K is finished by ONE
+// workgroup (k_ddf_small) on the pieces of k_roots_small and the Horner loop of k_compose_small; above that the host drives the
+// same loop on the poly_pow_mod / gcd / division bodies and a kept composition.
+// ---------------------------------------------------------------------------------------------
+// gcd_remainder_loop without cofactors on (R0, R1) with deg R0 = d0 known and R1 scanned below n1 coefficients: unlike
+// roots_gcd_rows, deg R1 may exceed d0 (the loop swaps first).  On return R0 is a non-zero multiple of the gcd (R1 = 0: R0 itself)
+// and the result its degree.
+template <class F>
+__device__ __forceinline__ int ddf_gcd_rows(typename F::elem*& R0, typename F::elem*& R1, int d0, int n1, int* sdeg, uint32_t t) {
+    using E = typename F::elem;
+    if (t < 2) sdeg[t] = -1;
+    __syncthreads();
+    if ((int)t < n1 && !F::is_zero(R1[t])) atomicMax(&sdeg[1], (int)t);
+    __syncthreads();
+    int d1 = sdeg[1];
+    __syncthreads();
+    if (t < 2) sdeg[t] = -1;
+    __syncthreads();
+    E* none = nullptr;
+    int c = 0;
+    gcd_remainder_loop<F>(R0, R1, d0, d1, none, none, none, none, c, c, 0u, 0, sdeg, t);
+    return d0;
+}
+// quo[0 .. e - du] = A / u for the monic A of degree e (low e plain coefficients in a) and the monic u of degree du <= e (low du
+// plain coefficients in u): the synthetic division of k_roots_small.  work: e + 1 entries; quo[e - du] = 1.  a, u, quo, work
+// are four different rows.
+template <class F>
+__device__ __forceinline__ void ddf_div_monic(typename F::elem* quo, typename F::elem* work, const typename F::elem* a, int e,
+                                              const typename F::elem* u, int du, uint32_t t) {
+    using E = typename F::elem;
+    if ((int)t < e) work[t] = a[t];
+    if (t == 0) work[e] = F::one();
+    __syncthreads();
+    for (int k = e - du; k >= 0; --k) {
+        const E qk = work[k + du];
+        if ((int)t < du) work[k + t] = F::canon(F::sub(work[k + t], F::canon(F::mul(qk, u[t]))));
+        if (t == 0) quo[k] = qk;
+        __syncthreads();
+    }
+}
+// The squarefree part (mode 1) or the distinct-degree factors (mode 0) of one polynomial of degree <= K in one workgroup of K
+// threads, everything in LDS.  Block b reads nin <= K + 1 coefficients (crate form, untrimmed, any non-zero leading coefficient)
+// at in + b*ldin.
+//   s = f / gcd(f, f') on the monic f (plain residues): f'_j = (j + 1) f_(j+1) with the plain integer j + 1, which is non-zero in
+//     the field because p > K; so f' = 0 only for constants and there is no p-th-power case.
+//   mode 1: out + b*ldout receives the nw <= K + 1 low coefficients of the monic s in crate form (its leading 1 included where it
+//     fits, zero above); deg_out[b*lddeg] = deg s, 0 for a non-zero constant (s = 1), -1 for the zero polynomial (a zero row).
+//   mode 0: h_1 = x^p mod s (roots_pow_scan, base x); then for i = 1, 2, ... while deg f* >= 2i (f* = s at first): g = gcd(f*,
+//     h_i - x) is the product of the irreducible factors of degree i; a g of positive degree is made monic, appended and divided
+//     out; h_(i+1) = h_i(h_1) mod s by Horner (deg s - 1 products of modmul_*), skipped when the loop is about to end.  What is
+//     left of f* has no factor of degree <= i and degree < 2(i + 1), so it is irreducible: g_(deg f*).  out + b*ldout receives
+//     nw <= K entries: the g_d of positive degree in ascending d, each as its low deg g_d coefficients (crate form), then zeros;
+//     deg_out[b*lddeg + d - 1] = deg g_d for d <= nw (zero polynomial: -1, 0, 0, ...).
+// Loop bounds are fixed at launch: the bit count of p and degrees <= K.  Every thread takes every barrier: degrees come from LDS
+// behind a barrier (gcd_remainder_loop).  exp_p: p as little-endian bytes, bit nbits_p - 1 set; rinv = R^-1 (table form), r1 = R.
+template <class F, int K>
+__global__ __launch_bounds__(K) void k_ddf_small(const typename F::elem* __restrict__ in, size_t ldin, uint32_t nin,
+                                                 typename F::elem* __restrict__ out, size_t ldout, uint32_t nw,
+                                                 long long* __restrict__ deg_out, size_t lddeg, uint32_t mode,
+                                                 const uint8_t* __restrict__ exp_p, uint32_t nbits_p, typename F::telem rinv,
+                                                 typename F::elem r1) {
+    using E = typename F::elem;
+    __shared__ E smod[K], sfs[K], sh1[K], shi[K], sres[K], sx[K], squo[K + 1], sout[K], sprod[2 * K], rows[2 * (K + 1)];
+    __shared__ E snorm;
+    __shared__ int sdeg[2], sdegs[K];
+    const uint32_t t = threadIdx.x;
+    const size_t b = blockIdx.x;
+    const E* fb = in + b * ldin;
+    E* ob = out + b * ldout;
+    long long* db = deg_out + b * lddeg;
+    // ---- the true degree, and the row made monic (plain residues f_t / f_d) ----
+    if (t == 0) sdeg[0] = -1;
+    sout[t] = F::zero();
+    sdegs[t] = 0;
+    __syncthreads();
+    E mine = F::zero();
+    if (t < nin) mine = F::canon(fb[t]);
+    if (!F::is_zero(mine)) atomicMax(&sdeg[0], (int)t);
+    if (t == 0 && nin == K + 1 && !F::is_zero(F::canon(fb[K]))) atomicMax(&sdeg[0], K);
+    __syncthreads();
+    const int d = sdeg[0];
+    int ds = d;                                              // deg s
+    if (d >= 1) {
+        if (t == 0) snorm = F::canon(F::inv(F::canon(fb[d])));
+        __syncthreads();
+        {
+            E v = F::zero();
+            if ((int)t < d) v = F::canon(F::mul(mine, snorm));
+            smod[t] = v;
+        }
+        __syncthreads();
+    }
+    if (d >= 2) {
+        // ---- s = f / gcd(f, f') ----
+        E* R0 = rows;
+        E* R1 = rows + K + 1;
+        if ((int)t < d) {
+            R0[t] = smod[t];
+            E v = F::from_u32(t + 1);
+            if ((int)t + 1 < d) v = F::canon(F::mul(v, smod[t + 1]));
+            R1[t] = v;
+        }
+        if (t == 0) R0[d] = F::one();
+        const int dg = roots_gcd_rows<F, K>(R0, R1, d, sdeg, t);
+        if (dg > 0) {
+            if (t == 0) snorm = F::canon(F::inv(R0[dg]));
+            __syncthreads();
+            if ((int)t < dg) sx[t] = F::canon(F::mul(R0[t], snorm));
+            __syncthreads();
+            ddf_div_monic<F>(squo, sprod, smod, d, sx, dg, t);
+            ds = d - dg;
+            {
+                E v = F::zero();
+                if ((int)t < ds) v = squo[t];
+                __syncthreads();
+                smod[t] = v;
+            }
+            __syncthreads();
+        }
+    }
+    if (mode) {
+        if (t < nw) {
+            E v = F::zero();
+            if ((int)t < ds) v = F::canon(F::mul(smod[t], r1));
+            if ((int)t == ds) v = r1;
+            ob[t] = v;
+        }
+        if (t == 0 && nw == K + 1) { E v = F::zero(); if (ds == K) v = r1; ob[K] = v; }
+        if (t == 0) db[0] = ds;
+        return;
+    }
+    int e = ds < 0 ? 0 : ds;                                 // deg f*
+    uint32_t pos = 0;                                        // coefficients appended so far
+    if (ds >= 2) {
+        sfs[t] = smod[t];
+        __syncthreads();
+        roots_pow_scan<F, K>(sres, sx, sprod, smod, (uint32_t)ds, 0u, exp_p, nbits_p, rinv, r1, t);
+        {
+            E v = F::zero();
+            if ((int)t < ds) v = sres[t];
+            sh1[t] = v;
+            shi[t] = v;
+        }
+        __syncthreads();
+        for (int i = 1; e >= 2 * i; ++i) {
+            E* R0 = rows;
+            E* R1 = rows + K + 1;
+            if ((int)t < e) R0[t] = sfs[t];
+            if (t == 0) R0[e] = F::one();
+            {
+                E v = shi[t];
+                if (t == 1) v = F::canon(F::sub(v, r1));
+                R1[t] = v;
+            }
+            const int dg = ddf_gcd_rows<F>(R0, R1, e, ds, sdeg, t);
+            if (dg > 0) {
+                if (t == 0) { snorm = F::canon(F::inv(R0[dg])); sdegs[i - 1] = dg; }
+                __syncthreads();
+                if ((int)t < dg) {
+                    const E v = F::canon(F::mul(R0[t], snorm));
+                    sx[t] = v;
+                    sout[pos + t] = F::canon(F::mul(v, r1));
+                }
+                __syncthreads();
+                if (dg < e) {
+                    ddf_div_monic<F>(squo, sprod, sfs, e, sx, dg, t);
+                    if ((int)t < e - dg) sfs[t] = squo[t];
+                    __syncthreads();
+                }
+                pos += (uint32_t)dg;
+                e -= dg;
+            }
+            if (e < 2 * (i + 1)) break;
+            // h_(i+1) = h_i(h_1) mod s
+            {
+                E v = F::zero();
+                if (t == 0) v = shi[ds - 1];
+                sres[t] = v;
+            }
+            __syncthreads();
+            for (int j = ds - 1; j-- > 0;) {
+                modmul_plain<F>(sx, sres, rinv, t);
+                modmul_reduce<F>(sprod, sx, sh1, smod, (uint32_t)ds, t);
+                if ((int)t < ds) {
+                    E v = sprod[t];
+                    if (t == 0) v = F::canon(F::add(v, shi[j]));
+                    sres[t] = v;
+                }
+                __syncthreads();
+            }
+            if ((int)t < ds) shi[t] = sres[t];
+            __syncthreads();
+        }
+    } else if (ds == 1) {
+        sfs[t] = smod[t];
+        __syncthreads();
+    }
+    if (e > 0) {
+        if ((int)t < e) sout[pos + t] = F::canon(F::mul(sfs[t], r1));
+        if (t == 0) sdegs[e - 1] = e;
+    }
+    if (t == 0 && d < 0) sdegs[0] = -1;
+    __syncthreads();
+    if (t < nw) { ob[t] = sout[t]; db[t] = sdegs[t]; }
+}
+
+// ---------------------------------------------------------------------------------------------
 // generic element-wise helper for tree construction: functor(i) for i < n
 // ---------------------------------------------------------------------------------------------
 template <class Fn>

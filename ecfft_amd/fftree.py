@@ -34,7 +34,7 @@ EXPORTS = ["ecfft_elem_size", "ecfft_build_fftree", "ecfft_fftree_new", "ecfft_c
            "ecfft_fftree_serialize", "ecfft_fftree_deserialize", "ecfft_tree_rational_maps", "ecfft_ctx_trim", "ecfft_comm_abort", "ecfft_comm_set_rccl_library", "ecfft_comm_set_link_striping",
            "ecfft_poly_mul", "ecfft_poly_inv_series", "ecfft_poly_divrem", "ecfft_poly_eval_points", "ecfft_poly_interpolate",
            "ecfft_poly_pow_mod", "ecfft_poly_mul_mod", "ecfft_poly_gcd", "ecfft_poly_xgcd", "ecfft_poly_find_roots",
-           "ecfft_poly_compose_mod",
+           "ecfft_poly_compose_mod", "ecfft_poly_squarefree", "ecfft_poly_distinct_degree",
            "ecfft_find_curve_candidate", "ecfft_curve_two_sylow", "ecfft_find_curve", "ecfft_build_fftree_on_curve"]
 # include/ecfft_hip.h ECFFT_GCD_SMALL_MAX: max(na, nb) up to which a gcd runs in one workgroup per pair, on any tree
 GCD_SMALL_MAX = 256
@@ -42,9 +42,11 @@ GCD_SMALL_MAX = 256
 ROOTS_SMALL_MAX = 65
 # include/ecfft_hip.h ECFFT_COMPOSE_SMALL_MAX: nm up to which poly_compose_mod runs Horner for a triple in one workgroup, on any tree
 COMPOSE_SMALL_MAX = 65
+# include/ecfft_hip.h ECFFT_DDF_SMALL_MAX: nf up to which poly_squarefree / poly_distinct_degree finish a polynomial in one workgroup, on any tree
+DDF_SMALL_MAX = 65
 
 # include/ecfft_hip_hooks.h: only in a build with -DECFFT_TEST_HOOKS (tests/hooks/libecfft_hip_hooks.so), never in the shipped library
-HOOK_EXPORTS = ['ecfft_selftest_field', 'ecfft_selfcheck_pointwise_z', 'ecfft_test_fail_next_collective', 'ecfft_selftest_blk16', 'ecfft_selftest_blk16_small', 'ecfft_test_fail_build_rank', 'ecfft_comm_init_projection', 'ecfft_selftest_blk32', 'ecfft_ctx_low_map', 'ecfft_curve_search_stats']
+HOOK_EXPORTS = ['ecfft_selftest_field', 'ecfft_selfcheck_pointwise_z', 'ecfft_test_fail_next_collective', 'ecfft_selftest_blk16', 'ecfft_selftest_blk16_small', 'ecfft_test_fail_build_rank', 'ecfft_comm_init_projection', 'ecfft_selftest_blk32', 'ecfft_ctx_low_map', 'ecfft_curve_search_stats', 'ecfft_test_ddf_iterate']
 
 EXCHANGE_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_void_p),
                                ctypes.POINTER(ctypes.c_size_t), ctypes.c_int, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_void_p),
@@ -86,6 +88,8 @@ def _bind(L):
     L.ecfft_poly_gcd.restype, L.ecfft_poly_gcd.argtypes = ci, [vp, vp, sz, vp, sz, vp, vp, sz, ci, vp]
     L.ecfft_poly_xgcd.restype, L.ecfft_poly_xgcd.argtypes = ci, [vp, vp, sz, vp, sz, vp, vp, vp, vp, sz, ci, vp]
     L.ecfft_poly_find_roots.restype, L.ecfft_poly_find_roots.argtypes = ci, [vp, vp, sz, vp, vp, sz, ci, vp]
+    L.ecfft_poly_squarefree.restype, L.ecfft_poly_squarefree.argtypes = ci, [vp, vp, sz, vp, vp, sz, ci, vp]
+    L.ecfft_poly_distinct_degree.restype, L.ecfft_poly_distinct_degree.argtypes = ci, [vp, vp, sz, vp, vp, sz, ci, vp]
     L.ecfft_tree_table.restype, L.ecfft_tree_table.argtypes = ci, [vp, sz, ci, vp, sz, ctypes.POINTER(sz)]
     L.ecfft_build_points.restype, L.ecfft_build_points.argtypes = ci, [ci, sz, vp, vp, vp]
     L.ecfft_device_info.restype, L.ecfft_device_info.argtypes = ci, [ci, ctypes.c_char_p, sz]
@@ -148,6 +152,7 @@ def _bind(L):
         L.ecfft_selftest_blk32.restype, L.ecfft_selftest_blk32.argtypes = ci, [vp, vp, vp, sz, ci]
         L.ecfft_ctx_low_map.restype, L.ecfft_ctx_low_map.argtypes = ci, [vp, ci]
         L.ecfft_curve_search_stats.restype, L.ecfft_curve_search_stats.argtypes = ci, [ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_double), sz, ci]
+        L.ecfft_test_ddf_iterate.restype, L.ecfft_test_ddf_iterate.argtypes = ci, [ci]
         L.ecfft_comm_init_projection.restype = ci
         L.ecfft_comm_init_projection.argtypes = [ci, ci, ci, ctypes.c_double, ctypes.c_double, ctypes.POINTER(vp)]
     return L
@@ -676,6 +681,59 @@ class FFTree:
             raise ValueError("poly_find_roots: empty operand, count = 0 or a context that holds no full tree")
         _check(rc)
         return roots, n_roots
+
+    def poly_squarefree(self, f, count=1):
+        """(s, degrees): the monic squarefree part s_b = f_b / gcd(f_b, f_b') (ecfft_poly_squarefree <-> utils::square_free_factors,
+        src/utils.rs:46-50, made monic) of `count` polynomials laid end to end, f of count * nf coefficients; rows need not be
+        trimmed.  s has count * nf coefficients, zero-padded; degrees is a numpy int64 array of deg s_b, 0 for a non-zero constant
+        (s = 1) and -1 for the zero polynomial (a zero row).  nf <= DDF_SMALL_MAX works on any tree (one launch for all rows);
+        otherwise a tree of next_pow2(2 nf - 1) leaves.  numpy arrays (host) or contiguous CUDA tensors (device, on the current
+        stream).  Synchronous."""
+        (f,), (pf,), new, mem, stream = self._poly_io([f])
+        assert count > 0 and f.shape[0] % count == 0
+        nf = f.shape[0] // count
+        out = new(count * nf)
+        degrees = np.empty(count, np.int64)
+        rc = self._L.ecfft_poly_squarefree(self._h, pf, nf, self._ptr(out) if nf else None, degrees.ctypes.data, count, mem, stream)
+        if rc == ERR_BAD_ARG:
+            raise ValueError("poly_squarefree: empty operand, count = 0 or a context that holds no full tree")
+        _check(rc)
+        return out, degrees
+
+    def poly_distinct_degree(self, f, count=1):
+        """(factors, degrees): the distinct-degree factorisation (ecfft_poly_distinct_degree <-> utils::distinct_degree_factors,
+        src/utils.rs:52-78, with x^(p^i) where the reference takes x^(p i)) of `count` polynomials laid end to end, f of count * nf
+        coefficients; rows need not be trimmed and multiplicities do not matter.  With nd = max(nf - 1, 1), degrees is a numpy int64
+        array of shape (count, nd): degrees[b, d-1] = deg g_d, g_d the product of the monic irreducible factors of degree d of f_b (the
+        zero polynomial: -1, 0, 0, ...).  factors has count * nd elements: row b holds the g_d of positive degree in ascending d, each
+        as its low deg g_d coefficients (the leading 1 is implied), then zeros; ddf_unpack(row, degrees[b]) makes a dict of them.
+        nf <= DDF_SMALL_MAX works on any tree (one launch for all rows); otherwise a tree of next_pow2(2 nf - 1) leaves.  numpy arrays
+        (host) or contiguous CUDA tensors (device, on the current stream).  Synchronous."""
+        (f,), (pf,), new, mem, stream = self._poly_io([f])
+        assert count > 0 and f.shape[0] % count == 0
+        nf = f.shape[0] // count
+        nd = max(nf - 1, 1)
+        factors = new(count * nd if nf else 0)
+        degrees = np.empty((count, nd), np.int64)
+        rc = self._L.ecfft_poly_distinct_degree(self._h, pf, nf, self._ptr(factors) if nf else None, degrees.ctypes.data, count, mem, stream)
+        if rc == ERR_BAD_ARG:
+            raise ValueError("poly_distinct_degree: empty operand, count = 0 or a context that holds no full tree")
+        _check(rc)
+        return factors, degrees
+
+    def ddf_unpack(self, row, degrees):
+        """One row of poly_distinct_degree as {d: g_d}: g_d the deg g_d + 1 coefficients of the product of the irreducible factors of
+        degree d, its leading 1 (in the crate's form) included.  Host arrays."""
+        row = np.ascontiguousarray(row, self.field.dtype)
+        std = np.zeros(self.field.shape(1), self.field.dtype)
+        std.flat[0] = 1
+        one = self.field.from_standard(std)
+        out, pos = {}, 0
+        for d, n in enumerate(np.asarray(degrees).tolist(), 1):
+            if n > 0:
+                out[d] = np.concatenate([row[pos:pos + n], one])
+                pos += n
+        return out
 
     # ---- the remaining FFTree algorithms (host numpy arrays; synchronous) ---------------------
     def _np(self, x):

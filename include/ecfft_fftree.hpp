@@ -8,6 +8,7 @@
 #include <array>
 #include <cstdint>
 #include <cstring>
+#include <map>
 #include <optional>
 #include <stdexcept>
 #include <string>
@@ -287,6 +288,44 @@ public:
         require(n >= 0, "find_roots: the zero polynomial (every element is a root)");
         roots.resize((size_t)n);
         return roots;
+    }
+    // the monic squarefree part f / gcd(f, f') (ecfft_poly_squarefree <-> utils::square_free_factors, src/utils.rs:46-50, made
+    // monic), trimmed: {1} for a non-zero constant.  f need not be trimmed.  The zero polynomial throws.  Up to ECFFT_DDF_SMALL_MAX
+    // coefficients on any tree; tree rule in ecfft_hip.h.  Synchronous.
+    std::vector<Elem> square_free(const std::vector<Elem>& f) const {
+        require(!f.empty(), "square_free: the polynomial must not be empty");
+        std::vector<Elem> s(f.size());
+        int64_t deg = 0;
+        check(ecfft_poly_squarefree(ctx_, f.data(), f.size(), s.data(), &deg, 1, ECFFT_MEM_HOST, nullptr));
+        require(deg >= 0, "square_free: the zero polynomial");
+        s.resize((size_t)deg + 1);
+        return s;
+    }
+    // degree d -> the monic product of the irreducible factors of degree d of f, with its leading 1 (ecfft_poly_distinct_degree <->
+    // utils::distinct_degree_factors, src/utils.rs:52-78, which returns such a BTreeMap; this one follows the definition at every
+    // degree, where the reference takes x^(p i) for x^(p^i)).  Multiplicities do not matter; a non-zero constant gives an empty map;
+    // the zero polynomial throws.  Tree rule as square_free.  Synchronous.
+    std::map<size_t, std::vector<Elem>> distinct_degree_factors(const std::vector<Elem>& f) const {
+        require(!f.empty(), "distinct_degree_factors: the polynomial must not be empty");
+        const size_t nd = f.size() > 1 ? f.size() - 1 : 1;
+        std::vector<Elem> fac(nd);
+        std::vector<int64_t> deg(nd);
+        check(ecfft_poly_distinct_degree(ctx_, f.data(), f.size(), fac.data(), deg.data(), 1, ECFFT_MEM_HOST, nullptr));
+        require(deg[0] >= 0, "distinct_degree_factors: the zero polynomial");
+        Elem std_one{}, one{};
+        const uint32_t u = 1;
+        std::memcpy(&std_one, &u, sizeof u);                    // standard form is little-endian
+        check(ecfft_elems_from_standard(F::id, &std_one, &one, 1));
+        std::map<size_t, std::vector<Elem>> out;
+        size_t pos = 0;
+        for (size_t d = 1; d <= nd; ++d) {
+            if (deg[d - 1] <= 0) continue;
+            std::vector<Elem> g(fac.data() + pos, fac.data() + pos + (size_t)deg[d - 1]);
+            g.push_back(one);
+            out.emplace(d, std::move(g));
+            pos += (size_t)deg[d - 1];
+        }
+        return out;
     }
     size_t device_bytes() const { return ecfft_ctx_device_bytes(ctx_); }     // HBM held between calls: tables + scratch
     // device-resident variants (pointers into HBM, caller's stream)

@@ -276,6 +276,38 @@ int ecfft_poly_xgcd(ecfft_ctx* ctx, const void* a, size_t na, const void* b, siz
 #define ECFFT_ROOTS_SMALL_MAX 65     /* nf up to which a polynomial is finished in one workgroup, on any tree */
 int ecfft_poly_find_roots(ecfft_ctx* ctx, const void* f, size_t nf, void* roots, int64_t* n_roots, size_t count, int mem, void* stream);
 
+/* The squarefree part and the distinct-degree factors of polynomials over the field: the deterministic core of factorisation.
+ *   ecfft_poly_squarefree      <-> ecfft::utils::square_free_factors(poly), made monic        src/utils.rs:46-50
+ *   ecfft_poly_distinct_degree <-> ecfft::utils::distinct_degree_factors(poly), see below     src/utils.rs:52-78
+ * Layout: f is count x nf coefficients in the crate's form; the rows NEED NOT BE TRIMMED and any non-zero leading coefficient is
+ * accepted.  Outputs are fully reduced, in the crate's form, and must not overlap f.  `degrees` is a HOST pointer whatever `mem` is.
+ * ecfft_poly_squarefree: out is count x nf; row b holds the monic s_b = f_b / gcd(f_b, f_b'), the product of the distinct monic
+ *   irreducible factors of f_b, zero-padded.  degrees[b] = deg s_b: 0 (s = 1) for a non-zero constant, -1 for the zero polynomial
+ *   (a zero row).  Both fields have p larger than any degree a tree holds, so f' = 0 only for constants: there is no p-th-power case.
+ * ecfft_poly_distinct_degree (any multiplicities: it takes the squarefree part first): with nd = max(nf - 1, 1), degrees is
+ *   count x nd and degrees[b][d-1] = deg g_d, where g_d is the product of all monic irreducible factors of degree d of f_b: d times
+ *   their number, 0 where there are none.  The zero polynomial gives degrees[b][0] = -1 and zeros; a non-zero constant all zeros.
+ *   factors is count x nd elements: row b holds the g_d with deg g_d > 0 in ascending d, laid end to end, each as its LOW deg g_d
+ *   coefficients (the leading 1 is implied); they sum to deg s_b <= nf - 1, and the rest of the row is zero.
+ * Method: h_1 = x^p mod s; for i = 1, 2, ...: g_i = gcd(f*, h_i - x) with every g_j, j < i, already divided out of f* (f* = s at
+ *   first), and h_(i+1) = x^(p^(i+1)) mod s = h_i(h_1) mod s, a modular composition (ecfft_poly_compose_mod) or the power h_i^p,
+ *   whichever takes fewer modular products.  Once deg f* < 2(i + 1), what is left is irreducible of its own degree.  There is no
+ *   randomness and the outputs are defined mathematically, so they are bit-exact.  The reference computes pow_mod(x^p, i), which
+ *   is x^(p i) and not x^(p^i): the two agree at i = 1 only, the one degree its own find_roots uses; this call returns the g_d of
+ *   the definition above for every d.
+ * ECFFT_DDF_SMALL_MAX: nf up to which a polynomial is finished by one workgroup, everything in LDS; all `count` rows are ONE
+ * launch.  Above it the polynomials run one after another on the bodies of ecfft_poly_gcd, ecfft_poly_divrem, ecfft_poly_pow_mod
+ * and ecfft_poly_compose_mod with the modulus s, x^p mod s and its baby steps kept for the whole row; a polynomial whose true
+ * length, or whose squarefree part, fits the workgroup kernel goes there.
+ * Tree: nf <= ECFFT_DDF_SMALL_MAX needs no transform (any tree).  Otherwise the rule of ecfft_poly_find_roots, next_pow2(2 nf - 1)
+ * leaves, checked on the row length before anything runs.  Else ECFFT_ERR_TREE_TOO_SMALL.
+ * ECFFT_ERR_BAD_ARG: a NULL pointer, nf or count 0, a context that holds no full tree, a byte count that would wrap.  Nothing
+ * fails on the data.  Both calls are SYNCHRONOUS.  Memory, stream, threading and pooled temporaries as for ecfft_poly_gcd. */
+#define ECFFT_DDF_SMALL_MAX 65       /* coefficients per row that one workgroup finishes, any tree */
+int ecfft_poly_squarefree(ecfft_ctx* ctx, const void* f, size_t nf, void* out, int64_t* degrees, size_t count, int mem, void* stream);
+int ecfft_poly_distinct_degree(ecfft_ctx* ctx, const void* f, size_t nf, void* factors, int64_t* degrees, size_t count, int mem,
+                               void* stream);
+
 /* The remaining FFTree algorithms, composed from the same GPU kernels.  Synchronous.
  *   ecfft_mextend         <-> FFTree::mextend(&self, &[F], Moiety)      src/fftree.rs:138-141
  *   ecfft_redc            <-> FFTree::redc_z0 / redc_z1(&self, evals, a)  src/fftree.rs:264-275  (moiety S0 / S1)

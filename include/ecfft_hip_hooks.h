@@ -59,6 +59,11 @@ int ecfft_ctx_low_map(const ecfft_ctx* ctx, int dir);
  * array that is not NULL, clears the counters when `reset` is set, returns how many entries there are.  Not thread safe. */
 int ecfft_curve_search_stats(uint64_t* lens, double* seconds, size_t cap, int reset);
 
+/* test / measurement hook, process wide: how the large regime of ecfft_poly_distinct_degree takes a Frobenius iterate h_(i+1) from
+ * h_i.  0: the shipped rule (the count of modular products)   1: always the kept composition h_i(h_1)   2: always the fresh power
+ * h_i^p on the kept modulus.  The outputs are the same bytes either way (tests/test_gpu_polyddf.py, tools/polyddf_time.py). */
+int ecfft_test_ddf_iterate(int mode);
+
 #ifdef __cplusplus
 }
 #endif
