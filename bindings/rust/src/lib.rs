@@ -61,6 +61,7 @@ pub mod ffi {
         pub fn ecfft_poly_compose_mod(ctx: *mut EcfftCtx, f: *const c_void, nf: usize, g: *const c_void, ng: usize, modulus: *const c_void, nm: usize, out: *mut c_void, count: usize, mem: i32, stream: *mut c_void) -> i32;
         pub fn ecfft_poly_squarefree(ctx: *mut EcfftCtx, f: *const c_void, nf: usize, out: *mut c_void, degrees: *mut i64, count: usize, mem: i32, stream: *mut c_void) -> i32;
         pub fn ecfft_poly_distinct_degree(ctx: *mut EcfftCtx, f: *const c_void, nf: usize, factors: *mut c_void, degrees: *mut i64, count: usize, mem: i32, stream: *mut c_void) -> i32;
+        pub fn ecfft_poly_equal_degree(ctx: *mut EcfftCtx, g: *const c_void, ng: usize, d: usize, factors: *mut c_void, n_factors: *mut i64, count: usize, mem: i32, stream: *mut c_void) -> i32;
         pub fn ecfft_poly_find_roots(ctx: *mut EcfftCtx, f: *const c_void, nf: usize, roots: *mut c_void, n_roots: *mut i64, count: usize, mem: i32, stream: *mut c_void) -> i32;
         pub fn ecfft_poly_gcd(ctx: *mut EcfftCtx, a: *const c_void, na: usize, b: *const c_void, nb: usize, g: *mut c_void, degrees: *mut i64, count: usize, mem: i32, stream: *mut c_void) -> i32;
         pub fn ecfft_poly_xgcd(ctx: *mut EcfftCtx, a: *const c_void, na: usize, b: *const c_void, nb: usize, s: *mut c_void, t: *mut c_void, g: *mut c_void, degrees: *mut i64, count: usize, mem: i32, stream: *mut c_void) -> i32;
@@ -453,6 +454,30 @@ impl<F: HipField> HipFFTree<F> {
             }
         }
         out
+    }
+
+    /// `ecfft::utils::equal_degree_factorization` (src/utils.rs:82-113): the monic irreducible factors of degree `d` of `f`, each
+    /// with its leading 1, in ascending lexicographic order of `(c_0, .., c_(d-1))` as standard-form integers.  `f` must be a
+    /// squarefree product of irreducibles of degree `d`, which is what `distinct_degree_factors` returns; it need not be trimmed or
+    /// monic.  A non-zero constant gives an empty vector.  Panics on the zero polynomial and where `d` does not divide the degree.
+    /// Deterministic: the shifts are 1, 2, 3, ... where the reference draws random polynomials.  Up to `ECFFT_EDF_SMALL_MAX`
+    /// coefficients work on any tree; tree rule: include/ecfft_hip.h.
+    pub fn equal_degree_factorization(&self, f: &[F], d: usize) -> Vec<Vec<F>> {
+        assert!(!f.is_empty() && d > 0);
+        let nd = core::cmp::max(f.len() - 1, 1);
+        let mut fac = Self::out_vec(nd);
+        let mut n = 0i64;
+        check(unsafe { ffi::ecfft_poly_equal_degree(self.ctx, f.as_ptr().cast(), f.len(), d, fac.as_mut_ptr().cast(), &mut n, 1, ffi::MEM_HOST, core::ptr::null_mut()) });
+        assert!(n != -1, "equal_degree_factorization: the zero polynomial");
+        assert!(n >= 0, "equal_degree_factorization: d does not divide the degree");
+        unsafe { fac.set_len(nd) };
+        (0..n as usize)
+            .map(|i| {
+                let mut q = fac[i * d..(i + 1) * d].to_vec();
+                q.push(F::one());
+                q
+            })
+            .collect()
     }
 
     /// `FFTree::mextend` (src/fftree.rs:138-141)

@@ -2553,6 +2553,46 @@ private:
         ok = divrem_body(fm, la, g, (size_t)dg + 1, sq, nullptr, 1, gcd_flag_, s);
         return ok;
     }
+    // The Frobenius iterates of one row on its kept modulus (degree ds, N leaves; `kept` holds 4 N elements, the modulus in the first
+    // two), as ddf_one_large and edf_one_large take them: h_(i+1) from h_i by ddf_iterate_composes, either
+    //   the kept composition h_i(h_1): h_1 lifted as the kept base (kept + 2 N) and the baby steps taken before the first iterate
+    //     that needs them (compose_prepare), then compose_apply per iterate, G at kept + 3 N;
+    //   or the fresh power h_i^p: h_i lifted once to kept + 3 N (lift_and_keep), then poly_pow_mod's scan on the kept modulus.
+    // frob_init takes the baby steps' and chunk sums' rows ((k + 1 + k') ds elements) where the composition is chosen.
+    struct FrobIterate { KeptModulus km; KeptCompose kc; const E* h1 = nullptr; E* kept = nullptr; bool composes = false, prepared = false; };
+    void frob_init(FrobIterate* fr, const KeptModulus& km, E* kept, const E* h1) {
+        const size_t ds = km.d, k = compose_chunk(ds), kp = (ds + k - 1) / k;
+        fr->km = km; fr->kept = kept; fr->h1 = h1;
+        fr->composes = ddf_iterate_composes(ds);
+        fr->prepared = false;
+        if (fr->composes) { fr->kc.B = temp((k + 1) * ds); fr->kc.C = temp(kp * ds); fr->kc.G = kept + 3 * km.N; }
+    }
+    // hn (ds elements) = h^p mod the kept modulus for h = x^(p^i): the next iterate.  ep: p as host bytes, bit nbits_p - 1 set.
+    bool frob_next(FrobIterate& fr, const E* h, E* hn, const uint8_t* ep, uint32_t nbits_p, hipStream_t s) {
+        const size_t ds = fr.km.d, N = fr.km.N;
+        const TE rinv = rinv_table();
+        E* lifted = fr.kept + 3 * N;                          // G of the kept composition, or the lifted h_i of a fresh power
+        bool ok = true;
+        const TempMark mark = temps_mark();
+        if (fr.composes) {
+            if (!fr.prepared) {
+                ok = lift_and_keep(fr.h1, ds, N, 1, fr.kept + 2 * N, s) && ok;
+                fr.km.base = fr.kept + 2 * N;
+                ok = compose_prepare(fr.km, fr.h1, ds, ds, ds, 1, &fr.kc, s) && ok;
+                fr.prepared = true;
+            }
+            ok = compose_apply(fr.kc, h, hn, s) && ok;
+        } else {
+            ok = lift_and_keep(h, ds, N, 1, lifted, s) && ok;
+            ok = hipMemcpyAsync(hn, h, ds * sizeof(E), hipMemcpyDeviceToDevice, s) == hipSuccess && ok;
+            for (size_t bit = nbits_p - 1; bit-- > 0;) {
+                ok = powmod_step(hn, nullptr, fr.km, 1, rinv, s) && ok;
+                if ((ep[bit >> 3] >> (bit & 7)) & 1) ok = powmod_step(hn, lifted, fr.km, 1, rinv, s) && ok;
+            }
+        }
+        temps_release(mark);
+        return ok;
+    }
     // The distinct-degree factors of ONE polynomial of nf > kDdfSmall + 1 coefficients: fac (device, nd = nf - 1 elements) and hdeg
     // (host, nd entries), both zero on entry.  ddeg: nd device entries of work.
     //   true length la <= kDdfSmall + 1, or deg s <= kDdfSmall after the squarefree part: k_ddf_small on that length.
@@ -2568,7 +2608,6 @@ private:
     bool ddf_one_large(const DdfCall& dc, const E* f, size_t nf, E* fac, long long* ddeg, long long* hdeg, hipStream_t s) {
         const size_t K = kDdfSmall, nd = nf - 1;
         const E r1 = crate_one();
-        const TE rinv = rinv_table();
         size_t la = 0;
         if (!gcd_row_lens(f, nf, nf, 1, &la, s)) return false;
         auto small = [&](const E* p, size_t ld, size_t len) {     // the small regime on `len` coefficients: len - 1 entries (at least one)
@@ -2589,12 +2628,8 @@ private:
         bool ok = keep_modulus(sq, ds, nullptr, 0, 0, 1, kept, gcd_flag_, &km, s);
         ok = roots_pow_kept(sq, km, 0u, dc.ep, dc.nbits_p, h1, next, 1, s) && ok;
         ok = hipMemcpyAsync(hb[0], h1, ds * sizeof(E), hipMemcpyDeviceToDevice, s) == hipSuccess && ok;
-        E* lifted = kept + 3 * N;                             // G of the kept composition, or the lifted h_i of a fresh power
-        KeptCompose kc;
-        const size_t k = compose_chunk(ds), kp = (ds + k - 1) / k;
-        const bool composes = ddf_iterate_composes(ds);
-        bool prepared = false;
-        if (composes) { kc.B = temp((k + 1) * ds); kc.C = temp(kp * ds); kc.G = lifted; }
+        FrobIterate fr;
+        frob_init(&fr, km, kept, h1);
         const E* fcur = sq;
         size_t e = ds, pos = 0;
         int hi = 0, fi = 0;
@@ -2618,25 +2653,7 @@ private:
                 temps_release(mark);
             }
             if (!ok || e < 2 * (i + 1)) break;
-            E* hn = hb[hi ^ 1];
-            const TempMark mark = temps_mark();
-            if (composes) {
-                if (!prepared) {
-                    ok = lift_and_keep(h1, ds, N, 1, kept + 2 * N, s) && ok;
-                    km.base = kept + 2 * N;
-                    ok = compose_prepare(km, h1, ds, ds, ds, 1, &kc, s) && ok;
-                    prepared = true;
-                }
-                ok = compose_apply(kc, h, hn, s) && ok;
-            } else {
-                ok = lift_and_keep(h, ds, N, 1, lifted, s) && ok;
-                ok = hipMemcpyAsync(hn, h, ds * sizeof(E), hipMemcpyDeviceToDevice, s) == hipSuccess && ok;
-                for (size_t bit = dc.nbits_p - 1; bit-- > 0;) {
-                    ok = powmod_step(hn, nullptr, km, 1, rinv, s) && ok;
-                    if ((dc.ep[bit >> 3] >> (bit & 7)) & 1) ok = powmod_step(hn, lifted, km, 1, rinv, s) && ok;
-                }
-            }
-            temps_release(mark);
+            ok = frob_next(fr, h, hb[hi ^ 1], dc.ep, dc.nbits_p, s) && ok;
             hi ^= 1;
         }
         if (ok && e > 0) {
@@ -2703,6 +2720,242 @@ public:
             temps_release(mark);
         }
         return finish_api(s) && ok;
+    }
+
+    // ---- ecfft_poly_equal_degree (utils::equal_degree_factorization, src/utils.rs:82-113) ----
+    // a polynomial of at most kEdfSmall + 1 coefficients is finished by k_edf_small, one workgroup each
+    static constexpr size_t kEdfSmall = kRootsSmall;
+    // The leaves the call needs for rows of ng coefficients, checked before anything runs: the rule of ecfft_poly_find_roots (the
+    // kept modulus g has at most ng coefficients; every pending factor, gcd and division is smaller)
+    static size_t edf_leaves(size_t ng) { return roots_leaves(ng); }
+private:
+    // what a call shares between its polynomials: p and (p - 1) / 2 as host and device bytes, and the flag of the attempt cap
+    struct EdfCall { const uint8_t* dexp = nullptr; uint8_t ep[32], eh[32]; uint32_t nbits_p = 0, nbits_h = 0; int* flag = nullptr; };
+    // one launch of k_edf_small over nblk rows or descriptors; the workspace of the h_i, d - 1 rows of the longest degree a
+    // workgroup can meet (nin - 1, or K for descriptors), is shared by the chunks, which run one after another on the stream
+    void edf_small_launch(const EdfCall& ec, const E* in, size_t ldin, size_t nin, size_t d, E* out, size_t ldout, const uint32_t* desc,
+                          long long* n_out, uint32_t c0, size_t nblk, double coeffs, hipStream_t s) {
+        const E r1 = crate_one();
+        const TE rinv = rinv_table();
+        const size_t chunk = nblk < ((size_t)1 << 16) ? nblk : (size_t)1 << 16;
+        const size_t nmax = desc || nin > kEdfSmall ? kEdfSmall : (nin ? nin - 1 : 0);
+        const size_t ldws = 2 * d <= nmax ? (d - 1) * nmax : 0;                // a row that splits has 2 d <= its degree
+        E* ws = ldws ? temp(chunk * ldws) : nullptr;
+        for_chunks(nblk, [&](size_t b0, size_t nb) {
+            ECFFT_LAUNCH(KC_POINTWISE, sizeof(E) * coeffs * (double)nb / (double)nblk + 64.0, (k_edf_small<F, (int)kEdfSmall>), dim3((unsigned)nb),
+                         dim3((unsigned)kEdfSmall), 0, s, desc ? in : in + b0 * ldin, ldin, (uint32_t)nin, (uint32_t)d, desc ? out : out + b0 * ldout,
+                         ldout, desc ? desc + 3 * b0 : (const uint32_t*)nullptr, n_out ? n_out + b0 : (long long*)nullptr, ws, ldws, c0, ec.dexp,
+                         ec.nbits_p, ec.dexp + 32, ec.nbits_h, rinv, r1, ec.flag);
+        });
+    }
+    // the canonical order: src (rows x lds, factors of d coefficients in any order) -> dst (rows x ldd), k_edf_rank on the standard
+    // form of src, converted once per element
+    void edf_rank_launch(E* dst, size_t ldd, const E* src, size_t lds, size_t d, const long long* n_dev, long long n_fixed, size_t rows,
+                         hipStream_t s) {
+        if (!ldd) return;
+        E* sf = temp(rows * lds);
+        const TE rinv = rinv_table();
+        foreach_n(s, rows * lds, [=] __device__(size_t i) {
+            E v = F::canon(src[i]);
+            if constexpr (sizeof(E) == 32) v = F::canon(F::tmul(rinv, v));
+            sf[i] = v;
+        });
+        for (size_t r0 = 0; r0 < rows; r0 += 32768) {
+            const size_t nr = rows - r0 < 32768 ? rows - r0 : 32768;
+            ECFFT_LAUNCH(KC_POINTWISE, sizeof(E) * 3.0 * (double)nr * (double)ldd, k_edf_rank<F>, dim3(nblocks(ldd), (unsigned)nr), dim3(kBlock), 0, s,
+                         dst + r0 * ldd, ldd, src + r0 * lds, (const E*)sf + r0 * lds, lds, (uint32_t)d, n_dev ? n_dev + r0 : (const long long*)nullptr,
+                         n_fixed);
+        }
+    }
+    // The irreducible factors of degree d of ONE polynomial of ng > kEdfSmall + 1 coefficients (untrimmed, crate form; a squarefree
+    // product of irreducibles of degree d) into fac (ng - 1 elements, ordered, zero on entry).
+    //   true degree <= kEdfSmall: k_edf_small on the true length.  Otherwise gm = g / lc(g) is kept ONCE for the row (keep_modulus
+    //   without a base), h_1 = x^p mod gm (roots_pow_kept, base x) and h_2 .. h_(d-1) by frob_next, kept as coefficient rows.
+    //   Rounds with one shift c = 1, 2, ... for all pending factors: N_c = (x + c) prod_i (h_i + c) mod gm, each h_i + c lifted for its
+    //   one powmod_step; per pending factor u != gm the base N_c mod u (divrem_body, remainder only); the factors grouped by
+    //   N = powmod_leaves(e + 1) and padded inside a group to its largest degree D as x^(D-e) u, ONE modular power per group with the
+    //   bases as rows (poly_pow_mod's large body: keep_modulus with the bases, then the powmod_step scan on (p - 1) / 2); per factor
+    //   gcd_pair(u, w - 1) and divrem_body.  A piece of degree d goes to the output, one of degree <= kEdfSmall to the leaf
+    //   buffer, the rest stay pending.  The leaves are finished by ONE launch of k_edf_small, then k_edf_rank orders the row.
+    // Temporaries beyond a step's own: 4 N for the kept modulus and the lifted operand, (d - 1) n for the h_i, the composition's
+    // baby steps, and the pending and leaf buffers of 2 n.  Synchronous (gcd_pair reads degrees back).
+    bool edf_one_large(const EdfCall& ec, const E* g, size_t ng, size_t d, E* fac, long long* n, hipStream_t s) {
+        const size_t K = kEdfSmall, nd = ng - 1;
+        const E r1 = crate_one();
+        const TE rinv = rinv_table();
+        *n = 0;
+        size_t la = 0;
+        if (!gcd_row_lens(g, ng, ng, 1, &la, s)) return false;
+        E* uns = temp(nd);                                    // the factors before they are ordered
+        if (la <= K + 1) {                                    // a short polynomial in a long row: the small regime on its true length
+            long long* dn = temp_as<long long>(1);
+            edf_small_launch(ec, g, ng, la ? la : 1, d, uns, nd, nullptr, dn, 1u, 1, (double)(la + K), s);
+            edf_rank_launch(fac, nd, uns, nd, d, dn, 0, 1, s);
+            return hipMemcpyAsync(n, dn, sizeof(long long), hipMemcpyDeviceToHost, s) == hipSuccess && hipStreamSynchronize(s) == hipSuccess;
+        }
+        const size_t dg = la - 1;
+        if (dg % d != 0) { *n = -2; return true; }
+        E* gm = temp(la); E* lc = temp(1);
+        foreach_n(s, 1, [=] __device__(size_t) { lc[0] = F::canon(F::mul(F::inv(F::canon(g[dg])), r1)); });
+        foreach_n(s, la, [=] __device__(size_t j) { E v = r1; if (j < dg) v = F::canon(F::mul(g[j], lc[0])); gm[j] = v; });
+        const size_t r = dg / d;
+        *n = (long long)r;
+        if (r == 1) return hipMemcpyAsync(fac, gm, d * sizeof(E), hipMemcpyDeviceToDevice, s) == hipSuccess;
+        // ---- the kept modulus and the Frobenius iterates, once for the row ----
+        const size_t N = powmod_leaves(la);
+        E* kept = temp(4 * N); E* next = temp(dg);
+        E* H = temp(d > 1 ? (d - 1) * dg : 1);                // h_1 .. h_(d-1), dg coefficients each
+        E* Nc = temp(dg); E* y = temp(dg);
+        KeptModulus km;
+        bool ok = keep_modulus(gm, dg, nullptr, 0, 0, 1, kept, gcd_flag_, &km, s);
+        if (d > 1) {
+            ok = roots_pow_kept(gm, km, 0u, ec.ep, ec.nbits_p, H, next, 1, s) && ok;
+            if (d > 2) {
+                FrobIterate fr;
+                frob_init(&fr, km, kept, H);
+                for (size_t i = 2; i < d && ok; ++i) ok = frob_next(fr, H + (i - 2) * dg, H + (i - 1) * dg, ec.ep, ec.nbits_p, s);
+            }
+        }
+        E* lifted = kept + 3 * N;                             // free once the iterates are taken: the lifted h_i + c of a norm's product
+        // pending factors packed with their leading 1 in two alternating buffers, leaves packed likewise
+        struct Fac { size_t off, e; uint32_t fails; };
+        E* pend[2] = {temp(2 * dg + 2), temp(2 * dg + 2)};
+        E* leaf = temp(2 * dg + 2);
+        std::vector<Fac> cur, nxt;
+        std::vector<uint32_t> ldesc;                          // (input offset, length, output offset) per leaf
+        size_t leaf_used = 0, out_used = 0;
+        ok = hipMemcpyAsync(pend[0], gm, la * sizeof(E), hipMemcpyDeviceToDevice, s) == hipSuccess && ok;
+        cur.push_back({0, dg, 0});
+        int pi = 0;
+        uint32_t c = 1;
+        for (; ok && !cur.empty(); ++c) {
+            const TempMark round = temps_mark();
+            nxt.clear();
+            size_t nxt_used = 0;
+            const E* P = pend[pi]; E* Q = pend[pi ^ 1];
+            auto keep = [&](const E* p, size_t e, uint32_t fails) {
+                if (e == d) {
+                    ok = hipMemcpyAsync(uns + out_used, p, d * sizeof(E), hipMemcpyDeviceToDevice, s) == hipSuccess && ok;
+                    out_used += d;
+                } else if (e <= K) {
+                    ok = hipMemcpyAsync(leaf + leaf_used, p, (e + 1) * sizeof(E), hipMemcpyDeviceToDevice, s) == hipSuccess && ok;
+                    ldesc.push_back((uint32_t)leaf_used); ldesc.push_back((uint32_t)(e + 1)); ldesc.push_back((uint32_t)out_used);
+                    leaf_used += e + 1; out_used += e;
+                } else {
+                    ok = hipMemcpyAsync(Q + nxt_used, p, (e + 1) * sizeof(E), hipMemcpyDeviceToDevice, s) == hipSuccess && ok;
+                    nxt.push_back({nxt_used, e, fails});
+                    nxt_used += e + 1;
+                }
+            };
+            // N_c modulo gm
+            {
+                const E c_crate = F::canon(F::mul(F::from_u32(c), r1));
+                foreach_n(s, dg, [=] __device__(size_t j) { E v = F::zero(); if (j == 0) v = c_crate; if (j == 1) v = r1; Nc[j] = v; });
+                for (size_t i = 1; i < d && ok; ++i) {
+                    const E* hi = H + (i - 1) * dg;
+                    foreach_n(s, dg, [=] __device__(size_t j) { E v = F::canon(hi[j]); if (j == 0) v = F::canon(F::add(v, c_crate)); y[j] = v; });
+                    ok = lift_and_keep(y, dg, N, 1, lifted, s) && ok;
+                    ok = powmod_step(Nc, lifted, km, 1, rinv, s) && ok;
+                }
+            }
+            std::vector<char> done(cur.size(), 0);
+            for (size_t i0 = 0; i0 < cur.size() && ok; ++i0) {
+                if (done[i0]) continue;
+                const size_t Ng = powmod_leaves(cur[i0].e + 1);
+                std::vector<size_t> grp;
+                size_t D = 0;
+                for (size_t i = i0; i < cur.size(); ++i)
+                    if (!done[i] && powmod_leaves(cur[i].e + 1) == Ng) { grp.push_back(i); done[i] = 1; if (cur[i].e > D) D = cur[i].e; }
+                const size_t cnt = grp.size(), nm = D + 1;
+                const TempMark gmk = temps_mark();
+                // the moduli x^(D - e) u and the bases N_c mod u, zero-padded to D coefficients
+                E* M = temp(cnt * nm); E* B = temp(cnt * D); E* W = temp(cnt * D);
+                ok = hipMemsetAsync(M, 0, cnt * nm * sizeof(E), s) == hipSuccess && ok;
+                ok = hipMemsetAsync(B, 0, cnt * D * sizeof(E), s) == hipSuccess && ok;
+                for (size_t i = 0; i < cnt && ok; ++i) {
+                    const Fac& fc = cur[grp[i]];
+                    ok = hipMemcpyAsync(M + i * nm + (D - fc.e), P + fc.off, (fc.e + 1) * sizeof(E), hipMemcpyDeviceToDevice, s) == hipSuccess;
+                    if (fc.e == dg) ok = hipMemcpyAsync(B + i * D, Nc, dg * sizeof(E), hipMemcpyDeviceToDevice, s) == hipSuccess && ok;
+                    else ok = divrem_body(Nc, dg, P + fc.off, fc.e + 1, nullptr, B + i * D, 1, gcd_flag_, s) && ok;
+                }
+                // W = B^((p-1)/2) modulo the rows of M
+                E* kept2 = temp(3 * cnt * Ng);
+                KeptModulus kg;
+                ok = ok && keep_modulus(M, D, B, D, D, cnt, kept2, gcd_flag_, &kg, s);
+                ok = hipMemcpyAsync(W, B, cnt * D * sizeof(E), hipMemcpyDeviceToDevice, s) == hipSuccess && ok;
+                for (size_t bit = ec.nbits_h - 1; ok && bit-- > 0;) {
+                    ok = powmod_step(W, nullptr, kg, cnt, rinv, s);
+                    if (ok && ((ec.eh[bit >> 3] >> (bit & 7)) & 1)) ok = powmod_step(W, kg.base, kg, cnt, rinv, s);
+                }
+                foreach_n(s, cnt, [=] __device__(size_t b) { W[b * D] = F::canon(F::sub(F::canon(W[b * D]), r1)); });
+                E* u = temp(D + 1); E* v = temp(D + 1); E* rem = temp(D + 1);
+                for (size_t i = 0; i < cnt && ok; ++i) {
+                    const Fac& fc = cur[grp[i]];
+                    const E* hp = P + fc.off;
+                    long long du = -1;
+                    const TempMark fmk = temps_mark();
+                    ok = gcd_pair(hp, fc.e + 1, W + i * D, D, nullptr, 1, nullptr, 1, u, D + 1, &du, false, s);
+                    if (ok && du > 0 && (size_t)du < fc.e) {
+                        if ((size_t)du % d != 0) ok = false;                // outside the precondition
+                        ok = ok && divrem_body(hp, fc.e + 1, u, (size_t)du + 1, v, rem, 1, gcd_flag_, s);
+                        keep(u, (size_t)du, 0);
+                        keep(v, fc.e - (size_t)du, 0);         // copied on the stream before the next factor reuses u and v
+                    } else if (ok) {
+                        if (fc.fails + 1 >= 64) ok = false;                 // the attempt cap of k_edf_small, for the same reason
+                        keep(hp, fc.e, fc.fails + 1);
+                    }
+                    temps_release(fmk);
+                }
+                temps_release(gmk);
+            }
+            cur.swap(nxt);
+            pi ^= 1;
+            temps_release(round);
+        }
+        if (!ok) return false;
+        // ---- the leaves: one launch, then the order ----
+        const size_t nleaf = ldesc.size() / 3;
+        if (nleaf) {
+            uint32_t* ddesc = temp_as<uint32_t>(ldesc.size());
+            ok = hipMemcpyAsync(ddesc, ldesc.data(), ldesc.size() * sizeof(uint32_t), hipMemcpyHostToDevice, s) == hipSuccess && hipStreamSynchronize(s) == hipSuccess;
+            edf_small_launch(ec, leaf, 0, 0, d, uns, 0, ddesc, nullptr, c, nleaf, (double)(leaf_used + out_used), s);
+        }
+        edf_rank_launch(fac, nd, uns, nd, d, nullptr, (long long)r, 1, s);
+        return ok && hipGetLastError() == hipSuccess;
+    }
+public:
+    // ecfft_poly_equal_degree: with nd = max(ng - 1, 1), factors (count x nd, crate form) = the n_factors[b] monic irreducible
+    // factors of degree d of g_b, each as its low d coefficients, in ascending lexicographic order of their standard form, then
+    // zeros; n_factors (host): their number, -1 for the zero polynomial, 0 for a non-zero constant, -2 where d does not divide the
+    // degree.  ng <= kEdfSmall + 1: ONE launch of k_edf_small for all rows and one of k_edf_rank.  Otherwise the polynomials run one
+    // after another (edf_one_large).  *capped = a factor exhausted the attempt cap.  Synchronous.  Caller holds lock() and checks
+    // the tree rule (edf_leaves).
+    bool poly_equal_degree(const E* g, size_t ng, size_t d, E* factors, long long* n_factors, size_t count, bool* capped, hipStream_t s) {
+        EdfCall ec;
+        roots_exponents(ec.ep, &ec.nbits_p, ec.eh, &ec.nbits_h);
+        uint8_t* dexp = temp_as<uint8_t>(64);
+        uint8_t both[64];
+        for (int i = 0; i < 32; ++i) { both[i] = ec.ep[i]; both[32 + i] = ec.eh[i]; }
+        bool ok = hipMemcpyAsync(dexp, both, 64, hipMemcpyHostToDevice, s) == hipSuccess && hipStreamSynchronize(s) == hipSuccess;
+        ec.dexp = dexp;
+        ec.flag = new_flag(s);
+        const size_t nd = ng > 1 ? ng - 1 : 1;
+        if (ng <= kEdfSmall + 1) {
+            long long* dn = temp_as<long long>(count);
+            E* uns = temp(count * nd);
+            edf_small_launch(ec, g, ng, ng, d, uns, nd, nullptr, dn, 1u, count, (double)count * (double)(ng + nd), s);
+            edf_rank_launch(factors, nd, uns, nd, d, dn, 0, count, s);
+            ok = hipMemcpyAsync(n_factors, dn, count * sizeof(long long), hipMemcpyDeviceToHost, s) == hipSuccess && ok;
+        } else {
+            gcd_flag_ = new_flag(s);
+            ok = hipMemsetAsync(factors, 0, count * nd * sizeof(E), s) == hipSuccess && ok;
+            for (size_t p = 0; p < count && ok; ++p) {
+                const TempMark mark = temps_mark();
+                ok = edf_one_large(ec, g + p * ng, ng, d, factors + p * nd, &n_factors[p], s);
+                temps_release(mark);
+            }
+        }
+        return finish_flagged(ok, ec.flag, capped, s);
     }
 
     // coefficients of the reciprocal computed by k_series_base before the Newton steps take over (K0).  64 = one wave per pair: a

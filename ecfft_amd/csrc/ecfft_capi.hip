@@ -540,6 +540,31 @@ int run_poly_distinct_degree(ecfft_ctx* c, DeviceChain<F>& ch, const void* f, si
     });
 }
 
+// ecfft_poly_equal_degree: synchronous (degrees are read back between the rounds, and `n_factors` is a host array whatever `mem`
+// is).  Nothing fails on the data; ECFFT_ERR_HIP also reports a factor that exhausted the attempt cap.
+template <class F>
+int run_poly_equal_degree(ecfft_ctx* c, DeviceChain<F>& ch, const void* g, size_t ng, size_t d, void* factors, int64_t* n_factors,
+                          size_t count, int mem, void* stream) {
+    using E = typename F::elem;
+    if (!g || !factors || !n_factors) return ECFFT_ERR_BAD_ARG;
+    if (ng > SIZE_MAX / (64 * sizeof(E))) return ECFFT_ERR_BAD_ARG;
+    static_assert(DeviceChain<F>::kEdfSmall + 1 == ECFFT_EDF_SMALL_MAX, "the header states the small regime's bound");
+    static_assert(sizeof(long long) == sizeof(int64_t), "factor counts are read back as long long");
+    const size_t N = DeviceChain<F>::edf_leaves(ng);                          // checked on the row length, before anything runs
+    if (N > 1 && N > ch.size()) return ECFFT_ERR_TREE_TOO_SMALL;
+    size_t per = N > 4 * ng ? N : 4 * ng;
+    const size_t dm = d < ng ? d : ng;                                        // a d above every degree the row can hold divides none: ng stands for it
+    if (dm > SIZE_MAX / (64 * sizeof(E)) / ng) return ECFFT_ERR_BAD_ARG;
+    if (per < dm * ng) per = dm * ng;
+    if (count > SIZE_MAX / (16 * per * sizeof(E))) return ECFFT_ERR_BAD_ARG;  // byte counts of the rows and temporaries must not wrap
+    const size_t eb = count * sizeof(E), nd = ng > 1 ? ng - 1 : 1;
+    return staged(c, ch, mem, stream, {{g, ng * eb}}, {{factors, nd * eb}}, [&](auto dv, auto o) -> int {
+        bool capped = false;
+        if (!ch.poly_equal_degree((const E*)dv[0], ng, dm, (E*)o[0], (long long*)n_factors, count, &capped, (hipStream_t)stream)) return ECFFT_ERR_HIP;
+        return capped ? ECFFT_ERR_HIP : ECFFT_OK;
+    });
+}
+
 // standard = true: plain standard-form residues (the FFTree wire format) instead of the crate's in-memory representation
 template <class F>
 int table_of(DeviceChain<F>& ch, size_t m, int which, void* host_out, size_t cap, size_t* count, bool standard = false) {
@@ -1141,6 +1166,11 @@ int ecfft_poly_squarefree(ecfft_ctx* ctx, const void* f, size_t nf, void* out, i
 int ecfft_poly_distinct_degree(ecfft_ctx* ctx, const void* f, size_t nf, void* factors, int64_t* degrees, size_t count, int mem, void* stream) {
     if (nf == 0 || count == 0) return ECFFT_ERR_BAD_ARG;
     return on_chain(ctx, [&](auto& ch) { return run_poly_distinct_degree(ctx, ch, f, nf, factors, degrees, count, mem, stream); });
+}
+int ecfft_poly_equal_degree(ecfft_ctx* ctx, const void* g, size_t ng, size_t d, void* factors, int64_t* n_factors, size_t count, int mem,
+                            void* stream) {
+    if (ng == 0 || d == 0 || count == 0) return ECFFT_ERR_BAD_ARG;
+    return on_chain(ctx, [&](auto& ch) { return run_poly_equal_degree(ctx, ch, g, ng, d, factors, n_factors, count, mem, stream); });
 }
 #ifdef ECFFT_TEST_HOOKS
 int ecfft_test_ddf_iterate(int mode) {

@@ -3096,6 +3096,240 @@ __global__ __launch_bounds__(K) void k_ddf_small(const typename F::elem* __restr
 }
 
 // ---------------------------------------------------------------------------------------------
+// ecfft_poly_equal_degree (utils::equal_degree_factorization, src/utils.rs:82-113, with the splitting element taken through the
+// norm).  A polynomial or factor of degree <= K is finished by ONE workgroup (k_edf_small); above that the host drives rounds on
+// the kept modulus and the poly_pow_mod / gcd / division bodies that end in the same kernel, and k_edf_rank puts the factors in
+// their canonical order.
+// ---------------------------------------------------------------------------------------------
+// sres (e residues, crate form) = sbase^exp mod h for the monic h of degree e whose low e coefficients smod holds as PLAIN
+// residues and a general base of e crate-form coefficients in LDS: k_powmod_small's scan on its product (modmul_*).  exp: nbits
+// >= 1 bits, bit nbits - 1 set.
+template <class F>
+__device__ __forceinline__ void edf_pow_scan(typename F::elem* sres, typename F::elem* sx, typename F::elem* sprod,
+                                             const typename F::elem* sbase, const typename F::elem* smod, uint32_t e,
+                                             const uint8_t* __restrict__ exp, uint32_t nbits, const typename F::telem& rinv, uint32_t t) {
+    sres[t] = sbase[t];
+    __syncthreads();
+    for (uint32_t i = nbits - 1; i-- > 0;) {
+        const uint32_t passes = 1 + ((exp[i >> 3] >> (i & 7)) & 1);     // a squaring, then on a set bit a product with the base
+        for (uint32_t pass = 0; pass < passes; ++pass) {
+            modmul_plain<F>(sx, sres, rinv, t);
+            modmul_reduce<F>(sprod, sx, pass ? sbase : sres, smod, e, t);
+            if (t < e) sres[t] = sprod[t];
+            __syncthreads();
+        }
+    }
+}
+// The monic irreducible factors of degree dd of one polynomial, or of one factor, of degree n <= K in one workgroup of K threads.
+// Block b reads nin <= K + 1 coefficients (crate form, untrimmed, any non-zero leading coefficient) at in + b*ldin, taken to be a
+// squarefree product of r = n / dd irreducibles of degree dd, and writes them, each as its low dd coefficients in crate form and
+// in NO particular order, from out + b*ldout on; desc != nullptr gives block b the triple (input offset, input length, output
+// offset) instead.  n_out[b] (may be null) = r; -1 for the zero polynomial, 0 for a non-zero constant, -2 where dd does not
+// divide n (nothing is written in these three cases).  n = dd: the row itself, made monic.
+//   Otherwise h_1 = x^p mod g (roots_pow_scan, base x) and h_i = h_(i-1)(h_1) mod g for i = 2 .. dd - 1 by Horner's loop of
+//   k_compose_small, as k_ddf_small takes them; the dd - 1 residues go to the block's global workspace ws + b*ldws (row i - 1 at a
+//   stride of n; thread t writes and later reads element t only), because they are read once per attempt and do not fit in LDS.
+//   Then a stack of monic factors as in k_roots_small: a factor of degree dd is written out; a factor h of degree e > dd is
+//   attacked with the next shift c = c0, c0 + 1, ... (one counter per workgroup): the norm N_c = prod_{i<dd} (h_i + c) mod g
+//   (dd - 1 products, h_0 = x), reduced modulo h by synthetic division; w = N_c^((p-1)/2) mod h (edf_pow_scan), which is
+//   (x + c)^((p^dd - 1)/2); u = gcd(h, w - 1), v = h / u, a success when 0 < deg u < e.
+// Loop bounds are fixed at launch: the exponents' bit counts, degrees <= K, dd <= K and kCap consecutive failed shifts of one
+// factor, after which *flag = 1 and the workgroup stops; so does a split whose degree dd does not divide (an input outside the
+// precondition).  Every thread takes every barrier: degrees come from LDS behind a barrier.
+template <class F, int K>
+__global__ __launch_bounds__(K) void k_edf_small(const typename F::elem* __restrict__ in, size_t ldin, uint32_t nin, uint32_t dd,
+                                                 typename F::elem* __restrict__ out, size_t ldout, const uint32_t* __restrict__ desc,
+                                                 long long* __restrict__ n_out, typename F::elem* __restrict__ ws, size_t ldws,
+                                                 uint32_t c0, const uint8_t* __restrict__ exp_p, uint32_t nbits_p,
+                                                 const uint8_t* __restrict__ exp_h, uint32_t nbits_h, typename F::telem rinv,
+                                                 typename F::elem r1, int* __restrict__ flag) {
+    using E = typename F::elem;
+    constexpr uint32_t kCap = 64;
+    __shared__ E sg[K], stack[K], smod[K], sbase[K], sres[K], sx[K], sprod[2 * K], rows[2 * (K + 1)];
+    __shared__ E snorm;
+    __shared__ int sdeg[2], stk_deg[K], stk_off[K];
+    const uint32_t t = threadIdx.x;
+    const size_t b = blockIdx.x;
+    const E* fb = in + b * ldin;
+    E* ob = out + b * ldout;
+    E* wb = ws + b * ldws;
+    if (desc) { fb = in + desc[3 * b]; nin = desc[3 * b + 1]; ob = out + desc[3 * b + 2]; }
+    // ---- the true degree, and the row made monic (plain residues g_t / g_n) ----
+    if (t == 0) sdeg[0] = -1;
+    __syncthreads();
+    E mine = F::zero();
+    if (t < nin) mine = F::canon(fb[t]);
+    if (!F::is_zero(mine)) atomicMax(&sdeg[0], (int)t);
+    if (t == 0 && nin == K + 1 && !F::is_zero(F::canon(fb[K]))) atomicMax(&sdeg[0], K);
+    __syncthreads();
+    const int n = sdeg[0];
+    if (n <= 0 || (uint32_t)n % dd != 0) {
+        if (t == 0 && n_out) n_out[b] = n <= 0 ? n : -2;
+        return;
+    }
+    if (t == 0) snorm = F::canon(F::inv(F::canon(fb[n])));
+    __syncthreads();
+    {
+        E v = F::zero();
+        if ((int)t < n) v = F::canon(F::mul(mine, snorm));
+        sg[t] = v;
+    }
+    __syncthreads();
+    const uint32_t r = (uint32_t)n / dd;
+    if (r == 1) {
+        if (t < dd) ob[t] = F::canon(F::mul(sg[t], r1));
+        if (t == 0 && n_out) n_out[b] = 1;
+        return;
+    }
+    // ---- h_1 .. h_(dd-1) modulo g, into the workspace; stack doubles as h_i and sbase as h_1 until the recursion starts ----
+    if (dd >= 2) {
+        roots_pow_scan<F, K>(sres, sx, sprod, sg, (uint32_t)n, 0u, exp_p, nbits_p, rinv, r1, t);
+        {
+            E v = F::zero();
+            if ((int)t < n) { v = sres[t]; wb[t] = v; }
+            sbase[t] = v;
+            stack[t] = v;
+        }
+        __syncthreads();
+        for (uint32_t i = 2; i < dd; ++i) {
+            {
+                E v = F::zero();
+                if (t == 0) v = stack[n - 1];
+                sres[t] = v;
+            }
+            __syncthreads();
+            for (int j = n - 1; j-- > 0;) {
+                modmul_plain<F>(sx, sres, rinv, t);
+                modmul_reduce<F>(sprod, sx, sbase, sg, (uint32_t)n, t);
+                if ((int)t < n) {
+                    E v = sprod[t];
+                    if (t == 0) v = F::canon(F::add(v, stack[j]));
+                    sres[t] = v;
+                }
+                __syncthreads();
+            }
+            if ((int)t < n) { const E v = sres[t]; stack[t] = v; wb[(size_t)(i - 1) * (uint32_t)n + t] = v; }
+            __syncthreads();
+        }
+    }
+    stack[t] = sg[t];
+    if (t == 0) { stk_deg[0] = n; stk_off[0] = 0; }
+    __syncthreads();
+    // ---- the splitting recursion on the stack ----
+    int sp = 1;
+    uint32_t c = c0, fails = 0, nout = 0;
+    while (sp > 0) {
+        const int e = stk_deg[sp - 1], base = stk_off[sp - 1];
+        if ((uint32_t)e == dd) {
+            if (t < dd) ob[(size_t)nout * dd + t] = F::canon(F::mul(stack[base + t], r1));
+            ++nout; --sp;
+            continue;
+        }
+        const E cR = F::canon(F::mul(F::from_u32(c), r1));
+        // N_c = (x + c) prod_i (h_i + c) mod g
+        {
+            E v = F::zero();
+            if ((int)t < e) v = stack[base + t];
+            smod[t] = v;
+            v = F::zero();
+            if (t == 0) v = cR;
+            if (t == 1) v = r1;
+            sres[t] = v;
+        }
+        __syncthreads();
+        for (uint32_t i = 1; i < dd; ++i) {
+            {
+                E v = F::zero();
+                if ((int)t < n) v = wb[(size_t)(i - 1) * (uint32_t)n + t];
+                if (t == 0) v = F::canon(F::add(v, cR));
+                sbase[t] = v;
+            }
+            modmul_plain<F>(sx, sres, rinv, t);
+            modmul_reduce<F>(sprod, sx, sbase, sg, (uint32_t)n, t);
+            if ((int)t < n) sres[t] = sprod[t];
+            __syncthreads();
+        }
+        // N_c mod h: the remainder side of the synthetic division by the monic h, in place
+        for (int k = n - 1 - e; k >= 0; --k) {
+            const E qk = sres[k + e];
+            if ((int)t < e) sres[k + t] = F::canon(F::sub(sres[k + t], F::canon(F::mul(qk, smod[t]))));
+            __syncthreads();
+        }
+        {
+            E v = F::zero();
+            if ((int)t < e) v = sres[t];
+            __syncthreads();
+            sbase[t] = v;
+        }
+        __syncthreads();
+        edf_pow_scan<F>(sres, sx, sprod, sbase, smod, (uint32_t)e, exp_h, nbits_h, rinv, t);
+        E* R0 = rows;
+        E* R1 = rows + K + 1;
+        if ((int)t < e) {
+            E v = sres[t];
+            if (t == 0) v = F::canon(F::sub(v, r1));
+            R1[t] = v;
+            R0[t] = smod[t];
+        }
+        if (t == 0) R0[e] = F::one();
+        const int du = roots_gcd_rows<F, K>(R0, R1, e, sdeg, t);
+        ++c;
+        if (du <= 0 || du >= e) {
+            if (++fails >= kCap) { if (t == 0) *flag = 1; break; }
+            continue;
+        }
+        if ((uint32_t)du % dd != 0) { if (t == 0) *flag = 1; break; }
+        fails = 0;
+        // u = R0 / lc(R0) (sx); v = h / u by synthetic division of A = h (sprod, with its leading 1) -> sres
+        if (t == 0) snorm = F::canon(F::inv(R0[du]));
+        __syncthreads();
+        if ((int)t < du) sx[t] = F::canon(F::mul(R0[t], snorm));
+        __syncthreads();
+        ddf_div_monic<F>(sres, sprod, smod, e, sx, du, t);
+        if ((int)t < du) stack[base + t] = sx[t];
+        if ((int)t < e - du) stack[base + du + t] = sres[t];
+        if (t == 0) { stk_deg[sp - 1] = du; stk_deg[sp] = e - du; stk_off[sp] = base + du; }
+        ++sp;
+        __syncthreads();
+    }
+    if (t == 0 && n_out) n_out[b] = (long long)nout;
+}
+// Row r (blockIdx.y) of dst (ldd elements) = the n distinct factors of row r of src (lds apart, dd crate-form coefficients each,
+// any order) in ascending lexicographic order of (c_0, .., c_(dd-1)) as standard-form integers, zero above: k_roots_rank for rows
+// of dd elements.  stdf holds src in standard form (same layout), converted once per element before the launch; the compare exits
+// at the first differing coefficient.  Thread i < n scatters factor i to dd * rank(i); the threads from n dd on zero the tail.
+// n = n_dev[r] (negative: 0) or n_fixed.
+template <class F>
+__global__ __launch_bounds__(kBlock) void k_edf_rank(typename F::elem* __restrict__ dst, size_t ldd, const typename F::elem* __restrict__ src,
+                                                     const typename F::elem* __restrict__ stdf, size_t lds, uint32_t dd,
+                                                     const long long* __restrict__ n_dev, long long n_fixed) {
+    using E = typename F::elem;
+    const size_t r = blockIdx.y, i = (size_t)blockIdx.x * kBlock + threadIdx.x;
+    long long nn = n_dev ? n_dev[r] : n_fixed;
+    if (nn < 0) nn = 0;
+    const size_t n = (size_t)nn < ldd / dd ? (size_t)nn : ldd / dd;
+    const E* sr = src + r * lds;
+    const E* ss = stdf + r * lds;
+    if (i < n) {
+        const E* me = ss + i * dd;
+        size_t rank = 0;
+        for (size_t j = 0; j < n; ++j) {
+            const E* o = ss + j * dd;
+            bool lt = false;
+            for (uint32_t k = 0; k < dd; ++k) {
+                const E a = o[k], m = me[k];
+                if (roots_less<F>(a, m)) { lt = true; break; }
+                if (roots_less<F>(m, a)) break;
+            }
+            rank += lt ? 1u : 0u;
+        }
+        for (uint32_t k = 0; k < dd; ++k) dst[r * ldd + rank * dd + k] = F::canon(sr[i * dd + k]);
+    } else if (i >= n * dd && i < ldd) {
+        dst[r * ldd + i] = F::zero();
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
 // generic element-wise helper for tree construction: functor(i) for i < n
 // ---------------------------------------------------------------------------------------------
 template <class Fn>

@@ -34,7 +34,7 @@ EXPORTS = ["ecfft_elem_size", "ecfft_build_fftree", "ecfft_fftree_new", "ecfft_c
            "ecfft_fftree_serialize", "ecfft_fftree_deserialize", "ecfft_tree_rational_maps", "ecfft_ctx_trim", "ecfft_comm_abort", "ecfft_comm_set_rccl_library", "ecfft_comm_set_link_striping",
            "ecfft_poly_mul", "ecfft_poly_inv_series", "ecfft_poly_divrem", "ecfft_poly_eval_points", "ecfft_poly_interpolate",
            "ecfft_poly_pow_mod", "ecfft_poly_mul_mod", "ecfft_poly_gcd", "ecfft_poly_xgcd", "ecfft_poly_find_roots",
-           "ecfft_poly_compose_mod", "ecfft_poly_squarefree", "ecfft_poly_distinct_degree",
+           "ecfft_poly_compose_mod", "ecfft_poly_squarefree", "ecfft_poly_distinct_degree", "ecfft_poly_equal_degree",
            "ecfft_find_curve_candidate", "ecfft_curve_two_sylow", "ecfft_find_curve", "ecfft_build_fftree_on_curve"]
 # include/ecfft_hip.h ECFFT_GCD_SMALL_MAX: max(na, nb) up to which a gcd runs in one workgroup per pair, on any tree
 GCD_SMALL_MAX = 256
@@ -44,6 +44,8 @@ ROOTS_SMALL_MAX = 65
 COMPOSE_SMALL_MAX = 65
 # include/ecfft_hip.h ECFFT_DDF_SMALL_MAX: nf up to which poly_squarefree / poly_distinct_degree finish a polynomial in one workgroup, on any tree
 DDF_SMALL_MAX = 65
+# include/ecfft_hip.h ECFFT_EDF_SMALL_MAX: ng up to which poly_equal_degree finishes a polynomial in one workgroup, on any tree
+EDF_SMALL_MAX = 65
 
 # include/ecfft_hip_hooks.h: only in a build with -DECFFT_TEST_HOOKS (tests/hooks/libecfft_hip_hooks.so), never in the shipped library
 HOOK_EXPORTS = ['ecfft_selftest_field', 'ecfft_selfcheck_pointwise_z', 'ecfft_test_fail_next_collective', 'ecfft_selftest_blk16', 'ecfft_selftest_blk16_small', 'ecfft_test_fail_build_rank', 'ecfft_comm_init_projection', 'ecfft_selftest_blk32', 'ecfft_ctx_low_map', 'ecfft_curve_search_stats', 'ecfft_test_ddf_iterate']
@@ -90,6 +92,7 @@ def _bind(L):
     L.ecfft_poly_find_roots.restype, L.ecfft_poly_find_roots.argtypes = ci, [vp, vp, sz, vp, vp, sz, ci, vp]
     L.ecfft_poly_squarefree.restype, L.ecfft_poly_squarefree.argtypes = ci, [vp, vp, sz, vp, vp, sz, ci, vp]
     L.ecfft_poly_distinct_degree.restype, L.ecfft_poly_distinct_degree.argtypes = ci, [vp, vp, sz, vp, vp, sz, ci, vp]
+    L.ecfft_poly_equal_degree.restype, L.ecfft_poly_equal_degree.argtypes = ci, [vp, vp, sz, sz, vp, vp, sz, ci, vp]
     L.ecfft_tree_table.restype, L.ecfft_tree_table.argtypes = ci, [vp, sz, ci, vp, sz, ctypes.POINTER(sz)]
     L.ecfft_build_points.restype, L.ecfft_build_points.argtypes = ci, [ci, sz, vp, vp, vp]
     L.ecfft_device_info.restype, L.ecfft_device_info.argtypes = ci, [ci, ctypes.c_char_p, sz]
@@ -733,6 +736,54 @@ class FFTree:
             if n > 0:
                 out[d] = np.concatenate([row[pos:pos + n], one])
                 pos += n
+        return out
+
+    def poly_equal_degree(self, g, d, count=1):
+        """(factors, n_factors): the monic irreducible factors of degree d (ecfft_poly_equal_degree <->
+        utils::equal_degree_factorization, src/utils.rs:82-113) of `count` polynomials laid end to end, g of count * ng coefficients;
+        rows need not be trimmed.  Each g_b must be a squarefree product of irreducibles of degree d, which is what
+        poly_distinct_degree returns once the leading 1 is appended (ddf_unpack); on other inputs the factors are unspecified.
+        factors has count * max(ng - 1, 1) elements: row b holds its n_factors[b] factors, each as its low d coefficients (the leading
+        1 is implied), in ascending lexicographic order of (c_0, .., c_(d-1)) as standard-form integers (Python's sorted on low-to-high
+        coefficient lists), then zeros; edf_unpack(row, n, d) makes a list of them.  n_factors is a numpy int64 array: -1 for the
+        zero polynomial, 0 for a non-zero constant, -2 where d does not divide the degree (zero rows).  Deterministic: the splitting
+        shifts are 1, 2, 3, ...  ng <= EDF_SMALL_MAX works on any tree (one launch for all rows); otherwise a tree of
+        next_pow2(2 ng - 1) leaves.  numpy arrays (host) or contiguous CUDA tensors (device, on the current stream).  Synchronous."""
+        (g,), (pg,), new, mem, stream = self._poly_io([g])
+        assert count > 0 and g.shape[0] % count == 0
+        ng = g.shape[0] // count
+        factors = new(count * max(ng - 1, 1) if ng else 0)
+        n_factors = np.empty(count, np.int64)
+        rc = self._L.ecfft_poly_equal_degree(self._h, pg, ng, int(d), self._ptr(factors) if ng else None, n_factors.ctypes.data, count, mem, stream)
+        if rc == ERR_BAD_ARG:
+            raise ValueError("poly_equal_degree: empty operand, d = 0, count = 0 or a context that holds no full tree")
+        _check(rc)
+        return factors, n_factors
+
+    def _crate_one(self):
+        std = np.zeros(self.field.shape(1), self.field.dtype)
+        std.flat[0] = 1
+        return self.field.from_standard(std)
+
+    def edf_unpack(self, row, n, d):
+        """One row of poly_equal_degree as a list of its n factors, each the d + 1 coefficients with the leading 1 (in the crate's
+        form) included.  Host arrays."""
+        row = np.ascontiguousarray(row, self.field.dtype)
+        one = self._crate_one()
+        return [np.concatenate([row[i * d:(i + 1) * d], one]) for i in range(max(int(n), 0))]
+
+    def poly_irreducible_factors(self, f):
+        """{d: [factors]}: the DISTINCT monic irreducible factors of one polynomial f (host array), each with its leading 1, in the
+        order of poly_equal_degree: poly_distinct_degree, then poly_equal_degree per non-empty d.  It computes no multiplicities;
+        that policy stays with the caller.  The zero polynomial raises ValueError."""
+        f = np.ascontiguousarray(f, self.field.dtype)
+        fac, deg = self.poly_distinct_degree(f)
+        if deg[0][0] < 0:
+            raise ValueError("poly_irreducible_factors: the zero polynomial")
+        out = {}
+        for d, gd in self.ddf_unpack(fac, deg[0]).items():
+            row, n = self.poly_equal_degree(np.ascontiguousarray(gd), d)
+            out[d] = self.edf_unpack(row, n[0], d)
         return out
 
     # ---- the remaining FFTree algorithms (host numpy arrays; synchronous) ---------------------

@@ -327,6 +327,30 @@ public:
         }
         return out;
     }
+    // the monic irreducible factors of degree d of g, each with its leading 1, in ascending lexicographic order of (c_0, .., c_(d-1))
+    // as standard-form integers (ecfft_poly_equal_degree <-> utils::equal_degree_factorization, src/utils.rs:82-113).  g must be a
+    // squarefree product of irreducibles of degree d, which is what distinct_degree_factors returns; a non-zero constant gives an
+    // empty vector; the zero polynomial and a degree that d does not divide throw.  Tree rule as square_free.  Synchronous.
+    std::vector<std::vector<Elem>> equal_degree_factors(const std::vector<Elem>& g, size_t d) const {
+        require(!g.empty() && d > 0, "equal_degree_factors: the polynomial must not be empty and d must be positive");
+        const size_t nd = g.size() > 1 ? g.size() - 1 : 1;
+        std::vector<Elem> fac(nd);
+        int64_t n = 0;
+        check(ecfft_poly_equal_degree(ctx_, g.data(), g.size(), d, fac.data(), &n, 1, ECFFT_MEM_HOST, nullptr));
+        require(n != -1, "equal_degree_factors: the zero polynomial");
+        require(n >= 0, "equal_degree_factors: d does not divide the degree");
+        Elem std_one{}, one{};
+        const uint32_t u = 1;
+        std::memcpy(&std_one, &u, sizeof u);                    // standard form is little-endian
+        check(ecfft_elems_from_standard(F::id, &std_one, &one, 1));
+        std::vector<std::vector<Elem>> out;
+        for (size_t i = 0; i < (size_t)n; ++i) {
+            std::vector<Elem> q(fac.data() + i * d, fac.data() + (i + 1) * d);
+            q.push_back(one);
+            out.push_back(std::move(q));
+        }
+        return out;
+    }
     size_t device_bytes() const { return ecfft_ctx_device_bytes(ctx_); }     // HBM held between calls: tables + scratch
     // device-resident variants (pointers into HBM, caller's stream)
     void enter_device(const Elem* coeffs, Elem* evals, size_t n, void* stream) const { check(ecfft_enter(ctx_, coeffs, evals, n, ECFFT_MEM_DEVICE, stream)); }

@@ -308,6 +308,45 @@ int ecfft_poly_squarefree(ecfft_ctx* ctx, const void* f, size_t nf, void* out, i
 int ecfft_poly_distinct_degree(ecfft_ctx* ctx, const void* f, size_t nf, void* factors, int64_t* degrees, size_t count, int mem,
                                void* stream);
 
+/* Equal-degree splitting: the last step of factorisation over the field.
+ *   ecfft_poly_equal_degree <-> ecfft::utils::equal_degree_factorization(poly, d)      src/utils.rs:82-113
+ * Layout: g is count x ng coefficients in the crate's form; the rows NEED NOT BE TRIMMED and any non-zero leading coefficient is
+ * accepted (the row is made monic).  d >= 1 is one degree for the whole call.  factors is count x max(ng - 1, 1) elements: row b
+ * holds the n_factors[b] monic irreducible factors of degree d of g_b, each as its LOW d coefficients (the leading 1 is implied,
+ * the layout of ecfft_poly_distinct_degree's g_d), laid end to end, fully reduced, in the crate's form, the rest of the row zero.
+ * factors must not overlap g.
+ * Order: ascending under lexicographic comparison of (c_0, c_1, ..., c_(d-1)) as standard-form integers, c_0 the most significant
+ * (what Python's sorted gives on low-to-high coefficient lists).
+ * `n_factors` is a HOST pointer whatever `mem` is, `count` entries: the zero polynomial gives -1 and a zero row, a non-zero
+ * constant 0, a true degree that is not a multiple of d gives -2 and a zero row; nothing fails on that.
+ * Precondition: g_b is squarefree and all its irreducible factors have degree d, which is what ecfft_poly_distinct_degree returns
+ * once the leading 1 is appended.  On any other input the factors are unspecified, but every loop is still bounded.
+ * Method (both fields have odd p): with h_i = x^(p^i) mod g, (x + c)^(p^i) = h_i + c, and (p^d - 1)/2 = (1 + p + ... + p^(d-1))
+ *   (p - 1)/2; so with the norm N_c = prod_{i<d} (h_i + c) mod g the splitting element of Cantor-Zassenhaus is w =
+ *   (x + c)^((p^d - 1)/2) = N_c^((p-1)/2).  Modulo each irreducible factor N_c lies in F_p, so w is 0 or +-1 there, and
+ *   u = gcd(h, w - 1), v = h / u split a divisor h of g whenever two of its factors get different quadratic characters.  The h_i
+ *   do not depend on c: h_1 is one power x^p and h_2 .. h_(d-1) are d - 2 Frobenius iterates, taken once per g as
+ *   ecfft_poly_distinct_degree takes them.  An attempt then costs d - 1 modular products and one power with the exponent
+ *   (p - 1)/2, where the reference's (x + c)^((p^d - 1)/2) has a d times longer exponent.  The shifts are the plain integers
+ *   1, 2, 3, ... from an attempt counter: no randomness, and since the set of factors does not depend on the shifts and the order
+ *   is fixed the result is deterministic and bit-exact.
+ * ECFFT_EDF_SMALL_MAX: ng up to which a polynomial is finished by one workgroup; all `count` rows are ONE launch (plus the
+ * ordering).  Above it the polynomials run one after another: the modulus g is kept once, then rounds in which all pending factors
+ * of degree above 64 share one norm and the launches of one modular power, until every factor has degree d or at most 64; those
+ * are finished by one launch of the same workgroup kernel.
+ * Memory beyond the rows: the small regime takes (d - 1)(ng - 1) pooled elements per row of a launch (at most 65536 rows) for the
+ * h_i when 2 d <= ng - 1, none otherwise; the large regime 4 N for the kept modulus, (d - 1) n for the h_i, the composition's baby
+ * steps and buffers of 2 n.  An allocation that fails ends the call with ECFFT_ERR_HIP.
+ * A factor that fails 64 shifts in a row (for a valid input the chance is below 2^-63; the bound keeps a defect or an input outside
+ * the precondition from spinning) ends the call with ECFFT_ERR_HIP.
+ * Tree: ng <= ECFFT_EDF_SMALL_MAX needs no transform (any tree).  Otherwise the rule of ecfft_poly_find_roots, next_pow2(2 ng - 1)
+ * leaves, checked on the row length before anything runs.  Else ECFFT_ERR_TREE_TOO_SMALL.
+ * ECFFT_ERR_BAD_ARG: a NULL pointer, ng, d or count 0, a context that holds no full tree, a byte count that would wrap.  The call is
+ * SYNCHRONOUS.  Memory, stream, threading and pooled temporaries as for ecfft_poly_gcd. */
+#define ECFFT_EDF_SMALL_MAX 65       /* coefficients per row that one workgroup finishes, any tree */
+int ecfft_poly_equal_degree(ecfft_ctx* ctx, const void* g, size_t ng, size_t d, void* factors, int64_t* n_factors, size_t count, int mem,
+                            void* stream);
+
 /* The remaining FFTree algorithms, composed from the same GPU kernels.  Synchronous.
  *   ecfft_mextend         <-> FFTree::mextend(&self, &[F], Moiety)      src/fftree.rs:138-141
  *   ecfft_redc            <-> FFTree::redc_z0 / redc_z1(&self, evals, a)  src/fftree.rs:264-275  (moiety S0 / S1)
