@@ -62,6 +62,9 @@ pub mod ffi {
         pub fn ecfft_poly_squarefree(ctx: *mut EcfftCtx, f: *const c_void, nf: usize, out: *mut c_void, degrees: *mut i64, count: usize, mem: i32, stream: *mut c_void) -> i32;
         pub fn ecfft_poly_distinct_degree(ctx: *mut EcfftCtx, f: *const c_void, nf: usize, factors: *mut c_void, degrees: *mut i64, count: usize, mem: i32, stream: *mut c_void) -> i32;
         pub fn ecfft_poly_equal_degree(ctx: *mut EcfftCtx, g: *const c_void, ng: usize, d: usize, factors: *mut c_void, n_factors: *mut i64, count: usize, mem: i32, stream: *mut c_void) -> i32;
+        pub fn ecfft_division_polynomial(ctx: *mut EcfftCtx, a: *const c_void, b: *const c_void, n: usize, out: *mut c_void, count: usize, mem: i32, stream: *mut c_void) -> i32;
+        pub fn ecfft_curve_cardinality(ctx: *mut EcfftCtx, a: *const c_void, b: *const c_void, order: *mut c_void, traces: *mut i64, count: usize, mem: i32, stream: *mut c_void) -> i32;
+        pub fn ecfft_curve_trace_mod(ctx: *mut EcfftCtx, a: *const c_void, b: *const c_void, l: usize, t_out: *mut i64, count: usize, mem: i32, stream: *mut c_void) -> i32;
         pub fn ecfft_poly_find_roots(ctx: *mut EcfftCtx, f: *const c_void, nf: usize, roots: *mut c_void, n_roots: *mut i64, count: usize, mem: i32, stream: *mut c_void) -> i32;
         pub fn ecfft_poly_gcd(ctx: *mut EcfftCtx, a: *const c_void, na: usize, b: *const c_void, nb: usize, g: *mut c_void, degrees: *mut i64, count: usize, mem: i32, stream: *mut c_void) -> i32;
         pub fn ecfft_poly_xgcd(ctx: *mut EcfftCtx, a: *const c_void, na: usize, b: *const c_void, nb: usize, s: *mut c_void, t: *mut c_void, g: *mut c_void, degrees: *mut i64, count: usize, mem: i32, stream: *mut c_void) -> i32;
@@ -478,6 +481,34 @@ impl<F: HipField> HipFFTree<F> {
                 q
             })
             .collect()
+    }
+
+    /// `division_polynomial(n, &curve)` (examples/schoofs.rs:368-431) for y^2 = x^3 + a x + b: the L(n) coefficients of psi_n, low
+    /// to high, not monic, the factor 2y of an even index removed.  `n <= 4` on any tree, otherwise next_pow2(L(n)) leaves.
+    pub fn division_polynomial(&self, a: &F, b: &F, n: usize) -> Vec<F> {
+        let len = if n < 2 { 1 } else if n & 1 == 1 { (n * n - 1) / 2 + 1 } else { (n * n - 4) / 2 + 1 };
+        let mut out = Self::out_vec(len);
+        check(unsafe { ffi::ecfft_division_polynomial(self.ctx, (a as *const F).cast(), (b as *const F).cast(), n, out.as_mut_ptr().cast(), 1, ffi::MEM_HOST, core::ptr::null_mut()) });
+        unsafe { out.set_len(len) };
+        out
+    }
+
+    /// `frobenius_trace_mod_l` / `has_even_order` (examples/schoofs.rs:76-138, 345-366): t mod l with #E = p + 1 - t for the curves
+    /// y^2 = x^3 + a[i] x + b[i]; -1 for a singular curve.  `l` is 2 or an odd prime up to `ECFFT_SCHOOF_MAX_L`; `l <= 11` on
+    /// any tree, otherwise next_pow2(2 L(l) - 1) leaves.
+    pub fn curve_trace_mod(&self, a: &[F], b: &[F], l: usize) -> Vec<i64> {
+        assert!(!a.is_empty() && a.len() == b.len());
+        let mut t = vec![0i64; a.len()];
+        check(unsafe { ffi::ecfft_curve_trace_mod(self.ctx, a.as_ptr().cast(), b.as_ptr().cast(), l, t.as_mut_ptr(), a.len(), ffi::MEM_HOST, core::ptr::null_mut()) });
+        t
+    }
+
+    /// `cardinality(curve)` (examples/schoofs.rs:30-71): #E(F_p) of y^2 = x^3 + a x + b as 40 little-endian bytes, zero for a
+    /// singular curve.  Needs the tree of the largest prime of the rule (include/ecfft_hip.h).
+    pub fn curve_cardinality(&self, a: &F, b: &F) -> [u8; 40] {
+        let mut order = [0u8; 40];
+        check(unsafe { ffi::ecfft_curve_cardinality(self.ctx, (a as *const F).cast(), (b as *const F).cast(), order.as_mut_ptr().cast(), core::ptr::null_mut(), 1, ffi::MEM_HOST, core::ptr::null_mut()) });
+        order
     }
 
     /// `FFTree::mextend` (src/fftree.rs:138-141)

@@ -2958,6 +2958,437 @@ public:
         return finish_flagged(ok, ec.flag, capped, s);
     }
 
+    // ---- ecfft_division_polynomial (division_polynomial, examples/schoofs.rs:368-431) ----
+    static constexpr size_t kDivpolyMaxN = 199;
+    // L(n): the coefficients of psi_n with the factor 2y of an even index removed
+    static size_t divpoly_len(size_t n) { return n < 2 ? 1 : ((n & 1) ? (n * n - 1) / 2 + 1 : (n * n - 4) / 2 + 1); }
+    // The leaves the call needs: psi_0 .. psi_4 are closed forms (1: no transform); above, every product of the recurrence is a
+    // factor of one term of some psi_k, k <= n, so none has more than L(n) coefficients, and the last ones have exactly L(n)
+    static size_t divpoly_leaves(size_t n) { return n <= 4 ? 1 : next_pow2(divpoly_len(n)); }
+    // out (count x L(n), crate form, not monic) = psi_n of the curves (A[b], B[b]): a host driver on poly_mul_body, batched over
+    // count, memoised over the O(log n) indices the recurrence reaches (m - 2 .. m + 2 of m = k / 2, downwards), each computed
+    // once in ascending order.  A factor psi_1 = psi_2 = 1 costs no product.  Temporaries: after every index the products it
+    // took go back to the pool, and so does every psi_j that no index still to come reads, so at most the five psi of two
+    // neighbouring levels and one index's products are held at a time.  Asynchronous on s.  Caller holds lock() and checks n
+    // and the tree rule (divpoly_leaves).
+    bool division_polynomial(const E* A, const E* B, size_t n, E* out, size_t count, hipStream_t s) {
+        const bool ok = division_polynomial_body(A, B, n, out, count, s);
+        temps_done();
+        return ok && hipGetLastError() == hipSuccess;
+    }
+    // the same without handing every temporary back: what it took itself is released, what the caller holds stays
+    bool division_polynomial_body(const E* A, const E* B, size_t n, E* out, size_t count, hipStream_t s) {
+        struct Poly { const E* p; size_t len; bool one; };
+        auto deps = [](size_t k) {
+            const size_t m = k / 2;
+            std::vector<size_t> d{m - 1, m, m + 1, m + 2};
+            if (k % 2 == 0) d.push_back(m - 2);
+            return d;
+        };
+        std::set<size_t> seen;
+        {
+            std::vector<size_t> todo{n};
+            while (!todo.empty()) {
+                const size_t k = todo.back();
+                todo.pop_back();
+                if (!seen.insert(k).second || k <= 4) continue;
+                for (size_t j : deps(k)) todo.push_back(j);
+            }
+        }
+        std::vector<E*> memo(n + 4, nullptr);
+        bool ok = true;
+        const TempMark entry = temps_mark();
+        // the closed forms, and 16 f^2 = 16 (x^3 + A x + B)^2, one thread per curve
+        E* base = temp(count * 22);
+        E *q0 = base, *q1 = base + count, *q3 = base + 2 * count, *q4 = base + 7 * count, *F2 = base + 14 * count;
+        {
+            const E r1 = crate_one(), rinv = rinv_;
+            foreach_n(s, count, [=] __device__(size_t b) {
+                auto cm = [&](const E& x, const E& y) { return F::canon(F::mul(F::canon(F::mul(x, y)), rinv)); };
+                auto sc = [&](uint32_t k, const E& v) { return F::canon(F::mul(F::from_u32(k), v)); };
+                const E a = F::canon(A[b]), bb = F::canon(B[b]);
+                const E aa = cm(a, a), ab = cm(a, bb), b2 = cm(bb, bb), a3 = cm(aa, a);
+                q0[b] = F::zero();
+                q1[b] = r1;
+                E* p3 = q3 + 5 * b;
+                p3[0] = F::canon(F::neg(aa)); p3[1] = sc(12, bb); p3[2] = sc(6, a); p3[3] = F::zero(); p3[4] = sc(3, r1);
+                E* p4 = q4 + 7 * b;
+                p4[0] = F::canon(F::neg(F::canon(F::add(sc(2, a3), sc(16, b2)))));
+                p4[1] = F::canon(F::neg(sc(8, ab))); p4[2] = F::canon(F::neg(sc(10, aa))); p4[3] = sc(40, bb); p4[4] = sc(10, a);
+                p4[5] = F::zero(); p4[6] = sc(2, r1);
+                E* f2 = F2 + 7 * b;
+                f2[0] = sc(16, b2); f2[1] = sc(32, ab); f2[2] = sc(16, aa); f2[3] = sc(32, bb); f2[4] = sc(32, a); f2[5] = F::zero();
+                f2[6] = sc(16, r1);
+            });
+        }
+        memo[0] = q0; memo[1] = q1; memo[2] = q1; memo[3] = q3; memo[4] = q4;
+        auto P = [&](size_t j) { return Poly{memo[j], divpoly_len(j), j == 1 || j == 2}; };
+        auto prod = [&](const Poly& x, const Poly& y) {
+            if (x.one) return y;
+            if (y.one) return x;
+            const size_t len = x.len + y.len - 1;
+            E* o = temp(count * len);
+            ok = poly_mul_body(x.p, x.len, x.len, y.p, y.len, y.len, o, count, s) && ok;
+            return Poly{o, len, false};
+        };
+        auto diff = [&](const Poly& x, const Poly& y) {
+            const size_t len = x.len > y.len ? x.len : y.len, lx = x.len, ly = y.len;
+            E* o = temp(count * len);
+            const E *xp = x.p, *yp = y.p;
+            foreach_n(s, count * len, [=] __device__(size_t i) {
+                const size_t b = i / len, j = i - b * len;
+                E u = F::zero(), v = F::zero();
+                if (j < lx) u = F::canon(xp[b * lx + j]);
+                if (j < ly) v = F::canon(yp[b * ly + j]);
+                o[i] = F::canon(F::sub(u, v));
+            });
+            return Poly{o, len, false};
+        };
+        const Poly f2{F2, 7, false};
+        for (size_t k : seen) {
+            if (k <= 4 || !ok) continue;
+            const size_t m = k / 2;
+            Poly r;
+            if (k % 2 == 0) {
+                const Poly t0 = prod(prod(P(m - 1), P(m - 1)), P(m + 2)), t1 = prod(prod(P(m + 1), P(m + 1)), P(m - 2));
+                r = prod(diff(t0, t1), P(m));
+            } else {
+                Poly t0 = prod(P(m + 2), prod(prod(P(m), P(m)), P(m))), t1 = prod(P(m - 1), prod(prod(P(m + 1), P(m + 1)), P(m + 1)));
+                if (m % 2 == 0) t0 = prod(f2, t0); else t1 = prod(f2, t1);
+                r = diff(t0, t1);
+            }
+            memo[k] = const_cast<E*>(r.p);
+            ok = ok && r.len == divpoly_len(k);
+            // keep what was busy on entry, the closed forms, and every psi_j that k itself (the result) or a later index reads
+            TempMark keep = entry;
+            keep.push_back(base);
+            keep.push_back(memo[k]);
+            for (size_t k2 : seen)
+                if (k2 > k && k2 > 4)
+                    for (size_t j : deps(k2)) if (memo[j]) keep.push_back(memo[j]);
+            temps_release(keep);
+        }
+        ok = ok && hipMemcpyAsync(out, memo[n], count * divpoly_len(n) * sizeof(E), hipMemcpyDeviceToDevice, s) == hipSuccess;
+        temps_release(entry);
+        return ok;
+    }
+
+    // ---- ecfft_curve_trace_mod (frobenius_trace_mod_l, examples/schoofs.rs:76-138) ----
+    // a modulus of at most kSchoofSmall + 1 coefficients is finished by k_schoof_small, one workgroup per curve
+    static constexpr size_t kSchoofSmall = kRootsSmall;
+    static constexpr uint32_t kSchoofMaxL = 199;
+    // 2 and the odd primes up to kSchoofMaxL
+    static bool schoof_valid_l(uint32_t l) {
+        if (l == 2) return true;
+        if (l < 3 || l > kSchoofMaxL || l % 2 == 0) return false;
+        for (uint32_t q = 3; q * q <= l; q += 2) if (l % q == 0) return false;
+        return true;
+    }
+    // The leaves the call needs, checked before anything runs: none where psi_l fits the small regime (l <= 11); otherwise gcd's
+    // rule on rows of L(l) coefficients, next_pow2(2 L(l) - 1), which covers the kept-modulus products (2 d - 1 coefficients,
+    // d = L(l) - 1), the composition and the driver of psi_l (L(l) coefficients)
+    static size_t schoof_leaves(uint32_t l) {
+        const size_t L = divpoly_len(l);
+        return l == 2 || L <= kSchoofSmall + 1 ? 1 : next_pow2(2 * L - 1);
+    }
+    // the modular products of one general-base power with p: bits + popcount(p) - 2
+    static uint32_t schoof_pow_cost() {
+        uint8_t ep[32], eh[32];
+        uint32_t nbits_p = 0, nbits_h = 0, pop = 0;
+        roots_exponents(ep, &nbits_p, eh, &nbits_h);
+        for (int i = 0; i < 32; ++i) pop += (uint32_t)__builtin_popcount(ep[i]);
+        return nbits_p + pop - 2;
+    }
+    // How pi^2 = (x^(p^2), y^(p^2)) is taken from pi = (a, b y) on a modulus of degree d: true = the composition (a(a), b(a) b),
+    // false = the powers (a^p, b^p b), 2 c products with c = schoof_pow_cost().  The rule is the count of modular products, as
+    // ddf_iterate_composes has it: Horner's loop in the small regime takes 2 (d - 1) (k_schoof_small applies the same rule to
+    // the degree it meets); the kept composition of the large regime shares its k - 1 baby steps between a and b and takes
+    // k' - 1 products per coordinate.
+    static bool schoof_pi2_composes(size_t d) {
+#ifdef ECFFT_TEST_HOOKS
+        if (schoof_pi2_force() == 1) return false;
+        if (schoof_pi2_force() == 2) return true;
+#endif
+        const size_t c = schoof_pow_cost();
+        if (d <= kSchoofSmall) return d - 1 < c;
+        const size_t k = compose_chunk(d), kp = (d + k - 1) / k;
+        return (k - 1) + 2 * (kp - 1) < 2 * c;
+    }
+#ifdef ECFFT_TEST_HOOKS
+    // ecfft_test_schoof_pi2 (include/ecfft_hip_hooks.h): 0 = the rule, 1 = always the powers, 2 = always the composition
+    static int& schoof_pi2_force() { static int v = 0; return v; }
+#endif
+    // p as 32 little-endian bytes
+    static void modulus_bytes(uint8_t* ep) { uint8_t eh[32]; uint32_t a = 0, b = 0; roots_exponents(ep, &a, eh, &b); }
+    // p mod l for a small l
+    static uint32_t schoof_p_mod(uint32_t l) {
+        uint8_t ep[32], eh[32];
+        uint32_t nbits_p = 0, nbits_h = 0;
+        roots_exponents(ep, &nbits_p, eh, &nbits_h);
+        uint64_t r = 0;
+        for (int i = 31; i >= 0; --i) r = (r * 256 + ep[i]) % l;
+        return (uint32_t)r;
+    }
+private:
+    // what a call shares between its curves: the exponents p and (p - 1) / 2 as host and device bytes, p mod l, the flag
+    struct SchoofCall { const uint8_t* dexp = nullptr; uint8_t e[64]; uint32_t nbits_p = 0, nbits_h = 0, kq = 0, cost = 0, pi2 = 0; int* flag = nullptr; };
+    // one launch of k_schoof_small: psi_l built in the kernel (mod == nullptr) or the given monic moduli of nmod coefficients
+    void schoof_small_launch(const SchoofCall& sc, const E* A, const E* B, const E* mod, size_t nmod, uint32_t l, long long* dn, size_t count,
+                             hipStream_t s) {
+        const E r1 = crate_one();
+        const TE rinv = rinv_table();
+        for_chunks(count, [&](size_t b0, size_t nb) {
+            ECFFT_LAUNCH(KC_POINTWISE, sizeof(E) * (2.0 + (double)nmod) * (double)nb + 64.0, (k_schoof_small<F, (int)kSchoofSmall>),
+                         dim3((unsigned)nb), dim3((unsigned)kSchoofSmall), 0, s, A + b0, B + b0, mod ? mod + b0 * nmod : (const E*)nullptr,
+                         (uint32_t)nmod, l, sc.kq, dn + b0, sc.pi2, sc.cost, sc.dexp, sc.nbits_p, sc.dexp + 32, sc.nbits_h, rinv, r1, sc.flag);
+        });
+    }
+    // t mod l of ONE curve whose psi_l has more than kSchoofSmall + 1 coefficients.  psi_l comes from division_polynomial_body and
+    // is made monic; then attempts on a modulus h of degree d, the steps of k_schoof_small on device rows of d coefficients:
+    //   d <= kSchoofSmall (after a split): the modulus is handed to k_schoof_small, which finishes the curve;
+    //   otherwise h is kept ONCE for the attempt (keep_modulus); a product is a lift of its right operand and one powmod_step
+    //   (the product of compose_apply); pi_a = x^p by roots_pow_kept's scan, pi_b and the powers of pi^2 by the powmod_step scan
+    //   of poly_pow_mod; the composition shares ONE compose_prepare (the baby steps of pi_a) between pi_a(pi_a) and pi_b(pi_a);
+    //   an inverse is the s cofactor of the gcd of (denominator, h) — k_gcd_small up to kGcdSmall coefficients, gcd_pair above —
+    //   whose degree is read back; a proper gcd becomes the modulus, which is kept again by the next attempt.
+    // Row equality is decided on the device and read back.  Temporaries: the rows and the kept modulus of the attempt; a product's
+    // or a sum's own go back to the pool when it ends, so nothing grows with l.  *t = the residue.  Returns false on a HIP error;
+    // a sum the group law excludes raises *sc.flag.
+    bool schoof_one_large(const SchoofCall& sc, const E* A, const E* B, uint32_t l, long long* t, hipStream_t s) {
+        const size_t d0 = divpoly_len(l) - 1, ld = d0 + 1;
+        const E r1 = crate_one(), rinvE = rinv_;
+        const TE rinv = rinv_table();
+        bool ok = true;
+        int* dint = temp_as<int>(2);
+        auto read_int = [&]() { int h = 0; ok = hipMemcpyAsync(&h, dint, sizeof(int), hipMemcpyDeviceToHost, s) == hipSuccess && hipStreamSynchronize(s) == hipSuccess && ok; return h; };
+        foreach_n(s, 1, [=] __device__(size_t) {
+            auto cm = [&](const E& x, const E& y) { return F::canon(F::mul(F::canon(F::mul(x, y)), rinvE)); };
+            const E a = F::canon(A[0]), b = F::canon(B[0]);
+            const E disc = F::canon(F::add(F::canon(F::mul(F::from_u32(4), cm(cm(a, a), a))), F::canon(F::mul(F::from_u32(27), cm(b, b)))));
+            dint[0] = F::is_zero(disc) ? 1 : 0;
+        });
+        if (read_int()) { *t = -1; return ok; }
+        E* h = temp(ld);
+        {
+            E* psi = temp(ld);
+            ok = division_polynomial_body(A, B, l, psi, 1, s) && ok;
+            E* cinv = temp(1);                                    // 1 / lc(psi_l) as a plain number: the one inversion of the curve
+            foreach_n(s, 1, [=] __device__(size_t) { cinv[0] = F::canon(F::mul(F::inv(F::canon(psi[d0])), r1)); });
+            foreach_n(s, d0, [=] __device__(size_t j) { h[j] = F::canon(F::mul(psi[j], cinv[0])); });
+            foreach_n(s, 1, [=] __device__(size_t) { h[d0] = r1; });
+        }
+        enum { X, ONE, FX, PA, PB, EA, EB, QA, QB, NUM, DEN, RR, A3, B3, INV, TMP, NROWS };
+        E* W = temp((size_t)NROWS * ld);
+        E* G = temp(ld);
+        long long* dn = temp_as<long long>(1);
+        auto row = [&](int i) { return W + (size_t)i * ld; };
+        size_t d = d0;
+        *t = 0;
+        for (;;) {
+            if (d <= kSchoofSmall) {
+                schoof_small_launch(sc, A, B, h, d + 1, l, dn, 1, s);
+                ok = hipMemcpyAsync(t, dn, sizeof(long long), hipMemcpyDeviceToHost, s) == hipSuccess && hipStreamSynchronize(s) == hipSuccess && ok;
+                return ok;
+            }
+            const TempMark am = temps_mark();
+            const size_t N = powmod_leaves(d + 1);
+            E* kept = temp(2 * N);
+            KeptModulus km;
+            ok = keep_modulus(h, d, nullptr, 0, 0, 1, kept, sc.flag, &km, s) && ok;
+            const size_t dd = d;
+            auto copy = [&](E* dst, const E* src) { if (dst != src) ok = hipMemcpyAsync(dst, src, dd * sizeof(E), hipMemcpyDeviceToDevice, s) == hipSuccess && ok; };
+            // out = a b mod h; out may be a or b
+            auto mulmod = [&](E* out, const E* a, const E* b) {
+                const TempMark m = temps_mark();
+                if (a == b) { copy(out, a); ok = powmod_step(out, nullptr, km, 1, rinv, s) && ok; }
+                else {
+                    E* K = temp(N);
+                    ok = lift_and_keep(b, dd, N, 1, K, s) && ok;
+                    copy(out, a);
+                    ok = powmod_step(out, K, km, 1, rinv, s) && ok;
+                }
+                temps_release(m);
+            };
+            // out = base^e mod h for nbits >= 1 bits of e (host bytes, top bit set); out is not base
+            auto powgen = [&](E* out, const E* base, const uint8_t* e, uint32_t nbits) {
+                const TempMark m = temps_mark();
+                E* K = temp(N);
+                ok = lift_and_keep(base, dd, N, 1, K, s) && ok;
+                copy(out, base);
+                for (uint32_t i = nbits - 1; i-- > 0;) {
+                    ok = powmod_step(out, nullptr, km, 1, rinv, s) && ok;
+                    if ((e[i >> 3] >> (i & 7)) & 1) ok = powmod_step(out, K, km, 1, rinv, s) && ok;
+                }
+                temps_release(m);
+            };
+            // out = a + sign b on the d coefficients
+            auto lin = [&](E* out, const E* a, const E* b, bool minus) {
+                foreach_n(s, dd, [=] __device__(size_t j) { out[j] = F::canon(minus ? F::sub(F::canon(a[j]), F::canon(b[j])) : F::add(F::canon(a[j]), F::canon(b[j]))); });
+            };
+            // a == b (plus == false) or a == -b, decided on the device
+            auto same = [&](const E* a, const E* b, bool plus) {
+                ok = hipMemsetAsync(dint, 0, sizeof(int), s) == hipSuccess && ok;
+                foreach_n(s, dd, [=] __device__(size_t j) {
+                    const E v = F::canon(plus ? F::add(F::canon(a[j]), F::canon(b[j])) : F::sub(F::canon(a[j]), F::canon(b[j])));
+                    if (!F::is_zero(v)) dint[0] = 1;
+                });
+                return read_int() == 0;
+            };
+            // the gcd of (den, h): its degree; INV = the cofactor of den, G = the monic gcd
+            auto gcd_h = [&](const E* den) {
+                long long deg = -1;
+                const size_t na = dd, nb = dd + 1, nt = na > 1 ? na - 1 : 1;
+                const TempMark m = temps_mark();
+                if (nb <= kGcdSmall) {
+                    long long* ddeg = temp_as<long long>(1);
+                    ECFFT_LAUNCH(KC_POINTWISE, sizeof(E) * 4.0 * (double)nb, (k_gcd_small<F, (int)kGcdSmall>), dim3(1u), dim3((unsigned)kGcdSmall), 0, s,
+                                 den, na, (uint32_t)na, (const E*)h, nb, (uint32_t)nb, (int32_t)0, 0u, 1u, G, (uint32_t)nb, row(INV), (uint32_t)na,
+                                 (E*)nullptr, (uint32_t)nt, ddeg, (E*)nullptr, (size_t)0, 0u, (int32_t*)nullptr, r1);
+                    ok = hipMemcpyAsync(&deg, ddeg, sizeof(long long), hipMemcpyDeviceToHost, s) == hipSuccess && hipStreamSynchronize(s) == hipSuccess && ok;
+                } else {
+                    ok = gcd_pair(den, na, h, nb, row(INV), na, nullptr, nt, G, nb, &deg, true, s) && ok;
+                }
+                temps_release(m);
+                return deg;
+            };
+            auto split_to = [&](long long dg) {
+                ok = hipMemcpyAsync(h, G, ((size_t)dg + 1) * sizeof(E), hipMemcpyDeviceToDevice, s) == hipSuccess && ok;
+                d = (size_t)dg;
+            };
+            // SchoofWg::add on device rows: (A3, B3) = (a1, b1) + (a2, b2); 0 done, 1 infinity, 2 the modulus was split, 3 a defect
+            auto add = [&](const E* a1, const E* b1, const E* a2, const E* b2) {
+                if (same(a1, a2, false)) {
+                    if (same(b1, b2, true)) return 1;
+                    if (same(b1, b2, false)) {
+                        mulmod(row(NUM), a1, a1);
+                        { E* num = row(NUM); const E* pA = A; foreach_n(s, dd, [=] __device__(size_t j) {
+                              E v = F::canon(F::mul(F::from_u32(3), num[j]));
+                              if (j == 0) v = F::canon(F::add(v, F::canon(pA[0])));
+                              num[j] = v; }); }
+                        mulmod(row(DEN), row(FX), b1);
+                        lin(row(DEN), row(DEN), row(DEN), false);
+                    } else {
+                        for (int sgn = 0; sgn < 2; ++sgn) {
+                            lin(row(DEN), b1, b2, sgn == 0);
+                            const long long dg = gcd_h(row(DEN));
+                            if (dg > 0 && dg < (long long)dd) { split_to(dg); return 2; }
+                        }
+                        return 3;
+                    }
+                } else {
+                    lin(row(NUM), b1, b2, true);
+                    lin(row(DEN), a1, a2, true);
+                }
+                const long long dg = gcd_h(row(DEN));
+                if (!ok || dg < 0 || dg >= (long long)dd) return 3;
+                if (dg > 0) { split_to(dg); return 2; }
+                mulmod(row(RR), row(NUM), row(INV));
+                mulmod(row(A3), row(RR), row(RR));
+                mulmod(row(A3), row(A3), row(FX));
+                lin(row(A3), row(A3), a1, true);
+                lin(row(A3), row(A3), a2, true);
+                lin(row(B3), a1, row(A3), true);
+                mulmod(row(B3), row(RR), row(B3));
+                lin(row(B3), row(B3), b1, true);
+                return 0;
+            };
+            // x, 1, f
+            {
+                E *x = row(X), *one = row(ONE), *fx = row(FX);
+                const E *pA = A, *pB = B;
+                foreach_n(s, dd, [=] __device__(size_t j) {
+                    x[j] = j == 1 ? r1 : F::zero();
+                    one[j] = j == 0 ? r1 : F::zero();
+                    fx[j] = j == 0 ? F::canon(pB[0]) : j == 1 ? F::canon(pA[0]) : j == 3 ? r1 : F::zero();
+                });
+            }
+            ok = roots_pow_kept(h, km, 0u, sc.e, sc.nbits_p, row(PA), row(TMP), 1, s) && ok;
+            powgen(row(PB), row(FX), sc.e + 32, sc.nbits_h);
+            if (schoof_pi2_composes(d)) {
+                E* K = temp(N);
+                ok = lift_and_keep(row(PA), d, N, 1, K, s) && ok;
+                const KeptModulus kb{km.g, km.f, K, d, N};
+                const size_t k = compose_chunk(d), kp = (d + k - 1) / k;
+                KeptCompose kc;
+                kc.B = temp((k + 1) * d); kc.C = temp(kp * d);
+                ok = compose_prepare(kb, row(PA), d, d, d, 1, &kc, s) && ok;
+                ok = compose_apply(kc, row(PA), row(EA), s) && ok;
+                ok = compose_apply(kc, row(PB), row(TMP), s) && ok;
+            } else {
+                powgen(row(EA), row(PA), sc.e, sc.nbits_p);
+                powgen(row(TMP), row(PB), sc.e, sc.nbits_p);
+            }
+            mulmod(row(EB), row(TMP), row(PB));
+            int st = 0;
+            long long res = 0;
+            copy(row(QA), row(X)); copy(row(QB), row(ONE));
+            for (uint32_t i = 1; i < sc.kq && st == 0 && ok; ++i) {
+                st = add(row(QA), row(QB), row(X), row(ONE));
+                if (st == 0) { copy(row(QA), row(A3)); copy(row(QB), row(B3)); }
+            }
+            if (st == 1) st = 3;                                  // [i](x, y) is never the point at infinity below l
+            if (st == 0 && ok) {
+                st = add(row(EA), row(EB), row(QA), row(QB));
+                if (st == 1) st = 4;                              // pi^2 + [p] = O: the residue is 0
+            }
+            if (st == 0 && ok) {
+                copy(row(EA), row(A3)); copy(row(EB), row(B3));
+                copy(row(QA), row(PA)); copy(row(QB), row(PB));
+                for (uint32_t j = 1; j < l && ok; ++j) {
+                    if (same(row(QA), row(EA), false) && same(row(QB), row(EB), false)) { res = (long long)j; break; }
+                    if (j + 1 == l) break;
+                    st = add(row(QA), row(QB), row(PA), row(PB));
+                    if (st != 0) break;
+                    copy(row(QA), row(A3)); copy(row(QB), row(B3));
+                }
+                if (st == 1) st = 4;
+            }
+            temps_release(am);
+            if (!ok) return false;
+            if (st == 2) continue;
+            if (st == 3) { const int one = 1; ok = hipMemcpyAsync(sc.flag, &one, sizeof(int), hipMemcpyHostToDevice, s) == hipSuccess && hipStreamSynchronize(s) == hipSuccess; }
+            *t = res;
+            return ok;
+        }
+    }
+public:
+    // ecfft_curve_trace_mod: t_out[b] (host) = t mod l for the curve (A[b], B[b]) with #E = p + 1 - t, -1 for a singular curve.
+    // psi_l of at most kSchoofSmall + 1 coefficients (l <= 11) and l = 2: ONE launch of k_schoof_small for all curves, no
+    // transform.  Otherwise the curves run one after another (schoof_one_large).  *defect = a sum the group law excludes.
+    // Synchronous.  Caller holds lock() and checks l (schoof_valid_l) and the tree rule (schoof_leaves).  done == false leaves
+    // the temporaries to a caller that goes on (curve_cardinality).
+    bool curve_trace_mod(const E* A, const E* B, uint32_t l, long long* t_out, size_t count, bool* defect, hipStream_t s, bool done = true) {
+        const TempMark entry = temps_mark();
+        SchoofCall sc;
+        roots_exponents(sc.e, &sc.nbits_p, sc.e + 32, &sc.nbits_h);
+        uint8_t* dexp = temp_as<uint8_t>(64);
+        bool ok = hipMemcpyAsync(dexp, sc.e, 64, hipMemcpyHostToDevice, s) == hipSuccess && hipStreamSynchronize(s) == hipSuccess;
+        sc.dexp = dexp;
+        sc.flag = new_flag(s);
+        sc.kq = schoof_p_mod(l); sc.cost = schoof_pow_cost();
+#ifdef ECFFT_TEST_HOOKS
+        sc.pi2 = (uint32_t)schoof_pi2_force();
+#endif
+        if (schoof_leaves(l) == 1) {
+            long long* dn = temp_as<long long>(count);
+            schoof_small_launch(sc, A, B, nullptr, 0, l, dn, count, s);
+            ok = hipMemcpyAsync(t_out, dn, count * sizeof(long long), hipMemcpyDeviceToHost, s) == hipSuccess && ok;
+        } else {
+            gcd_flag_ = new_flag(s);
+            for (size_t p = 0; p < count && ok; ++p) {
+                const TempMark mark = temps_mark();
+                ok = schoof_one_large(sc, A + p, B + p, l, &t_out[p], s);
+                temps_release(mark);
+            }
+        }
+        int hflag = 0;
+        ok = ok && hipMemcpyAsync(&hflag, sc.flag, sizeof(int), hipMemcpyDeviceToHost, s) == hipSuccess;
+        ok = hipGetLastError() == hipSuccess && hipStreamSynchronize(s) == hipSuccess && ok;
+        *defect = hflag != 0;
+        if (done) temps_done(); else temps_release(entry);
+        return ok;
+    }
+
     // coefficients of the reciprocal computed by k_series_base before the Newton steps take over (K0).  64 = one wave per pair: a
     // Newton step at p <= 64 costs a lift + EXIT in the latency regime, the recurrence's 63 tree sums a few us.
     static constexpr size_t kSeriesBase = 64;

@@ -565,6 +565,130 @@ int run_poly_equal_degree(ecfft_ctx* c, DeviceChain<F>& ch, const void* g, size_
     });
 }
 
+// ecfft_division_polynomial: inputs of one element per curve and an output of L(n) elements per curve; asynchronous like ecfft_poly_mul
+template <class F>
+int run_division_polynomial(ecfft_ctx* c, DeviceChain<F>& ch, const void* A, const void* B, size_t n, void* out, size_t count, int mem,
+                            void* stream) {
+    using E = typename F::elem;
+    if (!A || !B || !out) return ECFFT_ERR_BAD_ARG;
+    static_assert(DeviceChain<F>::kDivpolyMaxN == ECFFT_SCHOOF_MAX_L, "the header states the largest index");
+    if (n > ECFFT_SCHOOF_MAX_L) return ECFFT_ERR_BAD_ARG;
+    const size_t N = DeviceChain<F>::divpoly_leaves(n), len = DeviceChain<F>::divpoly_len(n);
+    if (N > 1 && N > ch.size()) return ECFFT_ERR_TREE_TOO_SMALL;              // checked before anything runs
+    if (count > SIZE_MAX / (64 * (N > 32 ? N : 32) * sizeof(E))) return ECFFT_ERR_BAD_ARG;   // byte counts of the temporaries must not wrap
+    const size_t eb = count * sizeof(E);
+    return staged(c, ch, mem, stream, {{A, eb}, {B, eb}}, {{out, len * eb}}, [&](auto d, auto o) -> int {
+        return ch.division_polynomial((const E*)d[0], (const E*)d[1], n, (E*)o[0], count, (hipStream_t)stream) ? ECFFT_OK : ECFFT_ERR_HIP;
+    });
+}
+
+// ecfft_curve_trace_mod: synchronous (`t_out` is a host array whatever `mem` is).  Nothing fails on the data; ECFFT_ERR_HIP also
+// reports a sum the group law excludes.
+template <class F>
+int run_curve_trace_mod(ecfft_ctx* c, DeviceChain<F>& ch, const void* A, const void* B, size_t l, int64_t* t_out, size_t count, int mem,
+                        void* stream) {
+    using E = typename F::elem;
+    if (!A || !B || !t_out) return ECFFT_ERR_BAD_ARG;
+    static_assert(DeviceChain<F>::kSchoofSmall + 1 == ECFFT_SCHOOF_SMALL_MAX, "the header states the small regime's bound");
+    static_assert(DeviceChain<F>::kSchoofMaxL == ECFFT_SCHOOF_MAX_L, "the header states the largest l");
+    static_assert(sizeof(long long) == sizeof(int64_t), "residues are read back as long long");
+    if (l > ECFFT_SCHOOF_MAX_L || !DeviceChain<F>::schoof_valid_l((uint32_t)l)) return ECFFT_ERR_BAD_ARG;
+    const size_t N = DeviceChain<F>::schoof_leaves((uint32_t)l);
+    if (N > 1 && N > ch.size()) return ECFFT_ERR_TREE_TOO_SMALL;              // checked before anything runs
+    if (count > SIZE_MAX / (16 * sizeof(E))) return ECFFT_ERR_BAD_ARG;        // byte counts must not wrap
+    const size_t eb = count * sizeof(E);
+    return staged(c, ch, mem, stream, {{A, eb}, {B, eb}}, {{nullptr, 0}}, [&](auto dv, auto) -> int {
+        bool defect = false;
+        if (!ch.curve_trace_mod((const E*)dv[0], (const E*)dv[1], (uint32_t)l, (long long*)t_out, count, &defect, (hipStream_t)stream)) return ECFFT_ERR_HIP;
+        return defect ? ECFFT_ERR_HIP : ECFFT_OK;
+    });
+}
+
+// Unsigned integers of 384 bits for the CRT of ecfft_curve_cardinality (the modulus stays below 2^140, its square below 2^280)
+struct U384 { uint32_t w[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}; };
+inline void u_mul_small(U384& a, uint32_t m) { uint64_t c = 0; for (int i = 0; i < 12; ++i) { c += (uint64_t)a.w[i] * m; a.w[i] = (uint32_t)c; c >>= 32; } }
+inline uint32_t u_mod_small(const U384& a, uint32_t m) { uint64_t r = 0; for (int i = 11; i >= 0; --i) r = ((r << 32) | a.w[i]) % m; return (uint32_t)r; }
+inline void u_add(U384& a, const U384& b) { uint64_t c = 0; for (int i = 0; i < 12; ++i) { c += (uint64_t)a.w[i] + b.w[i]; a.w[i] = (uint32_t)c; c >>= 32; } }
+inline void u_sub(U384& a, const U384& b) { int64_t c = 0; for (int i = 0; i < 12; ++i) { c += (int64_t)a.w[i] - b.w[i]; a.w[i] = (uint32_t)c; c >>= 32; } }   // a >= b
+inline int u_cmp(const U384& a, const U384& b) { for (int i = 11; i >= 0; --i) if (a.w[i] != b.w[i]) return a.w[i] < b.w[i] ? -1 : 1; return 0; }
+inline U384 u_mul(const U384& a, const U384& b) {
+    U384 r;
+    for (int i = 0; i < 12; ++i) { uint64_t c = 0; for (int j = 0; i + j < 12; ++j) { c += (uint64_t)a.w[i] * b.w[j] + r.w[i + j]; r.w[i + j] = (uint32_t)c; c >>= 32; } }
+    return r;
+}
+// the field's p
+template <class F>
+U384 field_modulus() {
+    uint8_t ep[32];
+    DeviceChain<F>::modulus_bytes(ep);
+    U384 p;
+    for (int i = 0; i < 32; ++i) p.w[i / 4] |= (uint32_t)ep[i] << (8 * (i % 4));
+    return p;
+}
+// l = 2, 3, 5, ... until the product exceeds 4 sqrt(p), i.e. its square exceeds 16 p (schoofs.rs:32-37)
+template <class F>
+std::vector<uint32_t> schoof_primes() {
+    U384 p16 = field_modulus<F>(), m;
+    u_mul_small(p16, 16);
+    m.w[0] = 1;
+    std::vector<uint32_t> out;
+    for (uint32_t l = 2; u_cmp(u_mul(m, m), p16) <= 0 && l <= ECFFT_SCHOOF_MAX_L; ++l)
+        if (DeviceChain<F>::schoof_valid_l(l)) { out.push_back(l); u_mul_small(m, l); }
+    return out;
+}
+// ecfft_curve_cardinality: the residues of ecfft_curve_trace_mod for every prime of the rule, then the incremental CRT of
+// schoofs.rs:52-70 on the host with the representative in (-m/2, m/2].  Synchronous.
+template <class F>
+int run_curve_cardinality(ecfft_ctx* c, DeviceChain<F>& ch, const void* A, const void* B, void* order, int64_t* traces, size_t count, int mem,
+                          void* stream) {
+    using E = typename F::elem;
+    if (!A || !B || !order) return ECFFT_ERR_BAD_ARG;
+    if (count > SIZE_MAX / (64 * sizeof(E))) return ECFFT_ERR_BAD_ARG;        // byte counts must not wrap
+    const std::vector<uint32_t> primes = schoof_primes<F>();
+    const size_t np = primes.size();
+    const size_t N = DeviceChain<F>::schoof_leaves(primes.back());            // the rule of the largest l covers the others
+    if (N > 1 && N > ch.size()) return ECFFT_ERR_TREE_TOO_SMALL;
+    const size_t eb = count * sizeof(E);
+    std::vector<long long> tr(np * count);
+    const int rc = staged(c, ch, mem, stream, {{A, eb}, {B, eb}}, {{nullptr, 0}}, [&](auto dv, auto) -> int {
+        for (size_t i = 0; i < np; ++i) {
+            bool defect = false;
+            if (!ch.curve_trace_mod((const E*)dv[0], (const E*)dv[1], primes[i], tr.data() + i * count, count, &defect, (hipStream_t)stream)) return ECFFT_ERR_HIP;
+            if (defect) return ECFFT_ERR_HIP;
+        }
+        return ECFFT_OK;
+    });
+    if (rc != ECFFT_OK) return rc;
+    const U384 p = field_modulus<F>();
+    uint8_t* ob = (uint8_t*)order;
+    for (size_t b = 0; b < count; ++b) {
+        U384 t, m, n = p, one;
+        m.w[0] = 1; one.w[0] = 1;
+        bool singular = false;
+        for (size_t i = 0; i < np; ++i) {
+            const long long r = tr[i * count + b];
+            if (traces) traces[b * np + i] = r;
+            if (r < 0) { singular = true; continue; }
+            const uint32_t l = primes[i], tm = u_mod_small(t, l), mm = u_mod_small(m, l);
+            uint32_t inv = 1;
+            while ((uint64_t)inv * mm % l != 1) ++inv;
+            const uint32_t k = (uint32_t)((uint64_t)(((uint32_t)r + l - tm) % l) * inv % l);
+            U384 step = m;
+            u_mul_small(step, k);
+            u_add(t, step);
+            u_mul_small(m, l);
+        }
+        U384 twice = t;
+        u_add(twice, t);
+        u_add(n, one);
+        if (u_cmp(twice, m) > 0) { U384 neg = m; u_sub(neg, t); u_add(n, neg); }      // t - m < 0: #E = p + 1 + (m - t)
+        else u_sub(n, t);
+        if (singular) n = U384();
+        for (int i = 0; i < ECFFT_ORDER_BYTES; ++i) ob[b * ECFFT_ORDER_BYTES + i] = (uint8_t)(n.w[i / 4] >> (8 * (i % 4)));
+    }
+    return ECFFT_OK;
+}
+
 // standard = true: plain standard-form residues (the FFTree wire format) instead of the crate's in-memory representation
 template <class F>
 int table_of(DeviceChain<F>& ch, size_t m, int which, void* host_out, size_t cap, size_t* count, bool standard = false) {
@@ -1172,11 +1296,29 @@ int ecfft_poly_equal_degree(ecfft_ctx* ctx, const void* g, size_t ng, size_t d, 
     if (ng == 0 || d == 0 || count == 0) return ECFFT_ERR_BAD_ARG;
     return on_chain(ctx, [&](auto& ch) { return run_poly_equal_degree(ctx, ch, g, ng, d, factors, n_factors, count, mem, stream); });
 }
+int ecfft_division_polynomial(ecfft_ctx* ctx, const void* A, const void* B, size_t n, void* out, size_t count, int mem, void* stream) {
+    if (count == 0) return ECFFT_ERR_BAD_ARG;
+    return on_chain(ctx, [&](auto& ch) { return run_division_polynomial(ctx, ch, A, B, n, out, count, mem, stream); });
+}
+int ecfft_curve_trace_mod(ecfft_ctx* ctx, const void* A, const void* B, size_t l, int64_t* t_out, size_t count, int mem, void* stream) {
+    if (count == 0) return ECFFT_ERR_BAD_ARG;
+    return on_chain(ctx, [&](auto& ch) { return run_curve_trace_mod(ctx, ch, A, B, l, t_out, count, mem, stream); });
+}
+int ecfft_curve_cardinality(ecfft_ctx* ctx, const void* A, const void* B, void* order, int64_t* traces, size_t count, int mem, void* stream) {
+    if (count == 0) return ECFFT_ERR_BAD_ARG;
+    return on_chain(ctx, [&](auto& ch) { return run_curve_cardinality(ctx, ch, A, B, order, traces, count, mem, stream); });
+}
 #ifdef ECFFT_TEST_HOOKS
 int ecfft_test_ddf_iterate(int mode) {
     if (mode < 0 || mode > 2) return ECFFT_ERR_BAD_ARG;
     DeviceChain<Secp256k1>::ddf_iterate_force() = mode;
     DeviceChain<M31>::ddf_iterate_force() = mode;
+    return ECFFT_OK;
+}
+int ecfft_test_schoof_pi2(int mode) {
+    if (mode < 0 || mode > 2) return ECFFT_ERR_BAD_ARG;
+    DeviceChain<Secp256k1>::schoof_pi2_force() = mode;
+    DeviceChain<M31>::schoof_pi2_force() = mode;
     return ECFFT_OK;
 }
 #endif  // ECFFT_TEST_HOOKS

@@ -3330,6 +3330,406 @@ __global__ __launch_bounds__(kBlock) void k_edf_rank(typename F::elem* __restric
 }
 
 // ---------------------------------------------------------------------------------------------
+// ecfft_curve_trace_mod (frobenius_trace_mod_l, examples/schoofs.rs:76-138): the trace of Frobenius of y^2 = x^3 + A x + B modulo
+// a small prime l, in the ring F_p[x]/(h) that starts at h = psi_l made monic.  A modulus of degree <= K is finished by ONE
+// workgroup (k_schoof_small), everything in LDS, on the pieces of k_roots_small / k_edf_small / k_compose_small.
+// ---------------------------------------------------------------------------------------------
+// What the workgroup shares: LDS rows of K entries, thread t owning coefficient t of every row, every row in crate form, fully
+// reduced and zero from d on.  An endomorphism is a pair of rows (a, b) standing for (a(x), b(x) y).
+template <class F, int K>
+struct SchoofWg {
+    using E = typename F::elem;
+    using TE = typename F::telem;
+    E *smod, *sx, *sprod, *sres, *fx, *num, *rr, *iv, *tz, *a3, *b3, *rows, *snorm;
+    int* sdeg;                                               // [0], [1]: gcd_remainder_loop's degrees; [2]: a vote
+    TE rinv;
+    E r1, cA;
+    uint32_t d, t;
+
+    // crate x crate -> crate for scalars
+    __device__ __forceinline__ E cmul(const E& a, const E& b) const {
+        E v = F::mul(a, b);
+        if constexpr (sizeof(E) == 32) v = F::tmul(rinv, v);
+        return F::canon(v);
+    }
+    // dst = a b mod h (dst may be a or b)
+    __device__ __forceinline__ void mm(E* dst, const E* a, const E* b) {
+        modmul_plain<F>(sx, a, rinv, t);
+        modmul_reduce<F>(sprod, sx, b, smod, d, t);
+        E v = F::zero();
+        if (t < d) v = sprod[t];
+        dst[t] = v;
+        __syncthreads();
+    }
+    // dst = a b mod x^K without a modulus (psi_l from the recurrence: every product there has at most 61 coefficients)
+    __device__ __forceinline__ void pmul(E* dst, const E* a, const E* b) {
+        modmul_plain<F>(sx, a, rinv, t);
+        E acc = F::zero();
+        for (uint32_t i = 0; i <= t; ++i) acc = F::canon(F::mul_add(sx[i], b[t - i], acc));
+        __syncthreads();
+        dst[t] = acc;
+        __syncthreads();
+    }
+    // does pred hold at every coefficient below d?  The same answer in every thread.
+    __device__ __forceinline__ bool all(bool pred) {
+        if (t == 0) sdeg[2] = 0;
+        __syncthreads();
+        if (t < d && !pred) sdeg[2] = 1;
+        __syncthreads();
+        const bool r = sdeg[2] == 0;
+        __syncthreads();
+        return r;
+    }
+    __device__ __forceinline__ bool eq(const E* a, const E* b) { return all(F::eq(a[t], b[t])); }
+    __device__ __forceinline__ bool negeq(const E* a, const E* b) { return all(F::is_zero(F::canon(F::add(a[t], b[t])))); }
+    // dst = c(g) mod h for the d coefficients of the row c: Horner's loop of k_compose_small (dst is neither c nor g)
+    __device__ __forceinline__ void compose(E* dst, const E* c, const E* g) {
+        {
+            E v = F::zero();
+            if (t == 0) v = c[d - 1];
+            dst[t] = v;
+        }
+        __syncthreads();
+        for (uint32_t i = d - 1; i-- > 0;) {
+            mm(dst, dst, g);
+            if (t == 0) dst[0] = F::canon(F::add(dst[0], c[i]));
+            __syncthreads();
+        }
+    }
+    // The remainder sequence of (h, e) for the row e whose coefficient t is `den` (zero from d on), with the cofactor of e:
+    // gcd_remainder_loop with its S rows aliased to the T rows (the cofactor of h is never needed, and both get the same values).
+    // Returns deg gcd (d itself for e = 0); R0 is a non-zero multiple of the gcd and R0 = T0 e mod h.
+    __device__ __forceinline__ int gcd_h(const E& den, E*& R0, E*& T0) {
+        R0 = rows;
+        E* R1 = rows + K + 1;
+        T0 = iv;
+        E* T1 = tz;
+        if (t < 2) sdeg[t] = -1;
+        __syncthreads();
+        if (t < d) R0[t] = smod[t];
+        if (t == 0) R0[d] = F::one();
+        R1[t] = den;
+        if (!F::is_zero(den)) atomicMax(&sdeg[1], (int)t);
+        {
+            E o = F::zero();
+            if (t == 0) o = r1;
+            T0[t] = F::zero(); T1[t] = o;
+        }
+        __syncthreads();
+        int d0 = (int)d, d1 = sdeg[1], c0 = 1, c1 = 1;
+        __syncthreads();
+        if (t < 2) sdeg[t] = -1;
+        __syncthreads();
+        E *S0 = T0, *S1 = T1;
+        gcd_remainder_loop<F>(R0, R1, d0, d1, S0, S1, T0, T1, c0, c1, 1u, 0, sdeg, t);
+        return d0;
+    }
+    // the modulus becomes R0 / lc(R0), of degree dg: plain residues, zero from dg on
+    __device__ __forceinline__ void remodulus(const E* R0, int dg) {
+        if (t == 0) *snorm = F::canon(F::inv(R0[dg]));
+        __syncthreads();
+        E v = F::zero();
+        if ((int)t < dg) v = F::canon(F::mul(R0[t], *snorm));
+        __syncthreads();
+        smod[t] = v;
+        d = (uint32_t)dg;
+        __syncthreads();
+    }
+    // (a3, b3) = (a1, b1) + (a2, b2), the reference's Add (schoofs.rs:237-273) with the case it lacks.  Returns 0: done; 1: the
+    // sum is the point at infinity (a1 = a2, b1 = -b2); 2: a denominator was not invertible and the modulus is now the proper
+    // factor gcd(denominator, h) — with a1 = a2 and b1 != +-b2 the factor gcd(b1 - b2, h), else gcd(b1 + b2, h); 3: neither is
+    // proper, or a denominator is zero (a defect: for an odd prime l it cannot happen).  a3, b3 are none of the operands.
+    __device__ __forceinline__ int add(const E* a1, const E* b1, const E* a2, const E* b2) {
+        E den;
+        E *R0, *T0;
+        if (eq(a1, a2)) {
+            if (negeq(b1, b2)) return 1;
+            if (eq(b1, b2)) {                                // the tangent: (3 a1^2 + A) / (2 f b1)
+                mm(num, a1, a1);
+                E v = F::canon(F::mul(F::from_u32(3), num[t]));
+                if (t == 0) v = F::canon(F::add(v, cA));
+                num[t] = v;
+                mm(rr, fx, b1);
+                den = F::canon(F::add(rr[t], rr[t]));
+            } else {
+                for (int sgn = 0; sgn < 2; ++sgn) {
+                    den = sgn ? F::canon(F::add(b1[t], b2[t])) : F::canon(F::sub(b1[t], b2[t]));
+                    const int dg = gcd_h(den, R0, T0);
+                    if (dg > 0 && dg < (int)d) { remodulus(R0, dg); return 2; }
+                }
+                return 3;
+            }
+        } else {                                             // the chord: (b1 - b2) / (a1 - a2)
+            num[t] = F::canon(F::sub(b1[t], b2[t]));
+            den = F::canon(F::sub(a1[t], a2[t]));
+        }
+        const int dg = gcd_h(den, R0, T0);
+        if (dg < 0 || dg >= (int)d) return 3;
+        if (dg > 0) { remodulus(R0, dg); return 2; }
+        if (t == 0) *snorm = F::canon(F::mul(F::inv(R0[0]), r1));   // the one inversion of the sum, as k_gcd_small normalises
+        __syncthreads();
+        {
+            E v = F::zero();
+            if (t < d) v = F::canon(F::mul(T0[t], *snorm));
+            a3[t] = v;
+        }
+        __syncthreads();
+        mm(rr, num, a3);                                     // the slope r
+        mm(a3, rr, rr);
+        mm(a3, a3, fx);                                      // r^2 y^2
+        {
+            const E v = F::canon(F::sub(F::canon(F::sub(a3[t], a1[t])), a2[t]));
+            a3[t] = v;
+            b3[t] = F::canon(F::sub(a1[t], v));
+        }
+        __syncthreads();
+        mm(b3, rr, b3);
+        b3[t] = F::canon(F::sub(b3[t], b1[t]));
+        __syncthreads();
+        return 0;
+    }
+    __device__ __forceinline__ void copy(E* dst, const E* src) {
+        E v = F::zero();
+        if (t < d) v = src[t];
+        dst[t] = v;
+    }
+};
+// t mod l for one curve per workgroup of K threads, with #E = p + 1 - t.  Block b takes the curve (A[b], B[b]) (crate form) and
+// writes t_out[b]: -1 for a singular curve (4 A^3 + 27 B^2 = 0), else the residue in [0, l).  kq = p mod l.
+//   l = 2: the residue is 0 iff f = x^3 + A x + B has a root, i.e. gcd(x^p - x mod f, f) != 1 (roots_pow_scan, base x).
+//   mod_in != nullptr (l odd): the first modulus is block b's row of nmod <= K + 1 coefficients at mod_in + b*nmod, a monic factor
+//     of psi_l in crate form that the large regime hands down after a split; psi_l is not built.
+//   l = 3, 5, 7, 11: psi_l is built here from the closed forms of psi_3, psi_4 and the recurrence (schoofs.rs:368-431) by
+//     products without a modulus (at most 61 coefficients), so the call needs no transform and no other launch.  Then attempts
+//     on a monic modulus h of degree d, at first psi_l / l:
+//       f mod h from x mod h by two products; pi = (x^p, f^((p-1)/2)) (roots_pow_scan, base x; edf_pow_scan, base f);
+//       pi^2 = (pi_a(pi_a), pi_b(pi_a) pi_b) by Horner's loop where d - 1 < pow_cost, the products of one power with p, else
+//       (pi_a^p, pi_b^p pi_b); pi2 = 1 / 2 force the power / the composition (the test-build hook);
+//       Q = [kq](x, y) by kq - 1 sums with (x, y); E = pi^2 + Q — the point at infinity gives 0; then j pi for j = 1, 2, ...,
+//       each from the last by one sum with pi, compared with E: the j that matches, 0 if none does below l.
+//     A sum whose denominator is not invertible replaces h by a proper factor (SchoofWg::add) and the attempt starts over: every
+//     non-zero point of E[l] gives the same residue.  Degrees fall strictly, so there are at most d + 1 attempts; d = 1 is an
+//     attempt like any other (a root of psi_l says nothing about its y, so there is no shortcut).
+// A defect (SchoofWg::add's 3) stores 1 to *flag and gives 0.  Every thread takes every barrier: all decisions come from LDS
+// behind a barrier.
+// LDS: 20 rows of K and the two remainder rows of K + 1: smod, sx, sprod (2), sres, fx, x, 1, pi (2), pi^2 then E (2), Q then
+// j pi (2), num, r, the cofactor rows (2), the sum (2) = 22 K + 2 elements, and snorm and three ints beside them; secp256k1 at
+// K = 64: 45164 bytes of the 65536 a workgroup gets.  The rows from fx on serve the psi recurrence first.
+template <class F, int K>
+__global__ __launch_bounds__(K) void k_schoof_small(const typename F::elem* __restrict__ A, const typename F::elem* __restrict__ B,
+                                                    const typename F::elem* __restrict__ mod_in, uint32_t nmod, uint32_t l,
+                                                    uint32_t kq, long long* __restrict__ t_out, uint32_t pi2,
+                                                    uint32_t pow_cost, const uint8_t* __restrict__ exp_p, uint32_t nbits_p,
+                                                    const uint8_t* __restrict__ exp_h, uint32_t nbits_h, typename F::telem rinv,
+                                                    typename F::elem r1, int* __restrict__ flag) {
+    using E = typename F::elem;
+    constexpr int NR = 20;
+    __shared__ E buf[NR * K + 2 * (K + 1)];
+    __shared__ E snorm;
+    __shared__ int sdeg[3];
+    const uint32_t t = threadIdx.x;
+    const size_t b = blockIdx.x;
+    SchoofWg<F, K> w;
+    w.smod = buf; w.sx = buf + K; w.sprod = buf + 2 * K; w.sres = buf + 4 * K; w.fx = buf + 5 * K;
+    E *xr = buf + 6 * K, *one = buf + 7 * K, *pa = buf + 8 * K, *pb = buf + 9 * K, *ea = buf + 10 * K, *eb = buf + 11 * K;
+    E *qa = buf + 12 * K, *qb = buf + 13 * K;
+    w.num = buf + 14 * K; w.rr = buf + 15 * K; w.iv = buf + 16 * K; w.tz = buf + 17 * K; w.a3 = buf + 18 * K; w.b3 = buf + 19 * K;
+    w.rows = buf + NR * K; w.snorm = &snorm; w.sdeg = sdeg; w.rinv = rinv; w.r1 = r1; w.t = t; w.d = 3;
+    const E cA = F::canon(A[b]), cB = F::canon(B[b]);
+    w.cA = cA;
+    if (t == 0) {
+        const E a3 = w.cmul(w.cmul(cA, cA), cA), b2 = w.cmul(cB, cB);
+        const E disc = F::canon(F::add(F::canon(F::mul(F::from_u32(4), a3)), F::canon(F::mul(F::from_u32(27), b2))));
+        sdeg[2] = F::is_zero(disc) ? 1 : 0;
+    }
+    __syncthreads();
+    const bool singular = sdeg[2] != 0;
+    __syncthreads();
+    if (singular) {
+        if (t == 0) t_out[b] = -1;
+        return;
+    }
+    // f = x^3 + A x + B as a row
+    E* frow = w.fx;
+    {
+        E v = F::zero();
+        if (t == 0) v = cB;
+        if (t == 1) v = cA;
+        if (t == 3) v = r1;
+        frow[t] = v;
+    }
+    __syncthreads();
+    if (l == 2) {
+        modmul_plain<F>(w.sx, frow, rinv, t);
+        {
+            E v = F::zero();
+            if (t < 3) v = w.sx[t];
+            w.smod[t] = v;
+        }
+        __syncthreads();
+        roots_pow_scan<F, K>(w.sres, w.sx, w.sprod, w.smod, 3u, 0u, exp_p, nbits_p, rinv, r1, t);
+        E den = F::zero();
+        if (t < 3) den = w.sres[t];
+        if (t == 1) den = F::canon(F::sub(den, r1));
+        E *R0, *T0;
+        const int dg = w.gcd_h(den, R0, T0);
+        if (t == 0) t_out[b] = dg > 0 ? 0 : 1;
+        return;
+    }
+    if (mod_in) {
+        // ---- the modulus is given: a monic factor of psi_l in crate form, nmod = degree + 1 coefficients ----
+        const uint32_t dm = nmod - 1;
+        E v = F::zero();
+        if (t < dm) v = F::canon(mod_in[b * (size_t)nmod + t]);
+        w.num[t] = v;
+        __syncthreads();
+        modmul_plain<F>(w.sx, w.num, rinv, t);
+        w.smod[t] = w.sx[t];
+        w.d = dm;
+        __syncthreads();
+    } else {
+        // ---- psi_l, not monic, into hrow; then the modulus ----
+        E *F2 = buf + 6 * K, *p3 = buf + 7 * K, *p4 = buf + 8 * K, *c3 = buf + 9 * K, *p5 = buf + 10 * K, *c4 = buf + 11 * K;
+        E *p7 = buf + 12 * K, *p6 = buf + 13 * K, *tA = buf + 14 * K, *tB = buf + 15 * K;
+        auto sc = [&](uint32_t k, const E& v) { return F::canon(F::mul(F::from_u32(k), v)); };
+        {
+            E v3 = F::zero(), v4 = F::zero();
+            if (t == 0) {
+                const E aa = w.cmul(cA, cA), ab = w.cmul(cA, cB), bb = w.cmul(cB, cB), aaa = w.cmul(aa, cA);
+                p3[0] = F::canon(F::neg(aa)); p3[1] = sc(12, cB); p3[2] = sc(6, cA); p3[3] = F::zero(); p3[4] = sc(3, r1);
+                p4[0] = F::canon(F::neg(F::canon(F::add(sc(2, aaa), sc(16, bb)))));
+                p4[1] = F::canon(F::neg(sc(8, ab))); p4[2] = F::canon(F::neg(sc(10, aa))); p4[3] = sc(40, cB); p4[4] = sc(10, cA);
+                p4[5] = F::zero(); p4[6] = sc(2, r1);
+            }
+            if (t >= 5) p3[t] = v3;
+            if (t >= 7) p4[t] = v4;
+        }
+        __syncthreads();
+        const E* hrow = p3;
+        if (l >= 5) {
+            w.pmul(F2, frow, frow);
+            F2[t] = sc(16, F2[t]);
+            w.pmul(c3, p3, p3);
+            w.pmul(c3, c3, p3);                              // psi_3^3
+            w.pmul(p5, F2, p4);
+            p5[t] = F::canon(F::sub(p5[t], c3[t]));          // psi_5 = 16 f^2 psi_4 psi_2^3 - psi_1 psi_3^3
+            __syncthreads();
+            hrow = p5;
+        }
+        if (l >= 7) {
+            w.pmul(c4, p4, p4);                              // psi_4^2
+            w.pmul(tA, c4, p4);
+            w.pmul(tA, tA, F2);
+            w.pmul(p7, p5, c3);
+            p7[t] = F::canon(F::sub(p7[t], tA[t]));          // psi_7 = psi_5 psi_3^3 - 16 f^2 psi_2 psi_4^3
+            __syncthreads();
+            hrow = p7;
+        }
+        if (l == 11) {
+            tA[t] = F::canon(F::sub(p5[t], c4[t]));
+            __syncthreads();
+            w.pmul(p6, p3, tA);                              // psi_6 = psi_3 (psi_5 psi_2^2 - psi_1 psi_4^2)
+            w.pmul(tA, p5, p5);
+            w.pmul(tA, tA, p5);
+            w.pmul(tA, tA, p7);                              // psi_7 psi_5^3
+            w.pmul(tB, p6, p6);
+            w.pmul(tB, tB, p6);
+            w.pmul(tB, tB, p4);
+            w.pmul(tB, tB, F2);                              // 16 f^2 psi_4 psi_6^3
+            tA[t] = F::canon(F::sub(tA[t], tB[t]));          // psi_11
+            __syncthreads();
+            hrow = tA;
+        }
+        const uint32_t dl = (l * l - 1) / 2;
+        if (t == 0) snorm = F::canon(F::inv(hrow[dl]));
+        __syncthreads();
+        {
+            E v = F::zero();
+            if (t < dl) v = F::canon(F::mul(hrow[t], snorm));
+            w.smod[t] = v;
+        }
+        w.d = dl;
+        __syncthreads();
+    }
+    // ---- attempts ----
+    long long res = 0;
+    for (int attempt = 0; attempt <= K; ++attempt) {
+        const uint32_t d = w.d;
+        // x, 1 and f modulo h
+        {
+            E vx = F::zero(), v1 = F::zero();
+            if (d == 1) { if (t == 0) vx = F::canon(F::neg(F::canon(F::mul(w.smod[0], r1)))); }
+            else if (t == 1) vx = r1;
+            if (t == 0) v1 = r1;
+            xr[t] = vx; one[t] = v1;
+        }
+        __syncthreads();
+        w.mm(w.fx, xr, xr);
+        w.mm(w.fx, w.fx, xr);
+        {
+            E v = F::canon(F::add(w.fx[t], w.cmul(cA, xr[t])));
+            if (t == 0) v = F::canon(F::add(v, cB));
+            w.fx[t] = v;
+        }
+        __syncthreads();
+        // pi
+        if (d >= 2) {
+            roots_pow_scan<F, K>(w.sres, w.sx, w.sprod, w.smod, d, 0u, exp_p, nbits_p, rinv, r1, t);
+            w.copy(pa, w.sres);
+        } else {
+            w.copy(pa, xr);                                  // a constant is its own p-th power
+        }
+        __syncthreads();
+        edf_pow_scan<F>(w.sres, w.sx, w.sprod, w.fx, w.smod, d, exp_h, nbits_h, rinv, t);
+        w.copy(pb, w.sres);
+        __syncthreads();
+        // pi^2
+        if (pi2 == 2 || (pi2 == 0 && d - 1 < pow_cost)) {
+            w.compose(ea, pa, pa);
+            w.compose(w.num, pb, pa);
+            w.mm(eb, w.num, pb);
+        } else {
+            edf_pow_scan<F>(w.sres, w.sx, w.sprod, pa, w.smod, d, exp_p, nbits_p, rinv, t);
+            w.copy(ea, w.sres);
+            __syncthreads();
+            edf_pow_scan<F>(w.sres, w.sx, w.sprod, pb, w.smod, d, exp_p, nbits_p, rinv, t);
+            w.mm(eb, w.sres, pb);
+        }
+        // Q = [kq](x, y)
+        w.copy(qa, xr); w.copy(qb, one);
+        __syncthreads();
+        int st = 0;
+        for (uint32_t i = 1; i < kq && st == 0; ++i) {
+            st = w.add(qa, qb, xr, one);
+            if (st == 0) { w.copy(qa, w.a3); w.copy(qb, w.b3); __syncthreads(); }
+        }
+        if (st == 2) continue;
+        if (st != 0) { if (t == 0) *flag = 1; break; }       // [i](x, y) is never the point at infinity below l
+        // E = pi^2 + Q
+        st = w.add(ea, eb, qa, qb);
+        if (st == 2) continue;
+        if (st == 1) break;                                  // pi^2 + [p] = O: the trace is 0 modulo l
+        if (st == 3) { if (t == 0) *flag = 1; break; }
+        w.copy(ea, w.a3); w.copy(eb, w.b3);
+        w.copy(qa, pa); w.copy(qb, pb);
+        __syncthreads();
+        // j pi
+        for (uint32_t j = 1; j < l; ++j) {
+            if (w.eq(qa, ea) && w.eq(qb, eb)) { res = (long long)j; break; }
+            if (j + 1 == l) break;
+            st = w.add(qa, qb, pa, pb);
+            if (st != 0) break;
+            w.copy(qa, w.a3); w.copy(qb, w.b3);
+            __syncthreads();
+        }
+        if (st == 2) continue;
+        if (st == 3 && t == 0) *flag = 1;
+        break;
+    }
+    if (t == 0) t_out[b] = res;
+}
+
+// ---------------------------------------------------------------------------------------------
 // generic element-wise helper for tree construction: functor(i) for i < n
 // ---------------------------------------------------------------------------------------------
 template <class Fn>

@@ -34,7 +34,7 @@ EXPORTS = ["ecfft_elem_size", "ecfft_build_fftree", "ecfft_fftree_new", "ecfft_c
            "ecfft_fftree_serialize", "ecfft_fftree_deserialize", "ecfft_tree_rational_maps", "ecfft_ctx_trim", "ecfft_comm_abort", "ecfft_comm_set_rccl_library", "ecfft_comm_set_link_striping",
            "ecfft_poly_mul", "ecfft_poly_inv_series", "ecfft_poly_divrem", "ecfft_poly_eval_points", "ecfft_poly_interpolate",
            "ecfft_poly_pow_mod", "ecfft_poly_mul_mod", "ecfft_poly_gcd", "ecfft_poly_xgcd", "ecfft_poly_find_roots",
-           "ecfft_poly_compose_mod", "ecfft_poly_squarefree", "ecfft_poly_distinct_degree", "ecfft_poly_equal_degree",
+           "ecfft_poly_compose_mod", "ecfft_poly_squarefree", "ecfft_poly_distinct_degree", "ecfft_poly_equal_degree", "ecfft_division_polynomial", "ecfft_curve_trace_mod", "ecfft_curve_cardinality",
            "ecfft_find_curve_candidate", "ecfft_curve_two_sylow", "ecfft_find_curve", "ecfft_build_fftree_on_curve"]
 # include/ecfft_hip.h ECFFT_GCD_SMALL_MAX: max(na, nb) up to which a gcd runs in one workgroup per pair, on any tree
 GCD_SMALL_MAX = 256
@@ -46,9 +46,14 @@ COMPOSE_SMALL_MAX = 65
 DDF_SMALL_MAX = 65
 # include/ecfft_hip.h ECFFT_EDF_SMALL_MAX: ng up to which poly_equal_degree finishes a polynomial in one workgroup, on any tree
 EDF_SMALL_MAX = 65
+# include/ecfft_hip.h ECFFT_SCHOOF_SMALL_MAX / ECFFT_SCHOOF_MAX_L / ECFFT_ORDER_BYTES: coefficients of a modulus that one workgroup of
+# curve_trace_mod finishes; the largest prime l and the largest index of division_polynomial; bytes of an order
+SCHOOF_SMALL_MAX = 65
+SCHOOF_MAX_L = 199
+ORDER_BYTES = 40
 
 # include/ecfft_hip_hooks.h: only in a build with -DECFFT_TEST_HOOKS (tests/hooks/libecfft_hip_hooks.so), never in the shipped library
-HOOK_EXPORTS = ['ecfft_selftest_field', 'ecfft_selfcheck_pointwise_z', 'ecfft_test_fail_next_collective', 'ecfft_selftest_blk16', 'ecfft_selftest_blk16_small', 'ecfft_test_fail_build_rank', 'ecfft_comm_init_projection', 'ecfft_selftest_blk32', 'ecfft_ctx_low_map', 'ecfft_curve_search_stats', 'ecfft_test_ddf_iterate']
+HOOK_EXPORTS = ['ecfft_selftest_field', 'ecfft_selfcheck_pointwise_z', 'ecfft_test_fail_next_collective', 'ecfft_selftest_blk16', 'ecfft_selftest_blk16_small', 'ecfft_test_fail_build_rank', 'ecfft_comm_init_projection', 'ecfft_selftest_blk32', 'ecfft_ctx_low_map', 'ecfft_curve_search_stats', 'ecfft_test_ddf_iterate', 'ecfft_test_schoof_pi2']
 
 EXCHANGE_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_void_p),
                                ctypes.POINTER(ctypes.c_size_t), ctypes.c_int, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_void_p),
@@ -93,6 +98,9 @@ def _bind(L):
     L.ecfft_poly_squarefree.restype, L.ecfft_poly_squarefree.argtypes = ci, [vp, vp, sz, vp, vp, sz, ci, vp]
     L.ecfft_poly_distinct_degree.restype, L.ecfft_poly_distinct_degree.argtypes = ci, [vp, vp, sz, vp, vp, sz, ci, vp]
     L.ecfft_poly_equal_degree.restype, L.ecfft_poly_equal_degree.argtypes = ci, [vp, vp, sz, sz, vp, vp, sz, ci, vp]
+    L.ecfft_division_polynomial.restype, L.ecfft_division_polynomial.argtypes = ci, [vp, vp, vp, sz, vp, sz, ci, vp]
+    L.ecfft_curve_cardinality.restype, L.ecfft_curve_cardinality.argtypes = ci, [vp, vp, vp, vp, vp, sz, ci, vp]
+    L.ecfft_curve_trace_mod.restype, L.ecfft_curve_trace_mod.argtypes = ci, [vp, vp, vp, sz, vp, sz, ci, vp]
     L.ecfft_tree_table.restype, L.ecfft_tree_table.argtypes = ci, [vp, sz, ci, vp, sz, ctypes.POINTER(sz)]
     L.ecfft_build_points.restype, L.ecfft_build_points.argtypes = ci, [ci, sz, vp, vp, vp]
     L.ecfft_device_info.restype, L.ecfft_device_info.argtypes = ci, [ci, ctypes.c_char_p, sz]
@@ -156,6 +164,7 @@ def _bind(L):
         L.ecfft_ctx_low_map.restype, L.ecfft_ctx_low_map.argtypes = ci, [vp, ci]
         L.ecfft_curve_search_stats.restype, L.ecfft_curve_search_stats.argtypes = ci, [ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_double), sz, ci]
         L.ecfft_test_ddf_iterate.restype, L.ecfft_test_ddf_iterate.argtypes = ci, [ci]
+        L.ecfft_test_schoof_pi2.restype, L.ecfft_test_schoof_pi2.argtypes = ci, [ci]
         L.ecfft_comm_init_projection.restype = ci
         L.ecfft_comm_init_projection.argtypes = [ci, ci, ci, ctypes.c_double, ctypes.c_double, ctypes.POINTER(vp)]
     return L
@@ -362,6 +371,29 @@ class Field:
         if n.value == 0:
             return None
         return {"index": idx.value, "n": n.value, "a": a, "bb": bb, "gen": gen, "offset": off}
+
+    MODULUS = {"secp256k1": 2**256 - 2**32 - 977, "m31": 2**31 - 1}
+
+    def to_ints(self, a):
+        """in-memory elements -> a list of Python ints (standard form)"""
+        std = self.to_standard(a)
+        return [int.from_bytes(std[i].tobytes(), "little") for i in range(std.shape[0])]
+
+    def from_ints(self, vals):
+        """Python ints (reduced modulo p) -> in-memory elements"""
+        p, nb = self.MODULUS[self.name], self.dtype.itemsize * self.limbs
+        raw = b"".join((int(v) % p).to_bytes(nb, "little") for v in vals)
+        return self.from_standard(np.frombuffer(raw, self.dtype).reshape(self.shape(len(vals))).copy())
+
+    def short_weierstrass(self, a, bb):
+        """(A, B) of y^2 = x^3 + A x + B for the curves y^2 = x (x^2 + a[i] x + bb[i]) of find_curve, under x -> x - a/3:
+        A = bb - a^2/3, B = 2 a^3/27 - a bb/3.  Same group, so curve_trace_mod counts a found curve.  Host arrays in the crate's form."""
+        p = self.MODULUS[self.name]
+        i3, i27 = pow(3, -1, p), pow(27, -1, p)
+        av, bv = self.to_ints(a), self.to_ints(bb)
+        A = [(b - x * x * i3) % p for x, b in zip(av, bv)]
+        B = [(2 * x**3 * i27 - x * b * i3) % p for x, b in zip(av, bv)]
+        return self.from_ints(A), self.from_ints(B)
 
     def build_fftree_on_curve(self, n, a, bb, gen, gen_log_order, offset, device=0):
         """`build_fftree(n)` on the good curve y^2 = x(x^2 + a x + bb) (ecfft_build_fftree_on_curve): gen = (x, y) of order
@@ -785,6 +817,71 @@ class FFTree:
             row, n = self.poly_equal_degree(np.ascontiguousarray(gd), d)
             out[d] = self.edf_unpack(row, n[0], d)
         return out
+
+    @staticmethod
+    def division_polynomial_len(n):
+        """L(n): the number of coefficients of psi_n with the factor 2y of an even index removed"""
+        n = int(n)
+        return 1 if n < 2 else ((n * n - 1) // 2 + 1 if n & 1 else (n * n - 4) // 2 + 1)
+
+    def division_polynomial(self, A, B, n):
+        """psi_n of the curves y^2 = x^3 + A[b] x + B[b] (ecfft_division_polynomial <-> division_polynomial, examples/schoofs.rs:368-431):
+        count * L(n) coefficients laid end to end, low to high, in the crate's form, not monic; the factor 2y of an even n is removed
+        (psi_2 = 1).  A and B hold count elements each.  n <= 4 works on any tree, otherwise a tree of next_pow2(L(n)) leaves.
+        numpy arrays (host) or contiguous CUDA tensors (device, on the current stream).  Asynchronous for device tensors."""
+        (A, B), (pA, pB), new, mem, stream = self._poly_io([A, B])
+        count = A.shape[0]
+        assert count > 0 and B.shape[0] == count
+        out = new(count * self.division_polynomial_len(n))
+        rc = self._L.ecfft_division_polynomial(self._h, pA, pB, int(n), self._ptr(out), count, mem, stream)
+        if rc == ERR_BAD_ARG:
+            raise ValueError("division_polynomial: n must be at most SCHOOF_MAX_L, on a context that holds a full tree")
+        _check(rc)
+        return out
+
+    def curve_trace_mod(self, A, B, l):
+        """t mod l for the curves y^2 = x^3 + A[b] x + B[b] over the field, #E = p + 1 - t (ecfft_curve_trace_mod <->
+        frobenius_trace_mod_l / has_even_order, examples/schoofs.rs:76-138, 345-366): a numpy int64 array with one residue in [0, l)
+        per curve, -1 for a singular curve.  A and B hold count elements each in the crate's form (Field.from_standard), numpy
+        arrays (host) or contiguous CUDA tensors (device, on the current stream).  l is 2 or an odd prime up to SCHOOF_MAX_L;
+        anything else raises ValueError.  l <= 11: one launch for all curves, on any tree.  Above, the curves run one after
+        another on a tree of next_pow2(2 L(l) - 1) leaves, L = division_polynomial_len.  Synchronous."""
+        (A, B), (pA, pB), _, mem, stream = self._poly_io([A, B])
+        count = A.shape[0]
+        assert count > 0 and B.shape[0] == count
+        t = np.empty(count, np.int64)
+        rc = self._L.ecfft_curve_trace_mod(self._h, pA, pB, int(l), t.ctypes.data, count, mem, stream)
+        if rc == ERR_BAD_ARG:
+            raise ValueError("curve_trace_mod: l must be 2 or an odd prime up to SCHOOF_MAX_L, on a context that holds a full tree")
+        _check(rc)
+        return t
+
+    def schoof_primes(self):
+        """2, 3, 5, ... until the product exceeds 4 sqrt(p): the primes curve_cardinality uses"""
+        p, m, out, l = self.field.MODULUS[self.field.name], 1, [], 2
+        while m * m <= 16 * p:
+            if l == 2 or (l % 2 and all(l % q for q in range(3, int(l ** 0.5) + 1, 2))):
+                out.append(l)
+                m *= l
+            l += 1
+        return out
+
+    def curve_cardinality(self, A, B, traces=False):
+        """#E(F_p) of the curves y^2 = x^3 + A[b] x + B[b] as a list of Python ints, 0 for a singular curve (ecfft_curve_cardinality
+        <-> cardinality, examples/schoofs.rs:30-71): curve_trace_mod for every prime of schoof_primes(), then the CRT on the
+        host.  traces=True also returns the residues, a numpy int64 array of count x len(schoof_primes()).  Needs the tree of the
+        largest prime: 512 leaves for M31, 2^14 for secp256k1.  Synchronous."""
+        (A, B), (pA, pB), _, mem, stream = self._poly_io([A, B])
+        count = A.shape[0]
+        assert count > 0 and B.shape[0] == count
+        order = np.zeros(count * ORDER_BYTES, np.uint8)
+        tr = np.empty((count, len(self.schoof_primes())), np.int64)
+        rc = self._L.ecfft_curve_cardinality(self._h, pA, pB, order.ctypes.data, tr.ctypes.data, count, mem, stream)
+        if rc == ERR_BAD_ARG:
+            raise ValueError("curve_cardinality: no curves, or a context that holds no full tree")
+        _check(rc)
+        out = [int.from_bytes(order[b * ORDER_BYTES:(b + 1) * ORDER_BYTES].tobytes(), "little") for b in range(count)]
+        return (out, tr) if traces else out
 
     # ---- the remaining FFTree algorithms (host numpy arrays; synchronous) ---------------------
     def _np(self, x):

@@ -351,6 +351,31 @@ public:
         }
         return out;
     }
+    // L(n): the coefficients of psi_n with the factor 2y of an even index removed
+    static size_t division_polynomial_len(size_t n) { return n < 2 ? 1 : ((n & 1) ? (n * n - 1) / 2 + 1 : (n * n - 4) / 2 + 1); }
+    // psi_n of y^2 = x^3 + A x + B, L(n) coefficients low to high, not monic (ecfft_division_polynomial <-> division_polynomial,
+    // examples/schoofs.rs:368-431).  n <= 4 on any tree, otherwise next_pow2(L(n)) leaves.
+    std::vector<Elem> division_polynomial(const Elem& A, const Elem& B, size_t n) const {
+        std::vector<Elem> out(division_polynomial_len(n));
+        check(ecfft_division_polynomial(ctx_, &A, &B, n, out.data(), 1, ECFFT_MEM_HOST, nullptr));
+        return out;
+    }
+    // t mod l with #E = p + 1 - t for the curves y^2 = x^3 + A[i] x + B[i], -1 for a singular curve (ecfft_curve_trace_mod <->
+    // frobenius_trace_mod_l / has_even_order, examples/schoofs.rs:76-138, 345-366).  l is 2 or an odd prime up to
+    // ECFFT_SCHOOF_MAX_L; l <= 11 on any tree, otherwise next_pow2(2 L(l) - 1) leaves.  Synchronous.
+    std::vector<int64_t> curve_trace_mod(const std::vector<Elem>& A, const std::vector<Elem>& B, size_t l) const {
+        require(!A.empty() && A.size() == B.size(), "curve_trace_mod: A and B must hold one element per curve");
+        std::vector<int64_t> t(A.size());
+        check(ecfft_curve_trace_mod(ctx_, A.data(), B.data(), l, t.data(), A.size(), ECFFT_MEM_HOST, nullptr));
+        return t;
+    }
+    // #E(F_p) of y^2 = x^3 + A x + B as ECFFT_ORDER_BYTES little-endian bytes, zero for a singular curve (ecfft_curve_cardinality <->
+    // cardinality, examples/schoofs.rs:30-71).  Needs the tree of the largest prime of the rule.  Synchronous.
+    std::array<uint8_t, ECFFT_ORDER_BYTES> curve_cardinality(const Elem& A, const Elem& B) const {
+        std::array<uint8_t, ECFFT_ORDER_BYTES> order{};
+        check(ecfft_curve_cardinality(ctx_, &A, &B, order.data(), nullptr, 1, ECFFT_MEM_HOST, nullptr));
+        return order;
+    }
     size_t device_bytes() const { return ecfft_ctx_device_bytes(ctx_); }     // HBM held between calls: tables + scratch
     // device-resident variants (pointers into HBM, caller's stream)
     void enter_device(const Elem* coeffs, Elem* evals, size_t n, void* stream) const { check(ecfft_enter(ctx_, coeffs, evals, n, ECFFT_MEM_DEVICE, stream)); }

@@ -347,6 +347,71 @@ int ecfft_poly_distinct_degree(ecfft_ctx* ctx, const void* f, size_t nf, void* f
 int ecfft_poly_equal_degree(ecfft_ctx* ctx, const void* g, size_t ng, size_t d, void* factors, int64_t* n_factors, size_t count, int mem,
                             void* stream);
 
+/* Division polynomials of short Weierstrass curves y^2 = x^3 + A x + B on the GPU.
+ *   ecfft_division_polynomial <-> division_polynomial(n, &curve)                          examples/schoofs.rs:368-431
+ * A and B are `count` elements each in the crate's form (host or device memory per `mem`); out is count x L(n) coefficients,
+ * low to high, in the crate's form, fully reduced and NOT made monic: psi_n in the reference's convention, where the factor
+ * 2y of an even index is removed (psi_2 -> 1, psi_4 -> the sextic with leading coefficient 2).
+ *   L(n) = (n^2 - 1)/2 + 1 for odd n; (n^2 - 4)/2 + 1 for even n >= 2; L(0) = L(1) = 1.  The leading coefficient is n for odd n
+ *   and n/2 for even n; psi_0 = 0.
+ * Method: a host driver on the products of ecfft_poly_mul, batched over `count`: only the O(log n) indices the recurrence
+ * reaches are computed (m - 2 .. m + 2 of m = k / 2, downwards from n), each once (the reference recurses exponentially).
+ * Tree: n <= 4 are closed forms and need no transform (any tree).  Otherwise next_pow2(L(n)) leaves: every product of the
+ * recurrence is a factor of one term of a psi_k with k <= n, so none has more than L(n) coefficients, and the last ones have
+ * exactly L(n).  Checked before anything runs, else ECFFT_ERR_TREE_TOO_SMALL.
+ * ECFFT_ERR_BAD_ARG: a NULL pointer, count 0, n above ECFFT_SCHOOF_MAX_L, a context that holds no full tree, a byte count that
+ * would wrap.  Nothing fails on the data (a singular curve has division polynomials too): the call is asynchronous on `stream`
+ * like ecfft_poly_mul.  Memory, stream, threading and pooled temporaries as for ecfft_poly_mul. */
+#define ECFFT_SCHOOF_MAX_L 199       /* the largest index and the largest prime l (the last entry of the reference's table) */
+int ecfft_division_polynomial(ecfft_ctx* ctx, const void* A, const void* B, size_t n, void* out, size_t count, int mem, void* stream);
+
+/* Schoof's algorithm, one prime at a time: the trace of Frobenius of a curve modulo a small prime.
+ *   ecfft_curve_trace_mod <-> frobenius_trace_mod_l(l, curve, ring) and has_even_order(curve)      examples/schoofs.rs:76-138, 345-366
+ * Curves are short Weierstrass pairs y^2 = x^3 + A x + B, `count` of them per call: A and B are `count` elements each in the
+ * crate's form, in host or device memory per `mem`.  `t_out` is a HOST pointer whatever `mem` is, `count` entries: t mod l in
+ * [0, l) where #E(F_p) = p + 1 - t.  A singular curve (4 A^3 + 27 B^2 = 0) gets -1 in its entry; nothing fails on it.
+ * Valid l: 2, and the odd primes up to ECFFT_SCHOOF_MAX_L = 199; anything else is ECFFT_ERR_BAD_ARG.
+ * Method: l = 2: t is even iff x^3 + A x + B has a root, i.e. gcd(x^p - x mod f, f) != 1.  Odd l: in the ring F_p[x]/(h), at
+ *   first with h = psi_l made monic (the l-th division polynomial, (l^2 - 1)/2 + 1 coefficients, built from the closed forms of
+ *   psi_3 and psi_4 and the reference's recurrence, schoofs.rs:368-431), with f = x^3 + A x + B:
+ *     pi = (x^p, f^((p-1)/2) y); pi^2 either as the composition (pi_a(pi_a), pi_b(pi_a) pi_b) or as the powers (pi_a^p,
+ *     pi_b^(p+1)), whichever takes fewer modular products at the degree of h (d - 1 against bits + popcount(p) - 2 per
+ *     coordinate); Q = [p mod l](x, y); E = pi^2 + Q; then the j in [1, l) with j pi = E, taking j pi from (j - 1) pi by one sum.
+ *     E = O, or no j, is t = 0.  The group law is the reference's Add (schoofs.rs:237-273) plus the case it lacks: a1 = a2 with
+ *     b1 = -b2 is the point at infinity.  A denominator that is not invertible replaces h by the proper factor gcd(denominator,
+ *     h) and the attempt starts over; with a1 = a2 and b1 != +-b2 the factor is gcd(b1 - b2, h), else gcd(b1 + b2, h).  Degrees
+ *     fall strictly, so the attempts are bounded.  Every non-zero point of E[l] satisfies the same characteristic equation, so the
+ *     residue is defined by the curve alone and does not depend on where the splits fall.
+ *   There is NO shortcut on a modulus of degree 1 (the reference's, schoofs.rs:86-95, takes a root of psi_l for a rational point
+ *   of order l; its y may lie in F_p^2, and then the eigenvalue is -1, not +1).
+ * ECFFT_SCHOOF_SMALL_MAX: coefficients of a modulus up to which ONE workgroup finishes a curve (k_schoof_small).  Where psi_l fits
+ * (l <= 11) all `count` curves are ONE launch, psi_l is built in the kernel, and the call needs no transform (any tree).
+ * Above it (l = 13 .. 199) the curves run one after another on a host driver: psi_l from ecfft_division_polynomial's driver,
+ * made monic; the modulus kept once per attempt as ecfft_poly_pow_mod keeps it; products, powers and the kept composition (one
+ * set of baby steps of pi_a shared by both coordinates of pi^2) on it; inverses as the cofactor of ecfft_poly_xgcd's bodies.
+ * After a split the new modulus is kept again, and a factor of at most ECFFT_SCHOOF_SMALL_MAX coefficients is handed to the
+ * workgroup kernel.
+ * Tree: l <= 11 none.  Otherwise next_pow2(2 L(l) - 1) leaves, ecfft_poly_gcd's rule on rows of L(l) coefficients, which covers
+ * every product on the modulus and the driver of psi_l; checked before anything runs, else ECFFT_ERR_TREE_TOO_SMALL.
+ * ECFFT_ERR_BAD_ARG: a NULL pointer, count 0, an l that is not valid, a context that holds no full tree, a byte count that would
+ * wrap.  ECFFT_ERR_HIP also reports a sum that the group law excludes (a defect, not a property of the data).  The call is
+ * SYNCHRONOUS.  Memory, stream, threading and pooled temporaries as for ecfft_poly_gcd. */
+#define ECFFT_SCHOOF_SMALL_MAX 65    /* coefficients of a modulus that one workgroup finishes, any tree */
+int ecfft_curve_trace_mod(ecfft_ctx* ctx, const void* A, const void* B, size_t l, int64_t* t_out, size_t count, int mem, void* stream);
+
+/* The number of points of a curve: Schoof's algorithm.
+ *   ecfft_curve_cardinality <-> cardinality(curve)                                          examples/schoofs.rs:30-71
+ * A and B as for ecfft_curve_trace_mod.  `order` is a HOST pointer of count x ECFFT_ORDER_BYTES little-endian bytes: #E(F_p) of
+ * curve b (it can exceed 2^256 for secp256k1); 0 for a singular curve.  `traces` (a HOST pointer, may be NULL) receives count x
+ * (number of primes used) residues, row b = t mod 2, 3, 5, ... of curve b (-1 in every entry of a singular curve).
+ * The primes are l = 2, 3, 5, ... until their product m exceeds 4 sqrt(p), decided exactly as m^2 > 16 p: l <= 17 (7 primes) for
+ * M31, l <= 103 (27 primes) for secp256k1.  Per prime one ecfft_curve_trace_mod over all curves; then on the host the incremental
+ * CRT of schoofs.rs:52-70 with the representative of t in (-m/2, m/2] and #E = p + 1 - t.
+ * Tree: the rule of the largest l: 512 leaves for M31, 2^14 for secp256k1; checked before anything runs.
+ * Errors and everything else as ecfft_curve_trace_mod.  SYNCHRONOUS. */
+#define ECFFT_ORDER_BYTES 40
+int ecfft_curve_cardinality(ecfft_ctx* ctx, const void* A, const void* B, void* order, int64_t* traces, size_t count, int mem, void* stream);
+
 /* The remaining FFTree algorithms, composed from the same GPU kernels.  Synchronous.
  *   ecfft_mextend         <-> FFTree::mextend(&self, &[F], Moiety)      src/fftree.rs:138-141
  *   ecfft_redc            <-> FFTree::redc_z0 / redc_z1(&self, evals, a)  src/fftree.rs:264-275  (moiety S0 / S1)

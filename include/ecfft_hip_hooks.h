@@ -64,6 +64,11 @@ int ecfft_curve_search_stats(uint64_t* lens, double* seconds, size_t cap, int re
  * h_i^p on the kept modulus.  The outputs are the same bytes either way (tests/test_gpu_polyddf.py, tools/polyddf_time.py). */
 int ecfft_test_ddf_iterate(int mode);
 
+/* test / measurement hook, process wide: how ecfft_curve_trace_mod takes pi^2 from pi.  0: the shipped rule (the count of modular
+ * products at the degree of the modulus)   1: always the powers (pi_a^p, pi_b^(p+1))   2: always the composition (pi_a(pi_a),
+ * pi_b(pi_a) pi_b).  The residues are the same either way (tests/test_gpu_schoof.py). */
+int ecfft_test_schoof_pi2(int mode);
+
 #ifdef __cplusplus
 }
 #endif
