@@ -102,6 +102,11 @@ pub mod ffi {
         pub fn ecfft_curve_two_sylow(field: i32, device: i32, a: *const c_void, bb: *const c_void, count: usize, n_out: *mut u32, x_out: *mut c_void) -> i32;
         pub fn ecfft_find_curve(field: i32, device: i32, k: u32, seed: u64, start: u64, max_candidates: u64, index_out: *mut u64, n_out: *mut u32, a_out: *mut c_void, bb_out: *mut c_void, gen_xy_out: *mut c_void, offset_xy_out: *mut c_void) -> i32;
         pub fn ecfft_build_fftree_on_curve(field: i32, n: usize, a: *const c_void, bb: *const c_void, gen_xy: *const c_void, gen_log_order: u32, offset_xy: *const c_void, device: i32, out: *mut *mut EcfftCtx) -> i32;
+        // trees on short-Weierstrass curves y^2 = x^3 + A x + B (src/ec.rs:432-447, 498-554; src/utils.rs:356-365); host pointers, synchronous
+        pub fn ecfft_curve_point_mul(field: i32, device: i32, a: *const c_void, b: *const c_void, ncurves: usize, points_xy: *const c_void, inf_in: *const u8, scalars: *const c_void, nscalars: usize, scalar_bytes: usize, out_xy: *mut c_void, inf_out: *mut u8, count: usize) -> i32;
+        pub fn ecfft_curve_point_two_adicity(field: i32, device: i32, a: *const c_void, b: *const c_void, ncurves: usize, points_xy: *const c_void, inf_in: *const u8, cap: u32, out: *mut i32, count: usize) -> i32;
+        pub fn ecfft_curve_find_generator(field: i32, device: i32, a: *const c_void, b: *const c_void, order: *const c_void, start: u64, max_candidates: u64, log_order_out: *mut u32, gen_xy: *mut c_void, offset_xy: *mut c_void, x_out: *mut u64) -> i32;
+        pub fn ecfft_build_ec_fftree(field: i32, n: usize, a: *const c_void, b: *const c_void, gen_xy: *const c_void, gen_log_order: u32, offset_xy: *const c_void, device: i32, out: *mut *mut EcfftCtx) -> i32;
         pub fn ecfft_device_alloc(device: i32, bytes: usize, out: *mut *mut c_void) -> i32;
         pub fn ecfft_device_free(ptr: *mut c_void) -> i32;
         pub fn ecfft_device_copy(dst: *mut c_void, src: *const c_void, bytes: usize, kind: i32) -> i32; // 0 D2H, 1 H2D, 2 D2D
@@ -161,6 +166,16 @@ pub struct FoundCurve<F: HipField> {
     pub offset: [F; 2],
 }
 
+/// What `HipFFTree::curve_find_generator` returns: a generator (x, y) of order 2^log_order of y^2 = x^3 + A x + B, a coset offset
+/// ((0, 0) when the window holds none) and the integer x-coordinate the generator came from
+#[derive(Clone, Copy, Debug)]
+pub struct FoundGenerator<F: HipField> {
+    pub log_order: u32,
+    pub x: u64,
+    pub gen: [F; 2],
+    pub offset: [F; 2],
+}
+
 fn check(rc: i32) {
     match rc {
         ffi::OK => {}
@@ -216,6 +231,72 @@ impl<F: HipField> HipFFTree<F> {
         match unsafe {
             ffi::ecfft_build_fftree_on_curve(F::FIELD_ID, n, (&c.a as *const F).cast(), (&c.bb as *const F).cast(), c.gen.as_ptr().cast(), c.n,
                 c.offset.as_ptr().cast(), device, &mut ctx)
+        } {
+            ffi::ERR_TREE_TOO_LARGE => None,
+            rc => {
+                check(rc);
+                Some(Self { ctx, _f: PhantomData })
+            }
+        }
+    }
+
+    /// `out[i] = [k_i] P_i` on y^2 = x^3 + a x + b (ecfft_curve_point_mul <-> `Point::mul`, src/ec.rs:432-447): one curve for all
+    /// rows or one per row, `scalars` rows of `scalar_bytes` little-endian bytes (one row or one per point), `inf` empty or one byte
+    /// per point.  Returns the points and their infinity flags.  Panics for a point off its curve or a singular curve.
+    pub fn curve_point_mul(a: &[F], b: &[F], points: &[[F; 2]], scalars: &[u8], scalar_bytes: usize, inf: &[u8], device: i32) -> (Vec<[F; 2]>, Vec<u8>) {
+        assert_eq!(core::mem::size_of::<F>(), F::ELEM_BYTES, "unexpected in-memory size of the field element");
+        let count = points.len();
+        assert!(count > 0 && a.len() == b.len() && (a.len() == 1 || a.len() == count), "one curve, or one per point");
+        assert!(scalar_bytes >= 1 && scalars.len() % scalar_bytes == 0, "scalars: whole rows of scalar_bytes bytes");
+        let nscalars = scalars.len() / scalar_bytes;
+        assert!(nscalars == 1 || nscalars == count, "one scalar, or one per point");
+        assert!(inf.is_empty() || inf.len() == count, "inf: one byte per point");
+        let mut out = vec![[F::zero(); 2]; count];
+        let mut inf_out = vec![0u8; count];
+        check(unsafe {
+            ffi::ecfft_curve_point_mul(F::FIELD_ID, device, a.as_ptr().cast(), b.as_ptr().cast(), a.len(), points.as_ptr().cast(),
+                if inf.is_empty() { core::ptr::null() } else { inf.as_ptr() }, scalars.as_ptr().cast(), nscalars, scalar_bytes, out.as_mut_ptr().cast(),
+                inf_out.as_mut_ptr(), count)
+        });
+        (out, inf_out)
+    }
+
+    /// the smallest i <= cap with 2^i P the identity, -1 when there is none (ecfft_curve_point_two_adicity <-> `two_adicity`,
+    /// src/utils.rs:356-365)
+    pub fn curve_point_two_adicity(a: &[F], b: &[F], points: &[[F; 2]], cap: u32, inf: &[u8], device: i32) -> Vec<i32> {
+        assert_eq!(core::mem::size_of::<F>(), F::ELEM_BYTES, "unexpected in-memory size of the field element");
+        let count = points.len();
+        assert!(count > 0 && a.len() == b.len() && (a.len() == 1 || a.len() == count), "one curve, or one per point");
+        assert!(inf.is_empty() || inf.len() == count, "inf: one byte per point");
+        let mut out = vec![0i32; count];
+        check(unsafe {
+            ffi::ecfft_curve_point_two_adicity(F::FIELD_ID, device, a.as_ptr().cast(), b.as_ptr().cast(), a.len(), points.as_ptr().cast(),
+                if inf.is_empty() { core::ptr::null() } else { inf.as_ptr() }, cap, out.as_mut_ptr(), count)
+        });
+        out
+    }
+
+    /// The arguments of `build_ec_fftree` from a curve and its number of points as `curve_cardinality` returns it
+    /// (ecfft_curve_find_generator): `None` when the window `start .. start + max_candidates` holds no point of order 2^v.
+    pub fn curve_find_generator(a: &F, b: &F, order: &[u8; 40], start: u64, max_candidates: u64, device: i32) -> Option<FoundGenerator<F>> {
+        assert_eq!(core::mem::size_of::<F>(), F::ELEM_BYTES, "unexpected in-memory size of the field element");
+        let (mut log_order, mut x) = (0u32, 0u64);
+        let (mut gen, mut offset) = ([F::zero(); 2], [F::zero(); 2]);
+        check(unsafe {
+            ffi::ecfft_curve_find_generator(F::FIELD_ID, device, (a as *const F).cast(), (b as *const F).cast(), order.as_ptr().cast(), start, max_candidates,
+                &mut log_order, gen.as_mut_ptr().cast(), offset.as_mut_ptr().cast(), &mut x)
+        });
+        (log_order != 0).then_some(FoundGenerator { log_order, x, gen, offset })
+    }
+
+    /// `build_ec_fftree(subgroup_generator, subgroup_order, coset_offset, n)` (src/ec.rs:498-554) on y^2 = x^3 + a x + b
+    /// (ecfft_build_ec_fftree): `None` when log2 n exceeds the generator's log order
+    pub fn build_ec_fftree(n: usize, a: &F, b: &F, gen: &[F; 2], gen_log_order: u32, offset: &[F; 2], device: i32) -> Option<Self> {
+        assert_eq!(core::mem::size_of::<F>(), F::ELEM_BYTES, "unexpected in-memory size of the field element");
+        let mut ctx = core::ptr::null_mut();
+        match unsafe {
+            ffi::ecfft_build_ec_fftree(F::FIELD_ID, n, (a as *const F).cast(), (b as *const F).cast(), gen.as_ptr().cast(), gen_log_order,
+                offset.as_ptr().cast(), device, &mut ctx)
         } {
             ffi::ERR_TREE_TOO_LARGE => None,
             rc => {

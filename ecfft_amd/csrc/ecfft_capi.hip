@@ -1859,6 +1859,190 @@ int ecfft_build_fftree_on_curve(int field, size_t n, const void* a, const void* 
     });
 }
 
+}  // extern "C"
+
+// ---- points of short-Weierstrass curves: ecfft_curve_point_mul / _point_two_adicity / _find_generator / ecfft_build_ec_fftree ----
+namespace {
+// 2^-256 in plain form, what takes a crate-form element of secp256k1 to plain form by one multiply (1 for M31: nothing to do)
+template <class F>
+typename F::elem crate_rinv() {
+    if constexpr (std::is_same<F, Secp256k1>::value) { Fe256 r = Secp256k1::zero(); r.l[0] = 977; r.l[1] = 1; return Secp256k1::inv(r); }
+    else return 1u;
+}
+template <class F>
+typename F::elem elem_from_u64(uint64_t v) {
+    if constexpr (std::is_same<F, Secp256k1>::value) { Fe256 r = Secp256k1::zero(); r.l[0] = (uint32_t)v; r.l[1] = (uint32_t)(v >> 32); return r; }
+    else return (uint32_t)v;
+}
+inline bool one_or_count(size_t v, size_t count) { return v == 1 || v == count; }
+
+// The shared front of the two per-point calls, on the selected device: curves, points and flags to the device;
+// run(dA, dB, dP, dInf, dFlag) launches; then the flags are read, which waits for the kernel.
+template <class F, class Run>
+int point_call(const void* A, const void* B, size_t ncurves, const void* points_xy, const uint8_t* inf_in, size_t count, Run&& run) {
+    using E = typename F::elem;
+    DeviceBuffer dA(ncurves * sizeof(E)), dB(ncurves * sizeof(E)), dP(2 * count * sizeof(E)), dInf(count), dFlag(sizeof(unsigned));
+    if (!dA.ok || !dB.ok || !dP.ok || !dInf.ok || !dFlag.ok) return ECFFT_ERR_HIP;
+    if (hipMemcpy(dA.p, A, ncurves * sizeof(E), hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(dB.p, B, ncurves * sizeof(E), hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(dP.p, points_xy, 2 * count * sizeof(E), hipMemcpyHostToDevice) != hipSuccess || hipMemset(dFlag.p, 0, sizeof(unsigned)) != hipSuccess ||
+        (inf_in && hipMemcpy(dInf.p, inf_in, count, hipMemcpyHostToDevice) != hipSuccess)) return ECFFT_ERR_HIP;
+    const int rc = run(dA.template as<const E>(), dB.template as<const E>(), dP.template as<const E>(), inf_in ? dInf.template as<const uint8_t>() : nullptr,
+                       dFlag.template as<unsigned>());
+    if (rc != ECFFT_OK) return rc;
+    unsigned flag = 0;
+    if (hipMemcpy(&flag, dFlag.p, sizeof(unsigned), hipMemcpyDeviceToHost) != hipSuccess || hipGetLastError() != hipSuccess) return ECFFT_ERR_HIP;
+    return flag ? ECFFT_ERR_BAD_ARG : ECFFT_OK;                    // a singular curve or a point off its curve, flagged on the device
+}
+inline unsigned point_blocks(size_t count) { return (unsigned)((count + kPointBlock - 1) / kPointBlock); }
+}  // namespace
+
+extern "C" {
+
+int ecfft_curve_point_mul(int field, int device, const void* A, const void* B, size_t ncurves, const void* points_xy, const uint8_t* inf_in,
+                          const void* scalars, size_t nscalars, size_t scalar_bytes, void* out_xy, uint8_t* inf_out, size_t count) {
+    if (!known_field(field) || !A || !B || !points_xy || !scalars || !out_xy || !inf_out || count == 0 || count > SIZE_MAX / 128 ||
+        scalar_bytes == 0 || scalar_bytes > ecpoint::kMaxScalarBytes || !one_or_count(ncurves, count) || !one_or_count(nscalars, count)) return ECFFT_ERR_BAD_ARG;
+    return guarded([&] {
+        return with_field(field, [&](auto tag) -> int {
+            using F = typename decltype(tag)::type;
+            using E = typename F::elem;
+            const unsigned nbits = ecpoint::scalar_bits((const uint8_t*)scalars, nscalars, (unsigned)scalar_bytes);
+            if (!have_device(device)) return ECFFT_ERR_HIP;
+            DeviceGuard dev(device);
+            if (!dev.ok) return ECFFT_ERR_HIP;
+            DeviceBuffer dk(nscalars * scalar_bytes), d_out(2 * count * sizeof(E)), d_inf(count);
+            if (!dk.ok || !d_out.ok || !d_inf.ok || hipMemcpy(dk.p, scalars, nscalars * scalar_bytes, hipMemcpyHostToDevice) != hipSuccess) return ECFFT_ERR_HIP;
+            const int rc = point_call<F>(A, B, ncurves, points_xy, inf_in, count, [&](const E* dA, const E* dB, const E* dP, const uint8_t* dInf, unsigned* dFlag) -> int {
+                hipLaunchKernelGGL((k_point_mul<F>), dim3(point_blocks(count)), dim3(kPointBlock), 0, nullptr, dA, dB, (uint32_t)ncurves, dP, dInf,
+                                   dk.template as<const uint8_t>(), (uint32_t)nscalars, (uint32_t)scalar_bytes, nbits, d_out.template as<E>(),
+                                   d_inf.template as<uint8_t>(), count, crate_rinv<F>(), dFlag);
+                return ECFFT_OK;
+            });
+            if (rc != ECFFT_OK) return rc;
+            if (hipMemcpy(out_xy, d_out.p, 2 * count * sizeof(E), hipMemcpyDeviceToHost) != hipSuccess ||
+                hipMemcpy(inf_out, d_inf.p, count, hipMemcpyDeviceToHost) != hipSuccess) return ECFFT_ERR_HIP;
+            return ECFFT_OK;
+        });
+    });
+}
+
+int ecfft_curve_point_two_adicity(int field, int device, const void* A, const void* B, size_t ncurves, const void* points_xy, const uint8_t* inf_in,
+                                  unsigned cap, int32_t* out, size_t count) {
+    if (!known_field(field) || !A || !B || !points_xy || !out || count == 0 || count > SIZE_MAX / 128 || !one_or_count(ncurves, count) ||
+        cap > 8 * ecfft_elem_size(field) + 2) return ECFFT_ERR_BAD_ARG;
+    return guarded([&] {
+        return with_field(field, [&](auto tag) -> int {
+            using F = typename decltype(tag)::type;
+            using E = typename F::elem;
+            if (!have_device(device)) return ECFFT_ERR_HIP;
+            DeviceGuard dev(device);
+            if (!dev.ok) return ECFFT_ERR_HIP;
+            DeviceBuffer d_out(count * sizeof(int32_t));
+            if (!d_out.ok) return ECFFT_ERR_HIP;
+            const int rc = point_call<F>(A, B, ncurves, points_xy, inf_in, count, [&](const E* dA, const E* dB, const E* dP, const uint8_t* dInf, unsigned* dFlag) -> int {
+                hipLaunchKernelGGL((k_point_two_adicity<F>), dim3(point_blocks(count)), dim3(kPointBlock), 0, nullptr, dA, dB, (uint32_t)ncurves, dP, dInf,
+                                   (uint32_t)cap, d_out.template as<int32_t>(), count, crate_rinv<F>(), dFlag);
+                return ECFFT_OK;
+            });
+            if (rc != ECFFT_OK) return rc;
+            return hipMemcpy(out, d_out.p, count * sizeof(int32_t), hipMemcpyDeviceToHost) == hipSuccess ? ECFFT_OK : ECFFT_ERR_HIP;
+        });
+    });
+}
+
+int ecfft_curve_find_generator(int field, int device, const void* A, const void* B, const void* order, uint64_t start, uint64_t max_candidates,
+                               unsigned* log_order_out, void* gen_xy, void* offset_xy, uint64_t* x_out) {
+    if (!known_field(field) || !A || !B || !order || !log_order_out || start == 0 || max_candidates == 0 || start > curve::kMaxIndex ||
+        max_candidates > curve::kMaxIndex - start) return ECFFT_ERR_BAD_ARG;
+    if (field == ECFFT_FIELD_M31 && start + max_candidates > M31::P) return ECFFT_ERR_BAD_ARG;         // x runs over integers below p
+    return guarded([&] {
+        return with_field(field, [&](auto tag) -> int {
+            using F = typename decltype(tag)::type;
+            using E = typename F::elem;
+            // order = 2^v m
+            uint8_t m[ECFFT_ORDER_BYTES];
+            memcpy(m, order, ECFFT_ORDER_BYTES);
+            unsigned top = ECFFT_ORDER_BYTES;
+            while (top && !m[top - 1]) --top;
+            if (!top) return ECFFT_ERR_BAD_ARG;
+            unsigned v = 0;
+            while (!((m[v >> 3] >> (v & 7)) & 1)) ++v;
+            if (v > kMaxTwoAdicity<F>) return ECFFT_ERR_BAD_ARG;
+            for (unsigned i = 0; i < ECFFT_ORDER_BYTES; ++i) {          // m >>= v
+                const unsigned lo = i + (v >> 3), sh = v & 7;
+                const unsigned w = (lo < ECFFT_ORDER_BYTES ? m[lo] : 0u) | ((lo + 1 < ECFFT_ORDER_BYTES ? m[lo + 1] : 0u) << 8);
+                m[i] = (uint8_t)(w >> sh);
+            }
+            const unsigned mbits = ecpoint::scalar_bits(m, 1, ECFFT_ORDER_BYTES);
+            E a, b;
+            memcpy(&a, A, sizeof(E)); memcpy(&b, B, sizeof(E));
+            from_crate_host<F>(&a, 1); from_crate_host<F>(&b, 1);
+            if (sw_singular<F>(a, b)) return ECFFT_ERR_BAD_ARG;
+            *log_order_out = 0;
+            if (v == 0) return ECFFT_OK;                                // an odd order: no 2-power point to find
+            if (!have_device(device)) return ECFFT_ERR_HIP;
+            DeviceGuard dev(device);
+            if (!dev.ok) return ECFFT_ERR_HIP;
+            DeviceBuffer dm(ECFFT_ORDER_BYTES), dres(3 * sizeof(unsigned));
+            if (!dm.ok || !dres.ok || hipMemcpy(dm.p, m, ECFFT_ORDER_BYTES, hipMemcpyHostToDevice) != hipSuccess) return ECFFT_ERR_HIP;
+            // batches in order, the first one wave wide (half of the valid candidates generate on a cyclic curve), then four times
+            // the last; both answers are the smallest x of the whole window with their property, whatever the batches are
+            uint64_t gen_x = 0, off_x = 0;
+            uint32_t batch = kPointBlock;
+            for (uint64_t at = 0; at < max_candidates && (!gen_x || !off_x); at += batch, batch = batch < (1u << 16) ? batch * 4 : batch) {
+                const uint32_t cnt = (uint32_t)std::min<uint64_t>(batch, max_candidates - at);
+                const unsigned init[3] = {~0u, ~0u, 0u};
+                if (hipMemcpy(dres.p, init, sizeof(init), hipMemcpyHostToDevice) != hipSuccess) return ECFFT_ERR_HIP;
+                unsigned* r = dres.template as<unsigned>();
+                hipLaunchKernelGGL((k_find_generator<F>), dim3(point_blocks(cnt)), dim3(kPointBlock), 0, nullptr, a, b, start + at, cnt,
+                                   dm.template as<const uint8_t>(), (uint32_t)ECFFT_ORDER_BYTES, mbits, v, gen_x ? 0 : 1, off_x ? 0 : 1, r, r + 1, r + 2);
+                unsigned res[3];
+                if (hipMemcpy(res, dres.p, sizeof(res), hipMemcpyDeviceToHost) != hipSuccess || hipGetLastError() != hipSuccess) return ECFFT_ERR_HIP;
+                if (res[2]) return ECFFT_ERR_BAD_ARG;                   // [order] R != O for a point R of the curve: not its order
+                if (!gen_x && res[0] != ~0u) gen_x = start + at + res[0];
+                if (!off_x && res[1] != ~0u) off_x = start + at + res[1];
+            }
+            if (!gen_x) return ECFFT_OK;                                // no point of order 2^v in the window (a 2-Sylow subgroup that is not cyclic has none)
+            // the winner's [m] R once more on the host, by the same body, made affine
+            E g2[2], o2[2] = {F::zero(), F::zero()};
+            const E gx = elem_from_u64<F>(gen_x), gy = F::sqrt_canon(ecpoint::rhs<F>(gx, a, b));
+            if (!ecpoint::jac_to_affine<F>(ecpoint::jac_mul<F>(gx, gy, m, ECFFT_ORDER_BYTES, mbits, a), &g2[0], &g2[1])) return ECFFT_ERR_HIP;
+            if (off_x) { o2[0] = elem_from_u64<F>(off_x); o2[1] = F::sqrt_canon(ecpoint::rhs<F>(o2[0], a, b)); }
+            *log_order_out = v;
+            if (x_out) *x_out = gen_x;
+            store_elems<F>(gen_xy, g2, 2); store_elems<F>(offset_xy, o2, 2);
+            return ECFFT_OK;
+        });
+    });
+}
+
+int ecfft_build_ec_fftree(int field, size_t n, const void* A, const void* B, const void* gen_xy, unsigned gen_log_order, const void* offset_xy,
+                          int device, ecfft_ctx** out) {
+    if (!out) return ECFFT_ERR_BAD_ARG;
+    *out = nullptr;
+    if (!A || !B || !gen_xy || !offset_xy) return ECFFT_ERR_BAD_ARG;
+    if (!is_pow2(n)) return ECFFT_ERR_NOT_POW2;
+    if (!known_field(field)) return ECFFT_ERR_BAD_ARG;
+    if (ilog2(n) > gen_log_order) return ECFFT_ERR_TREE_TOO_LARGE;                                   // src/ec.rs:513-515: n may equal the order
+    if (gen_log_order == 0 || gen_log_order > 8 * ecfft_elem_size(field)) return ECFFT_ERR_BAD_ARG;
+    return guarded([&] {
+        return with_field(field, [&](auto tag) -> int {
+            using F = typename decltype(tag)::type;
+            using E = typename F::elem;
+            E a, b;
+            memcpy(&a, A, sizeof(E)); memcpy(&b, B, sizeof(E));
+            from_crate_host<F>(&a, 1); from_crate_host<F>(&b, 1);
+            const Pt<F> gen = load_point<F>(gen_xy), off = load_point<F>(offset_xy);
+            if (!check_short_weierstrass<F>(a, b, gen, gen_log_order, off)) return ECFFT_ERR_BAD_ARG;
+            HostTree<F> ht;
+            const int r = build_short_weierstrass<F>(a, b, gen, gen_log_order, off, ilog2(n), ht, /*points=*/false);
+            if (r) return r == 1 ? ECFFT_ERR_TREE_TOO_LARGE : ECFFT_ERR_BAD_ARG;
+            if (!have_device(device)) return ECFFT_ERR_HIP;
+            return new_ctx<F>(field, device, out, [&](DeviceChain<F>& ch) -> int { return build_chain(ch, std::move(ht), device); });
+        });
+    });
+}
+
 #ifdef ECFFT_TEST_HOOKS
 int ecfft_curve_search_stats(uint64_t* lens, double* seconds, size_t cap, int reset) {
     const size_t n = sizeof(g_stage_len) / sizeof(g_stage_len[0]);

@@ -102,9 +102,8 @@ static Pt<F> pt_add(const Curve<F>& c, const Pt<F>& p, const Pt<F>& q) {
     return r;
 }
 template <class F>
-static int pt_two_adicity(const Curve<F>& c, Pt<F> p) {  // src/utils.rs:356-365
-    for (int i = 0; i < 64; ++i) { if (p.inf) return i; p = pt_add(c, p, p); }
-    return -1;
+static int pt_two_adicity(const Curve<F>& c, Pt<F> p, unsigned cap = 8 * F::kBytes + 2) {  // src/utils.rs:356-365, at most `cap` doublings
+    for (unsigned i = 0;; ++i) { if (p.inf) return (int)i; if (i == cap) return -1; p = pt_add(c, p, p); }
 }
 
 // leaves[i] = x(offset + i*gen), i < n  (src/lib.rs:72-78 / src/ec.rs:545-551)
@@ -185,105 +184,167 @@ static inline int build_secp256k1(unsigned log_n, HostTree<Secp256k1>& t, bool p
                                F::from_dec("45508371059383884471556188660911097844526467659576498497548207627741160623272"), gen, 36, off, log_n, t, points);
 }
 
-// ---- Mersenne-31: Velu 2-isogenies of short Weierstrass curves (src/ec.rs:209-259, 498-554) ----
-namespace m31detail {
-struct Poly { uint32_t c[8]; int deg; };   // small dense polynomial over M31, deg = -1 for zero
-static inline void norm(Poly& p) { while (p.deg >= 0 && p.c[p.deg] == 0) --p.deg; }
-static inline Poly rem(Poly a, const Poly& m) {
-    uint32_t li = M31::inv(m.c[m.deg]);
+// ---- short Weierstrass curves y^2 = x^3 + A x + B: Velu 2-isogenies (src/ec.rs:209-259, 498-554) ----
+namespace swdetail {
+// the bits of p, low first, and their number
+template <class F> constexpr int kPBits = F::kBytes == 4 ? 31 : 256;
+template <class F>
+static inline bool p_bit(int i) {
+    if constexpr (F::kBytes == 4) return (M31::P >> i) & 1u;
+    else return (Secp256k1::p_limb(i >> 5) >> (i & 31)) & 1u;
+}
+template <class F>
+struct Poly { typename F::elem c[8]; int deg; };   // small dense polynomial over the field, deg = -1 for zero
+template <class F>
+static inline Poly<F> zero_poly() { Poly<F> r; for (auto& v : r.c) v = F::zero(); r.deg = -1; return r; }
+template <class F>
+static inline void norm(Poly<F>& p) { while (p.deg >= 0 && F::is_zero(p.c[p.deg])) --p.deg; }
+template <class F>
+static inline Poly<F> rem(Poly<F> a, const Poly<F>& m) {
+    const typename F::elem li = F::inv(m.c[m.deg]);
     while (a.deg >= m.deg) {
-        uint32_t q = M31::mul(a.c[a.deg], li); int sh = a.deg - m.deg;
-        for (int i = 0; i <= m.deg; ++i) a.c[i + sh] = M31::sub(a.c[i + sh], M31::mul(q, m.c[i]));
-        norm(a);
+        const typename F::elem q = F::mul(a.c[a.deg], li); int sh = a.deg - m.deg;
+        for (int i = 0; i <= m.deg; ++i) a.c[i + sh] = F::sub(a.c[i + sh], F::mul(q, m.c[i]));
+        norm<F>(a);
     }
     return a;
 }
-static inline Poly mulmod(const Poly& a, const Poly& b, const Poly& m) {
-    Poly r{}; r.deg = -1;
+template <class F>
+static inline Poly<F> mulmod(const Poly<F>& a, const Poly<F>& b, const Poly<F>& m) {
+    Poly<F> r = zero_poly<F>();
     if (a.deg < 0 || b.deg < 0) return r;
-    for (int i = 0; i <= a.deg; ++i) for (int j = 0; j <= b.deg; ++j) r.c[i + j] = M31::add(r.c[i + j], M31::mul(a.c[i], b.c[j]));
-    r.deg = a.deg + b.deg; norm(r);
-    return rem(r, m);
+    for (int i = 0; i <= a.deg; ++i) for (int j = 0; j <= b.deg; ++j) r.c[i + j] = F::add(r.c[i + j], F::mul(a.c[i], b.c[j]));
+    r.deg = a.deg + b.deg; norm<F>(r);
+    return rem<F>(r, m);
 }
-static inline Poly powmod(Poly base, uint64_t e, const Poly& m) {
-    Poly r{}; r.c[0] = 1; r.deg = 0; r = rem(r, m); base = rem(base, m);
-    for (; e; e >>= 1) { if (e & 1) r = mulmod(r, base, m); base = mulmod(base, base, m); }
+// base^e mod m for e = p >> shift (shift 0: p; shift 1: (p - 1) / 2)
+template <class F>
+static inline Poly<F> powmod_p(Poly<F> base, int shift, const Poly<F>& m) {
+    Poly<F> r = zero_poly<F>(); r.c[0] = F::one(); r.deg = 0; r = rem<F>(r, m); base = rem<F>(base, m);
+    for (int i = kPBits<F> - 1; i >= shift; --i) { r = mulmod<F>(r, r, m); if (p_bit<F>(i)) r = mulmod<F>(r, base, m); }
     return r;
 }
-static inline Poly monic(Poly a) { if (a.deg >= 0) { uint32_t li = M31::inv(a.c[a.deg]); for (int i = 0; i <= a.deg; ++i) a.c[i] = M31::mul(a.c[i], li); } return a; }
-static inline Poly gcd(Poly a, Poly b) { while (b.deg >= 0) { Poly r = rem(a, b); a = b; b = r; } return monic(a); }
-static inline Poly quo(Poly a, const Poly& b) {
-    Poly q{}; q.deg = a.deg - b.deg; uint32_t li = M31::inv(b.c[b.deg]);
+template <class F>
+static inline Poly<F> monic(Poly<F> a) {
+    if (a.deg >= 0) { const typename F::elem li = F::inv(a.c[a.deg]); for (int i = 0; i <= a.deg; ++i) a.c[i] = F::mul(a.c[i], li); }
+    return a;
+}
+template <class F>
+static inline Poly<F> gcd(Poly<F> a, Poly<F> b) { while (b.deg >= 0) { Poly<F> r = rem<F>(a, b); a = b; b = r; } return monic<F>(a); }
+template <class F>
+static inline Poly<F> quo(Poly<F> a, const Poly<F>& b) {
+    Poly<F> q = zero_poly<F>(); q.deg = a.deg - b.deg; const typename F::elem li = F::inv(b.c[b.deg]);
     while (a.deg >= b.deg) {
-        uint32_t t = M31::mul(a.c[a.deg], li); int sh = a.deg - b.deg; q.c[sh] = t;
-        for (int i = 0; i <= b.deg; ++i) a.c[i + sh] = M31::sub(a.c[i + sh], M31::mul(t, b.c[i]));
-        norm(a);
+        const typename F::elem t = F::mul(a.c[a.deg], li); int sh = a.deg - b.deg; q.c[sh] = t;
+        for (int i = 0; i <= b.deg; ++i) a.c[i + sh] = F::sub(a.c[i + sh], F::mul(t, b.c[i]));
+        norm<F>(a);
     }
     return q;
 }
-static inline void linear_roots(const Poly& g, std::vector<uint32_t>& out) {
+// the roots of a monic product of distinct linear factors: split on gcd(g, (x + s)^((p-1)/2) - 1), s = 1, 2, ...
+template <class F>
+static inline void linear_roots(const Poly<F>& g, std::vector<typename F::elem>& out) {
     if (g.deg <= 0) return;
-    if (g.deg == 1) { out.push_back(M31::neg(M31::mul(g.c[0], M31::inv(g.c[1])))); return; }
+    if (g.deg == 1) { out.push_back(F::neg(F::mul(g.c[0], F::inv(g.c[1])))); return; }
     for (uint32_t s = 1;; ++s) {
-        Poly h{}; h.c[0] = s; h.c[1] = 1; h.deg = 1;
-        Poly w = powmod(h, (M31::P - 1) / 2, g);
+        Poly<F> h = zero_poly<F>(); h.c[0] = F::from_u32(s); h.c[1] = F::one(); h.deg = 1;
+        Poly<F> w = powmod_p<F>(h, 1, g);
         if (w.deg < 0) w.deg = 0;
-        w.c[0] = M31::sub(w.c[0], 1); norm(w);
+        w.c[0] = F::sub(w.c[0], F::one()); norm<F>(w);
         if (w.deg < 0) continue;
-        Poly d = gcd(g, w);
-        if (d.deg > 0 && d.deg < g.deg) { linear_roots(d, out); linear_roots(monic(quo(g, d)), out); return; }
+        Poly<F> d = gcd<F>(g, w);
+        if (d.deg > 0 && d.deg < g.deg) { linear_roots<F>(d, out); linear_roots<F>(monic<F>(quo<F>(g, d)), out); return; }
     }
 }
-// roots in F_p of x^3 + a x + b, ascending (find_roots + sort, src/utils.rs:25-44)
-static inline std::vector<uint32_t> cubic_roots(uint32_t a, uint32_t b) {
-    Poly f{}; f.c[0] = b; f.c[1] = a; f.c[2] = 0; f.c[3] = 1; f.deg = 3;
-    Poly x{}; x.c[1] = 1; x.deg = 1;
-    Poly xp = powmod(x, M31::P, f);
+// roots in F_p of x^3 + a x + b, ascending in standard form (find_roots + sort, src/utils.rs:25-44)
+template <class F>
+static inline std::vector<typename F::elem> cubic_roots(const typename F::elem& a, const typename F::elem& b) {
+    Poly<F> f = zero_poly<F>(); f.c[0] = b; f.c[1] = a; f.c[3] = F::one(); f.deg = 3;
+    Poly<F> x = zero_poly<F>(); x.c[1] = F::one(); x.deg = 1;
+    Poly<F> xp = powmod_p<F>(x, 0, f);
     if (xp.deg < 1) xp.deg = 1;
-    xp.c[1] = M31::sub(xp.c[1], 1); norm(xp);
-    Poly g = xp.deg < 0 ? f : gcd(f, xp);
-    std::vector<uint32_t> r; linear_roots(g, r); std::sort(r.begin(), r.end());
+    xp.c[1] = F::sub(xp.c[1], F::one()); norm<F>(xp);
+    Poly<F> g = xp.deg < 0 ? f : gcd<F>(f, xp);
+    std::vector<typename F::elem> r; linear_roots<F>(g, r);
+    std::sort(r.begin(), r.end(), [](const typename F::elem& u, const typename F::elem& v) { return F::cmp(u, v) < 0; });
     return r;
 }
-}  // namespace m31detail
+}  // namespace swdetail
 
-static inline int build_m31(unsigned log_n, HostTree<M31>& t, bool points = true) {
-    using F = M31;
-    const unsigned two_adicity = 28;
-    if (log_n > two_adicity) return 1;                          // src/ec.rs:513-515
-    uint32_t ca = 1, cb = 0;                                    // y^2 = x^3 + x  (src/lib.rs:201)
-    Curve<F> c{0, ca, cb};
-    Pt<F> off{1048755163u, 279503108u, false}, gen{1273083559u, 804329170u, false};
-    for (unsigned i = 0; i < two_adicity - log_n; ++i) gen = pt_add(c, gen, gen);
+// doublings any point can need to reach the identity: the group has fewer than 2p + 2 points
+template <class F> constexpr unsigned kMaxTwoAdicity = 8 * F::kBytes + 2;
+
+template <class F>
+static inline bool sw_singular(const typename F::elem& A, const typename F::elem& B) {       // 4 A^3 + 27 B^2 = 0
+    return F::is_zero(F::add(F::mul(F::from_u32(4), F::mul(F::sqr(A), A)), F::mul(F::from_u32(27), F::sqr(B))));
+}
+template <class F>
+static inline bool sw_on_curve(const typename F::elem& A, const typename F::elem& B, const Pt<F>& p) {
+    return p.inf || F::eq(F::sqr(p.y), F::add(F::mul(F::add(F::sqr(p.x), A), p.x), B));
+}
+// The host checks of ecfft_build_ec_fftree on its curve and points, in the header's order.  true: y^2 = x^3 + A x + B is no
+// singular curve, gen and off are finite points of it, gen has order exactly 2^log_order and 2^(log_order + 1) off is not the identity.
+template <class F>
+static inline bool check_short_weierstrass(const typename F::elem& A, const typename F::elem& B, const Pt<F>& gen, unsigned log_order, const Pt<F>& off) {
+    if (sw_singular<F>(A, B)) return false;
+    if (gen.inf || off.inf || !sw_on_curve<F>(A, B, gen) || !sw_on_curve<F>(A, B, off)) return false;
+    const Curve<F> c{F::zero(), A, B};
+    if (pt_two_adicity(c, gen, log_order) != (int)log_order) return false;
+    Pt<F> o = off;
+    for (unsigned i = 0; i <= log_order; ++i) o = pt_add(c, o, o);
+    return !o.inf;
+}
+
+// build_ec_fftree (src/ec.rs:498-554) on y^2 = x^3 + A x + B: `gen` of order 2^log_order, leaves x(off + i * 2^(log_order - log_n) gen);
+// the map of each level is the first Velu 2-isogeny, over the roots of x^3 + a x + b in ascending order, that lowers the
+// generator's two-adicity by exactly one (:526-543).
+// returns 0 ok, 1 = n too large for the generator's order (-> None, :513-515), 2 = no suitable isogeny at some level or a leaf on a pole
+// points = false: only the maps and the generator data (the GPU computes leaves and layers)
+template <class F>
+static inline int build_short_weierstrass(const typename F::elem& A, const typename F::elem& B, Pt<F> gen, unsigned log_order, const Pt<F>& off,
+                                          unsigned log_n, HostTree<F>& t, bool points = true) {
+    using E = typename F::elem;
+    if (log_n > log_order) return 1;                            // src/ec.rs:513-515
+    Curve<F> c{F::zero(), A, B};
+    for (unsigned i = 0; i < log_order - log_n; ++i) gen = pt_add(c, gen, gen);
     size_t n = (size_t)1 << log_n;
     t.n = n; t.maps.resize(log_n);
     t.have_gen = true; t.curve = c; t.off = off; t.gen = gen;
     Pt<F> g = gen; Curve<F> cur = c;
     for (unsigned k = 0; k < log_n; ++k) {                      // src/ec.rs:526-543
-        std::vector<uint32_t> roots = m31detail::cubic_roots(cur.a4, cur.a6);
+        std::vector<E> roots = swdetail::cubic_roots<F>(cur.a4, cur.a6);
         int tg = pt_two_adicity(cur, g); bool found = false;
-        for (uint32_t x0 : roots) {
-            uint32_t tt = F::add(F::mul(F::mul(3, x0), x0), cur.a4);          // t = 3 x0^2 + a
-            Curve<F> cod{0, F::sub(cur.a4, F::mul(5, tt)), F::sub(cur.a6, F::mul(F::mul(7, x0), tt))};
+        for (const E& x0 : roots) {
+            E tt = F::add(F::mul(F::mul(F::from_u32(3), x0), x0), cur.a4);          // t = 3 x0^2 + a
+            Curve<F> cod{F::zero(), F::sub(cur.a4, F::mul(F::from_u32(5), tt)), F::sub(cur.a6, F::mul(F::mul(F::from_u32(7), x0), tt))};
             RatMap<F> m;
-            m.num[0] = tt; m.num[1] = F::neg(x0); m.num[2] = 1;
-            m.den[0] = F::neg(x0); m.den[1] = 1; m.den[2] = 0;
+            m.num[0] = tt; m.num[1] = F::neg(x0); m.num[2] = F::one();
+            m.den[0] = F::neg(x0); m.den[1] = F::one(); m.den[2] = F::zero();
             // phi(g) = (r(x), h(x) y), h = ((x - x0)^2 - t)/(x - x0)^2
-            uint32_t dx = F::sub(g.x, x0);
-            Pt<F> gp{0, 0, true};                                // vanishing denominator -> Point::zero (src/ec.rs:354-357)
-            if (dx != 0) {
-                uint32_t dx2 = F::sqr(dx), idx2 = F::inv(dx2);
+            E dx = F::sub(g.x, x0);
+            Pt<F> gp{F::zero(), F::zero(), true};                // vanishing denominator -> Point::zero (src/ec.rs:354-357)
+            if (!g.inf && !F::is_zero(dx)) {
+                E dx2 = F::sqr(dx), idx2 = F::inv(dx2);
                 gp = Pt<F>{F::mul(poly3<F>(m.num, g.x), F::inv(dx)), F::mul(F::mul(F::sub(dx2, tt), idx2), g.y), false};
             }
             int tp = pt_two_adicity(cod, gp);
             if (tg >= 0 && tp >= 0 && tg == tp + 1) { t.maps[k] = m; cur = cod; g = gp; found = true; break; }
         }
-        if (!found) { fprintf(stderr, "ecfft: cannot find a suitable isogeny\n"); return 2; }
+        if (!found) return 2;
     }
     if (!points) return 0;
-    t.f.assign(2 * n, 0);
+    t.f.assign(2 * n, F::zero());
     compute_leaves<F>(c, off, gen, n, t.f.data() + n);
     return fill_layers<F>(t) ? 0 : 2;
+}
+
+// Mersenne-31: the crate's curve y^2 = x^3 + x, generator of order 2^28 and coset offset (src/lib.rs:198-215)
+static inline int build_m31(unsigned log_n, HostTree<M31>& t, bool points = true) {
+    using F = M31;
+    const Pt<F> off{1048755163u, 279503108u, false}, gen{1273083559u, 804329170u, false};
+    const int r = build_short_weierstrass<F>(1u, 0u, gen, 28, off, log_n, t, points);
+    if (r == 2) fprintf(stderr, "ecfft: cannot find a suitable isogeny\n");
+    return r;
 }
 
 template <class F> int build_host_tree(unsigned log_n, HostTree<F>& t, bool points = true);

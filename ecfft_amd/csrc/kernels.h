@@ -16,6 +16,7 @@
 #include <stddef.h>
 #include <type_traits>
 #include "mfma_blk16.h"
+#include "curve_points.h"
 
 namespace ecfft {
 
@@ -3727,6 +3728,117 @@ __global__ __launch_bounds__(K) void k_schoof_small(const typename F::elem* __re
         break;
     }
     if (t == 0) t_out[b] = res;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Points of short-Weierstrass curves y^2 = x^3 + A x + B (curve_points.h has the group law): ecfft_curve_point_mul,
+// ecfft_curve_point_two_adicity and the scan of ecfft_curve_find_generator.  One thread per row, workgroups of one wave (a row is
+// a chain of thousands of dependent multiplies, so a small call spreads over as many CUs as it has waves); no LDS, no scratch.
+// Curves and points arrive in crate form and are taken to plain form here (secp256k1: one multiply by rinv = 2^-256; M31: the
+// crate's form is the plain one), results go back the same way.
+// ---------------------------------------------------------------------------------------------
+constexpr int kPointBlock = 64;
+enum { POINT_FLAG_OFF_CURVE = 1, POINT_FLAG_SINGULAR = 2, POINT_FLAG_BAD_ORDER = 4 };
+
+template <class F>
+__device__ __forceinline__ typename F::elem point_to_plain(const typename F::elem& v, const typename F::elem& rinv) {
+    if constexpr (sizeof(typename F::elem) == 32) return F::mul(v, rinv);
+    else return F::canon(v);
+}
+// row i of a point call: its curve (plain) and its base (plain; inf = the point at infinity).  false: a singular curve or a
+// point off its curve, flagged
+template <class F>
+__device__ __forceinline__ bool point_load(const typename F::elem* __restrict__ A, const typename F::elem* __restrict__ B, uint32_t ncurves,
+                                           const typename F::elem* __restrict__ P, const uint8_t* __restrict__ inf_in, size_t i,
+                                           const typename F::elem& rinv, typename F::elem& a, typename F::elem& x, typename F::elem& y,
+                                           bool& inf, unsigned* __restrict__ flag) {
+    const size_t ci = ncurves == 1 ? 0 : i;
+    a = point_to_plain<F>(A[ci], rinv);
+    const typename F::elem b = point_to_plain<F>(B[ci], rinv);
+    inf = inf_in && inf_in[i] != 0;
+    x = point_to_plain<F>(P[2 * i], rinv);
+    y = point_to_plain<F>(P[2 * i + 1], rinv);
+    unsigned bad = 0;
+    if (ecpoint::singular<F>(a, b)) bad |= POINT_FLAG_SINGULAR;
+    if (!inf && !ecpoint::on_curve<F>(x, y, a, b)) bad |= POINT_FLAG_OFF_CURVE;
+    if (bad) atomicOr(flag, bad);
+    return bad == 0;
+}
+
+// out[i] = [k_i] P_i: double-and-add from bit nbits - 1 (the longest scalar's) down, so every lane of a wave doubles at every
+// step and takes the mixed addition where its own bit is set; one inversion per row at the end.
+template <class F>
+__global__ __launch_bounds__(kPointBlock) void k_point_mul(const typename F::elem* __restrict__ A, const typename F::elem* __restrict__ B,
+                                                           uint32_t ncurves, const typename F::elem* __restrict__ P,
+                                                           const uint8_t* __restrict__ inf_in, const uint8_t* __restrict__ k,
+                                                           uint32_t nscalars, uint32_t nbytes, uint32_t nbits,
+                                                           typename F::elem* __restrict__ out, uint8_t* __restrict__ inf_out, size_t count,
+                                                           const typename F::elem rinv, unsigned* __restrict__ flag) {
+    using E = typename F::elem;
+    const size_t i = (size_t)blockIdx.x * kPointBlock + threadIdx.x;
+    if (i >= count) return;
+    E a, x, y;
+    bool inf;
+    E ox = F::zero(), oy = F::zero();
+    bool finite = false;
+    if (point_load<F>(A, B, ncurves, P, inf_in, i, rinv, a, x, y, inf, flag) && !inf) {
+        const ecpoint::Jac<F> r = ecpoint::jac_mul<F>(x, y, k + (nscalars == 1 ? 0 : i) * (size_t)nbytes, nbytes, nbits, a);
+        finite = ecpoint::jac_to_affine<F>(r, &ox, &oy);
+    }
+    out[2 * i] = F::to_mont(ox);
+    out[2 * i + 1] = F::to_mont(oy);
+    inf_out[i] = finite ? 0 : 1;
+}
+
+// out[i] = the smallest j <= cap with 2^j P_i = O, -1 when there is none: the doubling of the kernel above, nothing inverted
+template <class F>
+__global__ __launch_bounds__(kPointBlock) void k_point_two_adicity(const typename F::elem* __restrict__ A, const typename F::elem* __restrict__ B,
+                                                                   uint32_t ncurves, const typename F::elem* __restrict__ P,
+                                                                   const uint8_t* __restrict__ inf_in, uint32_t cap, int32_t* __restrict__ out,
+                                                                   size_t count, const typename F::elem rinv, unsigned* __restrict__ flag) {
+    using E = typename F::elem;
+    const size_t i = (size_t)blockIdx.x * kPointBlock + threadIdx.x;
+    if (i >= count) return;
+    E a, x, y;
+    bool inf;
+    int32_t r = -1;
+    if (point_load<F>(A, B, ncurves, P, inf_in, i, rinv, a, x, y, inf, flag))
+        r = inf ? 0 : ecpoint::jac_two_adicity<F>(ecpoint::Jac<F>{x, y, F::one()}, cap, a);
+    out[i] = r;
+}
+
+// One batch of ecfft_curve_find_generator: thread i takes the candidate x = x0 + i on the curve (a, b) (plain).  Where
+// x^3 + a x + b is a non-zero square, R = (x, its canonical root), and
+//   want_gen: G = [m] R (the shared scalar m = order / 2^v); two-adicity of G exactly v -> best_gen <- min(i); 2^v G not the
+//             identity -> the order is not the curve's, flagged
+//   want_off: 2^(v + 1) R not the identity -> best_off <- min(i)
+template <class F>
+__global__ __launch_bounds__(kPointBlock) void k_find_generator(const typename F::elem a, const typename F::elem b, uint64_t x0, uint32_t count,
+                                                                const uint8_t* __restrict__ m, uint32_t mbytes, uint32_t mbits, uint32_t v,
+                                                                int want_gen, int want_off, unsigned* __restrict__ best_gen,
+                                                                unsigned* __restrict__ best_off, unsigned* __restrict__ flag) {
+    using E = typename F::elem;
+    const uint32_t i = blockIdx.x * kPointBlock + threadIdx.x;
+    if (i >= count) return;
+    const uint64_t xi = x0 + i;
+    E x = F::from_u32((uint32_t)xi);
+    if constexpr (sizeof(E) == 32) x.l[1] = (uint32_t)(xi >> 32);
+    const E f = ecpoint::rhs<F>(x, a, b);
+    if (F::is_zero(f)) return;
+    const E y = F::sqrt_canon(f);
+    if (!F::eq(F::sqr(y), f)) return;
+    if (want_gen) {
+        const ecpoint::Jac<F> g = ecpoint::jac_mul<F>(x, y, m, mbytes, mbits, a);
+        const int t = ecpoint::jac_two_adicity<F>(g, v, a);
+        if (t < 0) atomicOr(flag, (unsigned)POINT_FLAG_BAD_ORDER);
+        else if ((uint32_t)t == v) atomicMin(best_gen, i);
+    }
+    if (want_off) {
+        ecpoint::Jac<F> d{x, y, F::one()};
+#pragma unroll 1
+        for (uint32_t j = 0; j <= v && !F::is_zero(d.Z); ++j) d = ecpoint::jac_double<F>(d, a);
+        if (!F::is_zero(d.Z)) atomicMin(best_off, i);
+    }
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -35,7 +35,8 @@ EXPORTS = ["ecfft_elem_size", "ecfft_build_fftree", "ecfft_fftree_new", "ecfft_c
            "ecfft_poly_mul", "ecfft_poly_inv_series", "ecfft_poly_divrem", "ecfft_poly_eval_points", "ecfft_poly_interpolate",
            "ecfft_poly_pow_mod", "ecfft_poly_mul_mod", "ecfft_poly_gcd", "ecfft_poly_xgcd", "ecfft_poly_find_roots",
            "ecfft_poly_compose_mod", "ecfft_poly_squarefree", "ecfft_poly_distinct_degree", "ecfft_poly_equal_degree", "ecfft_division_polynomial", "ecfft_curve_trace_mod", "ecfft_curve_cardinality",
-           "ecfft_find_curve_candidate", "ecfft_curve_two_sylow", "ecfft_find_curve", "ecfft_build_fftree_on_curve"]
+           "ecfft_find_curve_candidate", "ecfft_curve_two_sylow", "ecfft_find_curve", "ecfft_build_fftree_on_curve",
+           "ecfft_curve_point_mul", "ecfft_curve_point_two_adicity", "ecfft_curve_find_generator", "ecfft_build_ec_fftree"]
 # include/ecfft_hip.h ECFFT_GCD_SMALL_MAX: max(na, nb) up to which a gcd runs in one workgroup per pair, on any tree
 GCD_SMALL_MAX = 256
 # include/ecfft_hip.h ECFFT_ROOTS_SMALL_MAX: nf up to which poly_find_roots finishes a polynomial in one workgroup, on any tree
@@ -150,6 +151,11 @@ def _bind(L):
     L.ecfft_find_curve.restype, L.ecfft_find_curve.argtypes = ci, [ci, ci, ctypes.c_uint, u64, u64, u64, ctypes.POINTER(u64), ctypes.POINTER(u32),
                                                                    vp, vp, vp, vp]
     L.ecfft_build_fftree_on_curve.restype, L.ecfft_build_fftree_on_curve.argtypes = ci, [ci, sz, vp, vp, vp, ctypes.c_uint, vp, ci, ctypes.POINTER(vp)]
+    L.ecfft_curve_point_mul.restype, L.ecfft_curve_point_mul.argtypes = ci, [ci, ci, vp, vp, sz, vp, vp, vp, sz, sz, vp, vp, sz]
+    L.ecfft_curve_point_two_adicity.restype, L.ecfft_curve_point_two_adicity.argtypes = ci, [ci, ci, vp, vp, sz, vp, vp, ctypes.c_uint, vp, sz]
+    L.ecfft_curve_find_generator.restype, L.ecfft_curve_find_generator.argtypes = ci, [ci, ci, vp, vp, vp, u64, u64, ctypes.POINTER(ctypes.c_uint), vp, vp,
+                                                                                       ctypes.POINTER(u64)]
+    L.ecfft_build_ec_fftree.restype, L.ecfft_build_ec_fftree.argtypes = ci, [ci, sz, vp, vp, vp, ctypes.c_uint, vp, ci, ctypes.POINTER(vp)]
     L.ecfft_comm_set_rccl_library.restype, L.ecfft_comm_set_rccl_library.argtypes = ci, [ctypes.c_char_p]
     L.ecfft_comm_set_link_striping.restype, L.ecfft_comm_set_link_striping.argtypes = ci, [vp, sz]
     L.has_hooks = hasattr(L, "ecfft_selftest_field")
@@ -407,6 +413,95 @@ class Field:
             rc = lib().ecfft_build_fftree_on_curve(self.id, n, a.ctypes.data, bb.ctypes.data, gen.ctypes.data, gen_log_order, offset.ctypes.data, device, out)
             if rc == ERR_BAD_ARG:
                 raise ValueError("build_fftree_on_curve: not a good curve, a point off the curve, a generator of another order or an offset inside its subgroup")
+            return rc
+        return self._new_tree(make, device)
+
+    # ---- trees on short-Weierstrass curves y^2 = x^3 + A x + B (include/ecfft_hip.h: ecfft_curve_point_mul and what follows) ----
+    def _curves_and_points(self, A, B, points, inf, what):
+        A = np.ascontiguousarray(A, self.dtype).reshape(self.shape(-1)); B = np.ascontiguousarray(B, self.dtype).reshape(self.shape(-1))
+        points = np.ascontiguousarray(points, self.dtype)
+        if A.shape != B.shape or points.size == 0 or points.size % (2 * self.limbs):
+            raise ValueError(f"{what}: A and B must hold one element per curve and points two elements per point")
+        count = points.size // (2 * self.limbs)
+        if inf is not None:
+            inf = np.ascontiguousarray(inf, np.uint8)
+            if inf.shape != (count,):
+                raise ValueError(f"{what}: inf must hold one byte per point")
+        return A, B, points, inf, count
+
+    def curve_point_mul(self, A, B, points, scalars, scalar_bytes=None, inf=None, device=0):
+        """out[i] = [k_i] P_i on y^2 = x^3 + A x + B (ecfft_curve_point_mul <-> Point::mul, src/ec.rs:432-447).  A, B: one curve for
+        all rows or one per row; points: (count, 2) elements x, y in the crate's form; scalars: a list of Python ints (one for all
+        rows or one per row, at most 40 bytes) or a uint8 array of rows of little-endian bytes; inf: one byte per point, non-zero for
+        the point at infinity.  Returns (points, inf) of the same shapes.  ValueError for a point off its curve or a singular curve."""
+        A, B, points, inf, count = self._curves_and_points(A, B, points, inf, "curve_point_mul")
+        if isinstance(scalars, np.ndarray):
+            k = np.ascontiguousarray(scalars, np.uint8)
+            k = k.reshape(1, -1) if k.ndim == 1 else k
+        else:
+            scalars = [int(v) for v in scalars]
+            nb = scalar_bytes or max(1, max((v.bit_length() + 7) // 8 for v in scalars))
+            k = np.frombuffer(b"".join(v.to_bytes(nb, "little") for v in scalars), np.uint8).reshape(len(scalars), nb).copy()
+        out, inf_out = np.zeros_like(points), np.zeros(count, np.uint8)
+        rc = lib().ecfft_curve_point_mul(self.id, device, A.ctypes.data, B.ctypes.data, A.shape[0], points.ctypes.data,
+                                         None if inf is None else inf.ctypes.data, k.ctypes.data, k.shape[0], k.shape[1],
+                                         out.ctypes.data, inf_out.ctypes.data, count)
+        if rc == ERR_BAD_ARG:
+            raise ValueError("curve_point_mul: a point off its curve, a singular curve, scalars wider than 40 bytes, or curves / scalars that are neither one nor one per point")
+        _check(rc)
+        return out, inf_out
+
+    def curve_point_two_adicity(self, A, B, points, cap=None, inf=None, device=0):
+        """the smallest i >= 0 with 2^i P the identity for every point, among i <= cap, -1 where there is none (ecfft_curve_point_two_adicity
+        <-> two_adicity, src/utils.rs:356-365); a numpy int32 array.  cap defaults to its maximum, 8 * element bytes + 2."""
+        A, B, points, inf, count = self._curves_and_points(A, B, points, inf, "curve_point_two_adicity")
+        cap = 8 * self.elem_bytes + 2 if cap is None else int(cap)
+        out = np.zeros(count, np.int32)
+        rc = lib().ecfft_curve_point_two_adicity(self.id, device, A.ctypes.data, B.ctypes.data, A.shape[0], points.ctypes.data,
+                                                 None if inf is None else inf.ctypes.data, cap, out.ctypes.data, count)
+        if rc == ERR_BAD_ARG:
+            raise ValueError("curve_point_two_adicity: a point off its curve, a singular curve, a cap above 8 * element bytes + 2, or curves that are neither one nor one per point")
+        _check(rc)
+        return out
+
+    FIND_GENERATOR_DEFAULT_MAX = 1 << 12
+
+    def curve_find_generator(self, A, B, order, start=1, max_candidates=None, device=0):
+        """The arguments of build_ec_fftree from the curve y^2 = x^3 + A x + B and its number of points `order` (a Python int, or the 40
+        bytes curve_cardinality's C call writes): a dict log_order (v with order = 2^v * odd), gen (x, y of a point of order 2^v),
+        offset (x, y of a coset offset; 0, 0 when the window holds none) and x (the integer x-coordinate the generator came from).
+        None when the window start .. start + max_candidates - 1 holds no point of order 2^v (ecfft_curve_find_generator).
+        ValueError when `order` is not the curve's."""
+        A = np.ascontiguousarray(A, self.dtype); B = np.ascontiguousarray(B, self.dtype)
+        assert A.size == B.size == self.limbs
+        if max_candidates is None:
+            max_candidates = self.FIND_GENERATOR_DEFAULT_MAX
+        ob = bytes(order) if not isinstance(order, int) else order.to_bytes(ORDER_BYTES, "little")
+        assert len(ob) == ORDER_BYTES
+        v, x = ctypes.c_uint(), ctypes.c_uint64()
+        gen, off = np.zeros(self.shape(2), self.dtype), np.zeros(self.shape(2), self.dtype)
+        rc = lib().ecfft_curve_find_generator(self.id, device, A.ctypes.data, B.ctypes.data, ob, start, max_candidates, ctypes.byref(v),
+                                              gen.ctypes.data, off.ctypes.data, ctypes.byref(x))
+        if rc == ERR_BAD_ARG:
+            raise ValueError("curve_find_generator: not the order of this curve, a singular curve, or an empty or misplaced window")
+        _check(rc)
+        if v.value == 0:
+            return None
+        return {"log_order": v.value, "gen": gen, "offset": off, "x": x.value}
+
+    def build_ec_fftree(self, n, A, B, gen, gen_log_order, offset, device=0):
+        """`build_ec_fftree(subgroup_generator, subgroup_order, coset_offset, n)` (src/ec.rs:498-554) on y^2 = x^3 + A x + B
+        (ecfft_build_ec_fftree): gen = (x, y) of order 2^gen_log_order, offset = (x, y) of a coset offset; None if log2 n >
+        gen_log_order.  ValueError for a singular curve, a point off the curve, a generator of another order, an offset whose
+        double lies in the subgroup, or a curve without a suitable isogeny at some level."""
+        A = np.ascontiguousarray(A, self.dtype); B = np.ascontiguousarray(B, self.dtype)
+        gen = np.ascontiguousarray(gen, self.dtype); offset = np.ascontiguousarray(offset, self.dtype)
+        assert A.size == B.size == self.limbs and gen.size == offset.size == 2 * self.limbs
+
+        def make(out):
+            rc = lib().ecfft_build_ec_fftree(self.id, n, A.ctypes.data, B.ctypes.data, gen.ctypes.data, gen_log_order, offset.ctypes.data, device, out)
+            if rc == ERR_BAD_ARG:
+                raise ValueError("build_ec_fftree: a singular curve, a point off the curve, a generator of another order, an offset whose double lies in its subgroup, or no suitable isogeny")
             return rc
         return self._new_tree(make, device)
 

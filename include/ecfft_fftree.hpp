@@ -141,6 +141,57 @@ public:
         return FFTree(c);
     }
     static std::optional<FFTree> build_on_curve(size_t n, const FoundCurve& f, int device = 0) { return build_on_curve(n, f.a, f.bb, f.gen, f.n, f.offset, device); }
+    // ---- trees on short-Weierstrass curves y^2 = x^3 + A x + B (ecfft_hip.h: ecfft_curve_point_mul and what follows); synchronous ----
+    using Point = std::array<Elem, 2>;         // x, y
+    // out[i] = [k_i] P_i (ecfft_curve_point_mul <-> Point::mul, src/ec.rs:432-447).  A, B: one curve for all rows or one per row;
+    // scalars: rows of scalar_bytes little-endian bytes, one row for all points or one per point; inf (empty: every point finite)
+    // and inf_out: one byte per point, non-zero for the point at infinity.  A point off its curve or a singular curve throws.
+    static std::vector<Point> curve_point_mul(const std::vector<Elem>& A, const std::vector<Elem>& B, const std::vector<Point>& points,
+                                              const std::vector<uint8_t>& scalars, size_t scalar_bytes, std::vector<uint8_t>& inf_out,
+                                              const std::vector<uint8_t>& inf = {}, int device = 0) {
+        require(!points.empty() && A.size() == B.size() && (A.size() == 1 || A.size() == points.size()), "curve_point_mul: one curve, or one per point");
+        require(scalar_bytes >= 1 && scalars.size() % scalar_bytes == 0 && (scalars.size() == scalar_bytes || scalars.size() == scalar_bytes * points.size()),
+                "curve_point_mul: one scalar row, or one per point");
+        require(inf.empty() || inf.size() == points.size(), "curve_point_mul: inf must hold one byte per point");
+        std::vector<Point> out(points.size());
+        inf_out.assign(points.size(), 0);
+        check(ecfft_curve_point_mul(F::id, device, A.data(), B.data(), A.size(), points.data(), inf.empty() ? nullptr : inf.data(), scalars.data(),
+                                    scalars.size() / scalar_bytes, scalar_bytes, out.data(), inf_out.data(), points.size()));
+        return out;
+    }
+    // the smallest i <= cap with 2^i P the identity, -1 when there is none (ecfft_curve_point_two_adicity <-> two_adicity, src/utils.rs:356-365)
+    static std::vector<int32_t> curve_point_two_adicity(const std::vector<Elem>& A, const std::vector<Elem>& B, const std::vector<Point>& points,
+                                                        unsigned cap = 8 * sizeof(Elem) + 2, const std::vector<uint8_t>& inf = {}, int device = 0) {
+        require(!points.empty() && A.size() == B.size() && (A.size() == 1 || A.size() == points.size()), "curve_point_two_adicity: one curve, or one per point");
+        require(inf.empty() || inf.size() == points.size(), "curve_point_two_adicity: inf must hold one byte per point");
+        std::vector<int32_t> out(points.size());
+        check(ecfft_curve_point_two_adicity(F::id, device, A.data(), B.data(), A.size(), points.data(), inf.empty() ? nullptr : inf.data(), cap, out.data(), points.size()));
+        return out;
+    }
+    // the arguments of build_ec_fftree from a curve and its number of points (ecfft_curve_find_generator; `order` as
+    // curve_cardinality returns it): a generator of order 2^log_order and a coset offset (0, 0 when the window holds none), x the
+    // integer x-coordinate the generator came from; nullopt when the window holds no generator.  An order that is not the curve's throws.
+    struct FoundGenerator {
+        unsigned log_order; uint64_t x;
+        Point gen, offset;
+    };
+    static std::optional<FoundGenerator> curve_find_generator(const Elem& A, const Elem& B, const std::array<uint8_t, ECFFT_ORDER_BYTES>& order,
+                                                              uint64_t start = 1, uint64_t max_candidates = uint64_t(1) << 12, int device = 0) {
+        FoundGenerator g{};
+        check(ecfft_curve_find_generator(F::id, device, &A, &B, order.data(), start, max_candidates, &g.log_order, g.gen.data(), g.offset.data(), &g.x));
+        if (g.log_order == 0) return std::nullopt;
+        return g;
+    }
+    // build_ec_fftree (src/ec.rs:498-554) on y^2 = x^3 + A x + B (ecfft_build_ec_fftree): gen of order 2^gen_log_order; nullopt
+    // when log2 n > gen_log_order.  A singular curve, a point off the curve, a generator of another order or an offset whose
+    // double lies in the generator's subgroup throws.
+    static std::optional<FFTree> build_ec_fftree(size_t n, const Elem& A, const Elem& B, const Point& gen, unsigned gen_log_order, const Point& offset, int device = 0) {
+        ecfft_ctx* c = nullptr;
+        int rc = ecfft_build_ec_fftree(F::id, n, &A, &B, gen.data(), gen_log_order, offset.data(), device, &c);
+        if (rc == ECFFT_ERR_TREE_TOO_LARGE) return std::nullopt;
+        check(rc);
+        return FFTree(c);
+    }
     size_t size() const { return ecfft_tree_size(ctx_); }
 
     std::vector<Elem> enter(const std::vector<Elem>& coeffs) const {            // src/fftree.rs:164-167

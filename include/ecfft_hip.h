@@ -620,6 +620,63 @@ int ecfft_find_curve(int field, int device, unsigned k, uint64_t seed, uint64_t 
 int ecfft_build_fftree_on_curve(int field, size_t n, const void* a, const void* bb, const void* gen_xy, unsigned gen_log_order,
                                 const void* offset_xy, int device, ecfft_ctx** out);
 
+/* Trees on short-Weierstrass curves y^2 = x^3 + A x + B, the (A, B) of ecfft_curve_cardinality: from a curve and its number of
+ * points to a tree.
+ *   ecfft_curve_point_mul          <-> Point::mul, for many points                            src/ec.rs:432-447
+ *   ecfft_curve_point_two_adicity  <-> two_adicity, with an explicit cap                      src/utils.rs:356-365
+ *   ecfft_curve_find_generator     <-> what a caller of build_ec_fftree does by hand: a point of order 2^v and a coset offset
+ *   ecfft_build_ec_fftree          <-> build_ec_fftree(subgroup_generator, subgroup_order, coset_offset, n)   src/ec.rs:498-554
+ * Like the ecfft_find_curve family the four calls take `field` and `device`, need no context, take HOST pointers and are
+ * SYNCHRONOUS; elements are in the crate's in-memory form, a point is the pair x, y laid end to end.
+ *
+ * ecfft_curve_point_mul: out[i] = [k_i] P_i for i < count.  A and B hold `ncurves` elements each, `scalars` holds `nscalars` rows of
+ * `scalar_bytes` little-endian bytes (1 <= scalar_bytes <= 40, the width of a cardinality); ncurves and nscalars are each 1 (shared by
+ * every row) or count.  inf_in (may be NULL: every point finite) and inf_out hold one byte per point, non-zero for the point at
+ * infinity, whose x, y are not read on the way in and written as 0, 0 on the way out.  Method: one thread per row, Jacobian
+ * accumulator and affine base, left to right over the bits of the longest scalar: every lane doubles at every bit and takes the
+ * addition where its bit is set; one inversion per row at the end.  The exceptional cases of the group law (accumulator at infinity,
+ * equal to the base, its negative; y = 0 in a doubling; scalar 0; base at infinity) are decided exactly, and the affine result is
+ * unique, so the output is bit-exact against any model.  A point that is not on its curve or a singular curve (4 A^3 + 27 B^2 = 0)
+ * is flagged on the device: ECFFT_ERR_BAD_ARG, outputs untouched.  ECFFT_ERR_BAD_ARG also for a NULL pointer other than inf_in,
+ * count 0, scalar_bytes 0 or above 40, ncurves or nscalars neither 1 nor count, an unknown field.
+ *
+ * ecfft_curve_point_two_adicity: out[i] = the smallest j >= 0 with 2^j P_i the identity, among j <= cap; -1 when there is none
+ * (0 for the point at infinity).  cap <= 8 * element bytes + 2, above which no point of any curve over the field can need more.
+ * Curves, points, inf_in and errors as above.
+ *
+ * ecfft_curve_find_generator: the arguments of ecfft_build_ec_fftree from one curve and its number of points `order`
+ * (ECFFT_ORDER_BYTES little-endian bytes, as ecfft_curve_cardinality writes them).  With order = 2^v m, m odd, the candidates are
+ * x = start, start + 1, ..., start + max_candidates - 1 as integers (start >= 1); those whose x^3 + A x + B is a non-zero square
+ * give the point R = (x, y), y the canonical root v^((p+1)/4).  gen_xy = [m] R for the candidate of SMALLEST x whose [m] R has
+ * two-adicity exactly v, and *x_out = that x; offset_xy = the candidate R of smallest x in the window for which 2^(v+1) R is not the
+ * identity, 0, 0 when the window holds none (a group that is a 2-group, such as y^2 = x^3 + x over M31 with its 2^31 points, has none
+ * at all; a tree on such a curve takes four times the generator, gen_log_order = v - 2 and the generator itself as the offset).  Neither answer depends on how the scan is cut into batches; the scan ends as soon as both are known.  *log_order_out = v.
+ * No generator in the window (a 2-Sylow subgroup that is not cyclic has no point of order 2^v), or an odd order: ECFFT_OK with
+ * *log_order_out = 0 and the other outputs untouched.  A candidate R with [order] R not the identity proves that `order` is not
+ * the curve's: ECFFT_ERR_BAD_ARG.  ECFFT_ERR_BAD_ARG also for NULL A, B, order or log_order_out (gen_xy, offset_xy and x_out may be
+ * NULL), an order of zero, a singular curve, start 0, max_candidates 0, start + max_candidates above 2^60 or above p, an unknown
+ * field.  One batch is one launch: candidate, square test, the multiplication by the shared scalar m, two-adicity.
+ *
+ * ecfft_build_ec_fftree: leaf i = x of offset + i * 2^(gen_log_order - log2 n) gen.  The map of each level is chosen as the
+ * reference does (src/ec.rs:526-543): the Velu 2-isogenies of the current curve from the roots of x^3 + a x + b in ascending order
+ * of their standard form, the first that lowers the generator's two-adicity by exactly one.  Checked on the host before any device
+ * work, in this order:
+ *   n not a power of two                                                         ECFFT_ERR_NOT_POW2
+ *   log2 n > gen_log_order (the reference's rule, src/ec.rs:513: n may equal the order)   ECFFT_ERR_TREE_TOO_LARGE
+ *   a singular curve; a point not on the curve; gen not of order exactly 2^gen_log_order; 2^(gen_log_order + 1) offset the
+ *   identity; no suitable isogeny at some level; a NULL pointer; gen_log_order 0 or above 8 * element bytes     ECFFT_ERR_BAD_ARG
+ * The condition on the offset says that 2 offset is not in <gen>: then offset + P = +-(offset + Q) has no solution with P != Q in
+ * <gen>, which makes the n leaves distinct, and no layer meets the pole of its map (a pole is the x of a point of order 2 of the
+ * kernel, and a leaf there would put 2 offset into <gen> again). */
+int ecfft_curve_point_mul(int field, int device, const void* A, const void* B, size_t ncurves, const void* points_xy, const uint8_t* inf_in,
+                          const void* scalars, size_t nscalars, size_t scalar_bytes, void* out_xy, uint8_t* inf_out, size_t count);
+int ecfft_curve_point_two_adicity(int field, int device, const void* A, const void* B, size_t ncurves, const void* points_xy, const uint8_t* inf_in,
+                                  unsigned cap, int32_t* out, size_t count);
+int ecfft_curve_find_generator(int field, int device, const void* A, const void* B, const void* order, uint64_t start, uint64_t max_candidates,
+                               unsigned* log_order_out, void* gen_xy, void* offset_xy, uint64_t* x_out);
+int ecfft_build_ec_fftree(int field, size_t n, const void* A, const void* B, const void* gen_xy, unsigned gen_log_order, const void* offset_xy,
+                          int device, ecfft_ctx** out);
+
 /* Per-launch timing for benchmarks (no reference counterpart): while enabled, every hot-path kernel
  * launch is bracketed by HIP events on its stream.  ecfft_profile_read synchronises the device and
  * returns, for kernel class `cls` (0 <= cls < ecfft_profile_classes()), its name, number of launches,
