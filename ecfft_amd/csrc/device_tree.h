@@ -9,7 +9,8 @@
 //   c0t[s] = np0[s]*dinv[s]         likewise    (pair-split decompose of the latency regime: two independent products)
 //   w[s], winv[s]                   e entries   (normalisation weights of the parity's leaves)
 //   xe, w1x                         e entries   ENTER combine
-//   A1, B1, NB2, C1, D1, xie        e entries   EXIT pointwise steps with every inverse pre-fused
+//   A1, B1, NB2, C1, D1, xie        e entries   EXIT pointwise steps with every inverse pre-fused (four-core form, reduction over Z0)
+//   zA1, zB1, zNB2, zC1, zD1, zNB3  e entries   the same for the three-core form (reduction over Z1); a tree holds the set it runs
 // All tables are PLAIN residues; user data stays in the crate's Montgomery form (field_secp256k1.h).  The tables above are
 // stored as F::telem — for secp256k1 the pair (t, t*2^128 mod p) that the 12-word multiply wants, for M31 the doubled constant
 // 2t (field_m31.h) — and are written by to_tables() from plain temporaries; the reference's own tables (xnn, z*) stay plain
@@ -130,6 +131,7 @@ public:
     // tree is installed (the sharded EXIT build needs two different shares of one tree)
     const Tree& tree_at(unsigned log_m) const { return (ovr_tree_ && ovr_tree_->log_m == log_m) ? *ovr_tree_ : trees_[log_m]; }
     const HostTree<F>& host() const { return host_; }
+    int exit_cores() const { return exit3_ ? 3 : 4; }        // EXTEND cores per EXIT level of exit_levels
     int low_map(int dir) const {
         if (trees_.size() > 5 && trees_[5].low32_A[dir]) return 32;
         if (trees_.size() > 4 && trees_[4].low16_A[dir]) return 16;
@@ -156,11 +158,27 @@ public:
         // (F::telem each); + f (2N) + den coefficients
         size_t total = 2 * N_ + 64;
         for (unsigned l = 0; l <= L_; ++l) total += (6 + 11 * kTeElems) * ((size_t)1 << l) + 1024 + blk16_elems(l);
+        // three-core EXIT: the Z1 set has one table more than the Z0 set it replaces (e constants per tree); the trees of the
+        // low-level kernels hold both sets (6 e constants more, at most 2^kLogLow leaves)
+        if (!exit4_) for (unsigned l = 1; l <= L_; ++l) total += (l <= kLogLow ? 6 : 1) * kTeElems * ((size_t)1 << l) / 2 + 64;   // + take()'s rounding of six tables
         total += low16_elems();
         ECFFT_HIP_TRY(hipMalloc(&arena_, total * sizeof(E)));
         arena_cap_ = total; arena_used_ = 0;
         f_ = take(2 * N_);
         if (!points_on_device(f_, s)) { fprintf(stderr, "ecfft: point set construction failed\n"); return false; }
+        if (!exit4_) {
+            // the three-core EXIT level divides by X^(m/2) on BOTH moieties: every leaf must be non-zero (the leaves of a subtree
+            // are a subset of these, so one check covers every level); otherwise the context keeps the four-core form
+            unsigned long long* zc = nullptr; unsigned long long hz = 0;
+            ECFFT_HIP_TRY(hipMalloc(&zc, sizeof(unsigned long long)));
+            (void)hipMemsetAsync(zc, 0, sizeof(unsigned long long), s);
+            const E* leaves = f_ + N_;
+            foreach_n(s, N_, [=] __device__(size_t j) { if (F::is_zero(leaves[j])) atomicAdd(zc, 1ull); });
+            const bool got = hipMemcpyAsync(&hz, zc, sizeof(hz), hipMemcpyDeviceToHost, s) == hipSuccess && hipStreamSynchronize(s) == hipSuccess;
+            (void)hipFree(zc);
+            if (!got) { (void)hipGetLastError(); return false; }
+            exit3_ = hz == 0;
+        }
         // denominators of the maps: v_k(x) = den0 + den1 x (degree 1 for both curve families)
         std::vector<E> den(2 * (L_ ? L_ : 1));
         for (unsigned k = 0; k < L_; ++k) { den[2 * k] = host_.maps[k].den[0]; den[2 * k + 1] = host_.maps[k].den[1]; }
@@ -852,7 +870,7 @@ public:
             // load side
             if (first) { d = io; d.st_tr_logp = 0; } else { d = IoDesc<F>{}; d.src = plain_src; d.src_stride = 1; d.src_off = 0; d.ld_mode = LD_PLAIN; d.ld_tbl = nullptr; }
             // store side
-            if (last) { d.dst = io.dst; d.st_mode = io.st_mode; d.st_a = io.st_a; d.st_b = io.st_b; d.aux = io.aux; d.aux_stride = io.aux_stride; d.aux_off = io.aux_off; d.aux_out = io.aux_out;
+            if (last) { d.dst = io.dst; d.st_mode = io.st_mode; d.st_a = io.st_a; d.st_b = io.st_b; d.aux = io.aux; d.aux_stride = io.aux_stride; d.aux_off = io.aux_off; d.aux_out = io.aux_out; d.st_c = io.st_c; d.aux2 = io.aux2;
                         d.st_tr_logp = io.st_tr_logp; d.tr_chunk = io.tr_chunk; }
             else { d.dst = buf; d.st_mode = ST_PLAIN; d.st_a = d.st_b = nullptr; d.aux = nullptr; d.aux_stride = d.aux_off = 0; d.aux_out = nullptr; }
             d.nt_st = nt_st;
@@ -881,10 +899,12 @@ public:
                     ECFFT_LAUNCH(KC_ROW, bytes, (k_stages_row256<F>), dim3((unsigned)(total >> kLogLowSmall)), dim3(256), 0, s, d, T.dinv[srcpar], T.p0[tgt], T.p1[tgt], T.inner[srcpar],
                                  le, k_first, T.c0t[srcpar], mf ? T.blk16_A[srcpar] : (const uint8_t*)nullptr, mf ? T.blk16_K[srcpar] : (const unsigned long long*)nullptr);
                 } else
-                if (log_tile == kLogTileMax + 1 && ct_row)
+                if (log_tile == kLogTileMax + 1 && ct_row) {
+                    // (only instantiated for the fields that launch it: the 32-byte instantiation was dead code in the code object)
+                    if constexpr (ct_row)
                     ECFFT_LAUNCH(KC_ROW, bytes, (k_stages_lds<F, (int)kLogTileMax + 1>), dim3((unsigned)(total >> log_tile)), dim3(kBlockRow),
                                  ((size_t)sizeof(E)) << log_tile, s, d, T.np0[srcpar], T.dinv[srcpar], T.p0[tgt], T.p1[tgt], T.inner[srcpar], le, k_first, log_tile, T.c0t[srcpar], bA, bK);
-                else if (log_tile == kLogTileMax && (ct_row || bA))   // compile-time tile (always for the matrix-core row passes): +16% on M31 (8 pairs/thread unroll), -3% on secp256k1
+                } else if (log_tile == kLogTileMax && (ct_row || bA))   // compile-time tile (always for the matrix-core row passes): +16% on M31 (8 pairs/thread unroll), -3% on secp256k1
                     ECFFT_LAUNCH(KC_ROW, bytes, (k_stages_lds<F, (int)kLogTileMax>), dim3((unsigned)(total >> log_tile)), dim3(kBlockRow),
                                  ((size_t)sizeof(E)) << log_tile, s, d, T.np0[srcpar], T.dinv[srcpar], T.p0[tgt], T.p1[tgt], T.inner[srcpar], le, k_first, log_tile, T.c0t[srcpar], bA, bK);
                 else
@@ -925,7 +945,7 @@ public:
         // the paired form exists only on the kernels' 16-byte vector path: every buffer the pass touches must be 16-byte aligned
         // (user buffers may be only element-aligned) and the operator must be one the vector path implements
         auto al = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
-        if (!al(d.src) || !al(d.dst) || !al(d.aux) || !al(d.aux_out) || d.ld_tr_logp || d.st_tr_logp || le < 2) return 0;
+        if (!al(d.src) || !al(d.dst) || !al(d.aux) || !al(d.aux_out) || !al(d.aux2) || d.ld_tr_logp || d.st_tr_logp || le < 2) return 0;
         if (!((d.src_stride == 1 && d.src_off == 0) || (d.src_stride == 2 && d.src_off < 2))) return 0;
         const size_t nspans = total >> (le - ka);
         return (nspans >= 2 && (nspans & 1) == 0 && (total >> (log_ct + 1)) >= 512) ? 1u : 0u;
@@ -1496,6 +1516,9 @@ public:
 #ifndef ECFFT_SPLIT_MIN_LOG
 #define ECFFT_SPLIT_MIN_LOG 19
 #endif
+#ifndef ECFFT_EXIT_CORES
+#define ECFFT_EXIT_CORES 3      // EXTEND cores per EXIT level (exit_levels): 3 = reduction over Z1, 4 = the reference's form (A/B)
+#endif
     static constexpr unsigned kSplitMinLog = ECFFT_SPLIT_MIN_LOG;   // single transforms of at least 2^this run as concurrent halves
 #ifndef ECFFT_SPLIT_DEPTH
 #define ECFFT_SPLIT_DEPTH 1
@@ -1578,6 +1601,30 @@ public:
             //           store h1'~ = H * (c_odd zinv) - g1'~ * (x_odd zinv)  [h1'               : 1.5n + 2e]
             //   core 4  store u0 = W0 q0~ ; v0 = (e0 - u0) * xinv_even       [exit split        : 1.5n + 0.5e]
             double se = sizeof(E), ee = (double)T.e * tblw_;
+            if (T.zA1 && !exit4_) {
+                // THREE cores: the same Montgomery reduction over Z1, the vanishing polynomial of S1, lands on S0
+                //   core 1  load  t1 = e1 * (xinv_odd / W1)                      [t1 = e1/a1]
+                //           store h0~ = e0 * (z1inv/W0) - g0~ * (x_even z1inv)    [h0], kept in H
+                //   core 2  h0~ -> h1~ (S0 -> S1)
+                //   core 3  load  t1' = h1~ * (c'_odd xinv_odd)                   [h*c' and t1']
+                //           store u0 = H * (c'_even z1inv W0) - g0'~ * (x_even z1inv W0) ; v0 = (e0 - u0) * xinv_even
+                // The level is credited exit_level_alg_bytes all the same (the closed form models the reference's four cores): the
+                // fourth core's stage bytes and the split's pointwise bytes go to core 3's last pass.
+                IoDesc<F> io1 = io_plain(cur, G);
+                io1.src_stride = 2; io1.src_off = 1; io1.ld_mode = LD_SCALE; io1.ld_tbl = T.zA1;
+                io1.st_mode = ST_AXPBY; io1.st_a = T.zNB2; io1.st_b = T.zB1; io1.aux = cur; io1.aux_stride = 2; io1.aux_off = 0; io1.aux_out = H;
+                NextLoad nl2{LD_PLAIN, nullptr, 0.0}, nl3{LD_SCALE, T.zC1, se * (3.0 * n + 3.0 * ee)};
+                bool f1 = extend_core(l, io1, G, nh, 1, s, se * (1.0 * n + ee), se * (1.5 * n + 2.0 * ee), 0, &nl2, false);
+                bool f2 = extend_core(l, io_plain(G, G), G, nh, 0, s, 0.0, 0.0, 0, &nl3, f1);
+                IoDesc<F> io3 = io_plain(G, dst);
+                io3.ld_mode = LD_SCALE; io3.ld_tbl = T.zC1;
+                io3.st_mode = ST_EXIT3; io3.st_a = T.zNB3; io3.st_b = T.zD1; io3.aux = H; io3.aux_stride = 1; io3.aux_off = 0;
+                io3.st_c = T.xie; io3.aux2 = cur;
+                const double core4 = se * (2.0 * (l - 1) * (double)n + tblw_ * 8.0 * ((double)T.e - 1.0));
+                extend_core(l, io3, G, nh, 1, s, f2 ? 0.0 : se * (3.0 * n + 3.0 * ee), se * (1.5 * n + 2.0 * ee) + core4 + se * (1.5 * n + 0.5 * ee), 0, nullptr, f2);
+                cur = dst;
+                continue;
+            }
             IoDesc<F> io1 = io_plain(cur, G);
             io1.src_stride = 2; io1.src_off = 0; io1.ld_mode = LD_SCALE; io1.ld_tbl = T.A1;
             io1.st_mode = ST_AXPBY; io1.st_a = T.NB2; io1.st_b = T.B1; io1.aux = cur; io1.aux_stride = 2; io1.aux_off = 1; io1.aux_out = H;
@@ -4347,8 +4394,28 @@ private:
                 C1[i] = F::mul(c[2 * i], xiev);
                 D1[i] = F::mul(c[2 * i + 1], z);
             });
-            T.xe = to_tables(xe, es, s); T.w1x = to_tables(w1x, es, s); T.A1 = to_tables(A1, es, s); T.B1 = to_tables(B1, es, s);
-            T.NB2 = to_tables(NB2, es, s); T.C1 = to_tables(C1, es, s); T.D1 = to_tables(D1, es, s); T.xie = to_tables(xie, es, s);
+            T.xe = to_tables(xe, es, s); T.w1x = to_tables(w1x, es, s); T.xie = to_tables(xie, es, s);
+            // a context holds ONE fused EXIT set per tree: the Z1 set where exit_levels runs the three-core form, the Z0 set where
+            // it runs the four-core form; the trees the low-level kernels (four cores) cover keep the Z0 set as well
+            if (!exit3_ || l <= kLogLow) {
+                T.A1 = to_tables(A1, es, s); T.B1 = to_tables(B1, es, s); T.NB2 = to_tables(NB2, es, s); T.C1 = to_tables(C1, es, s); T.D1 = to_tables(D1, es, s);
+            }
+            if (exit3_) {
+                // reduction over Z1 (c' = z1z1_rem_xnn_s): t1~ = e1 (xinv_odd/W1); h0~ = e0 (z1inv/W0) - g0~ (x_even z1inv);
+                // t1'~ = h1~ (c'_odd xinv_odd); u0 = H (c'_even z1inv W0) - g0'~ (x_even z1inv W0)
+                const E *w0 = hw[0], *z1i = T.z1_inv_s0, *c1 = T.z1z1;
+                foreach_n(s, e, [=] __device__(size_t i) {
+                    const E xev = xnn[2 * i], xiod = xi[2 * i + 1], z = z1i[i], zw = F::mul(z, w0[i]);
+                    A1[i] = F::mul(xiod, wi1[i]);
+                    B1[i] = F::mul(z, wi0[i]);
+                    NB2[i] = F::neg(F::mul(xev, z));
+                    C1[i] = F::mul(c1[2 * i + 1], xiod);
+                    D1[i] = F::mul(c1[2 * i], zw);
+                    xe[i] = F::neg(F::mul(xev, zw));       // xe is in its table form already: the temporary is free
+                });
+                T.zA1 = to_tables(A1, es, s); T.zB1 = to_tables(B1, es, s); T.zNB2 = to_tables(NB2, es, s); T.zC1 = to_tables(C1, es, s);
+                T.zD1 = to_tables(D1, es, s); T.zNB3 = to_tables(xe, es, s);
+            }
         }
         hipError_t err = hipGetLastError();
         if (err != hipSuccess) { fprintf(stderr, "ecfft: kernel launch failed: %s\n", hipGetErrorString(err)); return false; }
@@ -4405,6 +4472,10 @@ private:
     bool col256_off_ = ab_env("ECFFT_NO_COL256") != nullptr;            // A/B switch: small column passes on the generic kernels (pair-split LDS sweeps)
     bool row256_off_ = ab_env("ECFFT_NO_ROW256") != nullptr;            // A/B switch: small row passes on the generic kernel (pair-split LDS sweeps)
     bool ef_small_off_ = ab_env("ECFFT_NO_SMALL_TILES") != nullptr;   // A/B switch for the small-launch tile rule
+    // EXIT levels of exit_levels: three EXTEND cores (reduction over Z1) unless the build (-DECFFT_EXIT_CORES=4) or the A/B switch asks
+    // for the reference's four; exit3_ = the form this context's tables were built for (full contexts whose leaves are all non-zero)
+    bool exit4_ = ECFFT_EXIT_CORES == 4 || ab_env("ECFFT_EXIT_FOUR_CORES") != nullptr;
+    bool exit3_ = false;
 };
 
 }  // namespace ecfft

@@ -1573,6 +1573,10 @@ int ecfft_ctx_low_map(const ecfft_ctx* ctx, int dir) {
     if (!ctx || dir < 0 || dir > 1 || ctx->field != ECFFT_FIELD_SECP256K1 || !ctx->secp) return 0;
     return ctx->secp->low_map(dir);
 }
+int ecfft_ctx_exit_cores(const ecfft_ctx* ctx) {
+    if (!ctx) return 0;
+    return ctx->secp ? ctx->secp->exit_cores() : ctx->m31 ? ctx->m31->exit_cores() : 0;
+}
 
 #endif  // ECFFT_TEST_HOOKS
 int ecfft_mul_ceiling(int field, int device, int waves_per_simd, double* mul_per_s) {

@@ -99,7 +99,7 @@ __global__ __launch_bounds__(kBlock) void k_recombine_stage(typename F::elem* __
 // length e laid end to end), i = pos mod e.
 // ---------------------------------------------------------------------------------------------
 enum { LD_PLAIN = 0, LD_SCALE = 1 };
-enum { ST_PLAIN = 0, ST_SCALE = 1, ST_AXPBY = 2, ST_EXIT_SPLIT = 3, ST_ENTER = 4 };
+enum { ST_PLAIN = 0, ST_SCALE = 1, ST_AXPBY = 2, ST_EXIT_SPLIT = 3, ST_ENTER = 4, ST_EXIT3 = 5 };
 
 template <class F>
 struct IoDesc {
@@ -116,7 +116,10 @@ struct IoDesc {
     //        ST_ENTER  (pair operator, ENTER loop C src/fftree.rs:155-159 in normalised form; x = U1~ at pos = b*2e + i, y = V1~ at
     //                  pos + e, both still in the tile; aux = the level's input blocks [u0 | v0])
     //                  dst[b*2e + 2i] = aux[b*2e + i] + st_a[i]*aux[b*2e + e + i];  dst[b*2e + 2i + 1] = st_c[i]*x + st_b[i]*y
+    //        ST_EXIT3  (ST_AXPBY followed by ST_EXIT_SPLIT: the last store of the three-core EXIT level)
+    //                  u0 = st_a[i]*x + st_b[i]*aux[aux_stride*pos + aux_off]; v0 = st_c[i]*(aux2[2*pos] - u0); dst as for ST_EXIT_SPLIT
     E* dst; int st_mode; const TE* st_a; const TE* st_b; const E* aux; uint32_t aux_stride, aux_off; E* aux_out; const TE* st_c;
+    const E* aux2;       // ST_EXIT3: the level's input (even positions)
     uint32_t nt_st;      // != 0: non-temporal stores of the pass's results (data_st; launches of the latency regime)
 };
 
@@ -162,6 +165,14 @@ __device__ __forceinline__ void io_store(const IoDesc<F>& io, size_t pos, uint32
             E r = F::canon(F::tmul_add(io.st_a[i], x, F::tmul(io.st_b[i], io.aux[(size_t)io.aux_stride * pos + io.aux_off])));
             data_st(&io.dst[pos], r, io.nt_st);
             if (io.aux_out) io.aux_out[pos] = r;
+            break;
+        }
+        case ST_EXIT3: {
+            E u0 = F::canon(F::tmul_add(io.st_a[i], x, F::tmul(io.st_b[i], io.aux[(size_t)io.aux_stride * pos + io.aux_off])));
+            E v0 = F::canon(F::tmul(io.st_c[i], F::sub(io.aux2[2 * pos], u0)));
+            size_t base = (pos >> log_e) << (log_e + 1);
+            data_st(&io.dst[base + i], u0, io.nt_st);
+            data_st(&io.dst[base + ((size_t)1 << log_e) + i], v0, io.nt_st);
             break;
         }
         default: {  // ST_EXIT_SPLIT
@@ -259,6 +270,7 @@ __device__ __forceinline__ bool vio_ok(const IoDesc<F>& io, uint32_t log_e) {
     if (io.st_mode == ST_AXPBY || io.st_mode == ST_EXIT_SPLIT) ok = ok && al(io.st_b) && al(io.aux) && ((io.aux_stride == 1 && io.aux_off == 0) || (io.aux_stride == 2 && io.aux_off < 2));
     if (io.st_mode == ST_AXPBY && io.aux_out) ok = ok && al(io.aux_out);
     if (io.st_mode == ST_EXIT_SPLIT) ok = ok && io.aux_stride == 2 && io.aux_off == 0;
+    if (io.st_mode == ST_EXIT3) ok = ok && al(io.st_a) && al(io.st_b) && al(io.st_c) && al(io.aux) && al(io.aux2) && io.aux_stride == 1 && io.aux_off == 0;
     return ok;
 }
 template <class F, int NQ, int BLK, class PosFn>
@@ -278,13 +290,45 @@ __device__ __forceinline__ void vio_load(const IoDesc<F>& io, size_t emask, type
 #pragma unroll
     for (int c = 0; c < NQ; ++c) stq(tile + 4u * (tid + (uint32_t)c * BLK), d[c]);
 }
+// ST_EXIT3 on quads, two at a time (five operands per quad: more in flight would spill)
+template <class F, int NQ, int BLK, class PosFn>
+__device__ __forceinline__ void vio_store_exit3(const IoDesc<F>& io, uint32_t log_e, const typename F::elem* tile, PosFn pos_of, uint32_t tid) {
+    const size_t e = (size_t)1 << log_e, emask = e - 1;
+    static_assert(NQ % 2 == 0, "quads are taken two at a time");
+#pragma unroll 1
+    for (int c0 = 0; c0 < NQ; c0 += 2) {
+        Quad x[2], a[2], b[2], t[2], y[2], z[2];
+#pragma unroll
+        for (int c = 0; c < 2; ++c) {
+            const uint32_t j = 4u * (tid + (uint32_t)(c0 + c) * BLK);
+            const size_t pos = pos_of(j); const uint32_t i = (uint32_t)(pos & emask);
+            x[c] = ldq(tile + j);
+            a[c] = ldq_tab(io.st_a, i); b[c] = ldq_tab(io.st_b, i); t[c] = ldq_tab(io.st_c, i);
+            y[c] = ldq(io.aux + ECFFT_DPOS(pos));
+            z[c] = ldq_strided(io.aux2 + 2 * ECFFT_DPOS(pos), 2, 0);
+        }
+#pragma unroll
+        for (int c = 0; c < 2; ++c) {
+            const size_t pos = pos_of(4u * (tid + (uint32_t)(c0 + c) * BLK));
+            Quad r, r2;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                r.v[k] = F::canon(F::tmul_add(a[c].v[k], x[c].v[k], F::tmul(b[c].v[k], y[c].v[k])));
+                r2.v[k] = F::canon(F::tmul(t[c].v[k], F::sub(z[c].v[k], r.v[k])));
+            }
+            const size_t bs = (pos >> log_e) << (log_e + 1), i = pos & emask;
+            stq(io.dst + ECFFT_DPOS(bs + i), r); stq(io.dst + ECFFT_DPOS(bs + e + i), r2);
+        }
+    }
+}
 template <class F, int NQ, int BLK, class PosFn>
 __device__ __forceinline__ void vio_store(const IoDesc<F>& io, uint32_t log_e, const typename F::elem* tile, PosFn pos_of, uint32_t tid) {
     const size_t e = (size_t)1 << log_e, emask = e - 1;
+    const int m = io.st_mode;
+    if (m == ST_EXIT3) { vio_store_exit3<F, NQ, BLK>(io, log_e, tile, pos_of, tid); return; }
     Quad x[NQ], a[NQ], b[NQ], y[NQ];
 #pragma unroll
     for (int c = 0; c < NQ; ++c) x[c] = ldq(tile + 4u * (tid + (uint32_t)c * BLK));
-    const int m = io.st_mode;
     if (m != ST_PLAIN) {
 #pragma unroll
         for (int c = 0; c < NQ; ++c) { const size_t pos = pos_of(4u * (tid + (uint32_t)c * BLK)); a[c] = ldq_tab(io.st_a, (uint32_t)(pos & emask)); }
@@ -1354,6 +1398,9 @@ struct LevelTables {
     // low32_A / _K (only in the entry of the tree with 32 leaves; round 4): levels 1..5 of ENTER [0] / 5..1 of EXIT [1] of a 32-block as
     // ONE 32 x 32 map (1 MiB of matrices each, Blk16::phase32); nullptr: low16 (or the level code) runs
     const uint8_t* low32_A[2]; const unsigned long long* low32_K[2];
+    // three-core EXIT level (reduction over Z1, device_tree.h exit_levels): the Z1 counterparts of A1, B1, NB2, C1, D1 and the
+    // coefficient of the last store; nullptr: the level runs the four-core form
+    TE *zA1, *zB1, *zNB2, *zC1, *zD1, *zNB3;
 };
 
 // ---------------------------------------------------------------------------------------------
