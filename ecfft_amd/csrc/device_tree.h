@@ -131,7 +131,10 @@ public:
     // tree is installed (the sharded EXIT build needs two different shares of one tree)
     const Tree& tree_at(unsigned log_m) const { return (ovr_tree_ && ovr_tree_->log_m == log_m) ? *ovr_tree_ : trees_[log_m]; }
     const HostTree<F>& host() const { return host_; }
-    int exit_cores() const { return exit3_ ? 3 : 4; }        // EXTEND cores per EXIT level of exit_levels
+    int exit_cores() const { return exit3_ ? 3 : 4; }        // EXTEND cores per EXIT level of exit_levels: the form of the context
+    // EXTEND cores per level of k_exit_low's loop: the context's form, unless the build (-DECFFT_EXIT_LOW_CORES=4) or the A/B switch
+    // keeps the four-core kernel under a three-core driver
+    int exit_low_cores() const { return exit3_ && kExitLowForm == 3 && !exit_low4_ ? 3 : 4; }
     int low_map(int dir) const {
         if (trees_.size() > 5 && trees_[5].low32_A[dir]) return 32;
         if (trees_.size() > 4 && trees_[4].low16_A[dir]) return 16;
@@ -1519,6 +1522,10 @@ public:
 #ifndef ECFFT_EXIT_CORES
 #define ECFFT_EXIT_CORES 3      // EXTEND cores per EXIT level (exit_levels): 3 = reduction over Z1, 4 = the reference's form (A/B)
 #endif
+#ifndef ECFFT_EXIT_LOW_CORES
+#define ECFFT_EXIT_LOW_CORES 3  // EXTEND cores per level of k_exit_low's loop in a three-core context; 4 = the four-core kernel under a three-core driver (A/B)
+#endif
+    static constexpr int kExitLowForm = (ECFFT_EXIT_CORES == 4 || ECFFT_EXIT_LOW_CORES == 4) ? 4 : 3;   // the second k_exit_low form a build holds
     static constexpr unsigned kSplitMinLog = ECFFT_SPLIT_MIN_LOG;   // single transforms of at least 2^this run as concurrent halves
 #ifndef ECFFT_SPLIT_DEPTH
 #define ECFFT_SPLIT_DEPTH 1
@@ -1644,12 +1651,19 @@ public:
         if (l_to == 1 && l_from >= ll) {
             E* dst = out != in ? out : (cur == bufA ? bufB : bufA);
             double bytes = 0; for (unsigned l = 1; l <= ll; ++l) bytes += exit_level_alg_bytes(n, l);
-            if (ll == kLogLow)
-                ECFFT_LAUNCH(KC_FUSED_EXIT, bytes, (k_exit_low<F, (int)kLogLow>), dim3((unsigned)(n >> kLogLow)), dim3(kBlockLds),
-                             2 * (sizeof(E) << kLogLow), s, dst, cur, (const Tree*)d_trees_);
-            else
-                ECFFT_LAUNCH(KC_FUSED_EXIT, bytes, (k_exit_low<F, (int)kLogLowSmall, (int)kBlockLowSmall>), dim3((unsigned)(n >> kLogLowSmall)), dim3(kBlockLowSmall),
-                             2 * (sizeof(E) << kLogLowSmall), s, dst, cur, (const Tree*)d_trees_);
+            // the kernel's level loop runs the context's form (the credit above models the reference's four cores all the same)
+            const bool low3 = exit_low_cores() == 3;
+            if (ll == kLogLow) {
+                if (low3) ECFFT_LAUNCH(KC_FUSED_EXIT, bytes, (k_exit_low<F, (int)kLogLow, (int)kBlockLds, kExitLowForm>), dim3((unsigned)(n >> kLogLow)), dim3(kBlockLds),
+                                       2 * (sizeof(E) << kLogLow), s, dst, cur, (const Tree*)d_trees_);
+                else ECFFT_LAUNCH(KC_FUSED_EXIT, bytes, (k_exit_low<F, (int)kLogLow, (int)kBlockLds, 4>), dim3((unsigned)(n >> kLogLow)), dim3(kBlockLds),
+                                  2 * (sizeof(E) << kLogLow), s, dst, cur, (const Tree*)d_trees_);
+            } else {
+                if (low3) ECFFT_LAUNCH(KC_FUSED_EXIT, bytes, (k_exit_low<F, (int)kLogLowSmall, (int)kBlockLowSmall, kExitLowForm>), dim3((unsigned)(n >> kLogLowSmall)), dim3(kBlockLowSmall),
+                                       2 * (sizeof(E) << kLogLowSmall), s, dst, cur, (const Tree*)d_trees_);
+                else ECFFT_LAUNCH(KC_FUSED_EXIT, bytes, (k_exit_low<F, (int)kLogLowSmall, (int)kBlockLowSmall, 4>), dim3((unsigned)(n >> kLogLowSmall)), dim3(kBlockLowSmall),
+                                  2 * (sizeof(E) << kLogLowSmall), s, dst, cur, (const Tree*)d_trees_);
+            }
             cur = dst;
         }
         if (cur != out) (void)hipMemcpyAsync(out, cur, n * sizeof(E), hipMemcpyDeviceToDevice, s);
@@ -4396,7 +4410,8 @@ private:
             });
             T.xe = to_tables(xe, es, s); T.w1x = to_tables(w1x, es, s); T.xie = to_tables(xie, es, s);
             // a context holds ONE fused EXIT set per tree: the Z1 set where exit_levels runs the three-core form, the Z0 set where
-            // it runs the four-core form; the trees the low-level kernels (four cores) cover keep the Z0 set as well
+            // it runs the four-core form; the trees k_exit_low covers (at most 2^kLogLow leaves) keep both: its loop runs the
+            // context's form on the Z1 set, and the four-core kernel under a three-core driver (ECFFT_EXIT_LOW_CORES=4, A/B) the Z0 set
             if (!exit3_ || l <= kLogLow) {
                 T.A1 = to_tables(A1, es, s); T.B1 = to_tables(B1, es, s); T.NB2 = to_tables(NB2, es, s); T.C1 = to_tables(C1, es, s); T.D1 = to_tables(D1, es, s);
             }
@@ -4476,6 +4491,7 @@ private:
     // for the reference's four; exit3_ = the form this context's tables were built for (full contexts whose leaves are all non-zero)
     bool exit4_ = ECFFT_EXIT_CORES == 4 || ab_env("ECFFT_EXIT_FOUR_CORES") != nullptr;
     bool exit3_ = false;
+    bool exit_low4_ = ab_env("ECFFT_EXIT_LOW_FOUR_CORES") != nullptr;   // A/B switch: k_exit_low keeps four cores per level in a three-core context
 };
 
 }  // namespace ecfft

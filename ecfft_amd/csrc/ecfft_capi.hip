@@ -1577,6 +1577,10 @@ int ecfft_ctx_exit_cores(const ecfft_ctx* ctx) {
     if (!ctx) return 0;
     return ctx->secp ? ctx->secp->exit_cores() : ctx->m31 ? ctx->m31->exit_cores() : 0;
 }
+int ecfft_ctx_exit_low_cores(const ecfft_ctx* ctx) {
+    if (!ctx) return 0;
+    return ctx->secp ? ctx->secp->exit_low_cores() : ctx->m31 ? ctx->m31->exit_low_cores() : 0;
+}
 
 #endif  // ECFFT_TEST_HOOKS
 int ecfft_mul_ceiling(int field, int device, int waves_per_simd, double* mul_per_s) {

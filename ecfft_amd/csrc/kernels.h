@@ -1904,10 +1904,18 @@ __global__ __launch_bounds__(BLK, (BLK >= 512 ? ECFFT_MIN_WAVES : 2)) void k_ent
 
 // EXIT levels log_tile .. 1 (src/fftree.rs:200-224 with redc_impl :232-259 inlined, normalised form, see
 // DeviceChain::exit).  LDS: cur (tile) + G (tile/2) + H (tile/2).
-template <class F, int LOG_TILE, int BLK = kBlockLds>
+// CORES: the form of a level of the loop, uniform over the launch (the driver instantiates the context's form).
+//   4  the reference's: reduction over Z0, four EXTEND cores (S0->S1, S1->S0, S0->S1, S1->S0) and five pointwise steps
+//   3  reduction over Z1 (the z* tables): G = zA1 cur[odd]; core S1->S0; G = H = zNB2 G + zB1 cur[even]; core S0->S1; G = zC1 G;
+//      core S1->S0; u0 = zNB3 G + zD1 H, v0 = xie (cur[even] - u0) — three cores, 7 multiplies per pair instead of 8
+// The matrix-core maps of the lowest levels (low16 / low32) are exact linear maps of the whole levels and serve both forms.
+template <class F, int LOG_TILE, int BLK = kBlockLds, int CORES = 4>
 __global__ __launch_bounds__(BLK, (BLK >= 512 ? ECFFT_MIN_WAVES : 1)) void k_exit_low(typename F::elem* __restrict__ dst, const typename F::elem* __restrict__ src,
                                                          const LevelTables<F>* __restrict__ trees) {
     using E = typename F::elem;
+    static_assert(CORES == 3 || CORES == 4, "three or four EXTEND cores per level");
+    constexpr bool k3 = CORES == 3;
+    constexpr int par1 = k3 ? 1 : 0;                                        // source parity of the level's first core
     extern __shared__ __attribute__((aligned(16))) unsigned char ecfft_smem[];
     constexpr uint32_t log_tile = LOG_TILE, T = 1u << LOG_TILE, nh = T >> 1;
     constexpr int PAIRS = (int)(nh / BLK);
@@ -1948,7 +1956,7 @@ __global__ __launch_bounds__(BLK, (BLK >= 512 ? ECFFT_MIN_WAVES : 1)) void k_exi
         const uint32_t le = l - 1, e = 1u << le;
         if constexpr (kQuad) {
             if (le >= 2) {
-                // the level's five pointwise steps on quads of the pair index g (loads first), the four EXTEND cores between them
+                // the level's pointwise steps on quads of the pair index g (loads first), the EXTEND cores between them
                 constexpr int NP = (int)(nh / (4 * BLK));
                 auto gq = [=](int c) { return 4u * (tid + (uint32_t)c * BLK); };
                 auto tq = [=](const typename F::telem* t, int c) { return ldq_tab(t, gq(c) & (e - 1)); };
@@ -1957,7 +1965,7 @@ __global__ __launch_bounds__(BLK, (BLK >= 512 ? ECFFT_MIN_WAVES : 1)) void k_exi
                 {
                     Quad t[NP], x[NP];
 #pragma unroll
-                    for (int c = 0; c < NP; ++c) { t[c] = tq(L.A1, c); x[c] = evenq(c); }
+                    for (int c = 0; c < NP; ++c) { t[c] = tq(k3 ? L.zA1 : L.A1, c); x[c] = k3 ? oddq(c) : evenq(c); }
 #pragma unroll
                     for (int c = 0; c < NP; ++c) {
 #pragma unroll
@@ -1966,11 +1974,11 @@ __global__ __launch_bounds__(BLK, (BLK >= 512 ? ECFFT_MIN_WAVES : 1)) void k_exi
                     }
                 }
                 __syncthreads();
-                lds_extend_core<F, BLK>(G, nh, le, L, 0);
+                lds_extend_core<F, BLK>(G, nh, le, L, par1);
                 {
                     Quad ta[NP], tb[NP], x[NP], y[NP];
 #pragma unroll
-                    for (int c = 0; c < NP; ++c) { ta[c] = tq(L.NB2, c); tb[c] = tq(L.B1, c); x[c] = ldq(G + gq(c)); y[c] = oddq(c); }
+                    for (int c = 0; c < NP; ++c) { ta[c] = tq(k3 ? L.zNB2 : L.NB2, c); tb[c] = tq(k3 ? L.zB1 : L.B1, c); x[c] = ldq(G + gq(c)); y[c] = k3 ? evenq(c) : oddq(c); }
 #pragma unroll
                     for (int c = 0; c < NP; ++c) {
 #pragma unroll
@@ -1979,11 +1987,11 @@ __global__ __launch_bounds__(BLK, (BLK >= 512 ? ECFFT_MIN_WAVES : 1)) void k_exi
                     }
                 }
                 __syncthreads();
-                lds_extend_core<F, BLK>(G, nh, le, L, 1);
+                lds_extend_core<F, BLK>(G, nh, le, L, 1 - par1);
                 {
                     Quad t[NP], x[NP];
 #pragma unroll
-                    for (int c = 0; c < NP; ++c) { t[c] = tq(L.C1, c); x[c] = ldq(G + gq(c)); }
+                    for (int c = 0; c < NP; ++c) { t[c] = tq(k3 ? L.zC1 : L.C1, c); x[c] = ldq(G + gq(c)); }
 #pragma unroll
                     for (int c = 0; c < NP; ++c) {
 #pragma unroll
@@ -1992,22 +2000,33 @@ __global__ __launch_bounds__(BLK, (BLK >= 512 ? ECFFT_MIN_WAVES : 1)) void k_exi
                     }
                 }
                 __syncthreads();
-                lds_extend_core<F, BLK>(G, nh, le, L, 0);
-                {
-                    Quad ta[NP], tb[NP], x[NP], y[NP];
-#pragma unroll
-                    for (int c = 0; c < NP; ++c) { ta[c] = tq(L.NB2, c); tb[c] = tq(L.D1, c); x[c] = ldq(G + gq(c)); y[c] = ldq(H + gq(c)); }
-#pragma unroll
-                    for (int c = 0; c < NP; ++c) {
-#pragma unroll
-                        for (int k = 0; k < 4; ++k) x[c].v[k] = F::tmul_add(ta[c].v[k], x[c].v[k], F::tmul(tb[c].v[k], y[c].v[k]));
-                        stq(G + gq(c), x[c]);
-                    }
-                }
-                __syncthreads();
-                lds_extend_core<F, BLK>(G, nh, le, L, 1);
+                lds_extend_core<F, BLK>(G, nh, le, L, par1);
                 Quad uq[NP], vq[NP];
-                {
+                if constexpr (k3) {
+                    Quad ta[NP], tb[NP], tc[NP], x[NP], y[NP], z[NP];
+#pragma unroll
+                    for (int c = 0; c < NP; ++c) { ta[c] = tq(L.zNB3, c); tb[c] = tq(L.zD1, c); tc[c] = tq(L.xie, c); x[c] = ldq(G + gq(c)); y[c] = ldq(H + gq(c)); z[c] = evenq(c); }
+#pragma unroll
+                    for (int c = 0; c < NP; ++c)
+#pragma unroll
+                        for (int k = 0; k < 4; ++k) {
+                            uq[c].v[k] = F::tmul_add(ta[c].v[k], x[c].v[k], F::tmul(tb[c].v[k], y[c].v[k]));
+                            vq[c].v[k] = F::tmul(tc[c].v[k], F::sub(z[c].v[k], uq[c].v[k]));
+                        }
+                } else {
+                    {
+                        Quad ta[NP], tb[NP], x[NP], y[NP];
+#pragma unroll
+                        for (int c = 0; c < NP; ++c) { ta[c] = tq(L.NB2, c); tb[c] = tq(L.D1, c); x[c] = ldq(G + gq(c)); y[c] = ldq(H + gq(c)); }
+#pragma unroll
+                        for (int c = 0; c < NP; ++c) {
+#pragma unroll
+                            for (int k = 0; k < 4; ++k) x[c].v[k] = F::tmul_add(ta[c].v[k], x[c].v[k], F::tmul(tb[c].v[k], y[c].v[k]));
+                            stq(G + gq(c), x[c]);
+                        }
+                    }
+                    __syncthreads();
+                    lds_extend_core<F, BLK>(G, nh, le, L, 1);
                     Quad ta[NP], tb[NP], x[NP], y[NP];
 #pragma unroll
                     for (int c = 0; c < NP; ++c) { ta[c] = tq(L.w[0], c); tb[c] = tq(L.xie, c); x[c] = ldq(G + gq(c)); y[c] = evenq(c); }
@@ -2026,30 +2045,33 @@ __global__ __launch_bounds__(BLK, (BLK >= 512 ? ECFFT_MIN_WAVES : 1)) void k_exi
                 continue;
             }
         }
-        for (uint32_t g = tid; g < nh; g += BLK) lds_put<F, kSwz>(G, g, F::tmul(ldt(L.A1, g & (e - 1)), lds_get<F, kSwz>(cur, 2 * g)));
+        for (uint32_t g = tid; g < nh; g += BLK) lds_put<F, kSwz>(G, g, F::tmul(ldt(k3 ? L.zA1 : L.A1, g & (e - 1)), lds_get<F, kSwz>(cur, 2 * g + par1)));
         __syncthreads();
-        lds_extend_core<F, BLK, kSwz>(G, nh, le, L, 0);
+        lds_extend_core<F, BLK, kSwz>(G, nh, le, L, par1);
         for (uint32_t g = tid; g < nh; g += BLK) {
             uint32_t i = g & (e - 1);
-            E r = F::tmul_add(ldt(L.NB2, i), lds_get<F, kSwz>(G, g), F::tmul(ldt(L.B1, i), lds_get<F, kSwz>(cur, 2 * g + 1)));
+            E r = F::tmul_add(ldt(k3 ? L.zNB2 : L.NB2, i), lds_get<F, kSwz>(G, g), F::tmul(ldt(k3 ? L.zB1 : L.B1, i), lds_get<F, kSwz>(cur, 2 * g + 1 - par1)));
             lds_put<F, kSwz>(G, g, r); lds_put<F, kSwz>(H, g, r);
         }
         __syncthreads();
-        lds_extend_core<F, BLK, kSwz>(G, nh, le, L, 1);
-        for (uint32_t g = tid; g < nh; g += BLK) lds_put<F, kSwz>(G, g, F::tmul(ldt(L.C1, g & (e - 1)), lds_get<F, kSwz>(G, g)));
+        lds_extend_core<F, BLK, kSwz>(G, nh, le, L, 1 - par1);
+        for (uint32_t g = tid; g < nh; g += BLK) lds_put<F, kSwz>(G, g, F::tmul(ldt(k3 ? L.zC1 : L.C1, g & (e - 1)), lds_get<F, kSwz>(G, g)));
         __syncthreads();
-        lds_extend_core<F, BLK, kSwz>(G, nh, le, L, 0);
-        for (uint32_t g = tid; g < nh; g += BLK) {
-            uint32_t i = g & (e - 1);
-            lds_put<F, kSwz>(G, g, F::tmul_add(ldt(L.NB2, i), lds_get<F, kSwz>(G, g), F::tmul(ldt(L.D1, i), lds_get<F, kSwz>(H, g))));
+        lds_extend_core<F, BLK, kSwz>(G, nh, le, L, par1);
+        if constexpr (!k3) {
+            for (uint32_t g = tid; g < nh; g += BLK) {
+                uint32_t i = g & (e - 1);
+                lds_put<F, kSwz>(G, g, F::tmul_add(ldt(L.NB2, i), lds_get<F, kSwz>(G, g), F::tmul(ldt(L.D1, i), lds_get<F, kSwz>(H, g))));
+            }
+            __syncthreads();
+            lds_extend_core<F, BLK, kSwz>(G, nh, le, L, 1);
         }
-        __syncthreads();
-        lds_extend_core<F, BLK, kSwz>(G, nh, le, L, 1);
         E u[PAIRS], v[PAIRS];
 #pragma unroll
         for (int c = 0; c < PAIRS; ++c) {
             uint32_t g = tid + (uint32_t)c * BLK, i = g & (e - 1);
-            u[c] = F::tmul(ldt(L.w[0], i), lds_get<F, kSwz>(G, g));
+            if constexpr (k3) u[c] = F::tmul_add(ldt(L.zNB3, i), lds_get<F, kSwz>(G, g), F::tmul(ldt(L.zD1, i), lds_get<F, kSwz>(H, g)));
+            else u[c] = F::tmul(ldt(L.w[0], i), lds_get<F, kSwz>(G, g));
             v[c] = F::tmul(ldt(L.xie, i), F::sub(lds_get<F, kSwz>(cur, 2 * g), u[c]));
         }
         __syncthreads();

@@ -6,7 +6,7 @@
  * the tests and the measurement tools load explicitly.  The same build also reads the A/B switches of the tuning experiments from
  * the environment (ECFFT_NO_MFMA, ECFFT_NO_LOW16, ECFFT_LOW32, ECFFT_NO_ROW256, ECFFT_NO_COL256, ECFFT_NO_SMALL_TILES,
  * ECFFT_SMALL_TILES_MAX, ECFFT_SMALL_LOW_MAX, ECFFT_SMALL_MIN_LOGC, ECFFT_NO_FULL_CYCLIC, ECFFT_SPLIT_GATHER_MAX_LOG,
- * ECFFT_SPLIT_Q2_SPLIT, ECFFT_EXIT_FOUR_CORES); the shipped library reads no environment variable at all. */
+ * ECFFT_SPLIT_Q2_SPLIT, ECFFT_EXIT_FOUR_CORES, ECFFT_EXIT_LOW_FOUR_CORES); the shipped library reads no environment variable at all. */
 #ifndef ECFFT_HIP_HOOKS_H
 #define ECFFT_HIP_HOOKS_H
 #include "ecfft_hip.h"
@@ -56,6 +56,9 @@ int ecfft_ctx_low_map(const ecfft_ctx* ctx, int dir);
 /* test / measurement hook: EXTEND cores per EXIT level of the context's level driver: 3 = the reduction over Z1 (full contexts whose
  * leaves are all non-zero), 4 = the reference's form (a zero leaf, shard contexts, A/B: ECFFT_EXIT_FOUR_CORES, -DECFFT_EXIT_CORES=4) */
 int ecfft_ctx_exit_cores(const ecfft_ctx* ctx);
+/* ... and per level of the loop of the fused low-level EXIT kernel (k_exit_low): the context's form, or 4 in a three-core context
+ * that keeps the four-core kernel (A/B: ECFFT_EXIT_LOW_FOUR_CORES, -DECFFT_EXIT_LOW_CORES=4) */
+int ecfft_ctx_exit_low_cores(const ecfft_ctx* ctx);
 /* measurement hook (tools/findcurve_time.py): the number of queue entries every stage of the curve search has read since the last
  * reset, summed over batches: [0] bb square, [1] discriminant, [2] point of order 4, [3 + r] halving round r; and the host seconds
  * spent around each stage's launch and the read of its queue length, which waits for it.  Copies up to `cap` entries into each
