@@ -6,6 +6,8 @@
 // HBM layout ("Moiety precompute layout"): per tree T_m (m = 2e leaves), per moiety
 // parity s in {0,1}, structure-of-arrays tables holding only the half that parity uses:
 //   p0[s], p1[s], np0[s], dinv[s]   e-1 entries, stage k at offset e - 2*h_k   (h_k = e >> (k+1))
+//                                   (p0 / p1 = the two pre-images of a layer point — or, in a symmetric context, DESIGN.md 2.2a, their
+//                                   images under the layer's sigma = (x - c1)/(x - c2), where p1 = -p0; np0 = -p0, dinv = 1/(p1 - p0))
 //   c0t[s] = np0[s]*dinv[s]         likewise    (pair-split decompose of the latency regime: two independent products)
 //   w[s], winv[s]                   e entries   (normalisation weights of the parity's leaves)
 //   xe, w1x                         e entries   ENTER combine
@@ -112,6 +114,9 @@ private:
 #ifndef ECFFT_BATCH_SPLIT
 #define ECFFT_BATCH_SPLIT 1
 #endif
+#ifndef ECFFT_SYM_BFLY
+#define ECFFT_SYM_BFLY 1        // 0: general basis and two-multiply butterflies in every context
+#endif
 #ifndef ECFFT_BATCH_WAYS
 #define ECFFT_BATCH_WAYS 2      // a batch runs as up to this many concurrent parts (whole polynomials each, one stream per part); A/B: profiles/r06/batch_ways_ab.txt
 #endif
@@ -135,6 +140,9 @@ public:
     // EXTEND cores per level of k_exit_low's loop: the context's form, unless the build (-DECFFT_EXIT_LOW_CORES=4) or the A/B switch
     // keeps the four-core kernel under a three-core driver
     int exit_low_cores() const { return exit3_ && kExitLowForm == 3 && !exit_low4_ ? 3 : 4; }
+    // butterfly form of the context: 0 = general basis and butterflies, 1 = symmetric basis with the one-multiply butterflies in the
+    // full-size row and column passes, 2 = symmetric basis under the general kernels (A/B)
+    int sym_bfly() const { return !sym_ ? 0 : (sym_general_kernels_ ? 2 : 1); }
     int low_map(int dir) const {
         if (trees_.size() > 5 && trees_[5].low32_A[dir]) return 32;
         if (trees_.size() > 4 && trees_[4].low16_A[dir]) return 16;
@@ -159,7 +167,7 @@ public:
         hipStream_t s = nullptr;
         // arena per tree of m leaves: 6m elements of reference tables (xnn, z*) + 11m table constants of the hot path
         // (F::telem each); + f (2N) + den coefficients
-        size_t total = 2 * N_ + 64;
+        size_t total = 2 * N_ + 64 + 2 * (L_ ? L_ : 1) + 64;      // ... + the critical points of the maps
         for (unsigned l = 0; l <= L_; ++l) total += (6 + 11 * kTeElems) * ((size_t)1 << l) + 1024 + blk16_elems(l);
         // three-core EXIT: the Z1 set has one table more than the Z0 set it replaces (e constants per tree); the trees of the
         // low-level kernels hold both sets (6 e constants more, at most 2^kLogLow leaves)
@@ -187,6 +195,17 @@ public:
         for (unsigned k = 0; k < L_; ++k) { den[2 * k] = host_.maps[k].den[0]; den[2 * k + 1] = host_.maps[k].den[1]; }
         den_ = take(2 * (L_ ? L_ : 1));
         ECFFT_HIP_TRY(hipMemcpyAsync(den_, den.data(), den.size() * sizeof(E), hipMemcpyHostToDevice, s));
+        // symmetric basis: the library's own tree of a 32-byte field whose maps all have rational critical points
+        std::vector<E> crit(2 * (L_ ? L_ : 1), F::zero());
+        sym_ = false;
+        if constexpr (sizeof(E) == 32 && ECFFT_SYM_BFLY != 0) {
+            if (host_.sym_candidate && !sym_off_ && L_ >= 1) {
+                sym_ = true;
+                for (unsigned k = 0; k < L_ && sym_; ++k) sym_ = critical_points<F>(host_.maps[k], &crit[2 * k], &crit[2 * k + 1]);
+            }
+        }
+        crit_ = take(2 * (L_ ? L_ : 1));
+        ECFFT_HIP_TRY(hipMemcpyAsync(crit_, crit.data(), crit.size() * sizeof(E), hipMemcpyHostToDevice, s));
         // transform scratch: 5 N (grown on demand for batched calls); side stream for the two-halves schedule
         if (!ensure_scratch(N_)) return false;
         create_side_streams();
@@ -788,6 +807,7 @@ public:
     // max stages per column pass (A/B on MI355X: 8 stages x 4-element rows beat 5 x 32 on secp256k1; 9 x 16-element rows are 1 %
     // better than 8 on M31 at 2^24 and equal below, profiles/r02/knob_sweep.txt)
     static constexpr unsigned kColStages = sizeof(E) == 4 ? ECFFT_COL_STAGES_4B : ECFFT_COL_STAGES;
+    static constexpr bool kSymKernels = sizeof(E) == 32 && ECFFT_SYM_BFLY != 0;   // the SYM instantiations exist for 32-byte fields only
     static constexpr unsigned kLogColTileMax = (sizeof(E) == 32) ? ECFFT_LOG_COL_TILE_BYTES - 5 : ECFFT_LOG_COL_TILE_BYTES - 2;
     // Fusion of consecutive cores (EXIT): `next_ld` != nullptr says that another core of the same tree and size, opposite
     // direction, follows on `buf` with that load operator; if this core ends in a column pass, that pass and the next
@@ -805,6 +825,7 @@ public:
         const Tree& T = tree_at(log_m);
         size_t e = T.e; unsigned le = ilog2(e);
         int tgt = 1 - srcpar;
+        const bool symk = kSymKernels && sym_kernels();                       // symmetric context: one-multiply butterflies in the full-size passes
         unsigned tz = (unsigned)__builtin_ctzll((unsigned long long)total);   // tiles must divide count*e
         unsigned log_tile = tz < kLogTileMax ? tz : kLogTileMax;
         const bool small = small_launch(total) && !ef_small_off_;           // latency regime: 4x smaller tiles, 4x as many workgroups
@@ -848,6 +869,9 @@ public:
                 const unsigned lv = pair_spans(total, le, P.ka, log_ct, d);
                 if (col256_ok(log_ct, le) && T.c0t[tgt])      // latency regime: one element per thread in registers (reg_col_stages)
                     ECFFT_LAUNCH(KC_COL, bytes, k_stages_col_mid256<F>, dim3((unsigned)(total >> log_ct)), dim3(256), 0, s, d, T.p0[tgt], T.p1[tgt], T.c0t[tgt], T.dinv[tgt], le, P.ka, P.kb, log_c);
+                else if (symk)
+                ECFFT_LAUNCH(KC_COL, bytes, (k_stages_col_mid<F, kSymKernels>), dim3((unsigned)(total >> (log_ct + lv))), dim3(kBlockLds), (sizeof(E) * ((size_t)col_row_stride<E>(1u << log_c) << R)) << lv, s,
+                             d, T.p0[tgt], T.p1[tgt], T.np0[tgt], T.dinv[tgt], le, P.ka, P.kb, log_c, T.c0t[tgt], (uint32_t)lv);
                 else
                 ECFFT_LAUNCH(KC_COL, bytes, k_stages_col_mid<F>, dim3((unsigned)(total >> (log_ct + lv))), dim3(kBlockLds), (sizeof(E) * ((size_t)col_row_stride<E>(1u << log_c) << R)) << lv, s,
                              d, T.p0[tgt], T.p1[tgt], T.np0[tgt], T.dinv[tgt], le, P.ka, P.kb, log_c, T.c0t[tgt], (uint32_t)lv);
@@ -864,6 +888,10 @@ public:
                 if (col256_ok(log_ct, le))
                     ECFFT_LAUNCH(KC_COL, bytes, k_stages_col_enter256<F>, dim3((unsigned)(total >> (log_ct + 1))), dim3(512), 0, s,
                                  (const E*)buf, ef->src, ef->dst, T.p0[tgt], T.p1[tgt], T.xe, T.w[1], T.w1x, le, P.kb, log_c);
+                else if (symk)
+                ECFFT_LAUNCH(KC_COL, bytes, (k_stages_col_enter<F, kSymKernels>), dim3((unsigned)(total >> (log_ct + 1))), dim3(kBlockLds),
+                             2 * sizeof(E) * ((size_t)col_row_stride<E>(1u << log_c) << R), s,
+                             (const E*)buf, ef->src, ef->dst, T.p0[tgt], T.p1[tgt], T.xe, T.w[1], T.w1x, le, P.kb, log_c);
                 else
                 ECFFT_LAUNCH(KC_COL, bytes, k_stages_col_enter<F>, dim3((unsigned)(total >> (log_ct + 1))), dim3(kBlockLds),
                              2 * sizeof(E) * ((size_t)col_row_stride<E>(1u << log_c) << R), s,
@@ -907,7 +935,10 @@ public:
                     if constexpr (ct_row)
                     ECFFT_LAUNCH(KC_ROW, bytes, (k_stages_lds<F, (int)kLogTileMax + 1>), dim3((unsigned)(total >> log_tile)), dim3(kBlockRow),
                                  ((size_t)sizeof(E)) << log_tile, s, d, T.np0[srcpar], T.dinv[srcpar], T.p0[tgt], T.p1[tgt], T.inner[srcpar], le, k_first, log_tile, T.c0t[srcpar], bA, bK);
-                } else if (log_tile == kLogTileMax && (ct_row || bA))   // compile-time tile (always for the matrix-core row passes): +16% on M31 (8 pairs/thread unroll), -3% on secp256k1
+                } else if (log_tile == kLogTileMax && (ct_row || bA) && symk)   // ... with the one-multiply butterflies of a symmetric context
+                    ECFFT_LAUNCH(KC_ROW, bytes, (k_stages_lds<F, (int)kLogTileMax, kSymKernels>), dim3((unsigned)(total >> log_tile)), dim3(kBlockRow),
+                                 ((size_t)sizeof(E)) << log_tile, s, d, T.np0[srcpar], T.dinv[srcpar], T.p0[tgt], T.p1[tgt], T.inner[srcpar], le, k_first, log_tile, T.c0t[srcpar], bA, bK);
+                else if (log_tile == kLogTileMax && (ct_row || bA))   // compile-time tile (always for the matrix-core row passes): +16% on M31 (8 pairs/thread unroll), -3% on secp256k1
                     ECFFT_LAUNCH(KC_ROW, bytes, (k_stages_lds<F, (int)kLogTileMax>), dim3((unsigned)(total >> log_tile)), dim3(kBlockRow),
                                  ((size_t)sizeof(E)) << log_tile, s, d, T.np0[srcpar], T.dinv[srcpar], T.p0[tgt], T.p1[tgt], T.inner[srcpar], le, k_first, log_tile, T.c0t[srcpar], bA, bK);
                 else
@@ -928,6 +959,10 @@ public:
                 if (col256_ok(log_ct, le) && lv == 0 && (P.kind != 0 || T.c0t[srcpar])) {
                     if (P.kind == 0) ECFFT_LAUNCH(KC_COL, bytes, (k_stages_col256<F, true>), dim3((unsigned)(total >> log_ct)), dim3(256), 0, s, d, T.c0t[srcpar], T.dinv[srcpar], le, P.ka, P.kb, log_c);
                     else ECFFT_LAUNCH(KC_COL, bytes, (k_stages_col256<F, false>), dim3((unsigned)(total >> log_ct)), dim3(256), 0, s, d, T.p0[tgt], T.p1[tgt], le, P.ka, P.kb, log_c);
+                } else
+                if (symk && !ct) {
+                    if (P.kind == 0) ECFFT_LAUNCH(KC_COL, bytes, (k_stages_col<F, true, 0, kSymKernels>), grid, dim3(kBlockLds), lds, s, d, T.np0[srcpar], T.dinv[srcpar], le, P.ka, P.kb, log_c, T.c0t[srcpar], (uint32_t)lv);
+                    else ECFFT_LAUNCH(KC_COL, bytes, (k_stages_col<F, false, 0, kSymKernels>), grid, dim3(kBlockLds), lds, s, d, T.p0[tgt], T.p1[tgt], le, P.ka, P.kb, log_c, (const TE*)nullptr, (uint32_t)lv);
                 } else
                 if (P.kind == 0) {
                     if constexpr (kCtCol) { if (ct) { ECFFT_LAUNCH(KC_COL, bytes, (k_stages_col<F, true, (int)kLogColTileMax>), grid, dim3(kBlockLds), lds, s, d, T.np0[srcpar], T.dinv[srcpar], le, P.ka, P.kb, log_c, T.c0t[srcpar], (uint32_t)lv); continue; } }
@@ -4244,6 +4279,9 @@ private:
         size_t m = (size_t)1 << l, e = m / 2;
         T.m = m; T.e = e; T.log_m = l;
         const E* f = f_; size_t N = N_; size_t stride = N_ / m;
+        // symmetric basis: the stage tables hold sigma_k = (x - c1_k)/(x - c2_k) of the layer points instead of the points
+        // (then p1 = -p0), and the weights carry one factor (s_k - c2_k) per layer more; every derived table follows from these
+        const bool sym = sym_; const E* crit = crit_;
         T.xnn = take(m); T.xnn_inv = take(m);
         {
             E* xnn = T.xnn; uint64_t ex = m / 2;
@@ -4270,6 +4308,11 @@ private:
                     size_t lay = N >> k;                      // offset (= size) of layer k in the top tree
                     E a = f[lay + (2 * i + sg) * stride];
                     E b = f[lay + (2 * i + sg + 2 * h) * stride];
+                    if (sym) {      // u = a - c1, v = a - c2 and 2uv: ONE inverse gives sigma(a) = u/v and -1/(2 sigma(a)) below
+                        const E u = F::sub(a, crit[2 * k]), v = F::sub(a, crit[2 * k + 1]), uv = F::mul(u, v);
+                        p0[g] = u; p1[g] = v; dinv[g] = F::add(uv, uv);
+                        return;
+                    }
                     p0[g] = a; p1[g] = b; np0[g] = F::neg(a); dinv[g] = F::sub(b, a);
                 });
             }
@@ -4285,6 +4328,12 @@ private:
                     C = F::mul(C, V);
                     U = F::mul(F::sqr(U), C);
                 }
+                if (sym) {      // W' = W * prod over ALL le layers of (s_b - c2_b)
+                    for (unsigned b = 0; b < le; ++b) {
+                        size_t lsz = m >> b;
+                        U = F::mul(U, F::sub(f[(N >> b) + (j & (lsz - 1)) * stride], crit[2 * b + 1]));
+                    }
+                }
                 w[i] = U;
             });
         }
@@ -4294,6 +4343,16 @@ private:
             const InvSeg segs[6] = {{T.xnn, T.xnn_inv, m}, {hdinv[0], hdinv[0], e - 1}, {hdinv[1], hdinv[1], e - 1}, {hw[0], hwinv[0], e}, {hw[1], hwinv[1], e},
                                     {xq, xqi, l >= 2 ? m : 0}};
             batch_inv_multi(segs, 6, s);
+        }
+        if (sym && e > 1) {     // r = 1/(2uv): sigma(a) = 2 u^2 r, sigma(b) = -sigma(a), 1/(sigma(b) - sigma(a)) = -v^2 r
+            for (int sg = 0; sg < 2; ++sg) {
+                E *p0 = hp0[sg], *p1 = hp1[sg], *np0 = hnp0[sg], *dinv = hdinv[sg];
+                foreach_n(s, e - 1, [=] __device__(size_t g) {
+                    const E u = p0[g], v = p1[g], r = dinv[g];
+                    const E u2 = F::sqr(u), sg0 = F::mul(F::add(u2, u2), r), nsg = F::neg(sg0);
+                    p0[g] = sg0; p1[g] = nsg; np0[g] = nsg; dinv[g] = F::neg(F::mul(F::sqr(v), r));
+                });
+            }
         }
         // merged innermost stage pair (h = 1, stage k = le-1): out_j = a + c_j*(b - a) with
         // c_j = (p_j^target - p_0^source) / (p_1^source - p_0^source), table offset e-2 (kernels.h)
@@ -4492,6 +4551,15 @@ private:
     bool exit4_ = ECFFT_EXIT_CORES == 4 || ab_env("ECFFT_EXIT_FOUR_CORES") != nullptr;
     bool exit3_ = false;
     bool exit_low4_ = ab_env("ECFFT_EXIT_LOW_FOUR_CORES") != nullptr;   // A/B switch: k_exit_low keeps four cores per level in a three-core context
+    // symmetric butterflies: sym_ = this context's stage tables and weights are written in the symmetric basis (the
+    // library's own tree of a 32-byte field, full contexts only); the row and column passes of the full-size regime then run
+    // sym_bfly unless the A/B switch keeps the general kernels on the symmetric tables.  -DECFFT_SYM_BFLY=0 builds the general basis
+    // throughout, ECFFT_NO_SYM_BFLY=1 selects it per context in the hooks build.
+    E* crit_ = nullptr;                                                 // critical points (c1, c2) of the maps, per layer
+    bool sym_ = false;
+    bool sym_off_ = ab_env("ECFFT_NO_SYM_BFLY") != nullptr;
+    bool sym_general_kernels_ = ab_env("ECFFT_SYM_BFLY_GENERAL_KERNELS") != nullptr;
+    bool sym_kernels() const { return sym_ && !sym_general_kernels_; }
 };
 
 }  // namespace ecfft

@@ -828,7 +828,7 @@ int run_blk_selftest(const void* matrix, size_t tn, const void* x, void* out, si
 template <class F>
 int run_selftest(int op, const void* a, const void* b, const void* c, void* out, size_t n, int device) {
     using E = typename F::elem;
-    if (!a || !b || !out || ((op == 0 || op == 4) && !c) || op < 0 || op > 5) return ECFFT_ERR_BAD_ARG;
+    if (!a || !b || !out || ((op == 0 || op == 4) && !c) || op < 0 || op > 6) return ECFFT_ERR_BAD_ARG;
     if (!have_device(device)) return ECFFT_ERR_HIP;
     DeviceGuard dev(device);
     if (!dev.ok) return ECFFT_ERR_HIP;
@@ -846,7 +846,8 @@ int run_selftest(int op, const void* a, const void* b, const void* c, void* out,
             else if (op == 2) r = F::sub(pa[i], pb[i]);
             else if (op == 3) r = F::add(pa[i], pb[i]);
             else if (op == 4) r = F::tmul_add(F::to_table(pa[i]), pb[i], pc[i]);
-            else r = F::tmul(F::to_table(pa[i]), pb[i]);
+            else if (op == 5) r = F::tmul(F::to_table(pa[i]), pb[i]);
+            else r = F::half(pa[i]);
             po[i] = r;
         });
         ok = hipDeviceSynchronize() == hipSuccess && hipMemcpy(out, dout.p, bytes, hipMemcpyDeviceToHost) == hipSuccess;
@@ -1580,6 +1581,10 @@ int ecfft_ctx_exit_cores(const ecfft_ctx* ctx) {
 int ecfft_ctx_exit_low_cores(const ecfft_ctx* ctx) {
     if (!ctx) return 0;
     return ctx->secp ? ctx->secp->exit_low_cores() : ctx->m31 ? ctx->m31->exit_low_cores() : 0;
+}
+int ecfft_ctx_sym_bfly(const ecfft_ctx* ctx) {
+    if (!ctx) return -1;
+    return ctx->secp ? ctx->secp->sym_bfly() : ctx->m31 ? ctx->m31->sym_bfly() : -1;
 }
 
 #endif  // ECFFT_TEST_HOOKS

@@ -23,6 +23,7 @@ struct M31 {
     // representative — min(d, d + p) picks the right one in 3 plain VALU instructions with no compare / VCC
     __host__ __device__ static inline elem sub(elem a, elem b) { uint32_t d = a - b, w = d + P; return d < w ? d : w; }
     __host__ __device__ static inline elem neg(elem a) { return a ? P - a : 0; }
+    __host__ __device__ static inline elem half(elem a) { return (a + ((a & 1u) ? P : 0u)) >> 1; }   // a / 2, a in [0, p]
     __host__ __device__ static inline elem red64(uint64_t t) {  // t < 2^62 + 2^31 (a product of residues plus a residue)
         uint32_t lo = (uint32_t)t & P, hi = (uint32_t)(t >> 31);     // hi <= 2^31, so lo + hi < 2^32
         uint32_t r = lo + hi;

@@ -103,6 +103,49 @@ struct Secp256k1 {
 #endif
     }
     __host__ __device__ static inline elem neg(const elem& a) { return sub(zero(), a); }
+    // a / 2 mod p, input canonical: (a odd ? a + p : a) >> 1 (the sum is even and below 2p, so the quotient is canonical)
+    __host__ __device__ static inline elem half(const elem& a) {
+#if defined(__HIP_DEVICE_COMPILE__) && !defined(ECFFT_NO_ASM_MUL)
+        // 20 instructions: m = -(a & 1), the 9-word sum a + (p & m) (words 2..7 of p & m are m itself), then eight funnel shifts
+        uint32_t r0, r1, r2, r3, r4, r5, r6, r7, m, k;
+        const uint32_t p0 = 0xFFFFFC2Fu, p1 = 0xFFFFFFFEu;
+        asm("v_bfe_i32 %8, %10, 0, 1\n\t"
+            "v_and_b32_e32 %9, %18, %8\n\t"
+            "v_add_co_u32_e32 %0, vcc, %9, %10\n\t"
+            "v_and_b32_e32 %9, %19, %8\n\t"
+            "v_addc_co_u32_e32 %1, vcc, %9, %11, vcc\n\t"
+            "v_addc_co_u32_e32 %2, vcc, %8, %12, vcc\n\t"
+            "v_addc_co_u32_e32 %3, vcc, %8, %13, vcc\n\t"
+            "v_addc_co_u32_e32 %4, vcc, %8, %14, vcc\n\t"
+            "v_addc_co_u32_e32 %5, vcc, %8, %15, vcc\n\t"
+            "v_addc_co_u32_e32 %6, vcc, %8, %16, vcc\n\t"
+            "v_addc_co_u32_e32 %7, vcc, %8, %17, vcc\n\t"
+            "v_cndmask_b32_e64 %9, 0, 1, vcc\n\t"
+            "v_alignbit_b32 %0, %1, %0, 1\n\t"
+            "v_alignbit_b32 %1, %2, %1, 1\n\t"
+            "v_alignbit_b32 %2, %3, %2, 1\n\t"
+            "v_alignbit_b32 %3, %4, %3, 1\n\t"
+            "v_alignbit_b32 %4, %5, %4, 1\n\t"
+            "v_alignbit_b32 %5, %6, %5, 1\n\t"
+            "v_alignbit_b32 %6, %7, %6, 1\n\t"
+            "v_alignbit_b32 %7, %9, %7, 1"
+            : "=&v"(r0), "=&v"(r1), "=&v"(r2), "=&v"(r3), "=&v"(r4), "=&v"(r5), "=&v"(r6), "=&v"(r7), "=&v"(m), "=&v"(k)
+            : "v"(a.l[0]), "v"(a.l[1]), "v"(a.l[2]), "v"(a.l[3]), "v"(a.l[4]), "v"(a.l[5]), "v"(a.l[6]), "v"(a.l[7]), "s"(p0), "s"(p1)
+            : "vcc");
+        elem r; r.l[0] = r0; r.l[1] = r1; r.l[2] = r2; r.l[3] = r3; r.l[4] = r4; r.l[5] = r5; r.l[6] = r6; r.l[7] = r7;
+        return r;
+#else
+        const uint32_t m = 0u - (a.l[0] & 1u);
+        uint32_t s[9]; uint64_t c = 0;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) { c += (uint64_t)a.l[i] + (p_limb(i) & m); s[i] = (uint32_t)c; c >>= 32; }
+        s[8] = (uint32_t)c;
+        elem r;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) r.l[i] = (s[i] >> 1) | (s[i + 1] << 31);
+        return r;
+#endif
+    }
 
     // value = s + carry*2^256 < 2^256 + 2^255 (say); returns it mod p, canonical
     __host__ __device__ static inline elem finish(const uint32_t s[8], uint32_t carry) {

@@ -43,7 +43,30 @@ struct HostTree {  // what FFTree::new derives before from_tree: f layers (heap 
     bool have_gen = false;
     Curve<F> curve{}; Pt<F> off{}, gen{};
     bool leaves_only = false;                 // f holds the leaves (f[n..2n)) only: the layers are computed on the GPU (FFTree::new)
+    // the library's own tree of a 32-byte field (build_secp256k1): its context may write its stage tables in the symmetric basis
+    //  when every map has rational critical points; trees on a caller's curve keep the general basis
+    bool sym_candidate = false;
 };
+
+// The two critical points c1, c2 of the degree-2 map N/D: the roots of N'D - N D' = (n2 d1 - n1 d2) x^2 + 2 (n2 d0 - n0 d2) x + (n1 d0 - n0 d1).
+// true: both are finite, distinct and rational (the discriminant is a non-zero square).  In the coordinate sigma = (x - c1)/(x - c2)
+// the map is a Moebius image of sigma^2, so the two pre-images of a point have opposite sigma.
+// The good isogeny (x - b)^2 / x has c1, c2 = +-b.
+template <class F>
+static inline bool critical_points(const RatMap<F>& m, typename F::elem* c1, typename F::elem* c2) {
+    using E = typename F::elem;
+    const E A = F::sub(F::mul(m.num[2], m.den[1]), F::mul(m.num[1], m.den[2]));
+    const E Bh = F::sub(F::mul(m.num[2], m.den[0]), F::mul(m.num[0], m.den[2]));      // half the linear coefficient
+    const E C = F::sub(F::mul(m.num[1], m.den[0]), F::mul(m.num[0], m.den[1]));
+    if (F::is_zero(A)) return false;                                                   // a critical point at infinity
+    const E disc = F::sub(F::sqr(Bh), F::mul(A, C));                                   // a quarter of the discriminant
+    E r;
+    if (F::is_zero(disc) || !F::sqrt(disc, &r)) return false;
+    const E ai = F::inv(A);
+    *c1 = F::mul(F::sub(r, Bh), ai);
+    *c2 = F::mul(F::sub(F::neg(r), Bh), ai);
+    return true;
+}
 
 template <class F>
 static void batch_inverse(std::vector<typename F::elem>& v) {  // all entries non-zero
@@ -180,6 +203,7 @@ static inline int build_secp256k1(unsigned log_n, HostTree<Secp256k1>& t, bool p
                     F::from_dec("7709812624542158994629670452026922591039826164720902911013234773380889499231"), false};
     const Pt<F> gen{F::from_dec("41293412487153066667050767300223451435019201659857889215769525847559135483332"),
                     F::from_dec("73754924733368840065089190002333366411120578552679996887076912271884749237510"), false};
+    t.sym_candidate = true;
     return build_good_curve<F>(F::from_dec("31172306031375832341232376275243462303334845584808513005362718476441963632613"),
                                F::from_dec("45508371059383884471556188660911097844526467659576498497548207627741160623272"), gen, 36, off, log_n, t, points);
 }

@@ -527,6 +527,20 @@ __device__ __forceinline__ void bfly(typename F::elem& a, typename F::elem& b, c
     else { E o0 = F::tmul_add(t0, b, a), o1 = F::tmul_add(t1, b, a); a = o0; b = o1; }
 }
 
+// SYMMETRIC butterfly: on tables written in the coordinate sigma = (x - c1)/(x - c2) of each layer (c1, c2 the
+// critical points of its map) the two pre-images of a point have p1 = -p0, so np0 = p1 and dinv = -1/(2 p0), and the general forms
+//      recombine (A, B) -> (A + p0 B, A + p1 B)         decompose (a, b) -> q1 = dinv (b - a), q0 = a + np0 q1
+// are  recombine (A, B) -> (A + m, A - m), m = p0 B     decompose (a, b) -> q1 = dinv (b - a), q0 = (a + b)/2
+// ONE multiply and one constant (t = dinv | p0) per pair.  Same residues, canonical: the same bits as the general form.
+// Written with modular subtractions only (18 instructions each for the 32-byte field, where a modular addition is over 40):
+// (a + b)/2 = b - (b - a)/2 with the difference the multiply needs anyway, A - m = A - ((A + m) - A) with the addition inside the multiply.
+template <class F, bool DEC>
+__device__ __forceinline__ void sym_bfly(typename F::elem& a, typename F::elem& b, const typename F::telem& t) {
+    using E = typename F::elem;
+    if (DEC) { const E d = F::sub(b, a); a = F::sub(b, F::half(d)); b = F::tmul(t, d); }
+    else { const E o0 = F::tmul_add(t, b, a); b = F::sub(a, F::sub(o0, a)); a = o0; }
+}
+
 // NS stages on NG groups of 2^NS elements: group g = LDS positions pbase[g] + j*pstride (j < 2^NS).  Stage s' < NS pairs
 // (j, j + 2^s') and reads table entry (e - 2*(tstride << s')) + tbase[g] + (j mod 2^s')*tstride of ta / tb.
 // DEC runs s' = NS-1 .. 0 (large distance first), recombine 0 .. NS-1.  Starts with the barrier that makes the previous
@@ -667,7 +681,7 @@ __device__ __forceinline__ void lds_extend_fast(typename F::elem* a, const typen
 // (downwards for DEC, upwards otherwise), table entry e - 2h + (pair index mod h).  Ends with a barrier.
 // lh_after: pair-distance log of a one-pair-per-thread consumer that follows the last sweep (then the closing barrier is relaxed
 // like the ones between wave-local sweeps), or 99 = the consumer reads other waves' elements.
-template <class F, bool DEC>
+template <class F, bool DEC, bool SYM = false>
 __device__ __forceinline__ void row_stages_pipe(typename F::elem* tile, const typename F::telem* __restrict__ ta, const typename F::telem* __restrict__ tb,
                                                 uint32_t e, int lh_from, int lh_to, uint32_t tid, int lh_after = 99) {
     using E = typename F::elem;
@@ -679,6 +693,22 @@ __device__ __forceinline__ void row_stages_pipe(typename F::elem* tile, const ty
     };
     uint32_t idx, ti;
     geom(lh_from, idx, ti);
+    if constexpr (SYM) {      // symmetric butterflies (sym_bfly below): ONE constant per pair, dinv (DEC) or p0
+        const TE* __restrict__ tk = DEC ? tb : ta;
+        TE nk = ldt(tk, ti);
+#pragma unroll 1
+        for (int lh = lh_from; DEC ? lh >= lh_to : lh <= lh_to; lh += DEC ? -1 : 1) {
+            const TE t = nk;
+            const uint32_t lo = idx, up = idx + (1u << lh);
+            E a = tile[lo], b = tile[up];
+            sym_bfly<F, DEC>(a, b, t);
+            tile[lo] = a; tile[up] = b;
+            if (lh != lh_to) { geom(lh + (DEC ? -1 : 1), idx, ti); nk = ldt(tk, ti); }
+            const int nxt = lh != lh_to ? lh + (DEC ? -1 : 1) : lh_after;
+            if (wave_local_lh(lh) && wave_local_lh(nxt)) wave_local_sync(); else lds_barrier();
+        }
+        return;
+    }
     TE na = ldt(ta, ti), nb = ldt(tb, ti);
 #pragma unroll 1
     for (int lh = lh_from; DEC ? lh >= lh_to : lh <= lh_to; lh += DEC ? -1 : 1) {
@@ -740,7 +770,7 @@ __device__ __forceinline__ void row_regs_rec(typename F::elem* tile, const typen
     tile[idx6] = a; tile[idx6 + 64] = b;
 }
 
-template <class F, int LOG_TILE_CT>      // LOG_TILE_CT > 0: tile size known at compile time (loops unroll); 0: runtime log_tile
+template <class F, int LOG_TILE_CT, bool SYM = false>      // LOG_TILE_CT > 0: tile size known at compile time (loops unroll); 0: runtime log_tile
 __global__ __launch_bounds__(kBlockRow, ECFFT_MIN_WAVES) void k_stages_lds(IoDesc<F> io,
                                                            const typename F::telem* __restrict__ np0,
                                                            const typename F::telem* __restrict__ dinv,
@@ -752,6 +782,7 @@ __global__ __launch_bounds__(kBlockRow, ECFFT_MIN_WAVES) void k_stages_lds(IoDes
                                                            const uint8_t* __restrict__ blkA, const unsigned long long* __restrict__ blkK) {
     // blkA / blkK != nullptr (32-byte field, tiles of whole 1024-element sub-tiles, >= 4 in-tile stages): the stages with pair
     // distance <= 8 run on the int8 matrix cores as one 16 x 16 map per block (mfma_blk16.h) instead of 7 VALU sweeps
+    // SYM (symmetric contexts of a 32-byte field): the pipelined sweeps and the fused sweeps at distance 16 run sym_bfly
     using E = typename F::elem;
     extern __shared__ __attribute__((aligned(16))) unsigned char ecfft_smem[];
     E* tile = reinterpret_cast<E*>(ecfft_smem);
@@ -801,7 +832,7 @@ __global__ __launch_bounds__(kBlockRow, ECFFT_MIN_WAVES) void k_stages_lds(IoDes
     // registers across the sweeps at distance 64 / 32 / 16 (ECFFT_ROW_REGS): the pipelined sweeps stop above distance 64
     const bool regs = ECFFT_ROW_REGS && sizeof(E) == 32 && pipe && fuse16 && log_e - k_first >= 7;
     if (pipe) {
-        if constexpr (sizeof(E) == 32) row_stages_pipe<F, true>(tile, np0, dinv, (uint32_t)e, (int)(log_e - k_first) - 1, regs ? 7 : (int)(log_e - (k_dec_end - (fuse16 ? 1u : 0u))), tid, fuse16 && !regs ? 4 : 99);
+        if constexpr (sizeof(E) == 32) row_stages_pipe<F, true, SYM>(tile, np0, dinv, (uint32_t)e, (int)(log_e - k_first) - 1, regs ? 7 : (int)(log_e - (k_dec_end - (fuse16 ? 1u : 0u))), tid, fuse16 && !regs ? 4 : 99);
     } else
     for (uint32_t k = k_first; k < k_dec_end - (fuse16 ? 1u : 0u); ++k) {
         const uint32_t lh = log_e - k - 1, h = 1u << lh;
@@ -816,8 +847,9 @@ __global__ __launch_bounds__(kBlockRow, ECFFT_MIN_WAVES) void k_stages_lds(IoDes
                 E a, b;
                 if constexpr (ECFFT_ROW_REGS && sizeof(E) == 32) { if (regs) row_regs_dec<F>(tile, np0, dinv, (uint32_t)e, tid, a, b); else { a = tile[idx]; b = tile[idx + 16]; } }
                 else { a = tile[idx]; b = tile[idx + 16]; }
-                const E q1 = F::tmul(ldt(dinv + (e - 32), i), F::sub(b, a));
-                const E q0 = F::tmul_add(ldt(np0 + (e - 32), i), q1, a);
+                E q0, q1;
+                if constexpr (SYM) { q0 = a; q1 = b; sym_bfly<F, true>(q0, q1, ldt(dinv + (e - 32), i)); }
+                else { q1 = F::tmul(ldt(dinv + (e - 32), i), F::sub(b, a)); q0 = F::tmul_add(ldt(np0 + (e - 32), i), q1, a); }
                 __builtin_amdgcn_sched_barrier(0);
                 pre = Blk16::prefetch(blkA, tid);                        // after the multiplies (they need the registers), before the barriers
                 __builtin_amdgcn_sched_barrier(0);
@@ -840,7 +872,9 @@ __global__ __launch_bounds__(kBlockRow, ECFFT_MIN_WAVES) void k_stages_lds(IoDes
             if (fuse16) {                                                // recombine sweep at distance 16, reading the swizzled results
                 const uint32_t i = tid & 15u, idx = ((tid >> 4) << 5) + i;
                 const E a = Blk16::load_swizzled(tile, idx), b = Blk16::load_swizzled(tile, idx + 16);
-                const E o0 = F::tmul_add(ldt(p0 + (e - 32), i), b, a), o1 = F::tmul_add(ldt(p1 + (e - 32), i), b, a);
+                E o0, o1;
+                if constexpr (SYM) { o0 = a; o1 = b; sym_bfly<F, false>(o0, o1, ldt(p0 + (e - 32), i)); }
+                else { o0 = F::tmul_add(ldt(p0 + (e - 32), i), b, a); o1 = F::tmul_add(ldt(p1 + (e - 32), i), b, a); }
                 // the swizzled positions read above and the plain ones written below lie in the wave's own span; so do the pairs of the
                 // recombine sweep at distance 32 that follows in the pipelined form
                 bool done_regs = false;
@@ -883,7 +917,7 @@ __global__ __launch_bounds__(kBlockRow, ECFFT_MIN_WAVES) void k_stages_lds(IoDes
         __syncthreads();
     }
     if (pipe) {
-        if constexpr (sizeof(E) == 32) row_stages_pipe<F, false>(tile, p0, p1, (uint32_t)e, regs ? 7 : (int)(log_e - (k_dec_end - (fuse16 ? 1u : 0u))), (int)(log_e - k_first) - 1, tid);
+        if constexpr (sizeof(E) == 32) row_stages_pipe<F, false, SYM>(tile, p0, p1, (uint32_t)e, regs ? 7 : (int)(log_e - (k_dec_end - (fuse16 ? 1u : 0u))), (int)(log_e - k_first) - 1, tid);
     } else
     for (uint32_t k = k_dec_end - (fuse16 ? 1u : 0u); k-- > k_first;) {
         const uint32_t lh = log_e - k - 1, h = 1u << lh;
@@ -1051,7 +1085,7 @@ __device__ __forceinline__ void col_stage_sweep(typename F::elem* tile, const ty
 // multiplies of sweep s, when the registers are free again, and fly across the LDS-only barrier and the next sweep's LDS reads.
 // One pair per thread is pipelined (pair index tid); further pairs of the thread (two vectors per workgroup) load theirs in
 // place as before.  Same arithmetic, same order: bit-identical.  Ends with a barrier.
-template <class F, bool DEC, int BLK>
+template <class F, bool DEC, int BLK, bool SYM = false>
 __device__ __forceinline__ void col_stages_pipe(typename F::elem* tile, const typename F::telem* __restrict__ ta, const typename F::telem* __restrict__ tb,
                                                 uint32_t R, uint32_t log_c, uint32_t log_hs, size_t c0, size_t e, uint32_t tid, uint32_t npairs) {
     using E = typename F::elem;
@@ -1066,6 +1100,29 @@ __device__ __forceinline__ void col_stages_pipe(typename F::elem* tile, const ty
     };
     uint32_t lo, up, ti;
     geom(0, tid, lo, up, ti);
+    if constexpr (SYM) {      // symmetric butterflies: one constant per pair, dinv (DEC) or p0
+        const TE* __restrict__ tk = DEC ? tb : ta;
+        TE nk = ldt(tk, ti);
+#pragma unroll 1
+        for (uint32_t st = 0; st < R; ++st) {
+            const TE t = nk;
+            {
+                E a = tile[lo], b = tile[up];
+                sym_bfly<F, DEC>(a, b, t);
+                tile[lo] = a; tile[up] = b;
+            }
+            for (uint32_t g = tid + BLK; g < npairs; g += BLK) {
+                uint32_t l2, u2, i2; geom(st, g, l2, u2, i2);
+                E a = tile[l2], b = tile[u2];
+                sym_bfly<F, DEC>(a, b, ldt(tk, i2));
+                tile[l2] = a; tile[u2] = b;
+            }
+            if (st + 1 < R) { geom(st + 1, tid, lo, up, ti); nk = ldt(tk, ti); }
+            const uint32_t sft = DEC ? R - 1 - st : st, sft_n = DEC ? sft - 1 : sft + 1;
+            if (st + 1 < R && wave_local_lh((int)(sft + log_c)) && wave_local_lh((int)(sft_n + log_c))) wave_local_sync(); else lds_barrier();
+        }
+        return;
+    }
     TE na = ldt(ta, ti), nb = ldt(tb, ti);
 #pragma unroll 1
     for (uint32_t st = 0; st < R; ++st) {
@@ -1094,7 +1151,7 @@ __device__ __forceinline__ void col_stages_pipe(typename F::elem* tile, const ty
 // ((row mod 2^s) << log_hs) + c0 + column, table base e - 2*(hs << s)).  DECOMPOSE runs s = R-1 .. 0, recombine 0 .. R-1.
 // 4-byte fields with exactly 16 elements per thread use the register-resident radix steps (up to 3 stages per LDS round
 // trip, table constants requested before the barrier); everything else sweeps one stage at a time.  Ends with a barrier.
-template <class F, bool DEC>
+template <class F, bool DEC, bool SYM = false>      // SYM: the pipelined sweeps of a 32-byte field run sym_bfly (the other forms stay general)
 __device__ __forceinline__ void col_stages(typename F::elem* tile, const typename F::telem* __restrict__ ta, const typename F::telem* __restrict__ tb,
                                            uint32_t R, uint32_t log_c, uint32_t log_hs, size_t c0, size_t e, uint32_t tid, uint32_t halves = 1,
                                            const typename F::telem* __restrict__ tc = nullptr) {
@@ -1132,7 +1189,7 @@ __device__ __forceinline__ void col_stages(typename F::elem* tile, const typenam
     if constexpr (sizeof(E) == 32 && ECFFT_COL_PIPE) {
         const uint32_t npairs = (halves * T) >> 1;
         if (npairs >= (uint32_t)kBlockLds && npairs % kBlockLds == 0 && (e >> 32) == 0) {     // at least one pair per thread (not the pair-split small tiles)
-            col_stages_pipe<F, DEC, kBlockLds>(tile, ta, tb, R, log_c, log_hs, c0, e, tid, npairs);
+            col_stages_pipe<F, DEC, kBlockLds, SYM>(tile, ta, tb, R, log_c, log_hs, c0, e, tid, npairs);
             return;
         }
     }
@@ -1152,7 +1209,7 @@ __device__ __forceinline__ void col_stages(typename F::elem* tile, const typenam
 // ka -> kb (large distance first), RECOMBINE kb -> ka.  Table index of the pair (row r, column c) at
 // stage k: (r mod d)*hs + c_global with d = 2^(kb-k).
 // ---------------------------------------------------------------------------------------------
-template <class F, bool DECOMPOSE, int LOG_TILE_CT>     // LOG_TILE_CT > 0: log2(tile elements) known at compile time
+template <class F, bool DECOMPOSE, int LOG_TILE_CT, bool SYM = false>     // LOG_TILE_CT > 0: log2(tile elements) known at compile time
 __global__ __launch_bounds__(kBlockLds, ECFFT_MIN_WAVES) void k_stages_col(IoDesc<F> io,
                                                            const typename F::telem* __restrict__ ta,   // np0 | p0
                                                            const typename F::telem* __restrict__ tb,   // dinv | p1
@@ -1205,7 +1262,7 @@ __global__ __launch_bounds__(kBlockLds, ECFFT_MIN_WAVES) void k_stages_col(IoDes
 #endif
     }
     __syncthreads();
-    col_stages<F, DECOMPOSE>(tile, ta, tb, R, log_c, log_hs, c0, e, tid, 1, DECOMPOSE ? tc : nullptr);
+    col_stages<F, DECOMPOSE, SYM>(tile, ta, tb, R, log_c, log_hs, c0, e, tid, 1, DECOMPOSE ? tc : nullptr);
 #ifndef ECFFT_EXP_NO_TILE_IO
 #pragma unroll
     for (uint32_t j = tid; j < T; j += kBlockLds) {
@@ -1222,7 +1279,7 @@ __global__ __launch_bounds__(kBlockLds, ECFFT_MIN_WAVES) void k_stages_col(IoDes
 // load, R recombine stages, io_mid (A's store operator + B's load operator), R decompose stages, store — one launch and
 // one HBM round trip instead of two.
 // ---------------------------------------------------------------------------------------------
-template <class F>
+template <class F, bool SYM = false>
 __global__ __launch_bounds__(kBlockLds, ECFFT_MIN_WAVES) void k_stages_col_mid(IoDesc<F> io,
                                                                const typename F::telem* __restrict__ p0, const typename F::telem* __restrict__ p1,
                                                                const typename F::telem* __restrict__ np0, const typename F::telem* __restrict__ dinv,
@@ -1270,7 +1327,7 @@ __global__ __launch_bounds__(kBlockLds, ECFFT_MIN_WAVES) void k_stages_col_mid(I
     }
 #endif
     __syncthreads();
-    col_stages<F, false>(tile, p0, p1, R, log_c, log_hs, c0, e, tid);
+    col_stages<F, false, SYM>(tile, p0, p1, R, log_c, log_hs, c0, e, tid);
 #ifndef ECFFT_EXP_NO_MID
     for (uint32_t j = tid; j < T; j += kBlockLds) {
         uint32_t r = j >> log_c, cc = j & (C - 1);
@@ -1278,7 +1335,7 @@ __global__ __launch_bounds__(kBlockLds, ECFFT_MIN_WAVES) void k_stages_col_mid(I
     }
 #endif
     __syncthreads();
-    col_stages<F, true>(tile, np0, dinv, R, log_c, log_hs, c0, e, tid, 1, c0t);
+    col_stages<F, true, SYM>(tile, np0, dinv, R, log_c, log_hs, c0, e, tid, 1, c0t);
 #ifndef ECFFT_EXP_NO_TILE_IO
     for (uint32_t j = tid; j < T; j += kBlockLds) {
         uint32_t r = j >> log_c, cc = j & (C - 1);
@@ -1296,7 +1353,7 @@ __global__ __launch_bounds__(kBlockLds, ECFFT_MIN_WAVES) void k_stages_col_mid(I
 // straight to the level's output — the separate combine launch (3n element moves for 1.5n multiplies, HBM-bound) and the
 // EXTEND's write + re-read of its result are gone.
 // ---------------------------------------------------------------------------------------------
-template <class F>
+template <class F, bool SYM = false>
 __global__ __launch_bounds__(kBlockLds, ECFFT_MIN_WAVES) void k_stages_col_enter(const typename F::elem* __restrict__ work, const typename F::elem* __restrict__ src,
                                                                  typename F::elem* __restrict__ dst,
                                                                  const typename F::telem* __restrict__ p0, const typename F::telem* __restrict__ p1,
@@ -1354,7 +1411,7 @@ __global__ __launch_bounds__(kBlockLds, ECFFT_MIN_WAVES) void k_stages_col_enter
 #endif
     __syncthreads();
     // the U rows and the V rows are two independent column tiles that read the same table entries
-    col_stages<F, false>(tile, p0, p1, R, log_c, log_hs, c0, e, tid, 2);
+    col_stages<F, false, SYM>(tile, p0, p1, R, log_c, log_hs, c0, e, tid, 2);
 #ifdef ECFFT_EXP_NO_TILE_IO
     return;
 #endif

@@ -54,7 +54,7 @@ SCHOOF_MAX_L = 199
 ORDER_BYTES = 40
 
 # include/ecfft_hip_hooks.h: only in a build with -DECFFT_TEST_HOOKS (tests/hooks/libecfft_hip_hooks.so), never in the shipped library
-HOOK_EXPORTS = ['ecfft_selftest_field', 'ecfft_selfcheck_pointwise_z', 'ecfft_test_fail_next_collective', 'ecfft_selftest_blk16', 'ecfft_selftest_blk16_small', 'ecfft_test_fail_build_rank', 'ecfft_comm_init_projection', 'ecfft_selftest_blk32', 'ecfft_ctx_low_map', 'ecfft_curve_search_stats', 'ecfft_test_ddf_iterate', 'ecfft_test_schoof_pi2', 'ecfft_ctx_exit_cores', 'ecfft_ctx_exit_low_cores']
+HOOK_EXPORTS = ['ecfft_selftest_field', 'ecfft_selfcheck_pointwise_z', 'ecfft_test_fail_next_collective', 'ecfft_selftest_blk16', 'ecfft_selftest_blk16_small', 'ecfft_test_fail_build_rank', 'ecfft_comm_init_projection', 'ecfft_selftest_blk32', 'ecfft_ctx_low_map', 'ecfft_curve_search_stats', 'ecfft_test_ddf_iterate', 'ecfft_test_schoof_pi2', 'ecfft_ctx_exit_cores', 'ecfft_ctx_exit_low_cores', 'ecfft_ctx_sym_bfly']
 
 EXCHANGE_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_void_p),
                                ctypes.POINTER(ctypes.c_size_t), ctypes.c_int, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_void_p),
@@ -170,6 +170,8 @@ def _bind(L):
         L.ecfft_ctx_low_map.restype, L.ecfft_ctx_low_map.argtypes = ci, [vp, ci]
         L.ecfft_ctx_exit_cores.restype, L.ecfft_ctx_exit_cores.argtypes = ci, [vp]
         L.ecfft_ctx_exit_low_cores.restype, L.ecfft_ctx_exit_low_cores.argtypes = ci, [vp]
+        if hasattr(L, "ecfft_ctx_sym_bfly"):
+            L.ecfft_ctx_sym_bfly.restype, L.ecfft_ctx_sym_bfly.argtypes = ci, [vp]
         L.ecfft_curve_search_stats.restype, L.ecfft_curve_search_stats.argtypes = ci, [ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_double), sz, ci]
         L.ecfft_test_ddf_iterate.restype, L.ecfft_test_ddf_iterate.argtypes = ci, [ci]
         L.ecfft_test_schoof_pi2.restype, L.ecfft_test_schoof_pi2.argtypes = ci, [ci]
@@ -286,7 +288,7 @@ class Field:
         return self._new_tree(lambda out: lib().ecfft_build_exit_shard_opts(self.id, n, device, comm._h, 1 if min_memory else 0, out), device)
 
     def selftest(self, op, a, b, c=None, device=0):
-        """device field arithmetic on raw residues (test hook): op 0 a*b+c, 1 a*b, 2 a-b, 3 a+b, 4/5 the kernels' table multiply a*b+c / a*b"""
+        """device field arithmetic on raw residues (test hook): op 0 a*b+c, 1 a*b, 2 a-b, 3 a+b, 6 a/2, 4/5 the kernels' table multiply a*b+c / a*b"""
         a = np.ascontiguousarray(a, self.dtype); b = np.ascontiguousarray(b, self.dtype)
         cc = None if c is None else np.ascontiguousarray(c, self.dtype)
         out = np.empty_like(a)
@@ -1085,6 +1087,10 @@ class FFTree:
     def exit_low_cores(self):
         """3 / 4: EXTEND cores per level of the fused low-level EXIT kernel's loop (hooks build)"""
         return self._L.ecfft_ctx_exit_low_cores(self._h)
+
+    def sym_bfly(self):
+        """0 / 1 / 2: general basis, symmetric basis with one-multiply butterflies, symmetric basis under the general kernels (hooks build)"""
+        return self._L.ecfft_ctx_sym_bfly(self._h)
 
     def profile(self, on):
         _check(self._L.ecfft_profile_enable(self._h, int(on)))

@@ -6,7 +6,7 @@
  * the tests and the measurement tools load explicitly.  The same build also reads the A/B switches of the tuning experiments from
  * the environment (ECFFT_NO_MFMA, ECFFT_NO_LOW16, ECFFT_LOW32, ECFFT_NO_ROW256, ECFFT_NO_COL256, ECFFT_NO_SMALL_TILES,
  * ECFFT_SMALL_TILES_MAX, ECFFT_SMALL_LOW_MAX, ECFFT_SMALL_MIN_LOGC, ECFFT_NO_FULL_CYCLIC, ECFFT_SPLIT_GATHER_MAX_LOG,
- * ECFFT_SPLIT_Q2_SPLIT, ECFFT_EXIT_FOUR_CORES, ECFFT_EXIT_LOW_FOUR_CORES); the shipped library reads no environment variable at all. */
+ * ECFFT_SPLIT_Q2_SPLIT, ECFFT_EXIT_FOUR_CORES, ECFFT_EXIT_LOW_FOUR_CORES, ECFFT_NO_SYM_BFLY, ECFFT_SYM_BFLY_GENERAL_KERNELS); the shipped library reads no environment variable at all. */
 #ifndef ECFFT_HIP_HOOKS_H
 #define ECFFT_HIP_HOOKS_H
 #include "ecfft_hip.h"
@@ -32,7 +32,7 @@ int ecfft_test_fail_next_collective(ecfft_ctx* ctx);
 int ecfft_test_fail_build_rank(int rank);
 
 /* Test hook: the DEVICE field arithmetic on raw residues (plain integers < p, no Montgomery interpretation), host buffers.
- * op 0: out = a*b + c mod p   1: a*b   2: a - b   3: a + b   4 / 5: a*b + c / a*b with a taken as a TABLE constant, i.e. the
+ * op 0: out = a*b + c mod p   1: a*b   2: a - b   3: a + b   6: a / 2 (b ignored)   4 / 5: a*b + c / a*b with a taken as a TABLE constant, i.e. the
  * multiply of the butterfly kernels, result in the kernels' internal (lazy) range, not canonicalised.  Lets the tests drive the hand-written gfx950 multiply with
  * directed operands (results next to p and 2^256, carry-out of the second fold) that random data never reaches. */
 int ecfft_selftest_field(int field, int op, const void* a, const void* b, const void* c, void* out, size_t n, int device);
@@ -59,6 +59,11 @@ int ecfft_ctx_exit_cores(const ecfft_ctx* ctx);
 /* ... and per level of the loop of the fused low-level EXIT kernel (k_exit_low): the context's form, or 4 in a three-core context
  * that keeps the four-core kernel (A/B: ECFFT_EXIT_LOW_FOUR_CORES, -DECFFT_EXIT_LOW_CORES=4) */
 int ecfft_ctx_exit_low_cores(const ecfft_ctx* ctx);
+/* test / measurement hook: the butterfly form of the context.  0 = general basis, two multiplies per butterfly
+ * (shard contexts, M31, trees on a caller's curve, A/B: ECFFT_NO_SYM_BFLY, -DECFFT_SYM_BFLY=0)   1 = symmetric basis, one multiply per
+ * butterfly in the full-size row and column passes (the library's own secp256k1 tree)   2 = symmetric basis under the general
+ * kernels (A/B: ECFFT_SYM_BFLY_GENERAL_KERNELS)   -1 = no context */
+int ecfft_ctx_sym_bfly(const ecfft_ctx* ctx);
 /* measurement hook (tools/findcurve_time.py): the number of queue entries every stage of the curve search has read since the last
  * reset, summed over batches: [0] bb square, [1] discriminant, [2] point of order 4, [3 + r] halving round r; and the host seconds
  * spent around each stage's launch and the read of its queue length, which waits for it.  Copies up to `cap` entries into each
