@@ -2392,160 +2392,242 @@ private:
         }
         return ok;
     }
-    // p and (p - 1) / 2 of the field as little-endian bytes (p is odd: (p - 1) / 2 is p >> 1); returns their bit counts
-    static void roots_exponents(uint8_t* ep, uint32_t* nbits_p, uint8_t* eh, uint32_t* nbits_h) {
+    // What a factorisation call (find_roots, squarefree, distinct_degree, equal_degree, Schoof) shares between its rows: p and
+    // (p - 1) / 2 of the field as little-endian bytes (p is odd: (p - 1) / 2 is p >> 1) with their bit counts, the same 64 bytes on
+    // the device (p first), and the flag its kernels raise (the attempt cap; Schoof: a sum the group law excludes).
+    struct FactorCall {
+        uint8_t e[64]; uint32_t nbits_p = 0, nbits_h = 0; const uint8_t* dexp = nullptr; int* flag = nullptr;
+        const uint8_t* ep() const { return e; }
+        const uint8_t* eh() const { return e + 32; }
+    };
+    // the host half of a FactorCall: the bytes and bit counts
+    static FactorCall factor_exponents() {
+        FactorCall fc;
         uint32_t w[8] = {0, 0, 0, 0, 0, 0, 0, 0};
         int nw = 1;
         if constexpr (sizeof(E) == 4) w[0] = F::P;
         else { nw = 8; for (int i = 0; i < 8; ++i) w[i] = F::p_limb(i); }
-        for (int i = 0; i < 32; ++i) { ep[i] = 0; eh[i] = 0; }
+        for (int i = 0; i < 64; ++i) fc.e[i] = 0;
         for (int i = 0; i < nw; ++i) {
             const uint32_t hi = i + 1 < nw ? w[i + 1] : 0u, half = (w[i] >> 1) | (hi << 31);
-            for (int k = 0; k < 4; ++k) { ep[4 * i + k] = (uint8_t)(w[i] >> (8 * k)); eh[4 * i + k] = (uint8_t)(half >> (8 * k)); }
+            for (int k = 0; k < 4; ++k) { fc.e[4 * i + k] = (uint8_t)(w[i] >> (8 * k)); fc.e[32 + 4 * i + k] = (uint8_t)(half >> (8 * k)); }
         }
         auto bits = [](const uint8_t* e) { uint32_t n = 256; while (n && !((e[(n - 1) >> 3] >> ((n - 1) & 7)) & 1)) --n; return n; };
-        *nbits_p = bits(ep); *nbits_h = bits(eh);
+        fc.nbits_p = bits(fc.ep()); fc.nbits_h = bits(fc.eh());
+        return fc;
     }
-    // what a call of poly_find_roots shares between its polynomials: the exponents on the device and the flag of the attempt cap
-    struct RootsCall { const uint8_t* dexp = nullptr; uint8_t ep[32], eh[32]; uint32_t nbits_p = 0, nbits_h = 0; int* flag = nullptr; };
-    // one launch of k_roots_small over nblk rows or descriptors
-    void roots_small_launch(const RootsCall& rc, const E* in, size_t ldin, size_t nin, E* out, size_t ldout, const uint32_t* desc, long long* n_out,
-                            bool frob, uint32_t c0, size_t nblk, double coeffs, hipStream_t s) {
+    // the whole of it: the bytes uploaded once and, for the calls whose kernels raise one, a fresh flag
+    bool factor_call_init(FactorCall* fc, bool with_flag, hipStream_t s) {
+        *fc = factor_exponents();
+        uint8_t* dexp = temp_as<uint8_t>(64);
+        fc->dexp = dexp;
+        const bool ok = hipMemcpyAsync(dexp, fc->e, 64, hipMemcpyHostToDevice, s) == hipSuccess && hipStreamSynchronize(s) == hipSuccess;
+        if (with_flag) fc->flag = new_flag(s);
+        return ok;
+    }
+    // fm (d + 1 elements) = f / f[d], the row made monic: lc = R / (stored leading coefficient) is the PLAIN inverse of the leading
+    // coefficient (plain x crate stays crate), fm = f lc below a leading R
+    void monic_row(const E* f, size_t d, E* fm, hipStream_t s) {
+        const E r1 = crate_one();
+        E* lc = temp(1);
+        foreach_n(s, 1, [=] __device__(size_t) { lc[0] = F::canon(F::mul(F::inv(F::canon(f[d])), r1)); });
+        foreach_n(s, d + 1, [=] __device__(size_t j) { E v = r1; if (j < d) v = F::canon(F::mul(f[j], lc[0])); fm[j] = v; });
+    }
+    // One launch of the leaf kernel of the splitting calls over nblk rows or descriptors: k_roots_small (d == 0; frob: its Frobenius
+    // flag) or k_edf_small for factors of degree d.  The latter's workspace of the h_i, d - 1 rows of the longest degree a workgroup
+    // can meet (nin - 1, or K for descriptors), is shared by the chunks, which run one after another on the stream.
+    void split_small_launch(const FactorCall& fc, const E* in, size_t ldin, size_t nin, size_t d, E* out, size_t ldout, const uint32_t* desc,
+                            long long* n_out, bool frob, uint32_t c0, size_t nblk, double coeffs, hipStream_t s) {
+        constexpr size_t K = kRootsSmall;
+        static_assert(kEdfSmall == kRootsSmall, "one launch shape and one workspace rule for both leaf kernels");
         const E r1 = crate_one();
         const TE rinv = rinv_table();
+        const size_t chunk = nblk < ((size_t)1 << 16) ? nblk : (size_t)1 << 16;
+        const size_t nmax = desc || nin > K ? K : (nin ? nin - 1 : 0);
+        const size_t ldws = d && 2 * d <= nmax ? (d - 1) * nmax : 0;           // a row that splits has 2 d <= its degree
+        E* ws = ldws ? temp(chunk * ldws) : nullptr;
         for_chunks(nblk, [&](size_t b0, size_t nb) {
-            ECFFT_LAUNCH(KC_POINTWISE, sizeof(E) * coeffs * (double)nb / (double)nblk + 64.0, (k_roots_small<F, (int)kRootsSmall>), dim3((unsigned)nb),
-                         dim3((unsigned)kRootsSmall), 0, s, desc ? in : in + b0 * ldin, ldin, (uint32_t)nin, desc ? out : out + b0 * ldout, ldout,
-                         desc ? desc + 3 * b0 : (const uint32_t*)nullptr, n_out ? n_out + b0 : (long long*)nullptr, frob ? 1u : 0u, c0,
-                         rc.dexp, rc.nbits_p, rc.dexp + 32, rc.nbits_h, rinv, r1, rc.flag);
+            const double bytes = sizeof(E) * coeffs * (double)nb / (double)nblk + 64.0;
+            const E* ib = desc ? in : in + b0 * ldin;
+            E* ob = desc ? out : out + b0 * ldout;
+            const uint32_t* db = desc ? desc + 3 * b0 : (const uint32_t*)nullptr;
+            long long* nb_out = n_out ? n_out + b0 : (long long*)nullptr;
+            if (!d)
+                ECFFT_LAUNCH(KC_POINTWISE, bytes, (k_roots_small<F, (int)K>), dim3((unsigned)nb), dim3((unsigned)K), 0, s, ib, ldin, (uint32_t)nin, ob,
+                             ldout, db, nb_out, frob ? 1u : 0u, c0, fc.dexp, fc.nbits_p, fc.dexp + 32, fc.nbits_h, rinv, r1, fc.flag);
+            else
+                ECFFT_LAUNCH(KC_POINTWISE, bytes, (k_edf_small<F, (int)K>), dim3((unsigned)nb), dim3((unsigned)K), 0, s, ib, ldin, (uint32_t)nin,
+                             (uint32_t)d, ob, ldout, db, nb_out, ws, ldws, c0, fc.dexp, fc.nbits_p, fc.dexp + 32, fc.nbits_h, rinv, r1, fc.flag);
         });
     }
-    void roots_rank_launch(E* dst, size_t ldd, const E* src, size_t lds, const long long* n_dev, long long n_fixed, size_t rows, hipStream_t s) {
+    // The canonical order: src (rows x lds, roots (d == 0) or factors of d coefficients, in any order) -> dst (rows x ldd).
+    // k_roots_rank converts as it goes; k_edf_rank reads the standard form of src, converted once per element before it.
+    void split_rank_launch(E* dst, size_t ldd, const E* src, size_t lds, size_t d, const long long* n_dev, long long n_fixed, size_t rows,
+                           hipStream_t s) {
         if (!ldd) return;
+        const TE rinv = rinv_table();
+        E* sf = d ? temp(rows * lds) : nullptr;
+        if (d) foreach_n(s, rows * lds, [=] __device__(size_t i) {
+            E v = F::canon(src[i]);
+            if constexpr (sizeof(E) == 32) v = F::canon(F::tmul(rinv, v));
+            sf[i] = v;
+        });
         for (size_t r0 = 0; r0 < rows; r0 += 32768) {
             const size_t nr = rows - r0 < 32768 ? rows - r0 : 32768;
-            ECFFT_LAUNCH(KC_POINTWISE, sizeof(E) * 2.0 * (double)nr * (double)ldd, k_roots_rank<F>, dim3(nblocks(ldd), (unsigned)nr), dim3(kBlock), 0, s,
-                         dst + r0 * ldd, ldd, src + r0 * lds, lds, n_dev ? n_dev + r0 : (const long long*)nullptr, n_fixed, rinv_table());
+            const long long* nd = n_dev ? n_dev + r0 : (const long long*)nullptr;
+            if (!d)
+                ECFFT_LAUNCH(KC_POINTWISE, sizeof(E) * 2.0 * (double)nr * (double)ldd, k_roots_rank<F>, dim3(nblocks(ldd), (unsigned)nr), dim3(kBlock), 0, s,
+                             dst + r0 * ldd, ldd, src + r0 * lds, lds, nd, n_fixed, rinv);
+            else
+                ECFFT_LAUNCH(KC_POINTWISE, sizeof(E) * 3.0 * (double)nr * (double)ldd, k_edf_rank<F>, dim3(nblocks(ldd), (unsigned)nr), dim3(kBlock), 0, s,
+                             dst + r0 * ldd, ldd, src + r0 * lds, (const E*)sf + r0 * lds, lds, (uint32_t)d, nd, n_fixed);
         }
     }
-    // The roots of ONE polynomial of nf > kRootsSmall + 1 coefficients (untrimmed, crate form) into roots (nf - 1, sorted, zero-padded).
-    //   g = gcd(f, x^p - x mod f) on roots_pow_body (base x) and gcd_pair; then rounds with one shift c = 1, 2, ... for all pending
-    //   factors of degree > kRootsSmall: grouped by N = next_pow2(2e - 1), padded inside a group to its largest degree D as x^(D-e) h
-    //   (h divides it, so gcd(h, w - 1) is unchanged), ONE roots_pow_body per group, then per factor u = gcd_pair(h, w - 1) and
-    //   v = h / u (divrem_body).  Factors of degree <= kRootsSmall go to the leaf buffer, finished by ONE launch of k_roots_small.
-    bool roots_one_large(const RootsCall& rc, const E* f, size_t nf, E* roots, long long* n, hipStream_t s) {
+    // A short polynomial in a long row (true length la <= kRootsSmall + 1 of nf): the small regime on its true length, ordered
+    // into out; *n as the kernel reports it.  uns: nf - 1 elements of work.
+    bool split_short_row(const FactorCall& fc, const E* f, size_t nf, size_t la, size_t d, E* uns, E* out, long long* n, hipStream_t s) {
+        long long* dn = temp_as<long long>(1);
+        split_small_launch(fc, f, nf, la ? la : 1, d, uns, nf - 1, nullptr, dn, d == 0, 1u, 1, (double)(la + kRootsSmall), s);
+        split_rank_launch(out, nf - 1, uns, nf - 1, d, dn, 0, 1, s);
+        return hipMemcpyAsync(n, dn, sizeof(long long), hipMemcpyDeviceToHost, s) == hipSuccess && hipStreamSynchronize(s) == hipSuccess;
+    }
+    // The splitting rounds of roots_one_large and edf_one_large: g, monic of degree e0 > 0 with its leading 1, is a
+    // squarefree product of irreducibles of one degree (1 for the roots); its nfac factors go to out (ldo elements), ordered.
+    //   Pending factors (degree > kRootsSmall) are packed with their leading 1 in two alternating buffers, the leaves (degree <=
+    //   kRootsSmall) likewise in a third with a descriptor (input offset, length, output offset) each; a piece of degree dout > 0
+    //   goes straight to the output (dout = 0: none does; roots end in the leaf kernel), and a gcd whose degree dout does not
+    //   divide is outside the precondition.
+    //   Rounds with one shift c = 1, 2, ... for all pending factors, after round_start(c): the factors are grouped by N =
+    //   powmod_leaves(e + 1), the first pending one's group first, and padded inside a group to its largest degree D as the rows
+    //   x^(D-e) h of M (h divides its row, so gcd(h, w - 1) is unchanged; one gather kernel on an uploaded (offset, shift) descriptor
+    //   per row); group_pow(c, M, D, hs, W) takes ONE modular power per group, W (cnt x D) = the splitting element to
+    //   (p - 1) / 2 modulo the rows of M, hs = the group's factors; then per factor u = gcd_pair(h, w - 1) and
+    //   v = h / u (divrem_body), kept as u then v.  A factor that no shift has split in 64 consecutive rounds fails the call: the
+    //   attempt cap of the leaf kernels, for the same reason.
+    //   Temporaries go back to the pool per factor, per group and per round.  The leaves are finished by ONE launch of the leaf
+    //   kernel from the next shift on, then the rank kernel orders the row.  uns: ldo elements of work.
+    struct Fac { const E* p; size_t e; uint32_t fails; };     // a pending factor: where it lies, its degree, the shifts that failed
+    template <class RoundStart, class GroupPow>
+    bool split_rounds(const FactorCall& fc, const E* g, size_t e0, size_t dout, E* uns, E* out, size_t ldo, size_t nfac, RoundStart&& round_start,
+                      GroupPow&& group_pow, hipStream_t s) {
         const size_t K = kRootsSmall;
         const E r1 = crate_one();
-        *n = 0;
-        size_t la = 0;
-        if (!gcd_row_lens(f, nf, nf, 1, &la, s)) return false;
-        E* uns = temp(nf - 1);                                // the roots before they are ordered
-        if (la <= K + 1) {                                    // a short polynomial in a long row: the small regime on its true length
-            long long* dn = temp_as<long long>(1);
-            roots_small_launch(rc, f, nf, la ? la : 1, uns, nf - 1, nullptr, dn, true, 1u, 1, (double)(la + K), s);
-            roots_rank_launch(roots, nf - 1, uns, nf - 1, dn, 0, 1, s);
-            return hipMemcpyAsync(n, dn, sizeof(long long), hipMemcpyDeviceToHost, s) == hipSuccess && hipStreamSynchronize(s) == hipSuccess;
-        }
-        const size_t d = la - 1;
-        // ---- the linear part: fm = f / lc(f), w = x^p mod fm, g = gcd(fm, w - x) ----
-        E* fm = temp(la); E* w = temp(d); E* g = temp(la); E* lc = temp(1);
-        // lc = R / (stored leading coefficient) is the PLAIN inverse of the leading coefficient: plain x crate stays crate
-        foreach_n(s, 1, [=] __device__(size_t) { lc[0] = F::canon(F::mul(F::inv(F::canon(f[d])), r1)); });
-        foreach_n(s, la, [=] __device__(size_t j) { E v = r1; if (j < d) v = F::canon(F::mul(f[j], lc[0])); fm[j] = v; });
-        bool ok = roots_pow_body(fm, d, 0u, rc.ep, rc.nbits_p, w, 1, gcd_flag_, s);
-        foreach_n(s, 1, [=] __device__(size_t) { w[1] = F::canon(F::sub(F::canon(w[1]), r1)); });
-        long long dg = -1;
-        ok = ok && gcd_pair(fm, la, w, d, nullptr, 1, nullptr, 1, g, la, &dg, false, s);
-        if (!ok) return false;
-        if (dg <= 0) { roots_rank_launch(roots, nf - 1, uns, nf - 1, nullptr, 0, 1, s); return true; }
-        const size_t r = (size_t)dg;
-        // pending factors (degree > K) packed with their leading 1 in two alternating buffers, leaves packed likewise
-        struct Fac { size_t off, e; uint32_t fails; };
-        E* pend[2] = {temp(2 * r + 2), temp(2 * r + 2)};
-        E* leaf = temp(2 * r + 2);
+        E* pend[2] = {temp(2 * e0 + 2), temp(2 * e0 + 2)};
+        E* leaf = temp(2 * e0 + 2);
         std::vector<Fac> cur, nxt;
-        std::vector<uint32_t> ldesc;                          // (input offset, length, output offset) per leaf
-        size_t leaf_used = 0, roots_used = 0;
-        auto to_leaf = [&](const E* p, size_t e) {
-            ok = hipMemcpyAsync(leaf + leaf_used, p, (e + 1) * sizeof(E), hipMemcpyDeviceToDevice, s) == hipSuccess && ok;
-            ldesc.push_back((uint32_t)leaf_used); ldesc.push_back((uint32_t)(e + 1)); ldesc.push_back((uint32_t)roots_used);
-            leaf_used += e + 1; roots_used += e;
+        std::vector<uint32_t> ldesc;
+        size_t leaf_used = 0, out_used = 0, nxt_used = 0;
+        bool ok = true;
+        E* Q = pend[0];
+        auto copy = [&](E* dst, const E* src, size_t len) { ok = hipMemcpyAsync(dst, src, len * sizeof(E), hipMemcpyDeviceToDevice, s) == hipSuccess && ok; };
+        auto keep = [&](const E* p, size_t e, uint32_t fails) {
+            if (e == dout) {
+                copy(uns + out_used, p, e);
+                out_used += e;
+            } else if (e <= K) {
+                copy(leaf + leaf_used, p, e + 1);
+                ldesc.push_back((uint32_t)leaf_used); ldesc.push_back((uint32_t)(e + 1)); ldesc.push_back((uint32_t)out_used);
+                leaf_used += e + 1; out_used += e;
+            } else {
+                copy(Q + nxt_used, p, e + 1);
+                nxt.push_back({Q + nxt_used, e, fails});
+                nxt_used += e + 1;
+            }
         };
-        if (r <= K) to_leaf(g, r);
-        else {
-            ok = hipMemcpyAsync(pend[0], g, (r + 1) * sizeof(E), hipMemcpyDeviceToDevice, s) == hipSuccess && ok;
-            cur.push_back({0, r, 0});
-        }
-        int pi = 0;
+        keep(g, e0, 0);
+        cur.swap(nxt);
+        int pi = 0;                                           // the buffer the pending factors are copied to
         uint32_t c = 1;
         for (; ok && !cur.empty(); ++c) {
             const TempMark round = temps_mark();
             nxt.clear();
-            size_t nxt_used = 0;
-            const E* P = pend[pi]; E* Q = pend[pi ^ 1];
-            auto keep = [&](const E* p, size_t e, uint32_t fails) {
-                if (e <= K) { to_leaf(p, e); return; }
-                ok = hipMemcpyAsync(Q + nxt_used, p, (e + 1) * sizeof(E), hipMemcpyDeviceToDevice, s) == hipSuccess && ok;
-                nxt.push_back({nxt_used, e, fails});
-                nxt_used += e + 1;
-            };
+            nxt_used = 0;
+            const E* P = pend[pi]; Q = pend[pi ^= 1];
+            ok = round_start(c);
             std::vector<char> done(cur.size(), 0);
             for (size_t i0 = 0; i0 < cur.size() && ok; ++i0) {
                 if (done[i0]) continue;
                 const size_t N = powmod_leaves(cur[i0].e + 1);
-                std::vector<size_t> grp;
+                std::vector<Fac> hs;
                 size_t D = 0;
                 for (size_t i = i0; i < cur.size(); ++i)
-                    if (!done[i] && powmod_leaves(cur[i].e + 1) == N) { grp.push_back(i); done[i] = 1; if (cur[i].e > D) D = cur[i].e; }
-                const size_t cnt = grp.size();
+                    if (!done[i] && powmod_leaves(cur[i].e + 1) == N) { hs.push_back(cur[i]); done[i] = 1; if (cur[i].e > D) D = cur[i].e; }
+                const size_t cnt = hs.size(), nm = D + 1;
                 const TempMark gm = temps_mark();
                 // rows x^(D - e) h: row i reads P + off_i shifted up by D - e_i
                 std::vector<uint32_t> hd(2 * cnt);
-                for (size_t i = 0; i < cnt; ++i) { hd[2 * i] = (uint32_t)cur[grp[i]].off; hd[2 * i + 1] = (uint32_t)(D - cur[grp[i]].e); }
+                for (size_t i = 0; i < cnt; ++i) { hd[2 * i] = (uint32_t)(hs[i].p - P); hd[2 * i + 1] = (uint32_t)(D - hs[i].e); }
                 uint32_t* dd = temp_as<uint32_t>(2 * cnt);
                 ok = hipMemcpyAsync(dd, hd.data(), 2 * cnt * sizeof(uint32_t), hipMemcpyHostToDevice, s) == hipSuccess && hipStreamSynchronize(s) == hipSuccess && ok;
-                E* M = temp(cnt * (D + 1)); E* W = temp(cnt * D);
-                const size_t nm = D + 1;
+                E* M = temp(cnt * nm); E* W = temp(cnt * D);
                 foreach_n(s, cnt * nm, [=] __device__(size_t k) {
                     const size_t b = k / nm, j = k - b * nm, sh = dd[2 * b + 1];
                     E v = F::zero();
                     if (j >= sh) v = P[dd[2 * b] + (j - sh)];
                     M[k] = v;
                 });
-                ok = ok && roots_pow_body(M, D, c, rc.eh, rc.nbits_h, W, cnt, gcd_flag_, s);
+                ok = ok && group_pow(c, (const E*)M, D, hs, W);
                 foreach_n(s, cnt, [=] __device__(size_t b) { W[b * D] = F::canon(F::sub(F::canon(W[b * D]), r1)); });
                 E* u = temp(D + 1); E* v = temp(D + 1); E* rem = temp(D + 1);
                 for (size_t i = 0; i < cnt && ok; ++i) {
-                    const Fac& fc = cur[grp[i]];
-                    const E* hp = P + fc.off;
+                    const E* hp = hs[i].p;
+                    const size_t e = hs[i].e;
                     long long du = -1;
-                    const TempMark fm2 = temps_mark();
-                    ok = gcd_pair(hp, fc.e + 1, W + i * D, D, nullptr, 1, nullptr, 1, u, D + 1, &du, false, s);
-                    if (ok && du > 0 && (size_t)du < fc.e) {
-                        ok = divrem_body(hp, fc.e + 1, u, (size_t)du + 1, v, rem, 1, gcd_flag_, s);
+                    const TempMark fm = temps_mark();
+                    ok = gcd_pair(hp, e + 1, W + i * D, D, nullptr, 1, nullptr, 1, u, D + 1, &du, false, s);
+                    if (ok && du > 0 && (size_t)du < e) {
+                        if (dout && (size_t)du % dout != 0) ok = false;     // outside the precondition
+                        ok = ok && divrem_body(hp, e + 1, u, (size_t)du + 1, v, rem, 1, gcd_flag_, s);
                         keep(u, (size_t)du, 0);
-                        keep(v, fc.e - (size_t)du, 0);         // copied on the stream before the next factor reuses u and v
+                        keep(v, e - (size_t)du, 0);                   // copied on the stream before the next factor reuses u and v
                     } else if (ok) {
-                        if (fc.fails + 1 >= 64) ok = false;                 // the attempt cap of k_roots_small, for the same reason
-                        keep(hp, fc.e, fc.fails + 1);
+                        if (hs[i].fails + 1 >= 64) ok = false;
+                        keep(hp, e, hs[i].fails + 1);
                     }
-                    temps_release(fm2);
+                    temps_release(fm);
                 }
                 temps_release(gm);
             }
             cur.swap(nxt);
-            pi ^= 1;
             temps_release(round);
         }
         if (!ok) return false;
         // ---- the leaves: one launch, then the order ----
         const size_t nleaf = ldesc.size() / 3;
-        uint32_t* ddesc = temp_as<uint32_t>(ldesc.size());
-        ok = hipMemcpyAsync(ddesc, ldesc.data(), ldesc.size() * sizeof(uint32_t), hipMemcpyHostToDevice, s) == hipSuccess && hipStreamSynchronize(s) == hipSuccess;
-        roots_small_launch(rc, leaf, 0, 0, uns, 0, ddesc, nullptr, false, c, nleaf, (double)(leaf_used + roots_used), s);
-        roots_rank_launch(roots, nf - 1, uns, nf - 1, nullptr, (long long)r, 1, s);
-        *n = (long long)r;
+        if (nleaf) {
+            uint32_t* ddesc = temp_as<uint32_t>(ldesc.size());
+            ok = hipMemcpyAsync(ddesc, ldesc.data(), ldesc.size() * sizeof(uint32_t), hipMemcpyHostToDevice, s) == hipSuccess && hipStreamSynchronize(s) == hipSuccess;
+            split_small_launch(fc, leaf, 0, 0, dout, uns, 0, ddesc, nullptr, false, c, nleaf, (double)(leaf_used + out_used), s);
+        }
+        split_rank_launch(out, ldo, uns, ldo, dout, nullptr, (long long)nfac, 1, s);
         return ok && hipGetLastError() == hipSuccess;
+    }
+    // The roots of ONE polynomial of nf > kRootsSmall + 1 coefficients (untrimmed, crate form) into roots (nf - 1, sorted, zero-padded).
+    //   g = gcd(f, x^p - x mod f) on roots_pow_body (base x) and gcd_pair, the product of the distinct linear factors; then
+    //   split_rounds with no round start, no direct output and, as a group's power, (x + c)^((p-1)/2) by ONE roots_pow_body.
+    bool roots_one_large(const FactorCall& fc, const E* f, size_t nf, E* roots, long long* n, hipStream_t s) {
+        const E r1 = crate_one();
+        *n = 0;
+        size_t la = 0;
+        if (!gcd_row_lens(f, nf, nf, 1, &la, s)) return false;
+        E* uns = temp(nf - 1);                                // the roots before they are ordered
+        if (la <= kRootsSmall + 1) return split_short_row(fc, f, nf, la, 0, uns, roots, n, s);
+        const size_t d = la - 1;
+        // ---- the linear part: fm = f / lc(f), w = x^p mod fm, g = gcd(fm, w - x) ----
+        E* fm = temp(la); E* w = temp(d); E* g = temp(la);
+        monic_row(f, d, fm, s);
+        bool ok = roots_pow_body(fm, d, 0u, fc.ep(), fc.nbits_p, w, 1, gcd_flag_, s);
+        foreach_n(s, 1, [=] __device__(size_t) { w[1] = F::canon(F::sub(F::canon(w[1]), r1)); });
+        long long dg = -1;
+        ok = ok && gcd_pair(fm, la, w, d, nullptr, 1, nullptr, 1, g, la, &dg, false, s);
+        if (!ok) return false;
+        if (dg <= 0) { split_rank_launch(roots, nf - 1, uns, nf - 1, 0, nullptr, 0, 1, s); return true; }
+        ok = split_rounds(fc, g, (size_t)dg, 0, uns, roots, nf - 1, (size_t)dg, [](uint32_t) { return true; },
+                          [&](uint32_t c, const E* M, size_t D, const std::vector<Fac>& hs, E* W) {
+                              return roots_pow_body(M, D, c, fc.eh(), fc.nbits_h, W, hs.size(), gcd_flag_, s);
+                          }, s);
+        if (ok) *n = dg;
+        return ok;
     }
 public:
     // a polynomial of at most kRootsSmall + 1 coefficients (degree <= kRootsSmall) is finished by k_roots_small, one workgroup each
@@ -2560,20 +2642,14 @@ public:
     // (with its Frobenius flag) for all rows and one of k_roots_rank.  Otherwise the polynomials run one after another
     // (roots_one_large).  *capped = a factor exhausted the attempt cap.  Synchronous.  Caller holds lock() and checks the tree rule.
     bool poly_find_roots(const E* f, size_t nf, E* roots, long long* n_roots, size_t count, bool* capped, hipStream_t s) {
-        RootsCall rc;
-        roots_exponents(rc.ep, &rc.nbits_p, rc.eh, &rc.nbits_h);
-        uint8_t* dexp = temp_as<uint8_t>(64);
-        uint8_t both[64];
-        for (int i = 0; i < 32; ++i) { both[i] = rc.ep[i]; both[32 + i] = rc.eh[i]; }
-        bool ok = hipMemcpyAsync(dexp, both, 64, hipMemcpyHostToDevice, s) == hipSuccess && hipStreamSynchronize(s) == hipSuccess;
-        rc.dexp = dexp;
-        rc.flag = new_flag(s);
+        FactorCall rc;
+        bool ok = factor_call_init(&rc, true, s);
         const size_t nr = nf - 1;
         if (nf <= kRootsSmall + 1) {
             long long* dn = temp_as<long long>(count);
             E* uns = temp(count * nr);
-            roots_small_launch(rc, f, nf, nf, uns, nr, nullptr, dn, true, 1u, count, (double)count * (double)(nf + nr), s);
-            roots_rank_launch(roots, nr, uns, nr, dn, 0, count, s);
+            split_small_launch(rc, f, nf, nf, 0, uns, nr, nullptr, dn, true, 1u, count, (double)count * (double)(nf + nr), s);
+            split_rank_launch(roots, nr, uns, nr, 0, dn, 0, count, s);
             ok = hipMemcpyAsync(n_roots, dn, count * sizeof(long long), hipMemcpyDeviceToHost, s) == hipSuccess && ok;
         } else {
             gcd_flag_ = new_flag(s);
@@ -2600,28 +2676,16 @@ public:
         if (ddf_iterate_force() == 1) return true;
         if (ddf_iterate_force() == 2) return false;
 #endif
-        uint8_t ep[32], eh[32];
-        uint32_t nbits_p = 0, nbits_h = 0, pop = 0;
-        roots_exponents(ep, &nbits_p, eh, &nbits_h);
-        for (int i = 0; i < 32; ++i) pop += (uint32_t)__builtin_popcount(ep[i]);
         const size_t k = compose_chunk(ds), kp = (ds + k - 1) / k;
-        return kp - 1 <= (size_t)nbits_p + pop - 2;
+        return kp - 1 <= (size_t)schoof_pow_cost();
     }
 #ifdef ECFFT_TEST_HOOKS
     // ecfft_test_ddf_iterate (include/ecfft_hip_hooks.h): 0 = the rule, 1 = always the kept composition, 2 = always the fresh power
     static int& ddf_iterate_force() { static int v = 0; return v; }
 #endif
 private:
-    // what a call shares between its polynomials: p as host and device bytes
-    struct DdfCall { const uint8_t* dexp = nullptr; uint8_t ep[32], eh[32]; uint32_t nbits_p = 0, nbits_h = 0; };
-    bool ddf_call_init(DdfCall* dc, hipStream_t s) {
-        roots_exponents(dc->ep, &dc->nbits_p, dc->eh, &dc->nbits_h);
-        uint8_t* dexp = temp_as<uint8_t>(32);
-        dc->dexp = dexp;
-        return hipMemcpyAsync(dexp, dc->ep, 32, hipMemcpyHostToDevice, s) == hipSuccess && hipStreamSynchronize(s) == hipSuccess;
-    }
     // one launch of k_ddf_small over nblk rows: nin coefficients read and nw entries written per row
-    void ddf_small_launch(const DdfCall& dc, const E* in, size_t ldin, size_t nin, E* out, size_t ldout, size_t nw, long long* deg, size_t lddeg,
+    void ddf_small_launch(const FactorCall& dc, const E* in, size_t ldin, size_t nin, E* out, size_t ldout, size_t nw, long long* deg, size_t lddeg,
                           bool squarefree, size_t nblk, hipStream_t s) {
         const E r1 = crate_one();
         const TE rinv = rinv_table();
@@ -2636,10 +2700,8 @@ private:
     // tree holds (the C ABI asserts it), so f' = 0 only for constants and there is no p-th-power case.
     bool squarefree_one_large(const E* f, size_t la, E* sq, size_t* ls, hipStream_t s) {
         const size_t d = la - 1;
-        const E r1 = crate_one();
-        E* fm = temp(la); E* fd = temp(d); E* g = temp(la); E* lc = temp(1);
-        foreach_n(s, 1, [=] __device__(size_t) { lc[0] = F::canon(F::mul(F::inv(F::canon(f[d])), r1)); });
-        foreach_n(s, la, [=] __device__(size_t j) { E v = r1; if (j < d) v = F::canon(F::mul(f[j], lc[0])); fm[j] = v; });
+        E* fm = temp(la); E* fd = temp(d); E* g = temp(la);
+        monic_row(f, d, fm, s);
         foreach_n(s, d, [=] __device__(size_t j) { fd[j] = F::canon(F::mul(F::from_u32((uint32_t)(j + 1)), fm[j + 1])); });   // the plain integer j + 1 times a crate coefficient
         long long dg = -1;
         bool ok = gcd_pair(fm, la, fd, d, nullptr, 1, nullptr, 1, g, la, &dg, false, s);
@@ -2701,7 +2763,7 @@ private:
     //   What is left of f* is irreducible of its own degree.  The modulus stays s for the whole row.
     // Temporaries beyond a step's own: 4 N elements (the kept g, s, h_1 and G or the lifted h_i), (k + 1 + k') deg s for the baby
     // steps and chunk sums, and eight rows of at most nf.  Synchronous (gcd_pair reads degrees back).
-    bool ddf_one_large(const DdfCall& dc, const E* f, size_t nf, E* fac, long long* ddeg, long long* hdeg, hipStream_t s) {
+    bool ddf_one_large(const FactorCall& dc, const E* f, size_t nf, E* fac, long long* ddeg, long long* hdeg, hipStream_t s) {
         const size_t K = kDdfSmall, nd = nf - 1;
         const E r1 = crate_one();
         size_t la = 0;
@@ -2722,7 +2784,7 @@ private:
         E* fs[2] = {temp(ls), temp(ls)}; E* g = temp(ls);
         KeptModulus km;
         bool ok = keep_modulus(sq, ds, nullptr, 0, 0, 1, kept, gcd_flag_, &km, s);
-        ok = roots_pow_kept(sq, km, 0u, dc.ep, dc.nbits_p, h1, next, 1, s) && ok;
+        ok = roots_pow_kept(sq, km, 0u, dc.ep(), dc.nbits_p, h1, next, 1, s) && ok;
         ok = hipMemcpyAsync(hb[0], h1, ds * sizeof(E), hipMemcpyDeviceToDevice, s) == hipSuccess && ok;
         FrobIterate fr;
         frob_init(&fr, km, kept, h1);
@@ -2749,7 +2811,7 @@ private:
                 temps_release(mark);
             }
             if (!ok || e < 2 * (i + 1)) break;
-            ok = frob_next(fr, h, hb[hi ^ 1], dc.ep, dc.nbits_p, s) && ok;
+            ok = frob_next(fr, h, hb[hi ^ 1], dc.ep(), dc.nbits_p, s) && ok;
             hi ^= 1;
         }
         if (ok && e > 0) {
@@ -2765,8 +2827,8 @@ public:
     // goes to the same kernel on its true length, the others to squarefree_one_large.  Synchronous.  Caller holds lock() and checks
     // the tree rule (ddf_leaves).
     bool poly_squarefree(const E* f, size_t nf, E* out, long long* degrees, size_t count, hipStream_t s) {
-        DdfCall dc;
-        bool ok = ddf_call_init(&dc, s);
+        FactorCall dc;
+        bool ok = factor_call_init(&dc, false, s);
         long long* ddeg = temp_as<long long>(count);
         if (nf <= kDdfSmall + 1) {
             ddf_small_launch(dc, f, nf, nf, out, nf, nf, ddeg, 1, true, count, s);
@@ -2798,8 +2860,8 @@ public:
     // k_ddf_small for all rows.  Otherwise the rows run one after another (their degree sequences differ): ddf_one_large.
     // Synchronous.  Caller holds lock() and checks the tree rule (ddf_leaves).
     bool poly_distinct_degree(const E* f, size_t nf, E* factors, long long* degrees, size_t count, hipStream_t s) {
-        DdfCall dc;
-        bool ok = ddf_call_init(&dc, s);
+        FactorCall dc;
+        bool ok = factor_call_init(&dc, false, s);
         const size_t nd = nf > 1 ? nf - 1 : 1;
         long long* ddeg = temp_as<long long>(count * nd);
         if (nf <= kDdfSmall + 1) {
@@ -2825,75 +2887,29 @@ public:
     // kept modulus g has at most ng coefficients; every pending factor, gcd and division is smaller)
     static size_t edf_leaves(size_t ng) { return roots_leaves(ng); }
 private:
-    // what a call shares between its polynomials: p and (p - 1) / 2 as host and device bytes, and the flag of the attempt cap
-    struct EdfCall { const uint8_t* dexp = nullptr; uint8_t ep[32], eh[32]; uint32_t nbits_p = 0, nbits_h = 0; int* flag = nullptr; };
-    // one launch of k_edf_small over nblk rows or descriptors; the workspace of the h_i, d - 1 rows of the longest degree a
-    // workgroup can meet (nin - 1, or K for descriptors), is shared by the chunks, which run one after another on the stream
-    void edf_small_launch(const EdfCall& ec, const E* in, size_t ldin, size_t nin, size_t d, E* out, size_t ldout, const uint32_t* desc,
-                          long long* n_out, uint32_t c0, size_t nblk, double coeffs, hipStream_t s) {
-        const E r1 = crate_one();
-        const TE rinv = rinv_table();
-        const size_t chunk = nblk < ((size_t)1 << 16) ? nblk : (size_t)1 << 16;
-        const size_t nmax = desc || nin > kEdfSmall ? kEdfSmall : (nin ? nin - 1 : 0);
-        const size_t ldws = 2 * d <= nmax ? (d - 1) * nmax : 0;                // a row that splits has 2 d <= its degree
-        E* ws = ldws ? temp(chunk * ldws) : nullptr;
-        for_chunks(nblk, [&](size_t b0, size_t nb) {
-            ECFFT_LAUNCH(KC_POINTWISE, sizeof(E) * coeffs * (double)nb / (double)nblk + 64.0, (k_edf_small<F, (int)kEdfSmall>), dim3((unsigned)nb),
-                         dim3((unsigned)kEdfSmall), 0, s, desc ? in : in + b0 * ldin, ldin, (uint32_t)nin, (uint32_t)d, desc ? out : out + b0 * ldout,
-                         ldout, desc ? desc + 3 * b0 : (const uint32_t*)nullptr, n_out ? n_out + b0 : (long long*)nullptr, ws, ldws, c0, ec.dexp,
-                         ec.nbits_p, ec.dexp + 32, ec.nbits_h, rinv, r1, ec.flag);
-        });
-    }
-    // the canonical order: src (rows x lds, factors of d coefficients in any order) -> dst (rows x ldd), k_edf_rank on the standard
-    // form of src, converted once per element
-    void edf_rank_launch(E* dst, size_t ldd, const E* src, size_t lds, size_t d, const long long* n_dev, long long n_fixed, size_t rows,
-                         hipStream_t s) {
-        if (!ldd) return;
-        E* sf = temp(rows * lds);
-        const TE rinv = rinv_table();
-        foreach_n(s, rows * lds, [=] __device__(size_t i) {
-            E v = F::canon(src[i]);
-            if constexpr (sizeof(E) == 32) v = F::canon(F::tmul(rinv, v));
-            sf[i] = v;
-        });
-        for (size_t r0 = 0; r0 < rows; r0 += 32768) {
-            const size_t nr = rows - r0 < 32768 ? rows - r0 : 32768;
-            ECFFT_LAUNCH(KC_POINTWISE, sizeof(E) * 3.0 * (double)nr * (double)ldd, k_edf_rank<F>, dim3(nblocks(ldd), (unsigned)nr), dim3(kBlock), 0, s,
-                         dst + r0 * ldd, ldd, src + r0 * lds, (const E*)sf + r0 * lds, lds, (uint32_t)d, n_dev ? n_dev + r0 : (const long long*)nullptr,
-                         n_fixed);
-        }
-    }
     // The irreducible factors of degree d of ONE polynomial of ng > kEdfSmall + 1 coefficients (untrimmed, crate form; a squarefree
     // product of irreducibles of degree d) into fac (ng - 1 elements, ordered, zero on entry).
     //   true degree <= kEdfSmall: k_edf_small on the true length.  Otherwise gm = g / lc(g) is kept ONCE for the row (keep_modulus
     //   without a base), h_1 = x^p mod gm (roots_pow_kept, base x) and h_2 .. h_(d-1) by frob_next, kept as coefficient rows.
-    //   Rounds with one shift c = 1, 2, ... for all pending factors: N_c = (x + c) prod_i (h_i + c) mod gm, each h_i + c lifted for its
-    //   one powmod_step; per pending factor u != gm the base N_c mod u (divrem_body, remainder only); the factors grouped by
-    //   N = powmod_leaves(e + 1) and padded inside a group to its largest degree D as x^(D-e) u, ONE modular power per group with the
-    //   bases as rows (poly_pow_mod's large body: keep_modulus with the bases, then the powmod_step scan on (p - 1) / 2); per factor
-    //   gcd_pair(u, w - 1) and divrem_body.  A piece of degree d goes to the output, one of degree <= kEdfSmall to the leaf
-    //   buffer, the rest stay pending.  The leaves are finished by ONE launch of k_edf_small, then k_edf_rank orders the row.
+    //   Then split_rounds with pieces of degree d going straight to the output;
+    //     at the start of round c: N_c = (x + c) prod_i (h_i + c) mod gm, each h_i + c lifted for its one powmod_step;
+    //     a group's power: per factor u != gm the base N_c mod u (divrem_body, remainder only), then poly_pow_mod's large body with
+    //     the bases as rows (keep_modulus with the bases, then the powmod_step scan on (p - 1) / 2).
     // Temporaries beyond a step's own: 4 N for the kept modulus and the lifted operand, (d - 1) n for the h_i, the composition's
     // baby steps, and the pending and leaf buffers of 2 n.  Synchronous (gcd_pair reads degrees back).
-    bool edf_one_large(const EdfCall& ec, const E* g, size_t ng, size_t d, E* fac, long long* n, hipStream_t s) {
-        const size_t K = kEdfSmall, nd = ng - 1;
+    bool edf_one_large(const FactorCall& fc, const E* g, size_t ng, size_t d, E* fac, long long* n, hipStream_t s) {
+        const size_t nd = ng - 1;
         const E r1 = crate_one();
         const TE rinv = rinv_table();
         *n = 0;
         size_t la = 0;
         if (!gcd_row_lens(g, ng, ng, 1, &la, s)) return false;
         E* uns = temp(nd);                                    // the factors before they are ordered
-        if (la <= K + 1) {                                    // a short polynomial in a long row: the small regime on its true length
-            long long* dn = temp_as<long long>(1);
-            edf_small_launch(ec, g, ng, la ? la : 1, d, uns, nd, nullptr, dn, 1u, 1, (double)(la + K), s);
-            edf_rank_launch(fac, nd, uns, nd, d, dn, 0, 1, s);
-            return hipMemcpyAsync(n, dn, sizeof(long long), hipMemcpyDeviceToHost, s) == hipSuccess && hipStreamSynchronize(s) == hipSuccess;
-        }
+        if (la <= kEdfSmall + 1) return split_short_row(fc, g, ng, la, d, uns, fac, n, s);
         const size_t dg = la - 1;
         if (dg % d != 0) { *n = -2; return true; }
-        E* gm = temp(la); E* lc = temp(1);
-        foreach_n(s, 1, [=] __device__(size_t) { lc[0] = F::canon(F::mul(F::inv(F::canon(g[dg])), r1)); });
-        foreach_n(s, la, [=] __device__(size_t j) { E v = r1; if (j < dg) v = F::canon(F::mul(g[j], lc[0])); gm[j] = v; });
+        E* gm = temp(la);
+        monic_row(g, dg, gm, s);
         const size_t r = dg / d;
         *n = (long long)r;
         if (r == 1) return hipMemcpyAsync(fac, gm, d * sizeof(E), hipMemcpyDeviceToDevice, s) == hipSuccess;
@@ -2905,119 +2921,47 @@ private:
         KeptModulus km;
         bool ok = keep_modulus(gm, dg, nullptr, 0, 0, 1, kept, gcd_flag_, &km, s);
         if (d > 1) {
-            ok = roots_pow_kept(gm, km, 0u, ec.ep, ec.nbits_p, H, next, 1, s) && ok;
+            ok = roots_pow_kept(gm, km, 0u, fc.ep(), fc.nbits_p, H, next, 1, s) && ok;
             if (d > 2) {
                 FrobIterate fr;
                 frob_init(&fr, km, kept, H);
-                for (size_t i = 2; i < d && ok; ++i) ok = frob_next(fr, H + (i - 2) * dg, H + (i - 1) * dg, ec.ep, ec.nbits_p, s);
+                for (size_t i = 2; i < d && ok; ++i) ok = frob_next(fr, H + (i - 2) * dg, H + (i - 1) * dg, fc.ep(), fc.nbits_p, s);
             }
-        }
-        E* lifted = kept + 3 * N;                             // free once the iterates are taken: the lifted h_i + c of a norm's product
-        // pending factors packed with their leading 1 in two alternating buffers, leaves packed likewise
-        struct Fac { size_t off, e; uint32_t fails; };
-        E* pend[2] = {temp(2 * dg + 2), temp(2 * dg + 2)};
-        E* leaf = temp(2 * dg + 2);
-        std::vector<Fac> cur, nxt;
-        std::vector<uint32_t> ldesc;                          // (input offset, length, output offset) per leaf
-        size_t leaf_used = 0, out_used = 0;
-        ok = hipMemcpyAsync(pend[0], gm, la * sizeof(E), hipMemcpyDeviceToDevice, s) == hipSuccess && ok;
-        cur.push_back({0, dg, 0});
-        int pi = 0;
-        uint32_t c = 1;
-        for (; ok && !cur.empty(); ++c) {
-            const TempMark round = temps_mark();
-            nxt.clear();
-            size_t nxt_used = 0;
-            const E* P = pend[pi]; E* Q = pend[pi ^ 1];
-            auto keep = [&](const E* p, size_t e, uint32_t fails) {
-                if (e == d) {
-                    ok = hipMemcpyAsync(uns + out_used, p, d * sizeof(E), hipMemcpyDeviceToDevice, s) == hipSuccess && ok;
-                    out_used += d;
-                } else if (e <= K) {
-                    ok = hipMemcpyAsync(leaf + leaf_used, p, (e + 1) * sizeof(E), hipMemcpyDeviceToDevice, s) == hipSuccess && ok;
-                    ldesc.push_back((uint32_t)leaf_used); ldesc.push_back((uint32_t)(e + 1)); ldesc.push_back((uint32_t)out_used);
-                    leaf_used += e + 1; out_used += e;
-                } else {
-                    ok = hipMemcpyAsync(Q + nxt_used, p, (e + 1) * sizeof(E), hipMemcpyDeviceToDevice, s) == hipSuccess && ok;
-                    nxt.push_back({nxt_used, e, fails});
-                    nxt_used += e + 1;
-                }
-            };
-            // N_c modulo gm
-            {
-                const E c_crate = F::canon(F::mul(F::from_u32(c), r1));
-                foreach_n(s, dg, [=] __device__(size_t j) { E v = F::zero(); if (j == 0) v = c_crate; if (j == 1) v = r1; Nc[j] = v; });
-                for (size_t i = 1; i < d && ok; ++i) {
-                    const E* hi = H + (i - 1) * dg;
-                    foreach_n(s, dg, [=] __device__(size_t j) { E v = F::canon(hi[j]); if (j == 0) v = F::canon(F::add(v, c_crate)); y[j] = v; });
-                    ok = lift_and_keep(y, dg, N, 1, lifted, s) && ok;
-                    ok = powmod_step(Nc, lifted, km, 1, rinv, s) && ok;
-                }
-            }
-            std::vector<char> done(cur.size(), 0);
-            for (size_t i0 = 0; i0 < cur.size() && ok; ++i0) {
-                if (done[i0]) continue;
-                const size_t Ng = powmod_leaves(cur[i0].e + 1);
-                std::vector<size_t> grp;
-                size_t D = 0;
-                for (size_t i = i0; i < cur.size(); ++i)
-                    if (!done[i] && powmod_leaves(cur[i].e + 1) == Ng) { grp.push_back(i); done[i] = 1; if (cur[i].e > D) D = cur[i].e; }
-                const size_t cnt = grp.size(), nm = D + 1;
-                const TempMark gmk = temps_mark();
-                // the moduli x^(D - e) u and the bases N_c mod u, zero-padded to D coefficients
-                E* M = temp(cnt * nm); E* B = temp(cnt * D); E* W = temp(cnt * D);
-                ok = hipMemsetAsync(M, 0, cnt * nm * sizeof(E), s) == hipSuccess && ok;
-                ok = hipMemsetAsync(B, 0, cnt * D * sizeof(E), s) == hipSuccess && ok;
-                for (size_t i = 0; i < cnt && ok; ++i) {
-                    const Fac& fc = cur[grp[i]];
-                    ok = hipMemcpyAsync(M + i * nm + (D - fc.e), P + fc.off, (fc.e + 1) * sizeof(E), hipMemcpyDeviceToDevice, s) == hipSuccess;
-                    if (fc.e == dg) ok = hipMemcpyAsync(B + i * D, Nc, dg * sizeof(E), hipMemcpyDeviceToDevice, s) == hipSuccess && ok;
-                    else ok = divrem_body(Nc, dg, P + fc.off, fc.e + 1, nullptr, B + i * D, 1, gcd_flag_, s) && ok;
-                }
-                // W = B^((p-1)/2) modulo the rows of M
-                E* kept2 = temp(3 * cnt * Ng);
-                KeptModulus kg;
-                ok = ok && keep_modulus(M, D, B, D, D, cnt, kept2, gcd_flag_, &kg, s);
-                ok = hipMemcpyAsync(W, B, cnt * D * sizeof(E), hipMemcpyDeviceToDevice, s) == hipSuccess && ok;
-                for (size_t bit = ec.nbits_h - 1; ok && bit-- > 0;) {
-                    ok = powmod_step(W, nullptr, kg, cnt, rinv, s);
-                    if (ok && ((ec.eh[bit >> 3] >> (bit & 7)) & 1)) ok = powmod_step(W, kg.base, kg, cnt, rinv, s);
-                }
-                foreach_n(s, cnt, [=] __device__(size_t b) { W[b * D] = F::canon(F::sub(F::canon(W[b * D]), r1)); });
-                E* u = temp(D + 1); E* v = temp(D + 1); E* rem = temp(D + 1);
-                for (size_t i = 0; i < cnt && ok; ++i) {
-                    const Fac& fc = cur[grp[i]];
-                    const E* hp = P + fc.off;
-                    long long du = -1;
-                    const TempMark fmk = temps_mark();
-                    ok = gcd_pair(hp, fc.e + 1, W + i * D, D, nullptr, 1, nullptr, 1, u, D + 1, &du, false, s);
-                    if (ok && du > 0 && (size_t)du < fc.e) {
-                        if ((size_t)du % d != 0) ok = false;                // outside the precondition
-                        ok = ok && divrem_body(hp, fc.e + 1, u, (size_t)du + 1, v, rem, 1, gcd_flag_, s);
-                        keep(u, (size_t)du, 0);
-                        keep(v, fc.e - (size_t)du, 0);         // copied on the stream before the next factor reuses u and v
-                    } else if (ok) {
-                        if (fc.fails + 1 >= 64) ok = false;                 // the attempt cap of k_edf_small, for the same reason
-                        keep(hp, fc.e, fc.fails + 1);
-                    }
-                    temps_release(fmk);
-                }
-                temps_release(gmk);
-            }
-            cur.swap(nxt);
-            pi ^= 1;
-            temps_release(round);
         }
         if (!ok) return false;
-        // ---- the leaves: one launch, then the order ----
-        const size_t nleaf = ldesc.size() / 3;
-        if (nleaf) {
-            uint32_t* ddesc = temp_as<uint32_t>(ldesc.size());
-            ok = hipMemcpyAsync(ddesc, ldesc.data(), ldesc.size() * sizeof(uint32_t), hipMemcpyHostToDevice, s) == hipSuccess && hipStreamSynchronize(s) == hipSuccess;
-            edf_small_launch(ec, leaf, 0, 0, d, uns, 0, ddesc, nullptr, c, nleaf, (double)(leaf_used + out_used), s);
-        }
-        edf_rank_launch(fac, nd, uns, nd, d, nullptr, (long long)r, 1, s);
-        return ok && hipGetLastError() == hipSuccess;
+        E* lifted = kept + 3 * N;                             // free once the iterates are taken: the lifted h_i + c of a norm's product
+        auto norm = [&](uint32_t c) {                         // N_c modulo gm
+            bool ok = true;
+            const E c_crate = F::canon(F::mul(F::from_u32(c), r1));
+            foreach_n(s, dg, [=] __device__(size_t j) { E v = F::zero(); if (j == 0) v = c_crate; if (j == 1) v = r1; Nc[j] = v; });
+            for (size_t i = 1; i < d && ok; ++i) {
+                const E* hi = H + (i - 1) * dg;
+                foreach_n(s, dg, [=] __device__(size_t j) { E v = F::canon(hi[j]); if (j == 0) v = F::canon(F::add(v, c_crate)); y[j] = v; });
+                ok = lift_and_keep(y, dg, N, 1, lifted, s) && ok;
+                ok = powmod_step(Nc, lifted, km, 1, rinv, s) && ok;
+            }
+            return ok;
+        };
+        auto power = [&](uint32_t, const E* M, size_t D, const std::vector<Fac>& hs, E* W) {   // W = (N_c mod u)^((p-1)/2) modulo the rows of M
+            const size_t cnt = hs.size();
+            bool ok = true;
+            E* B = temp(cnt * D);                             // the bases, zero-padded to D coefficients
+            ok = hipMemsetAsync(B, 0, cnt * D * sizeof(E), s) == hipSuccess && ok;
+            for (size_t i = 0; i < cnt && ok; ++i) {
+                if (hs[i].e == dg) ok = hipMemcpyAsync(B + i * D, Nc, dg * sizeof(E), hipMemcpyDeviceToDevice, s) == hipSuccess;
+                else ok = divrem_body(Nc, dg, hs[i].p, hs[i].e + 1, nullptr, B + i * D, 1, gcd_flag_, s);
+            }
+            E* kept2 = temp(3 * cnt * powmod_leaves(D + 1));
+            KeptModulus kg;
+            ok = ok && keep_modulus(M, D, B, D, D, cnt, kept2, gcd_flag_, &kg, s);
+            ok = hipMemcpyAsync(W, B, cnt * D * sizeof(E), hipMemcpyDeviceToDevice, s) == hipSuccess && ok;
+            for (size_t bit = fc.nbits_h - 1; ok && bit-- > 0;) {
+                ok = powmod_step(W, nullptr, kg, cnt, rinv, s);
+                if (ok && ((fc.eh()[bit >> 3] >> (bit & 7)) & 1)) ok = powmod_step(W, kg.base, kg, cnt, rinv, s);
+            }
+            return ok;
+        };
+        return split_rounds(fc, gm, dg, d, uns, fac, nd, r, norm, power, s);
     }
 public:
     // ecfft_poly_equal_degree: with nd = max(ng - 1, 1), factors (count x nd, crate form) = the n_factors[b] monic irreducible
@@ -3027,20 +2971,14 @@ public:
     // after another (edf_one_large).  *capped = a factor exhausted the attempt cap.  Synchronous.  Caller holds lock() and checks
     // the tree rule (edf_leaves).
     bool poly_equal_degree(const E* g, size_t ng, size_t d, E* factors, long long* n_factors, size_t count, bool* capped, hipStream_t s) {
-        EdfCall ec;
-        roots_exponents(ec.ep, &ec.nbits_p, ec.eh, &ec.nbits_h);
-        uint8_t* dexp = temp_as<uint8_t>(64);
-        uint8_t both[64];
-        for (int i = 0; i < 32; ++i) { both[i] = ec.ep[i]; both[32 + i] = ec.eh[i]; }
-        bool ok = hipMemcpyAsync(dexp, both, 64, hipMemcpyHostToDevice, s) == hipSuccess && hipStreamSynchronize(s) == hipSuccess;
-        ec.dexp = dexp;
-        ec.flag = new_flag(s);
+        FactorCall ec;
+        bool ok = factor_call_init(&ec, true, s);
         const size_t nd = ng > 1 ? ng - 1 : 1;
         if (ng <= kEdfSmall + 1) {
             long long* dn = temp_as<long long>(count);
             E* uns = temp(count * nd);
-            edf_small_launch(ec, g, ng, ng, d, uns, nd, nullptr, dn, 1u, count, (double)count * (double)(ng + nd), s);
-            edf_rank_launch(factors, nd, uns, nd, d, dn, 0, count, s);
+            split_small_launch(ec, g, ng, ng, d, uns, nd, nullptr, dn, false, 1u, count, (double)count * (double)(ng + nd), s);
+            split_rank_launch(factors, nd, uns, nd, d, dn, 0, count, s);
             ok = hipMemcpyAsync(n_factors, dn, count * sizeof(long long), hipMemcpyDeviceToHost, s) == hipSuccess && ok;
         } else {
             gcd_flag_ = new_flag(s);
@@ -3189,11 +3127,10 @@ public:
     }
     // the modular products of one general-base power with p: bits + popcount(p) - 2
     static uint32_t schoof_pow_cost() {
-        uint8_t ep[32], eh[32];
-        uint32_t nbits_p = 0, nbits_h = 0, pop = 0;
-        roots_exponents(ep, &nbits_p, eh, &nbits_h);
-        for (int i = 0; i < 32; ++i) pop += (uint32_t)__builtin_popcount(ep[i]);
-        return nbits_p + pop - 2;
+        const FactorCall fc = factor_exponents();
+        uint32_t pop = 0;
+        for (int i = 0; i < 32; ++i) pop += (uint32_t)__builtin_popcount(fc.e[i]);
+        return fc.nbits_p + pop - 2;
     }
     // How pi^2 = (x^(p^2), y^(p^2)) is taken from pi = (a, b y) on a modulus of degree d: true = the composition (a(a), b(a) b),
     // false = the powers (a^p, b^p b), 2 c products with c = schoof_pow_cost().  The rule is the count of modular products, as
@@ -3215,14 +3152,12 @@ public:
     static int& schoof_pi2_force() { static int v = 0; return v; }
 #endif
     // p as 32 little-endian bytes
-    static void modulus_bytes(uint8_t* ep) { uint8_t eh[32]; uint32_t a = 0, b = 0; roots_exponents(ep, &a, eh, &b); }
+    static void modulus_bytes(uint8_t* ep) { const FactorCall fc = factor_exponents(); for (int i = 0; i < 32; ++i) ep[i] = fc.e[i]; }
     // p mod l for a small l
     static uint32_t schoof_p_mod(uint32_t l) {
-        uint8_t ep[32], eh[32];
-        uint32_t nbits_p = 0, nbits_h = 0;
-        roots_exponents(ep, &nbits_p, eh, &nbits_h);
+        const FactorCall fc = factor_exponents();
         uint64_t r = 0;
-        for (int i = 31; i >= 0; --i) r = (r * 256 + ep[i]) % l;
+        for (int i = 31; i >= 0; --i) r = (r * 256 + fc.e[i]) % l;
         return (uint32_t)r;
     }
 private:
@@ -3456,7 +3391,9 @@ public:
     bool curve_trace_mod(const E* A, const E* B, uint32_t l, long long* t_out, size_t count, bool* defect, hipStream_t s, bool done = true) {
         const TempMark entry = temps_mark();
         SchoofCall sc;
-        roots_exponents(sc.e, &sc.nbits_p, sc.e + 32, &sc.nbits_h);
+        const FactorCall fc = factor_exponents();
+        for (int i = 0; i < 64; ++i) sc.e[i] = fc.e[i];
+        sc.nbits_p = fc.nbits_p; sc.nbits_h = fc.nbits_h;
         uint8_t* dexp = temp_as<uint8_t>(64);
         bool ok = hipMemcpyAsync(dexp, sc.e, 64, hipMemcpyHostToDevice, s) == hipSuccess && hipStreamSynchronize(s) == hipSuccess;
         sc.dexp = dexp;

@@ -2835,6 +2835,66 @@ __device__ __forceinline__ int roots_gcd_rows(typename F::elem*& R0, typename F:
     gcd_remainder_loop<F>(R0, R1, d0, d1, none, none, none, none, c, c, 0u, 0, sdeg, t);
     return d0;
 }
+// quo[0 .. e - du] = A / u for the monic A of degree e (low e plain coefficients in a) and the monic u of degree du <= e (low du
+// plain coefficients in u): synthetic division, no inversion.  work: e + 1 entries; quo[e - du] = 1.  a, u, quo, work
+// are four different rows.
+template <class F>
+__device__ __forceinline__ void ddf_div_monic(typename F::elem* quo, typename F::elem* work, const typename F::elem* a, int e,
+                                              const typename F::elem* u, int du, uint32_t t) {
+    using E = typename F::elem;
+    if ((int)t < e) work[t] = a[t];
+    if (t == 0) work[e] = F::one();
+    __syncthreads();
+    for (int k = e - du; k >= 0; --k) {
+        const E qk = work[k + du];
+        if ((int)t < du) work[k + t] = F::canon(F::sub(work[k + t], F::canon(F::mul(qk, u[t]))));
+        if (t == 0) quo[k] = qk;
+        __syncthreads();
+    }
+}
+// The prologue of the small factorisation kernels, one workgroup of K threads per row: the true degree d of the row fb (nin <= K + 1
+// coefficients, crate form, untrimmed; thread t looks at coefficient t, thread 0 also at coefficient K of a full row) through
+// sdeg[0], returned to every thread from behind a barrier: -1 for the zero row.  For d >= 1 the row is made monic: srow[t] = the
+// PLAIN residue f_t / f_d, zero from d on, each thread writing its own entry (no barrier after it).  The inversion and the row are
+// done for every d >= 1, whatever the caller then rejects (k_edf_small: a degree its dd does not divide).
+template <class F, int K>
+__device__ __forceinline__ int small_row_monic(const typename F::elem* __restrict__ fb, uint32_t nin, typename F::elem* srow,
+                                               typename F::elem* snorm, int* sdeg, uint32_t t) {
+    using E = typename F::elem;
+    if (t == 0) sdeg[0] = -1;
+    __syncthreads();
+    E mine = F::zero();
+    if (t < nin) mine = F::canon(fb[t]);
+    if (!F::is_zero(mine)) atomicMax(&sdeg[0], (int)t);
+    if (t == 0 && nin == K + 1 && !F::is_zero(F::canon(fb[K]))) atomicMax(&sdeg[0], K);
+    __syncthreads();
+    const int d = sdeg[0];
+    if (d >= 1) {
+        if (t == 0) *snorm = F::canon(F::inv(F::canon(fb[d])));
+        __syncthreads();
+        E v = F::zero();
+        if ((int)t < d) v = F::canon(F::mul(mine, *snorm));
+        srow[t] = v;
+    }
+    return d;
+}
+// The tail of a successful split in k_roots_small and k_edf_small: the top stack entry h (degree e at stack + base, its plain
+// residues also in smod) has met a multiple R0 of its proper factor of degree du.  u = R0 / lc(R0) (sx) by the one inversion of the
+// split, v = h / u (sres) by ddf_div_monic on sprod; the entry becomes u and v is pushed above it.  Ends behind a barrier.
+template <class F>
+__device__ __forceinline__ void split_push(typename F::elem* stack, int* stk_deg, int* stk_off, int sp, int base, int e,
+                                           const typename F::elem* R0, int du, typename F::elem* snorm, typename F::elem* sx,
+                                           typename F::elem* sres, typename F::elem* sprod, const typename F::elem* smod, uint32_t t) {
+    if (t == 0) *snorm = F::canon(F::inv(R0[du]));
+    __syncthreads();
+    if ((int)t < du) sx[t] = F::canon(F::mul(R0[t], *snorm));
+    __syncthreads();
+    ddf_div_monic<F>(sres, sprod, smod, e, sx, du, t);
+    if ((int)t < du) stack[base + t] = sx[t];
+    if ((int)t < e - du) stack[base + du + t] = sres[t];
+    if (t == 0) { stk_deg[sp - 1] = du; stk_deg[sp] = e - du; stk_off[sp] = base + du; }
+    __syncthreads();
+}
 // All roots of one polynomial, or of one factor, of degree <= K in one workgroup of K threads, everything in LDS.  Block b reads
 // nin <= K + 1 coefficients (crate form, untrimmed, any non-zero leading coefficient) at in + b*ldin and writes its roots, in crate
 // form and in NO particular order, from out + b*ldout on; desc != nullptr gives block b the triple (input offset, input length,
@@ -2866,26 +2926,12 @@ __global__ __launch_bounds__(K) void k_roots_small(const typename F::elem* __res
     E* ob = out + b * ldout;
     if (desc) { fb = in + desc[3 * b]; nin = desc[3 * b + 1]; ob = out + desc[3 * b + 2]; }
     // ---- the true degree, and the row made monic (plain residues f_t / f_d) ----
-    if (t == 0) sdeg[0] = -1;
-    __syncthreads();
-    E mine = F::zero();
-    if (t < nin) mine = F::canon(fb[t]);
-    if (!F::is_zero(mine)) atomicMax(&sdeg[0], (int)t);
-    if (t == 0 && nin == K + 1 && !F::is_zero(F::canon(fb[K]))) atomicMax(&sdeg[0], K);
-    __syncthreads();
-    const int d = sdeg[0];
+    const int d = small_row_monic<F, K>(fb, nin, smod, &snorm, sdeg, t);
     if (d <= 0) {
         if (t == 0 && n_out) n_out[b] = d;                   // the zero polynomial: -1; a non-zero constant: no roots
         return;
     }
-    if (t == 0) snorm = F::canon(F::inv(F::canon(fb[d])));
-    __syncthreads();
-    {
-        E v = F::zero();
-        if ((int)t < d) v = F::canon(F::mul(mine, snorm));
-        stack[t] = v;
-        smod[t] = v;
-    }
+    stack[t] = smod[t];
     if (t == 0) { stk_deg[0] = d; stk_off[0] = 0; }
     __syncthreads();
     E* R0 = rows;
@@ -2942,24 +2988,8 @@ __global__ __launch_bounds__(K) void k_roots_small(const typename F::elem* __res
             continue;
         }
         fails = 0;
-        // u = R0 / lc(R0) (sx); v = h / u by synthetic division of A = h (sprod, with its leading 1) -> sres
-        if (t == 0) snorm = F::canon(F::inv(R0[du]));
-        __syncthreads();
-        if ((int)t < du) sx[t] = F::canon(F::mul(R0[t], snorm));
-        if ((int)t < e) sprod[t] = smod[t];
-        if (t == 0) sprod[e] = F::one();
-        __syncthreads();
-        for (int k = e - du; k >= 0; --k) {
-            const E qk = sprod[k + du];
-            if ((int)t < du) sprod[k + t] = F::canon(F::sub(sprod[k + t], F::canon(F::mul(qk, sx[t]))));
-            if (t == 0) sres[k] = qk;
-            __syncthreads();
-        }
-        if ((int)t < du) stack[base + t] = sx[t];
-        if ((int)t < e - du) stack[base + du + t] = sres[t];
-        if (t == 0) { stk_deg[sp - 1] = du; stk_deg[sp] = e - du; stk_off[sp] = base + du; }
+        split_push<F>(stack, stk_deg, stk_off, sp, base, e, R0, du, &snorm, sx, sres, sprod, smod, t);
         ++sp;
-        __syncthreads();
     }
     if (t == 0 && n_out) n_out[b] = (long long)nout;
 }
@@ -3039,23 +3069,6 @@ __device__ __forceinline__ int ddf_gcd_rows(typename F::elem*& R0, typename F::e
     gcd_remainder_loop<F>(R0, R1, d0, d1, none, none, none, none, c, c, 0u, 0, sdeg, t);
     return d0;
 }
-// quo[0 .. e - du] = A / u for the monic A of degree e (low e plain coefficients in a) and the monic u of degree du <= e (low du
-// plain coefficients in u): the synthetic division of k_roots_small.  work: e + 1 entries; quo[e - du] = 1.  a, u, quo, work
-// are four different rows.
-template <class F>
-__device__ __forceinline__ void ddf_div_monic(typename F::elem* quo, typename F::elem* work, const typename F::elem* a, int e,
-                                              const typename F::elem* u, int du, uint32_t t) {
-    using E = typename F::elem;
-    if ((int)t < e) work[t] = a[t];
-    if (t == 0) work[e] = F::one();
-    __syncthreads();
-    for (int k = e - du; k >= 0; --k) {
-        const E qk = work[k + du];
-        if ((int)t < du) work[k + t] = F::canon(F::sub(work[k + t], F::canon(F::mul(qk, u[t]))));
-        if (t == 0) quo[k] = qk;
-        __syncthreads();
-    }
-}
 // The squarefree part (mode 1) or the distinct-degree factors (mode 0) of one polynomial of degree <= K in one workgroup of K
 // threads, everything in LDS.  Block b reads nin <= K + 1 coefficients (crate form, untrimmed, any non-zero leading coefficient)
 // at in + b*ldin.
@@ -3087,27 +3100,11 @@ __global__ __launch_bounds__(K) void k_ddf_small(const typename F::elem* __restr
     E* ob = out + b * ldout;
     long long* db = deg_out + b * lddeg;
     // ---- the true degree, and the row made monic (plain residues f_t / f_d) ----
-    if (t == 0) sdeg[0] = -1;
     sout[t] = F::zero();
     sdegs[t] = 0;
-    __syncthreads();
-    E mine = F::zero();
-    if (t < nin) mine = F::canon(fb[t]);
-    if (!F::is_zero(mine)) atomicMax(&sdeg[0], (int)t);
-    if (t == 0 && nin == K + 1 && !F::is_zero(F::canon(fb[K]))) atomicMax(&sdeg[0], K);
-    __syncthreads();
-    const int d = sdeg[0];
+    const int d = small_row_monic<F, K>(fb, nin, smod, &snorm, sdeg, t);
     int ds = d;                                              // deg s
-    if (d >= 1) {
-        if (t == 0) snorm = F::canon(F::inv(F::canon(fb[d])));
-        __syncthreads();
-        {
-            E v = F::zero();
-            if ((int)t < d) v = F::canon(F::mul(mine, snorm));
-            smod[t] = v;
-        }
-        __syncthreads();
-    }
+    if (d >= 1) __syncthreads();
     if (d >= 2) {
         // ---- s = f / gcd(f, f') ----
         E* R0 = rows;
@@ -3282,24 +3279,10 @@ __global__ __launch_bounds__(K) void k_edf_small(const typename F::elem* __restr
     E* wb = ws + b * ldws;
     if (desc) { fb = in + desc[3 * b]; nin = desc[3 * b + 1]; ob = out + desc[3 * b + 2]; }
     // ---- the true degree, and the row made monic (plain residues g_t / g_n) ----
-    if (t == 0) sdeg[0] = -1;
-    __syncthreads();
-    E mine = F::zero();
-    if (t < nin) mine = F::canon(fb[t]);
-    if (!F::is_zero(mine)) atomicMax(&sdeg[0], (int)t);
-    if (t == 0 && nin == K + 1 && !F::is_zero(F::canon(fb[K]))) atomicMax(&sdeg[0], K);
-    __syncthreads();
-    const int n = sdeg[0];
+    const int n = small_row_monic<F, K>(fb, nin, sg, &snorm, sdeg, t);
     if (n <= 0 || (uint32_t)n % dd != 0) {
         if (t == 0 && n_out) n_out[b] = n <= 0 ? n : -2;
         return;
-    }
-    if (t == 0) snorm = F::canon(F::inv(F::canon(fb[n])));
-    __syncthreads();
-    {
-        E v = F::zero();
-        if ((int)t < n) v = F::canon(F::mul(mine, snorm));
-        sg[t] = v;
     }
     __syncthreads();
     const uint32_t r = (uint32_t)n / dd;
@@ -3407,17 +3390,8 @@ __global__ __launch_bounds__(K) void k_edf_small(const typename F::elem* __restr
         }
         if ((uint32_t)du % dd != 0) { if (t == 0) *flag = 1; break; }
         fails = 0;
-        // u = R0 / lc(R0) (sx); v = h / u by synthetic division of A = h (sprod, with its leading 1) -> sres
-        if (t == 0) snorm = F::canon(F::inv(R0[du]));
-        __syncthreads();
-        if ((int)t < du) sx[t] = F::canon(F::mul(R0[t], snorm));
-        __syncthreads();
-        ddf_div_monic<F>(sres, sprod, smod, e, sx, du, t);
-        if ((int)t < du) stack[base + t] = sx[t];
-        if ((int)t < e - du) stack[base + du + t] = sres[t];
-        if (t == 0) { stk_deg[sp - 1] = du; stk_deg[sp] = e - du; stk_off[sp] = base + du; }
+        split_push<F>(stack, stk_deg, stk_off, sp, base, e, R0, du, &snorm, sx, sres, sprod, smod, t);
         ++sp;
-        __syncthreads();
     }
     if (t == 0 && n_out) n_out[b] = (long long)nout;
 }

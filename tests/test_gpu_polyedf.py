@@ -5,7 +5,7 @@ to the kernel).  Every comparison is an equality of bytes or ints through the or
 outputs are known by CONSTRUCTION (tests/edf_ref.case): g = k prod q over distinct irreducibles q of degree d, the binomials
 x^d - a of tests/ddf_ref and their shifts (x + s)^d - a; the expected row is sorted(q[:-1] for q).
 
-Time on one MI355X: 22 s for the file (47 cases); the slowest case, (3, 100) for secp256k1 with both iterate methods forced, 3.9 s."""
+Time on one MI355X: 21 s for the file (49 cases); the slowest case, (3, 100) for secp256k1 with both iterate methods forced, 3.4 s."""
 import ctypes
 
 import numpy as np
@@ -14,6 +14,7 @@ import pytest
 import ddf_ref as D
 import edf_ref as E
 import poly_ref as R
+import roots_ref as RR
 from conftest import std_to_field
 
 pytestmark = pytest.mark.gpu
@@ -191,6 +192,34 @@ def test_large_regime_with_both_iterate_methods(oracle_mod, hooks_lib, field, d,
 def test_large_regime_shipped_rule(oracle_mod, field, d, r):
     """(2, 160): several rounds, no iterate at all; (63, 2) and (21, 4): the iterates dominate"""
     large(oracle_mod.field(field), field, d, r)
+
+
+@pytest.mark.parametrize("field", FIELDS)
+def test_linear_factors_and_find_roots_run_the_same_rounds(oracle_mod, field):
+    """200 distinct roots, 120 with r + 1 a square and 80 with r + 1 a non-square (chosen as test_gpu_polyroots.py's
+    test_unequal_splits_pad_a_group chooses them): 201 coefficients on the 512-leaf tree are the large regime of both calls.  The
+    first shift splits 200 = 120 + 80, both still pending and both of 256 leaves, so the second round is ONE group whose shorter
+    modulus is padded by x^40.  poly_equal_degree(g, 1) and poly_find_roots(g) run the one splitting loop: the negated constant
+    terms of the 200 factors, sorted, are exactly the roots array, and both are the constructed roots."""
+    F, p = oracle_mod.field(field), P[field]
+    a = 0x9E3779B1 if field == "m31" else 0x9E3779B97F4A7C15F39CC0605CEDC8341082276BF3A27251F86C6A11D0C18E95
+    sq, nsq = [], []
+    for i in range(2000):
+        x = (a * (i + 1) + 9000) % p
+        s = RR.legendre(x + 1, p)
+        if s == 1 and len(sq) < 120:
+            sq.append(x)
+        if s == -1 and len(nsq) < 80:
+            nsq.append(x)
+    roots = sq + nsq
+    assert len(sq) == 120 and len(nsq) == 80 and len(set(roots)) == 200
+    g = D.product([[-x % p, 1] for x in roots], p)
+    assert len(g) == 201 > small_max() and rule_leaves(201) == 512
+    t = tree(field, 512)
+    fac, n = check(F, field, t, 1, [g], [[[-x % p, 1] for x in roots]])
+    rho, nr = t.poly_find_roots(mem_rows(F, field, [g], 201))
+    assert n[0] == nr[0] == 200 and fac.shape[0] == rho.shape[0] == 200
+    assert sorted(-v % p for v in R.to_ints(field, to_std(F, fac))) == R.to_ints(field, to_std(F, rho)) == sorted(roots)
 
 
 @pytest.mark.parametrize("field", FIELDS)
