@@ -68,6 +68,8 @@ pub mod ffi {
         pub fn ecfft_poly_find_roots(ctx: *mut EcfftCtx, f: *const c_void, nf: usize, roots: *mut c_void, n_roots: *mut i64, count: usize, mem: i32, stream: *mut c_void) -> i32;
         pub fn ecfft_poly_gcd(ctx: *mut EcfftCtx, a: *const c_void, na: usize, b: *const c_void, nb: usize, g: *mut c_void, degrees: *mut i64, count: usize, mem: i32, stream: *mut c_void) -> i32;
         pub fn ecfft_poly_xgcd(ctx: *mut EcfftCtx, a: *const c_void, na: usize, b: *const c_void, nb: usize, s: *mut c_void, t: *mut c_void, g: *mut c_void, degrees: *mut i64, count: usize, mem: i32, stream: *mut c_void) -> i32;
+        pub fn ecfft_poly_xgcd_partial(ctx: *mut EcfftCtx, a: *const c_void, na: usize, b: *const c_void, nb: usize, stop: usize, r: *mut c_void, s: *mut c_void, t: *mut c_void, degrees: *mut i64, count: usize, mem: i32, stream: *mut c_void) -> i32;
+        pub fn ecfft_rs_decode(ctx: *mut EcfftCtx, points: *const c_void, m: usize, values: *const c_void, k: usize, message: *mut c_void, n_errors: *mut i64, count: usize, mem: i32, stream: *mut c_void) -> i32;
         pub fn ecfft_mextend(ctx: *mut EcfftCtx, inp: *const c_void, out: *mut c_void, e: usize, moiety: i32, count: usize, mem: i32, stream: *mut c_void) -> i32;
         pub fn ecfft_redc(ctx: *mut EcfftCtx, evals: *const c_void, a: *const c_void, out: *mut c_void, n: usize, moiety: i32, mem: i32, stream: *mut c_void) -> i32;
         pub fn ecfft_modular_reduce(ctx: *mut EcfftCtx, evals: *const c_void, a: *const c_void, c: *const c_void, out: *mut c_void, n: usize, mem: i32, stream: *mut c_void) -> i32;
@@ -496,6 +498,44 @@ impl<F: HipField> HipFFTree<F> {
             }
         }
         (s, t, g)
+    }
+
+    /// `ecfft_poly_xgcd_partial` (no reference counterpart): `(r, s, t)` with `r = s*a + t*b`, the first row of the classical
+    /// remainder sequence (`r_0 = a`, `r_1 = b`) with index `j >= 1` and `deg r < stop` (`deg 0 = -1`), scaled so that `t` is monic
+    /// (`s` where `t = 0`); all three trimmed to their degrees.  What rational reconstruction, Pade approximation and Gao's decoder
+    /// are built on.  Tree rule as `xgcd`: include/ecfft_hip.h.
+    pub fn xgcd_partial(&self, a: &[F], b: &[F], stop: usize) -> (Vec<F>, Vec<F>, Vec<F>) {
+        assert!(!a.is_empty() && !b.is_empty());
+        let n = a.len().max(b.len());
+        let mut r = Self::out_vec(n);
+        let mut s = Self::out_vec(b.len());
+        let mut t = Self::out_vec(a.len());
+        let mut deg: [i64; 3] = [-1; 3];
+        check(unsafe { ffi::ecfft_poly_xgcd_partial(self.ctx, a.as_ptr().cast(), a.len(), b.as_ptr().cast(), b.len(), stop, r.as_mut_ptr().cast(), s.as_mut_ptr().cast(), t.as_mut_ptr().cast(), deg.as_mut_ptr(), 1, ffi::MEM_HOST, core::ptr::null_mut()) });
+        unsafe {
+            r.set_len((deg[0] + 1) as usize);
+            s.set_len((deg[1] + 1) as usize);
+            t.set_len((deg[2] + 1) as usize);
+        }
+        (r, s, t)
+    }
+
+    /// `ecfft_rs_decode` (no reference counterpart): Reed-Solomon decoding with errors by Gao's algorithm.  `points`: `m` pairwise
+    /// distinct elements; `values`: the `m` received symbols; `1 <= k <= m`.  `Some((message, n_errors))`: the `k` coefficients of
+    /// the unique `f` of degree `< k` whose codeword differs from `values` in at most `(m - k) / 2` positions, and how many did;
+    /// `None` when there is none.  Up to `ECFFT_RS_SMALL_MAX` points work on any tree; tree rule: include/ecfft_hip.h.  Panics on
+    /// two equal points.
+    pub fn rs_decode(&self, points: &[F], values: &[F], k: usize) -> Option<(Vec<F>, usize)> {
+        assert!(!points.is_empty() && points.len() == values.len() && k >= 1 && k <= points.len());
+        let mut message = Self::out_vec(k);
+        let mut n_errors: i64 = -1;
+        check(unsafe { ffi::ecfft_rs_decode(self.ctx, points.as_ptr().cast(), points.len(), values.as_ptr().cast(), k, message.as_mut_ptr().cast(), &mut n_errors, 1, ffi::MEM_HOST, core::ptr::null_mut()) });
+        unsafe { message.set_len(k) };
+        if n_errors < 0 {
+            None
+        } else {
+            Some((message, n_errors as usize))
+        }
     }
 
     /// `ecfft::utils::find_roots` (src/utils.rs:25-44): the distinct roots of `f` in the field, in ascending order of their

@@ -2093,6 +2093,41 @@ public:
         if (degrees) for (size_t p = 0; p < count; ++p) degrees[p] = hdeg[p];
         return ok;
     }
+    // ---- ecfft_poly_xgcd_partial: the first row of the classical remainder sequence below a degree ----
+    // Per pair the row (r_j, s_j, t_j), r_j = s_j a + t_j b, with the smallest j >= 1 such that deg r_j < stop (deg 0 = -1), scaled
+    // so that t_j is monic (s_j where t_j = 0).  a: count x na, b: count x nb, r: count x max(na, nb), so: count x max(nb, 1) (may
+    // be null), to: count x max(na, 1), all zero-padded.  degrees (host, may be null): deg r, deg s, deg t per pair.
+    //   max(na, nb) <= kGcdSmall: one launch of k_xgcd_partial_small for all pairs.
+    //   otherwise the pairs run one after another: gcd_partial_pair.
+    // Synchronous.  Caller holds lock() and checks the tree rule (gcd_leaves).
+    bool poly_xgcd_partial(const E* a, size_t na, const E* b, size_t nb, size_t stop, E* r, E* so, E* to, long long* degrees, size_t count,
+                           hipStream_t s) {
+        const size_t ng = na > nb ? na : nb, ns = nb, nt = na;
+        if (stop > ng) stop = ng;                              // deg b < ng: every stop from ng up selects row 1
+        const E r1 = crate_one();
+        bool ok = true;
+        std::vector<long long> hdeg(3 * count, -1);
+        if (ng <= kGcdSmall) {
+            long long* ddeg = temp_as<long long>(3 * count);
+            for_chunks(count, [&](size_t c0, size_t c) {
+                ECFFT_LAUNCH(KC_POINTWISE, sizeof(E) * (double)c * (double)(na + nb + ng + ns + nt), (k_xgcd_partial_small<F, (int)kGcdSmall>),
+                             dim3((unsigned)c), dim3((unsigned)kGcdSmall), 0, s, a + c0 * na, na, (uint32_t)na, b + c0 * nb, nb, (uint32_t)nb,
+                             (int32_t)stop, r + c0 * ng, (uint32_t)ng, so ? so + c0 * ns : nullptr, (uint32_t)ns, to + c0 * nt, (uint32_t)nt,
+                             ddeg + 3 * c0, r1);
+            });
+            ok = hipMemcpyAsync(hdeg.data(), ddeg, 3 * count * sizeof(long long), hipMemcpyDeviceToHost, s) == hipSuccess;
+        } else {
+            gcd_flag_ = new_flag(s);
+            for (size_t p = 0; p < count && ok; ++p) {
+                const TempMark mark = temps_mark();
+                ok = gcd_partial_pair(a + p * na, na, b + p * nb, nb, stop, r + p * ng, ng, so ? so + p * ns : nullptr, ns, to + p * nt, nt, &hdeg[3 * p], s);
+                temps_release(mark);
+            }
+        }
+        ok = finish_api(s) && ok;
+        if (degrees) for (size_t p = 0; p < 3 * count; ++p) degrees[p] = hdeg[p];
+        return ok;
+    }
 
 private:
     // a 2x2 polynomial matrix of the half-GCD: rows 00, 01, 10, 11 at p + i*ld, each zero-padded to len <= ld coefficients
@@ -2205,6 +2240,20 @@ private:
         if (la <= kGcdSmall) ECFFT_LAUNCH(KC_POINTWISE, bytes, (k_gcd_small<F, (int)kGcdSmall>), dim3(1), dim3((unsigned)kGcdSmall), 0, s, args...);
         else ECFFT_LAUNCH(KC_POINTWISE, bytes, (k_gcd_small<F, (int)kGcdLeaf>), dim3(1), dim3((unsigned)kGcdLeaf), 0, s, args...);
     }
+    // The leaf of the recursion: out = the matrix of the remainder sequence of (a, b), la <= kGcdLeaf coefficients, down to the first
+    // row of degree below `bound`, by one launch of k_gcd_small in its leaf mode (out.p: 4 rows of out.ld >= la).  The row lengths
+    // and the number of swaps (0: the identity) are read back.
+    bool gcd_leaf_matrix(const E* a, size_t la, const E* b, size_t lb, size_t bound, GcdMat& out, hipStream_t s) {
+        int32_t* info = temp_as<int32_t>(8);
+        gcd_small_one(la, sizeof(E) * (double)(la + lb + 4 * la), s,
+                      a, la, (uint32_t)la, b, lb, (uint32_t)lb, (int32_t)bound, 1u, 1u, (E*)nullptr, 0u, (E*)nullptr, 0u, (E*)nullptr, 0u,
+                      (long long*)nullptr, out.p, out.ld, (uint32_t)la, info, crate_one());
+        int32_t h[8];
+        if (hipMemcpyAsync(h, info, sizeof(h), hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) return false;
+        out.ident = h[4] == 0;
+        out.len = (size_t)(h[2] > h[3] ? h[2] : h[3]);
+        return out.len <= la;
+    }
     // The half-GCD of (a, b), deg a > deg b (la > lb true lengths), in the form of Thull and Yap, which is correct for abnormal
     // remainder sequences: with n = deg a and m = ceil(n / 2), out = the matrix M_j of the Euclidean algorithm (rows scaled) with
     // deg r_j >= m > deg r_{j+1}, where (r_j, r_{j+1}) = M_j (a, b).  out.p holds 4 rows of out.ld >= la coefficients.
@@ -2215,17 +2264,7 @@ private:
         const size_t n = la - 1, m = (n + 1) / 2;
         out.ident = true; out.len = 1;
         if (lb < m + 1) return true;
-        if (la <= kGcdLeaf) {
-            int32_t* info = temp_as<int32_t>(8);
-            gcd_small_one(la, sizeof(E) * (double)(la + lb + 4 * la), s,
-                          a, la, (uint32_t)la, b, lb, (uint32_t)lb, (int32_t)m, 1u, 1u, (E*)nullptr, 0u, (E*)nullptr, 0u, (E*)nullptr, 0u,
-                          (long long*)nullptr, out.p, out.ld, (uint32_t)la, info, crate_one());
-            int32_t h[8];
-            if (hipMemcpyAsync(h, info, sizeof(h), hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) return false;
-            out.ident = h[4] == 0;
-            out.len = (size_t)(h[2] > h[3] ? h[2] : h[3]);
-            return out.len <= la;
-        }
+        if (la <= kGcdLeaf) return gcd_leaf_matrix(a, la, b, lb, m, out, s);
         const TempMark mark = temps_mark();
         GcdMat R; R.ld = la - m; R.p = temp(4 * R.ld);
         bool ok = gcd_half(a + m, la - m, b + m, lb - m, R, s);
@@ -2255,6 +2294,43 @@ private:
         temps_release(mark);
         return ok;
     }
+    // The state of the outer loop of gcd_pair and gcd_partial_pair: two consecutive rows (a, b) = M (a0, b0) of la and lb true
+    // coefficients on two alternating work buffers of 2 W, and M (cof only) on two alternating matrices of 4 W.
+    struct GcdRun {
+        const E* a; const E* b; size_t la, lb, W; bool cof;
+        E* work[2]; GcdMat acc[2]; int wi = 0, mi = 0;
+        GcdMat& mat() { return acc[mi]; }
+    };
+    GcdRun gcd_run_start(const E* a, size_t la, const E* b, size_t lb, size_t W, bool cof) {
+        GcdRun g{a, b, la, lb, W, cof};
+        g.work[0] = temp(2 * W); g.work[1] = temp(2 * W);
+        if (cof) for (auto& M : g.acc) { M.ld = W; M.p = temp(4 * W); }
+        return g;
+    }
+    // (a, b) <- R (a, b), M <- R M; the new lengths are read back
+    bool gcd_run_apply(GcdRun& g, const GcdMat& R, hipStream_t s) {
+        E* cd = g.work[g.wi]; g.wi ^= 1;
+        size_t l2[2] = {0, 0};
+        bool ok = gcd_apply(R, g.a, g.la, g.b, g.lb, cd, g.W, s) && gcd_row_lens(cd, g.W, g.W, 2, l2, s);
+        if (ok && g.cof) { ok = gcd_matmul(R, g.acc[g.mi], g.acc[g.mi ^ 1], s); g.mi ^= 1; }
+        g.a = cd; g.b = cd + g.W; g.la = l2[0]; g.lb = l2[1];
+        return ok;
+    }
+    // one division step (a, b) <- (b, a mod b), M <- Q M (la >= lb >= 1); the remainder's length is read back
+    bool gcd_run_divide(GcdRun& g, hipStream_t s) {
+        const size_t nq = g.la - g.lb + 1, W = g.W, lb = g.lb;
+        E* q = temp(nq);
+        E* cd = g.work[g.wi]; g.wi ^= 1;
+        size_t le = 0;
+        GcdRows<F> rows{}; rows.p[0] = g.b; rows.len[0] = lb;
+        gcd_gather(cd, rows, 1, W, s);
+        if (lb > 1) (void)hipMemsetAsync(cd + W + lb - 1, 0, (W - (lb - 1)) * sizeof(E), s);
+        else (void)hipMemsetAsync(cd + W, 0, W * sizeof(E), s);
+        bool ok = divrem_body(g.a, g.la, g.b, lb, q, cd + W, 1, gcd_flag_, s) && gcd_row_lens(cd + W, W, lb - 1, 1, &le, s);
+        if (ok && g.cof) { ok = gcd_qstep(q, nq, g.acc[g.mi], g.acc[g.mi ^ 1], s); g.mi ^= 1; }
+        g.a = cd; g.b = cd + W; g.la = lb; g.lb = le;
+        return ok;
+    }
     // One pair above kGcdSmall: true lengths first, the longer operand first (the cofactor outputs swap with it, as the Euclidean
     // algorithm's first step does), then { half-GCD; apply; one division step } on two alternating work buffers, the accumulated
     // matrix alternating likewise (want_cof only), until the pair fits k_gcd_small, which finishes and normalises it; its cofactors
@@ -2267,44 +2343,25 @@ private:
         const E* a = a0; const E* b = b0;
         if (la < lb) { std::swap(a, b); std::swap(la, lb); std::swap(so, to); std::swap(ns, nt); }
         if (!want_cof) so = to = nullptr;
-        const size_t W = ng + 1;
-        E* work[2] = {temp(2 * W), temp(2 * W)};
-        GcdMat acc[2];
-        if (want_cof) for (auto& M : acc) { M.ld = W; M.p = temp(4 * W); }
-        int wi = 0, mi = 0;
+        GcdRun run = gcd_run_start(a, la, b, lb, ng + 1, want_cof);
         bool ok = true;
         const E r1 = crate_one();
-        while (ok && lb > 0 && la > kGcdLeaf) {
+        while (ok && run.lb > 0 && run.la > kGcdLeaf) {
             const TempMark lvl = temps_mark();
-            if (la > lb) {
-                GcdMat R; R.ld = la; R.p = temp(4 * la);
-                ok = gcd_half(a, la, b, lb, R, s);
-                if (ok && !R.ident) {
-                    E* cd = work[wi]; wi ^= 1;
-                    size_t l2[2] = {0, 0};
-                    ok = gcd_apply(R, a, la, b, lb, cd, W, s) && gcd_row_lens(cd, W, W, 2, l2, s);
-                    if (ok && want_cof) { ok = gcd_matmul(R, acc[mi], acc[mi ^ 1], s); mi ^= 1; }
-                    a = cd; b = cd + W; la = l2[0]; lb = l2[1];
-                }
+            if (run.la > run.lb) {
+                GcdMat R; R.ld = run.la; R.p = temp(4 * run.la);
+                ok = gcd_half(run.a, run.la, run.b, run.lb, R, s);
+                if (ok && !R.ident) ok = gcd_run_apply(run, R, s);
             }
-            if (ok && lb > 0 && la > kGcdLeaf) {
-                if (la < lb) { temps_release(lvl); return false; }       // cannot happen: the rows of a remainder sequence
-                const size_t nq = la - lb + 1;
-                E* q = temp(nq);
-                E* cd = work[wi]; wi ^= 1;
-                size_t le = 0;
-                GcdRows<F> rows{}; rows.p[0] = b; rows.len[0] = lb;
-                gcd_gather(cd, rows, 1, W, s);
-                if (lb > 1) (void)hipMemsetAsync(cd + W + lb - 1, 0, (W - (lb - 1)) * sizeof(E), s);
-                else (void)hipMemsetAsync(cd + W, 0, W * sizeof(E), s);
-                ok = divrem_body(a, la, b, lb, q, cd + W, 1, gcd_flag_, s) && gcd_row_lens(cd + W, W, lb - 1, 1, &le, s);
-                if (ok && want_cof) { ok = gcd_qstep(q, nq, acc[mi], acc[mi ^ 1], s); mi ^= 1; }
-                a = cd; b = cd + W; la = lb; lb = le;
+            if (ok && run.lb > 0 && run.la > kGcdLeaf) {
+                if (run.la < run.lb) { temps_release(lvl); return false; }   // cannot happen: the rows of a remainder sequence
+                ok = gcd_run_divide(run, s);
             }
             temps_release(lvl);
         }
         if (!ok) return false;
-        GcdMat& M = acc[mi];
+        a = run.a; b = run.b; la = run.la; lb = run.lb;
+        GcdMat& M = run.mat();
         if (lb == 0) {
             // g = a / lc(a); (s, t) = the first row of M over lc(a)
             *deg = (long long)la - 1;
@@ -2347,6 +2404,84 @@ private:
         }
         ok = ok && hipMemcpyAsync(deg, ddeg, sizeof(long long), hipMemcpyDeviceToHost, s) == hipSuccess && hipStreamSynchronize(s) == hipSuccess;
         return ok;
+    }
+    // One pair of ecfft_poly_xgcd_partial above kGcdSmall: gcd_pair stopped at the straddle point.  deg b < stop: row 1 = (b, 0, 1).
+    // Otherwise the longer operand first (deg a < deg b: the sequence's own swap, the cofactor outputs swap with it), and with
+    // (x, y) = M (a, b) two consecutive rows, deg x >= stop, while deg y >= stop and x is above kGcdLeaf:
+    //   deg x = deg y: one division step (y has deg >= stop: the step cannot pass the wanted row).
+    //   m = ceil(deg x / 2) >= stop: gcd_half (it ends on rows of deg >= m > deg), then one division step if still deg y >= stop.
+    //   m < stop: gcd_half of (x div x^k, y div x^k), k = 2 stop - deg x: its operands have degree 2 (deg x - stop) and its
+    //     half-point deg x - stop, which is stop in the rows of (x, y) — the truncation of gcd_half's own second call — so it ends
+    //     on deg x' >= stop > deg y': y' is the wanted row.
+    // A pair that fits the leaf kernel finishes there with bound = stop, in its matrix form; its matrix joins M like any other.
+    // The wanted row is then y with the second row of M, made monic in t (in s where t = 0) by one inversion.  deg: deg r, s, t.
+    bool gcd_partial_pair(const E* a0, size_t na, const E* b0, size_t nb, size_t stop, E* r, size_t ng, E* so, size_t ns, E* to, size_t nt,
+                          long long* deg, hipStream_t s) {
+        size_t la = 0, lb = 0;
+        if (!gcd_row_lens(a0, na, na, 1, &la, s) || !gcd_row_lens(b0, nb, nb, 1, &lb, s)) return false;
+        const E r1 = crate_one();
+        if (lb <= stop) {
+            const size_t llb = lb;
+            foreach_n(s, ng, [=] __device__(size_t j) { E v = F::zero(); if (j < llb) v = F::canon(b0[j]); r[j] = v; });
+            if (so) (void)hipMemsetAsync(so, 0, ns * sizeof(E), s);
+            foreach_n(s, nt, [=] __device__(size_t j) { E v = F::zero(); if (j == 0) v = r1; to[j] = v; });
+            deg[0] = (long long)lb - 1; deg[1] = -1; deg[2] = 0;
+            return hipGetLastError() == hipSuccess;
+        }
+        const E* a = a0; const E* b = b0;
+        bool swapped = false;
+        if (la < lb) { std::swap(a, b); std::swap(la, lb); swapped = true; }
+        GcdRun run = gcd_run_start(a, la, b, lb, ng + 1, true);
+        bool ok = true;
+        while (ok && run.lb > stop && run.la > kGcdLeaf) {
+            const TempMark lvl = temps_mark();
+            if (run.la < run.lb) { temps_release(lvl); return false; }   // cannot happen: the rows of a remainder sequence
+            const size_t n = run.la - 1, m = (n + 1) / 2;
+            if (run.la == run.lb) {
+                ok = gcd_run_divide(run, s);
+            } else if (m >= stop) {
+                GcdMat R; R.ld = run.la; R.p = temp(4 * run.la);
+                ok = gcd_half(run.a, run.la, run.b, run.lb, R, s);
+                if (ok && !R.ident) ok = gcd_run_apply(run, R, s);
+                if (ok && run.lb > stop && run.la > kGcdLeaf) ok = gcd_run_divide(run, s);
+            } else {
+                const size_t k = 2 * stop - n;                           // stop <= deg y < n and 2 stop > n: 0 < k <= stop < lb
+                GcdMat R; R.ld = run.la - k; R.p = temp(4 * R.ld);
+                ok = gcd_half(run.a + k, run.la - k, run.b + k, run.lb - k, R, s);
+                ok = ok && !R.ident && gcd_run_apply(run, R, s);         // never the identity: deg y >= stop is its half-point,
+                ok = ok && run.lb <= stop;                               // and it ends below it
+            }
+            temps_release(lvl);
+        }
+        if (!ok) return false;
+        if (run.lb > stop) {
+            // the pair fits the kernel: its matrix down to the first row below stop (at least one swap: deg y >= stop)
+            GcdMat L; L.ld = run.la; L.p = temp(4 * run.la);
+            if (!gcd_leaf_matrix(run.a, run.la, run.b, run.lb, stop, L, s) || L.ident) return false;
+            if (!gcd_run_apply(run, L, s) || run.lb > stop) return false;
+        }
+        b = run.b; lb = run.lb;
+        GcdMat& M = run.mat();
+        if (M.ident) gcd_mat_materialise(M, s);
+        // the row (y; M10, M11), its cofactors in the order of (a0, b0)
+        const E* ps = M.at(swapped ? 3 : 2); const E* pt = M.at(swapped ? 2 : 3);
+        E* both = temp(2 * M.len);
+        GcdRows<F> rows{};
+        rows.p[0] = ps; rows.len[0] = M.len; rows.p[1] = pt; rows.len[1] = M.len;
+        gcd_gather(both, rows, 2, M.len, s);
+        size_t l2[2] = {0, 0};
+        if (!gcd_row_lens(both, M.len, M.len, 2, l2, s)) return false;
+        const size_t ls = l2[0], lt = l2[1], lr = lb;
+        if ((ls == 0 && lt == 0) || ls > ns || lt > nt || lr > ng) return false;   // cannot happen: a row of a unimodular matrix
+        const E* lead = lt ? both + M.len + lt - 1 : both + ls - 1;
+        const E* sp = both; const E* tp = both + M.len; const E* rp = b;
+        E* c = temp(1);
+        foreach_n(s, 1, [=] __device__(size_t) { c[0] = F::canon(F::mul(F::inv(F::canon(lead[0])), r1)); });
+        foreach_n(s, ng, [=] __device__(size_t j) { E v = F::zero(); if (j < lr) v = F::canon(F::mul(rp[j], c[0])); r[j] = v; });
+        if (so) foreach_n(s, ns, [=] __device__(size_t j) { E v = F::zero(); if (j < ls) v = F::canon(F::mul(sp[j], c[0])); so[j] = v; });
+        foreach_n(s, nt, [=] __device__(size_t j) { E v = F::zero(); if (j < lt) v = F::canon(F::mul(tp[j], c[0])); to[j] = v; });
+        deg[0] = (long long)lr - 1; deg[1] = (long long)ls - 1; deg[2] = (long long)lt - 1;
+        return hipGetLastError() == hipSuccess;
     }
     // ---- ecfft_poly_find_roots (utils::find_roots, src/utils.rs:25-44) ----
     // out (count x d, crate form) = (x + c)^exp mod f_b for `count` MONIC moduli of degree d > kRootsSmall laid end to end (f: count x
@@ -3694,15 +3829,21 @@ public:
     // P == B: k_interp_leaves is the whole interpolation, no transform.  Device pointers; synchronous (the flag of a zero weight
     // denominator is read back: *repeated = two equal points).  Caller holds lock() and checks the tree rule (P <= size() if P > B).
     bool poly_interpolate(const E* points, size_t m, const E* values, E* out, size_t count, bool* repeated, hipStream_t s) {
+        int* flag = new_flag(s);
+        const bool ok = interpolate_body(points, m, values, out, count, flag, nullptr, s);
+        return finish_flagged(ok, flag, repeated, s);
+    }
+    // poly_interpolate without its end of call: *flag is raised for two equal points, the temporaries stay the caller's.  m0 (may be
+    // null; needs P > B, m > kEvalLeaf): m + 1 coefficients that receive M = prod (x - x_i), which the weights pass through.
+    bool interpolate_body(const E* points, size_t m, const E* values, E* out, size_t count, int* flag, E* m0, hipStream_t s) {
         const size_t B = kEvalLeaf, P = eval_group(m), k = P - m, rpv = P / B, rows = count * rpv;
         const TE rinv = rinv_table();
-        int* flag = new_flag(s);
         bool ok = true;
         SubproductTree st;
         E* w = temp(m);                                          // plain 1 / M'(x_i)
         if (P > B) {
             ok = subproduct_tree(points, m, P, st, s) && ok;
-            ok = interp_weights(points, m, st, w, flag, s) && ok;
+            ok = interp_weights(points, m, st, w, flag, m0, s) && ok;
         } else {
             const E ri = rinv_;                                  // M'(x_i) = prod_{j != i} (x_i - x_j) over the m real points
             foreach_n(s, m, [=] __device__(size_t i) {
@@ -3744,13 +3885,78 @@ public:
         }
         if (k)
             ok = ok && hipMemcpy2DAsync(out, m * sizeof(E), top + k, P * sizeof(E), m * sizeof(E), count, hipMemcpyDeviceToDevice, s) == hipSuccess;
-        return finish_flagged(ok, flag, repeated, s);
+        return ok;
+    }
+    // ---- ecfft_rs_decode: Reed-Solomon decoding by Gao's algorithm ----
+    // code lengths up to this run a received word per workgroup (k_rs_decode_small), on any tree: g0 has m + 1 <= kGcdSmall coefficients
+    static constexpr size_t kRsSmall = kGcdSmall - 1;
+    static size_t rs_leaves(size_t m) { return m <= kRsSmall ? 1 : next_pow2(2 * m + 1); }
+    // message (count x k) = the coefficients of the f_b, deg f_b < k, that differ from values (count x m) on at most (m - k) / 2 of
+    // the m pairwise distinct points, n_errors[b] (host) the number of those positions; a zero row and -1 where there is none.
+    // g0 = prod (x - x_i), g1 = the interpolant of the row, (r, ., t) = the partial row of (g0, g1) with stop = ceil((m + k) / 2),
+    // f = r / t: the word decodes iff the division is exact and deg f < k, and then n_errors = deg t.
+    //   m <= kRsSmall: k_rs_prepare (g0, the Newton basis and the inverse denominators, shared by the rows), then ONE launch of
+    //     k_rs_decode_small for all rows.
+    //   otherwise interpolate_body for all rows at once (g0 from its weights pass), then per row gcd_partial_pair and divrem_body.
+    // Synchronous; *repeated = two equal points.  Caller holds lock() and checks the tree rule (rs_leaves).
+    bool rs_decode(const E* points, size_t m, const E* values, size_t k, E* message, long long* n_errors, size_t count, bool* repeated,
+                   hipStream_t s) {
+        const size_t stop = (m + k + 1) / 2;
+        const E r1 = crate_one();
+        int* flag = new_flag(s);
+        bool ok = true;
+        std::vector<long long> herr(count, -1);
+        E* g0 = temp(m + 1);
+        if (m <= kRsSmall) {
+            constexpr int G = (int)kGcdSmall;
+            E* np = temp(m * m); E* invd = temp(m * m);
+            long long* derr = temp_as<long long>(count);
+            ECFFT_LAUNCH(KC_POINTWISE, sizeof(E) * (2.0 * (double)m * (double)m + 2.0 * (double)m), (k_rs_prepare<F, G>), dim3((unsigned)m), dim3(G), 0, s,
+                         points, (uint32_t)m, np, g0, invd, rinv_, r1, flag);
+            for_chunks(count, [&](size_t c0, size_t c) {
+                ECFFT_LAUNCH(KC_POINTWISE, sizeof(E) * ((double)c * (double)(m + k) + 2.0 * (double)m * (double)m), (k_rs_decode_small<F, G>),
+                             dim3((unsigned)c), dim3(G), 0, s, values + c0 * m, (uint32_t)m, (uint32_t)k, (int32_t)stop, (const E*)np, (const E*)g0,
+                             (const E*)invd, message + c0 * k, derr + c0, r1);
+            });
+            ok = hipMemcpyAsync(herr.data(), derr, count * sizeof(long long), hipMemcpyDeviceToHost, s) == hipSuccess;
+        } else {
+            E* g1 = temp(count * m);
+            ok = interpolate_body(points, m, values, g1, count, flag, g0, s);
+            int h = 0;
+            ok = ok && hipMemcpyAsync(&h, flag, sizeof(int), hipMemcpyDeviceToHost, s) == hipSuccess && hipStreamSynchronize(s) == hipSuccess;
+            ok = ok && hipMemsetAsync(message, 0, count * k * sizeof(E), s) == hipSuccess;
+            gcd_flag_ = new_flag(s);
+            E* r = temp(m + 1); E* t = temp(m + 1);
+            for (size_t p = 0; p < count && ok && !h; ++p) {
+                const TempMark mark = temps_mark();
+                long long deg[3] = {-1, -1, -1};
+                ok = gcd_partial_pair(g0, m + 1, g1 + p * m, m, stop, r, m + 1, nullptr, m, t, m + 1, deg, s);
+                const long long dq = deg[0] - deg[2];
+                if (ok && deg[0] < 0) {
+                    herr[p] = deg[2];                            // r = 0: f = 0
+                } else if (ok && deg[2] >= 0 && dq >= 0 && dq < (long long)k) {
+                    const size_t lr = (size_t)deg[0] + 1, lt = (size_t)deg[2] + 1, lrem = lt - 1;
+                    E* q = temp((size_t)dq + 1); E* rem = temp(lrem ? lrem : 1);
+                    size_t nz = 0;
+                    ok = divrem_body(r, lr, t, lt, q, lrem ? rem : nullptr, 1, gcd_flag_, s) && gcd_row_lens(rem, lrem, lrem, 1, &nz, s);
+                    if (ok && nz == 0) {
+                        herr[p] = deg[2];
+                        ok = hipMemcpyAsync(message + p * k, q, ((size_t)dq + 1) * sizeof(E), hipMemcpyDeviceToDevice, s) == hipSuccess;
+                    }
+                }
+                temps_release(mark);
+            }
+        }
+        ok = finish_flagged(ok, flag, repeated, s);
+        for (size_t p = 0; p < count; ++p) n_errors[p] = herr[p];
+        return ok;
     }
     // The weights of ecfft_poly_interpolate: w[i] = 1 / M'(points[i]) in PLAIN form for i < m; raises *flag if some M'(x_i) is zero
     // (a repeated point).  The padded top polynomial Mp = x^k M has degree exactly P and does not fit T_P; with the two top nodes
     // M_l = x^(P/2) + A, M_r = x^(P/2) + B (one batched EXIT_P of the top level's M^): Mp = x^P + x^(P/2) (A + B) + A B, and A B
     // has < P coefficients: one product on T_P.  M'_j = (j + 1) Mp_{k+j+1}, the plain constant j + 1 keeps the crate form.
-    bool interp_weights(const E* points, size_t m, const SubproductTree& st, E* w, int* flag, hipStream_t s) {
+    // m0 (may be null): m + 1 coefficients that receive M itself, Mp's coefficients from k up, in crate form.
+    bool interp_weights(const E* points, size_t m, const SubproductTree& st, E* w, int* flag, E* m0, hipStream_t s) {
         const size_t P = st.npts, h = P / 2, k = P - m, B = kEvalLeaf;
         const TempMark mark = temps_mark();
         E* Mc = temp(2 * P); E* AB = temp(P); E* dM = temp(m); E* rem = temp(P);
@@ -3766,6 +3972,16 @@ public:
             }
             dM[j] = F::canon(F::mul(v, F::from_u32((uint32_t)(j + 1))));
         });
+        if (m0)
+            foreach_n(s, m + 1, [=] __device__(size_t j) {
+                const size_t c = k + j;
+                E v = r1;
+                if (c < P) {
+                    v = c < P - 1 ? AB[c] : F::zero();
+                    if (c >= h) v = F::add(v, F::add(F::canon(Mc[c - h]), F::canon(Mc[P + c - h])));
+                }
+                m0[j] = F::canon(v);
+            });
         ok = remainder_descent(dM, m, st, 1, rem, s) && ok;
         ECFFT_LAUNCH(KC_POINTWISE, sizeof(E) * ((double)P + 2.0 * (double)m), (k_eval_leaves<F, (int)kEvalLeaf>), dim3(nblocks(P)),
                      dim3(kBlock), 0, s, w, (const E*)rem, P, B, (uint32_t)B, points, m, P / B, P / B, rinv_table());

@@ -478,6 +478,51 @@ int run_poly_gcd(ecfft_ctx* c, DeviceChain<F>& ch, const void* a, size_t na, con
     });
 }
 
+// ecfft_poly_xgcd_partial: ecfft_poly_xgcd's checks and tree rule; three degrees per pair
+template <class F>
+int run_poly_xgcd_partial(ecfft_ctx* c, DeviceChain<F>& ch, const void* a, size_t na, const void* b, size_t nb, size_t stop, void* r, void* so,
+                          void* to, int64_t* degrees, size_t count, int mem, void* stream) {
+    using E = typename F::elem;
+    if (!a || !b || !r || !to) return ECFFT_ERR_BAD_ARG;
+    const size_t lim = SIZE_MAX / (64 * sizeof(E));
+    if (na > lim || nb > lim) return ECFFT_ERR_BAD_ARG;
+    const size_t ng = na > nb ? na : nb;
+    const size_t N = DeviceChain<F>::gcd_leaves(ng);
+    if (N > 1 && N > ch.size()) return ECFFT_ERR_TREE_TOO_SMALL;
+    const size_t per = N > 4 * ng ? N : 4 * ng;
+    if (count > SIZE_MAX / (16 * per * sizeof(E))) return ECFFT_ERR_BAD_ARG;  // byte counts of the rows and temporaries must not wrap
+    static_assert(DeviceChain<F>::kGcdSmall == ECFFT_XGCD_PARTIAL_SMALL_MAX, "the header states the small regime's bound");
+    const size_t eb = count * sizeof(E);
+    return staged(c, ch, mem, stream, {{a, na * eb}, {b, nb * eb}}, {{r, ng * eb}, {so, nb * eb}, {to, na * eb}}, [&](auto d, auto o) -> int {
+        return ch.poly_xgcd_partial((const E*)d[0], na, (const E*)d[1], nb, stop, (E*)o[0], (E*)o[1], (E*)o[2], (long long*)degrees, count,
+                                    (hipStream_t)stream) ? ECFFT_OK : ECFFT_ERR_HIP;
+    });
+}
+
+// ecfft_rs_decode: synchronous (the verdicts are returned to the host, and two equal points raise a device flag, reported as
+// ECFFT_ERR_BAD_ARG)
+template <class F>
+int run_rs_decode(ecfft_ctx* c, DeviceChain<F>& ch, const void* points, size_t m, const void* values, size_t k, void* message,
+                  int64_t* n_errors, size_t count, int mem, void* stream) {
+    using E = typename F::elem;
+    if (!points || !values || !message || !n_errors || k > m) return ECFFT_ERR_BAD_ARG;
+    if (m > SIZE_MAX / (64 * sizeof(E)) / 4) return ECFFT_ERR_BAD_ARG;
+    static_assert(DeviceChain<F>::kRsSmall == ECFFT_RS_SMALL_MAX, "the header states the small regime's bound");
+    static_assert(sizeof(long long) == sizeof(int64_t), "verdicts are read back as long long");
+    const size_t N = DeviceChain<F>::rs_leaves(m);                           // covers the interpolation and the partial xgcd of (m + 1, m)
+    if (N > 1 && N > ch.size()) return ECFFT_ERR_TREE_TOO_SMALL;
+    const size_t per = N > 4 * (m + 1) ? N : 4 * (m + 1);
+    if (N > SIZE_MAX / (8 * 64 * sizeof(E))) return ECFFT_ERR_BAD_ARG;       // node data of the interpolation
+    if (count > SIZE_MAX / (16 * per * sizeof(E))) return ECFFT_ERR_BAD_ARG;  // byte counts of the rows and temporaries must not wrap
+    const size_t eb = count * sizeof(E);
+    return staged(c, ch, mem, stream, {{points, m * sizeof(E)}, {values, m * eb}}, {{message, k * eb}}, [&](auto d, auto o) -> int {
+        bool repeated = false;
+        if (!ch.rs_decode((const E*)d[0], m, (const E*)d[1], k, (E*)o[0], (long long*)n_errors, count, &repeated, (hipStream_t)stream))
+            return ECFFT_ERR_HIP;
+        return repeated ? ECFFT_ERR_BAD_ARG : ECFFT_OK;                      // two equal points: no code
+    });
+}
+
 // ecfft_poly_find_roots: synchronous (degrees are read back between the rounds, and `n_roots` is a host array whatever `mem` is).
 // Nothing fails on the data; ECFFT_ERR_HIP also reports a factor that exhausted the attempt cap.
 template <class F>
@@ -1279,6 +1324,16 @@ int ecfft_poly_xgcd(ecfft_ctx* ctx, const void* a, size_t na, const void* b, siz
                     size_t count, int mem, void* stream) {
     if (na == 0 || nb == 0 || count == 0) return ECFFT_ERR_BAD_ARG;
     return on_chain(ctx, [&](auto& ch) { return run_poly_gcd(ctx, ch, a, na, b, nb, s, t, g, degrees, count, true, mem, stream); });
+}
+int ecfft_poly_xgcd_partial(ecfft_ctx* ctx, const void* a, size_t na, const void* b, size_t nb, size_t stop, void* r, void* s, void* t,
+                            int64_t* degrees, size_t count, int mem, void* stream) {
+    if (na == 0 || nb == 0 || count == 0) return ECFFT_ERR_BAD_ARG;
+    return on_chain(ctx, [&](auto& ch) { return run_poly_xgcd_partial(ctx, ch, a, na, b, nb, stop, r, s, t, degrees, count, mem, stream); });
+}
+int ecfft_rs_decode(ecfft_ctx* ctx, const void* points, size_t m, const void* values, size_t k, void* message, int64_t* n_errors,
+                    size_t count, int mem, void* stream) {
+    if (m == 0 || k == 0 || count == 0) return ECFFT_ERR_BAD_ARG;
+    return on_chain(ctx, [&](auto& ch) { return run_rs_decode(ctx, ch, points, m, values, k, message, n_errors, count, mem, stream); });
 }
 int ecfft_poly_find_roots(ecfft_ctx* ctx, const void* f, size_t nf, void* roots, int64_t* n_roots, size_t count, int mem, void* stream) {
     if (nf == 0 || count == 0) return ECFFT_ERR_BAD_ARG;

@@ -2742,6 +2742,187 @@ __global__ __launch_bounds__(G) void k_gcd_small(const typename F::elem* __restr
     if (s && t < ns) s[p * ns + t] = F::canon(F::mul(S0[t], c));
     if (tt && t < nt) tt[p * nt + t] = F::canon(F::mul(T0[t], c));
 }
+// ecfft_poly_xgcd_partial in one workgroup: k_gcd_small's rows and prologue, the loop stopped at bound = stop, and another
+// epilogue.  Every swap of gcd_remainder_loop is one row of the classical sequence (the first one, with deg a < deg b, its own
+// swap), so when the loop ends R1 is a scalar multiple of the first row r_j, j >= 1, with deg r_j < stop, and (S1, T1) of its
+// cofactors.  The scale is taken out by the one inversion of the pair: c = R / lc(T1), or R / lc(S1) where T1 = 0 (the row
+// (a, 1, 0)), so that t (else s) is monic.  r: row p of ng coefficients, s: ns (may be null), t: nt, zero-padded; deg_out + 3 p
+// (may be null) receives deg r, deg s, deg t, -1 for a zero row.
+template <class F, int G>
+__global__ __launch_bounds__(G) void k_xgcd_partial_small(const typename F::elem* __restrict__ a, size_t lda, uint32_t na,
+                                                          const typename F::elem* __restrict__ b, size_t ldb, uint32_t nb, int32_t stop,
+                                                          typename F::elem* __restrict__ r, uint32_t ng, typename F::elem* __restrict__ s,
+                                                          uint32_t ns, typename F::elem* __restrict__ tt, uint32_t nt,
+                                                          long long* __restrict__ deg_out, typename F::elem r1) {
+    using E = typename F::elem;
+    __shared__ E buf[6 * G];
+    __shared__ E snorm;
+    __shared__ int sdeg[2];
+    const uint32_t t = threadIdx.x;
+    const size_t p = blockIdx.x;
+    E *R0 = buf, *R1 = buf + G, *S0 = buf + 2 * G, *S1 = buf + 3 * G, *T0 = buf + 4 * G, *T1 = buf + 5 * G;
+    if (t < 2) sdeg[t] = -1;
+    __syncthreads();
+    {
+        E va = F::zero(), vb = F::zero(), one = F::zero();
+        if (t < na) va = F::canon(a[p * lda + t]);
+        if (t < nb) vb = F::canon(b[p * ldb + t]);
+        if (t == 0) one = r1;
+        R0[t] = va; R1[t] = vb;
+        if (!F::is_zero(va)) atomicMax(&sdeg[0], (int)t);
+        if (!F::is_zero(vb)) atomicMax(&sdeg[1], (int)t);
+        S0[t] = one; T0[t] = F::zero(); S1[t] = F::zero(); T1[t] = one;
+    }
+    __syncthreads();
+    int d0 = sdeg[0], d1 = sdeg[1], c0 = 1, c1 = 1;
+    __syncthreads();
+    if (t < 2) sdeg[t] = -1;
+    __syncthreads();
+    gcd_remainder_loop<F>(R0, R1, d0, d1, S0, S1, T0, T1, c0, c1, 1u, stop, sdeg, t);
+    __syncthreads();
+    if (t < 2) sdeg[t] = -1;
+    __syncthreads();
+    // the rows were all written at the start and are zero above their lengths: the true degrees of the two cofactors
+    if (!F::is_zero(S1[t])) atomicMax(&sdeg[0], (int)t);
+    if (!F::is_zero(T1[t])) atomicMax(&sdeg[1], (int)t);
+    __syncthreads();
+    const int ds = sdeg[0], dt = sdeg[1];
+    if (t == 0) {
+        E c = F::zero();
+        if (dt >= 0) c = F::canon(F::mul(F::inv(T1[dt]), r1));
+        else if (ds >= 0) c = F::canon(F::mul(F::inv(S1[ds]), r1));
+        snorm = c;
+        if (deg_out) { deg_out[3 * p] = d1; deg_out[3 * p + 1] = ds; deg_out[3 * p + 2] = dt; }
+    }
+    __syncthreads();
+    const E c = snorm;
+    if (t < ng) r[p * ng + t] = F::canon(F::mul(R1[t], c));
+    if (s && t < ns) s[p * ns + t] = F::canon(F::mul(S1[t], c));
+    if (t < nt) tt[p * nt + t] = F::canon(F::mul(T1[t], c));
+}
+// ---------------------------------------------------------------------------------------------
+// ecfft_rs_decode, small regime (m <= G - 1 points): Gao's decoder, a received word per workgroup.
+// ---------------------------------------------------------------------------------------------
+// What the rows of a call share, from the m points (crate form), in one launch of m workgroups of G threads:
+//   block 0: the Newton basis N_i = prod_{l < i} (x - x_l), i < m, as PLAIN coefficients (np + i m + t, t <= i; thread t owns
+//            coefficient t through the m steps N_{i+1} = x N_i - x_i N_i), and g0 = N_m in crate form (m + 1 coefficients);
+//   block j >= 1: the PLAIN inverse denominators of lag j, invd[j m + i] = 1 / (x_i - x_{i-j}) for j <= i < m: every pair of
+//            points meets in exactly one of them, so a zero difference (two equal points) raises *flag.
+// rinv = R^-1, r1 = R (M31: both 1): x R^-1 is the plain value of a crate-form x, and R / d the plain inverse of a crate-form d.
+template <class F, int G>
+__global__ __launch_bounds__(G) void k_rs_prepare(const typename F::elem* __restrict__ points, uint32_t m, typename F::elem* __restrict__ np,
+                                                  typename F::elem* __restrict__ g0, typename F::elem* __restrict__ invd,
+                                                  typename F::elem rinv, typename F::elem r1, int* __restrict__ flag) {
+    using E = typename F::elem;
+    __shared__ E row[G];
+    const uint32_t t = threadIdx.x, j = blockIdx.x;
+    if (j) {
+        if (t >= j && t < m) {
+            const E d = F::canon(F::sub(F::canon(points[t]), F::canon(points[t - j])));
+            E v = F::zero();
+            if (F::is_zero(d)) *flag = 1;
+            else v = F::canon(F::mul(F::inv(d), r1));
+            invd[(size_t)j * m + t] = v;
+        }
+        return;
+    }
+    E cur = F::zero();
+    if (t == 0) cur = F::one();
+    for (uint32_t i = 0; i < m; ++i) {
+        if (t <= i) np[(size_t)i * m + t] = cur;
+        row[t] = cur;
+        __syncthreads();
+        const E xi = F::canon(F::mul(F::canon(points[i]), rinv));
+        E lo = F::zero();
+        if (t) lo = row[t - 1];
+        cur = F::canon(F::sub(lo, F::canon(F::mul(xi, cur))));
+        __syncthreads();
+    }
+    if (t <= m) g0[t] = F::canon(F::mul(cur, r1));
+}
+// One received word of m <= G - 1 symbols per workgroup, everything in LDS, thread t owning coefficient t of every row:
+//   1. the interpolant g1: Newton's divided differences (m - 1 steps of one multiply by k_rs_prepare's inverse denominators; a
+//      thread keeps its own entry in a register and reads its neighbour's through two alternating rows, one barrier a step),
+//      then coefficient t of sum_i dd_i N_i as a sum over the basis rows in global memory — no sequential Horner;
+//   2. gcd_remainder_loop on (g0, g1) with bound = stop = ceil((m + k) / 2), the S rows aliased to the T rows (only the cofactor
+//      of g1 is needed): R1 = c r and T1 = c t for the wanted row (r, s, t) of the sequence and some scalar c;
+//   3. f = R1 / T1 by long division with T1 made monic as PLAIN numbers (one inversion, u = 1 / lc(T1)): the quotient of the
+//      stored numbers is lc(T1) times the plain f, so u R brings its coefficients to crate form.  The word decodes iff the
+//      remainder is zero and deg f < k.  message row p (k coefficients) = f, zero-padded, n_err[p] = deg t; else a zero row and -1.
+template <class F, int G>
+__global__ __launch_bounds__(G) void k_rs_decode_small(const typename F::elem* __restrict__ values, uint32_t m, uint32_t k, int32_t stop,
+                                                       const typename F::elem* __restrict__ np, const typename F::elem* __restrict__ g0,
+                                                       const typename F::elem* __restrict__ invd, typename F::elem* __restrict__ message,
+                                                       long long* __restrict__ n_err, typename F::elem r1) {
+    using E = typename F::elem;
+    __shared__ E buf[4 * G];
+    __shared__ E snorm;
+    __shared__ int sdeg[2];
+    const uint32_t t = threadIdx.x;
+    const size_t p = blockIdx.x;
+    E *R0 = buf, *R1 = buf + G, *T0 = buf + 2 * G, *T1 = buf + 3 * G;
+    E mine = F::zero();
+    if (t < m) mine = F::canon(values[p * m + t]);
+    {
+        E *A = T0, *B = T1;
+        for (uint32_t j = 1; j < m; ++j) {
+            A[t] = mine;
+            __syncthreads();
+            if (t >= j && t < m) mine = F::canon(F::mul(F::canon(F::sub(mine, A[t - 1])), invd[(size_t)j * m + t]));
+            E* x = A; A = B; B = x;
+        }
+    }
+    __syncthreads();
+    R0[t] = mine;                                            // the divided differences
+    if (t < 2) sdeg[t] = -1;
+    __syncthreads();
+    E acc = F::zero();
+    if (t < m)
+        for (uint32_t i = t; i < m; ++i) acc = F::canon(F::mul_add(np[(size_t)i * m + t], R0[i], acc));
+    __syncthreads();
+    {
+        E va = F::zero(), one = F::zero();
+        if (t <= m) va = g0[t];
+        if (t == 0) one = r1;
+        R0[t] = va; R1[t] = acc;
+        if (!F::is_zero(acc)) atomicMax(&sdeg[1], (int)t);
+        T0[t] = F::zero(); T1[t] = one;
+    }
+    __syncthreads();
+    int d0 = (int)m, d1 = sdeg[1], c0 = 1, c1 = 1;
+    __syncthreads();
+    if (t < 2) sdeg[t] = -1;
+    __syncthreads();
+    E *S0 = T0, *S1 = T1;
+    gcd_remainder_loop<F>(R0, R1, d0, d1, S0, S1, T0, T1, c0, c1, 1u, stop, sdeg, t);
+    __syncthreads();
+    if (t < 2) sdeg[t] = -1;
+    __syncthreads();
+    if (!F::is_zero(T1[t])) atomicMax(&sdeg[0], (int)t);     // written whole at the start and zero above its length
+    __syncthreads();
+    const int dt = sdeg[0], dq = d1 - dt;
+    bool good = dt >= 0 && (d1 < 0 || (dq >= 0 && dq < (int)k));
+    if (good && d1 >= 0) {
+        if (t == 0) snorm = F::canon(F::inv(T1[dt]));
+        __syncthreads();
+        if ((int)t < dt) T1[t] = F::canon(F::mul(T1[t], snorm));
+        __syncthreads();
+        for (int i = dq; i >= 0; --i) {
+            const E qi = R1[i + dt];
+            if ((int)t < dt) R1[i + (int)t] = F::canon(F::sub(R1[i + (int)t], F::canon(F::mul(qi, T1[t]))));
+            __syncthreads();
+        }
+        if ((int)t < dt && !F::is_zero(R1[t])) atomicMax(&sdeg[1], (int)t);
+        __syncthreads();
+        good = sdeg[1] < 0;
+    }
+    if (t < k) {
+        E v = F::zero();
+        if (good && d1 >= 0 && (int)t <= dq) v = F::canon(F::mul(R1[dt + (int)t], F::canon(F::mul(snorm, r1))));
+        message[p * k + t] = v;
+    }
+    if (t == 0) n_err[p] = good ? dt : -1;
+}
 // Rows of different lengths gathered into one zero-padded block: dst row r (blockIdx.y) of n coefficients = rows.p[r] below
 // rows.len[r].  The operands of the batched products of the half-GCD (matrix entries, remainders) live in separate buffers.
 template <class F>

@@ -33,12 +33,16 @@ EXPORTS = ["ecfft_elem_size", "ecfft_build_fftree", "ecfft_fftree_new", "ecfft_c
            "ecfft_comm_stats_enable", "ecfft_comm_stats_read", "ecfft_extend_sharded", "ecfft_enter_sharded", "ecfft_exit_sharded", "ecfft_device_copy", "ecfft_shader_clock", "ecfft_device_alloc", "ecfft_device_free", "ecfft_device_sync", "ecfft_build_extend_shard", "ecfft_ctx_device_bytes", "ecfft_extend_sharded_layout", "ecfft_build_enter_shard", "ecfft_build_exit_shard", "ecfft_build_exit_shard_opts",
            "ecfft_fftree_serialize", "ecfft_fftree_deserialize", "ecfft_tree_rational_maps", "ecfft_ctx_trim", "ecfft_comm_abort", "ecfft_comm_set_rccl_library", "ecfft_comm_set_link_striping",
            "ecfft_poly_mul", "ecfft_poly_inv_series", "ecfft_poly_divrem", "ecfft_poly_eval_points", "ecfft_poly_interpolate",
-           "ecfft_poly_pow_mod", "ecfft_poly_mul_mod", "ecfft_poly_gcd", "ecfft_poly_xgcd", "ecfft_poly_find_roots",
+           "ecfft_poly_pow_mod", "ecfft_poly_mul_mod", "ecfft_poly_gcd", "ecfft_poly_xgcd", "ecfft_poly_xgcd_partial", "ecfft_rs_decode", "ecfft_poly_find_roots",
            "ecfft_poly_compose_mod", "ecfft_poly_squarefree", "ecfft_poly_distinct_degree", "ecfft_poly_equal_degree", "ecfft_division_polynomial", "ecfft_curve_trace_mod", "ecfft_curve_cardinality",
            "ecfft_find_curve_candidate", "ecfft_curve_two_sylow", "ecfft_find_curve", "ecfft_build_fftree_on_curve",
            "ecfft_curve_point_mul", "ecfft_curve_point_two_adicity", "ecfft_curve_find_generator", "ecfft_build_ec_fftree"]
 # include/ecfft_hip.h ECFFT_GCD_SMALL_MAX: max(na, nb) up to which a gcd runs in one workgroup per pair, on any tree
 GCD_SMALL_MAX = 256
+# include/ecfft_hip.h ECFFT_XGCD_PARTIAL_SMALL_MAX: max(na, nb) up to which poly_xgcd_partial runs all pairs in one launch, on any tree
+XGCD_PARTIAL_SMALL_MAX = 256
+# include/ecfft_hip.h ECFFT_RS_SMALL_MAX: code length m up to which rs_decode decodes a row in one workgroup, on any tree
+RS_SMALL_MAX = 255
 # include/ecfft_hip.h ECFFT_ROOTS_SMALL_MAX: nf up to which poly_find_roots finishes a polynomial in one workgroup, on any tree
 ROOTS_SMALL_MAX = 65
 # include/ecfft_hip.h ECFFT_COMPOSE_SMALL_MAX: nm up to which poly_compose_mod runs Horner for a triple in one workgroup, on any tree
@@ -95,6 +99,8 @@ def _bind(L):
     L.ecfft_poly_compose_mod.restype, L.ecfft_poly_compose_mod.argtypes = ci, [vp, vp, sz, vp, sz, vp, sz, vp, sz, ci, vp]
     L.ecfft_poly_gcd.restype, L.ecfft_poly_gcd.argtypes = ci, [vp, vp, sz, vp, sz, vp, vp, sz, ci, vp]
     L.ecfft_poly_xgcd.restype, L.ecfft_poly_xgcd.argtypes = ci, [vp, vp, sz, vp, sz, vp, vp, vp, vp, sz, ci, vp]
+    L.ecfft_poly_xgcd_partial.restype, L.ecfft_poly_xgcd_partial.argtypes = ci, [vp, vp, sz, vp, sz, sz, vp, vp, vp, vp, sz, ci, vp]
+    L.ecfft_rs_decode.restype, L.ecfft_rs_decode.argtypes = ci, [vp, vp, sz, vp, sz, vp, vp, sz, ci, vp]
     L.ecfft_poly_find_roots.restype, L.ecfft_poly_find_roots.argtypes = ci, [vp, vp, sz, vp, vp, sz, ci, vp]
     L.ecfft_poly_squarefree.restype, L.ecfft_poly_squarefree.argtypes = ci, [vp, vp, sz, vp, vp, sz, ci, vp]
     L.ecfft_poly_distinct_degree.restype, L.ecfft_poly_distinct_degree.argtypes = ci, [vp, vp, sz, vp, vp, sz, ci, vp]
@@ -796,6 +802,45 @@ class FFTree:
             raise ValueError("poly_xgcd: empty operand, count = 0 or a context that holds no full tree")
         _check(rc)
         return s, t, g, degrees
+
+    def poly_xgcd_partial(self, a, b, stop, count=1):
+        """(r, s, t, degrees): the first row r = s*a + t*b of the classical remainder sequence (r_0 = a, r_1 = b, (s_0, t_0) = (1, 0),
+        (s_1, t_1) = (0, 1); deg a < deg b makes the first step a swap) with index j >= 1 and deg r < stop, where deg 0 = -1
+        (ecfft_poly_xgcd_partial): what rational reconstruction, Pade approximation and Gao's Reed-Solomon decoder need.  The row is
+        scaled so that t is monic (s where t = 0, the row (a, 1, 0)).  Operands as poly_gcd; r has count * max(na, nb), s count * nb
+        and t count * na coefficients, zero-padded; degrees is a numpy int64 array of shape (count, 3): deg r, deg s, deg t, -1 for
+        zero.  stop = 0 gives r = 0; any stop above deg b gives (b, 0, 1).  Tree, memory kinds and synchronisation as poly_gcd
+        (XGCD_PARTIAL_SMALL_MAX = GCD_SMALL_MAX)."""
+        (a, b), (pa, pb), new, mem, stream = self._poly_io([a, b])
+        assert count > 0 and a.shape[0] % count == 0 and b.shape[0] % count == 0 and stop >= 0
+        na, nb = a.shape[0] // count, b.shape[0] // count
+        r, s, t = new(count * max(na, nb)), new(count * nb), new(count * na)
+        degrees = np.empty((count, 3), np.int64)
+        rc = self._L.ecfft_poly_xgcd_partial(self._h, pa, na, pb, nb, int(stop), self._ptr(r) if r.shape[0] else None, self._ptr(s) if s.shape[0] else None,
+                                             self._ptr(t) if t.shape[0] else None, degrees.ctypes.data, count, mem, stream)
+        if rc == ERR_BAD_ARG:
+            raise ValueError("poly_xgcd_partial: empty operand, count = 0 or a context that holds no full tree")
+        _check(rc)
+        return r, s, t, degrees
+
+    def rs_decode(self, points, values, k, count=1):
+        """(message, n_errors): Reed-Solomon decoding with errors (ecfft_rs_decode, Gao's algorithm on poly_xgcd_partial).  points: m
+        pairwise distinct elements shared by all rows (the encoder is poly_eval_points at the same points); values: count * m received
+        symbols; 1 <= k <= m.  message has count * k coefficients: row b is the unique f of degree < k whose codeword differs from
+        row b of values in at most (m - k) // 2 positions; n_errors is a numpy int64 array of the number of corrected positions per
+        row, -1 where no such f exists (the message row is then zero).  m <= RS_SMALL_MAX works on any tree (one workgroup per row,
+        one launch for all rows); otherwise a tree of next_pow2(2 m + 1) leaves.  Two equal points, k = 0 or k > m raise ValueError.
+        numpy arrays (host) or contiguous CUDA tensors (device, on the current stream), both of the same kind.  Synchronous."""
+        (points, values), (pp, pv), new, mem, stream = self._poly_io([points, values])
+        m = points.shape[0]
+        assert count > 0 and m > 0 and values.shape[0] == count * m
+        message = new(count * max(int(k), 0))
+        n_errors = np.empty(count, np.int64)
+        rc = self._L.ecfft_rs_decode(self._h, pp, m, pv, int(k), self._ptr(message) if message.shape[0] else None, n_errors.ctypes.data, count, mem, stream)
+        if rc == ERR_BAD_ARG:
+            raise ValueError("rs_decode: two equal points, k = 0, k > m, count = 0 or a context that holds no full tree")
+        _check(rc)
+        return message, n_errors
 
     def poly_find_roots(self, f, count=1):
         """(roots, n_roots): the distinct roots in the field (ecfft_poly_find_roots <-> utils::find_roots, src/utils.rs:25-44) of

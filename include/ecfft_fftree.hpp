@@ -327,6 +327,29 @@ public:
         trim(s); trim(t);
         return {std::move(s), std::move(t), std::move(g)};
     }
+    // {r, s, t} with r = s*a + t*b: the first row of the classical remainder sequence (r_0 = a, r_1 = b) with index j >= 1 and
+    // deg r < stop (deg 0 = -1), scaled so that t is monic (s where t = 0), all three trimmed to their degrees
+    // (ecfft_poly_xgcd_partial; no reference counterpart).  Tree rule as xgcd.  Synchronous.
+    std::array<std::vector<Elem>, 3> xgcd_partial(const std::vector<Elem>& a, const std::vector<Elem>& b, size_t stop) const {
+        require(!a.empty() && !b.empty(), "xgcd_partial: operands must not be empty");
+        std::vector<Elem> r(std::max(a.size(), b.size())), s(b.size()), t(a.size());
+        int64_t deg[3] = {-1, -1, -1};
+        check(ecfft_poly_xgcd_partial(ctx_, a.data(), a.size(), b.data(), b.size(), stop, r.data(), s.data(), t.data(), deg, 1, ECFFT_MEM_HOST, nullptr));
+        r.resize((size_t)(deg[0] + 1)); s.resize((size_t)(deg[1] + 1)); t.resize((size_t)(deg[2] + 1));
+        return {std::move(r), std::move(s), std::move(t)};
+    }
+    // Reed-Solomon decoding with errors (ecfft_rs_decode, Gao's algorithm; no reference counterpart): the k coefficients of the
+    // unique f of degree < k whose codeword at the m pairwise distinct points differs from values in at most (m - k) / 2
+    // positions; n_errors (may be null) receives how many did, or -1 when there is no such f (the message is then zero).  Up to
+    // ECFFT_RS_SMALL_MAX points on any tree; tree rule in ecfft_hip.h.  Two equal points throw.  Synchronous.
+    std::vector<Elem> rs_decode(const std::vector<Elem>& points, const std::vector<Elem>& values, size_t k, int64_t* n_errors = nullptr) const {
+        require(!points.empty() && points.size() == values.size() && k >= 1 && k <= points.size(), "rs_decode: m points, m values and 1 <= k <= m");
+        std::vector<Elem> message(k);
+        int64_t n = -1;
+        check(ecfft_rs_decode(ctx_, points.data(), points.size(), values.data(), k, message.data(), &n, 1, ECFFT_MEM_HOST, nullptr));
+        if (n_errors) *n_errors = n;
+        return message;
+    }
     // the distinct roots of f in the field in ascending order of their standard form (ecfft_poly_find_roots <-> utils::find_roots,
     // src/utils.rs:25-44, whose result is sorted the same way).  f need not be trimmed; multiplicities do not matter; a non-zero
     // constant has none.  The zero polynomial, on which the reference panics, throws.  Up to ECFFT_ROOTS_SMALL_MAX coefficients on
@@ -469,6 +492,15 @@ public:
     // ... with the cofactors: s count x max(nb - 1, 1), t count x max(na - 1, 1); s or t may be null.  Synchronous.
     void xgcd_device(const Elem* a, size_t na, const Elem* b, size_t nb, Elem* s, Elem* t, Elem* g, int64_t* degrees, size_t count, void* stream) const {
         check(ecfft_poly_xgcd(ctx_, a, na, b, nb, s, t, g, degrees, count, ECFFT_MEM_DEVICE, stream));
+    }
+    // count pairs: the first row below `stop` (ecfft_poly_xgcd_partial): r count x max(na, nb), s count x nb (may be null), t count x na;
+    // degrees: count x 3 HOST entries (deg r, deg s, deg t) or null.  Synchronous.
+    void xgcd_partial_device(const Elem* a, size_t na, const Elem* b, size_t nb, size_t stop, Elem* r, Elem* s, Elem* t, int64_t* degrees, size_t count, void* stream) const {
+        check(ecfft_poly_xgcd_partial(ctx_, a, na, b, nb, stop, r, s, t, degrees, count, ECFFT_MEM_DEVICE, stream));
+    }
+    // count received words of m symbols at m shared points -> message count x k; n_errors: count HOST entries (-1: not decodable).  Synchronous.
+    void rs_decode_device(const Elem* points, size_t m, const Elem* values, size_t k, Elem* message, int64_t* n_errors, size_t count, void* stream) const {
+        check(ecfft_rs_decode(ctx_, points, m, values, k, message, n_errors, count, ECFFT_MEM_DEVICE, stream));
     }
     // count polynomials f count x nf (untrimmed), roots count x (nf - 1) sorted and zero-padded; n_roots: count HOST entries (-1: the
     // zero polynomial).  Synchronous.

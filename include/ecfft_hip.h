@@ -246,6 +246,54 @@ int ecfft_poly_gcd(ecfft_ctx* ctx, const void* a, size_t na, const void* b, size
 int ecfft_poly_xgcd(ecfft_ctx* ctx, const void* a, size_t na, const void* b, size_t nb, void* s, void* t, void* g, int64_t* degrees,
                     size_t count, int mem, void* stream);
 
+/* The first row of the remainder sequence below a degree: the half-GCD's own product, which rational reconstruction, Pade
+ * approximation, linear-recurrence synthesis (Berlekamp-Massey) and Gao's Reed-Solomon decoder are built on.  The reference has no
+ * counterpart (its xgcd, src/utils.rs:147-182, runs the sequence to its end).
+ * Layout as for ecfft_poly_xgcd: `count` pairs laid end to end, rows NEED NOT BE TRIMMED, either operand may be zero.
+ * Definition, per pair: the classical sequence r_0 = a, r_1 = b, r_{i+1} = r_{i-1} - q_i r_i with (s_0, t_0) = (1, 0) and
+ * (s_1, t_1) = (0, 1), so that r_i = s_i a + t_i b; a first quotient of 0 when deg a < deg b is the sequence's own swap
+ * (r_2 = a); the sequence ends at its first zero row.  The output is the row with the smallest j >= 1 such that
+ * deg r_j < stop, where deg 0 = -1, so such a row always exists (stop = 0 selects the zero row, whose t is +-a / gcd up to scale;
+ * any stop above deg b selects row 1).
+ * Normalisation: the row is scaled so that t is MONIC; where t = 0 — only the row (a, 1, 0), when deg a < stop <= deg b — so
+ * that s is monic.  That makes the output unique and bit-exact: b = 0 gives (0, 0, 1), a = 0 with stop <= deg b gives (0, 1, 0).
+ * Sizes: r is count x max(na, nb), s is count x nb, t is count x na, zero-padded, fully reduced, in the crate's form.  s may be
+ * NULL; r and t may not.  `degrees` is a HOST pointer whatever `mem` is, count x 3 entries (deg r, deg s, deg t; -1 for a zero
+ * polynomial), and may be NULL.
+ * ECFFT_XGCD_PARTIAL_SMALL_MAX (= ECFFT_GCD_SMALL_MAX): max(na, nb) up to which all pairs are ONE launch, a pair per workgroup in
+ * LDS, on any tree.  Above it the pairs run one after another on ecfft_poly_xgcd's bodies: half-GCD steps while their half-point
+ * is not below stop, then one half-GCD of the operands divided by x^k, k = 2 stop - deg, whose half-point is stop itself; a pair
+ * of at most 512 (secp256k1) or 1024 (M31) coefficients is finished by the workgroup kernel.  No step passes the wanted row.
+ * Tree rule, errors, synchrony, temporaries and threading are exactly those of ecfft_poly_xgcd (with r and t in the place of g). */
+#define ECFFT_XGCD_PARTIAL_SMALL_MAX 256
+int ecfft_poly_xgcd_partial(ecfft_ctx* ctx, const void* a, size_t na, const void* b, size_t nb, size_t stop, void* r, void* s, void* t,
+                            int64_t* degrees, size_t count, int mem, void* stream);
+
+/* Reed-Solomon decoding with errors, the headline application of the ECFFT: the encoder is ecfft_poly_eval_points (or ENTER on the
+ * tree's own points) and the erasure-only decoder ecfft_poly_interpolate.  The reference has no counterpart.
+ * points: m PAIRWISE DISTINCT elements shared by all rows, as in ecfft_poly_interpolate (0 and leaves of the tree are points like
+ * any other, in any order).  values: count x m received symbols.  1 <= k <= m.  message: count x k coefficients, fully reduced,
+ * in the crate's form: row b holds the unique f of degree < k whose codeword (f(x_0), ..., f(x_{m-1})) differs from row b of values
+ * in at most floor((m - k) / 2) positions.  `n_errors` is a HOST pointer whatever `mem` is, `count` entries, required: the number
+ * of corrected positions, or -1 when no such f exists; the message row is then zero.
+ * Method (Gao): g0 = prod (x - x_i), g1 = the interpolant of the row, (r, s, t) = the row of ecfft_poly_xgcd_partial(g0, g1) with
+ * stop = ceil((m + k) / 2), f = r / t.  Decoding succeeds iff the division leaves no remainder and deg f < k; then t is the error
+ * locator up to scale and n_errors = deg t.  Only the t cofactor is computed.
+ * ECFFT_RS_SMALL_MAX: m up to which a row is decoded by ONE workgroup, everything in LDS, on any tree — the shape of practical
+ * codes (length <= 255, many rows): one shared launch prepares g0, the Newton basis of the points and the inverse denominators
+ * of the divided differences, one launch decodes all `count` rows.  Above it g0 and all interpolants come from the body of
+ * ecfft_poly_interpolate at once and the rows then run one after another through the large regime of ecfft_poly_xgcd_partial
+ * and the division body of ecfft_poly_divrem.
+ * Tree: m <= ECFFT_RS_SMALL_MAX needs no transform (any tree).  Otherwise next_pow2(2 m + 1) leaves, which covers the
+ * interpolation (next_pow2(m)) and the partial xgcd of (m + 1, m) coefficients; else ECFFT_ERR_TREE_TOO_SMALL, checked before
+ * anything runs.
+ * ECFFT_ERR_BAD_ARG: a NULL pointer, m, k or count 0, k > m, a context that holds no full tree, a byte count that would wrap —
+ * and two equal points, which is checked on the device.  The call is SYNCHRONOUS; the context keeps working after an error.
+ * Outputs must not overlap the inputs.  Memory, stream, threading and pooled temporaries as for ecfft_poly_gcd. */
+#define ECFFT_RS_SMALL_MAX 255   /* code length m up to which a row is decoded by one workgroup, on any tree */
+int ecfft_rs_decode(ecfft_ctx* ctx, const void* points, size_t m, const void* values, size_t k, void* message, int64_t* n_errors,
+                    size_t count, int mem, void* stream);
+
 /* Roots of polynomials in the field.
  *   ecfft_poly_find_roots <-> ecfft::utils::find_roots(poly)                        src/utils.rs:25-44
  * Layout: f is count x nf coefficients in the crate's form; as in ecfft_poly_gcd the rows NEED NOT BE TRIMMED.  roots is
