@@ -143,6 +143,9 @@ public:
     // butterfly form of the context: 0 = general basis and butterflies, 1 = symmetric basis with the one-multiply butterflies in the
     // full-size row and column passes, 2 = symmetric basis under the general kernels (A/B)
     int sym_bfly() const { return !sym_ ? 0 : (sym_general_kernels_ ? 2 : 1); }
+    // which 1024-element low-level kernels run symmetric butterflies in their VALU sweeps: bit 0 = k_enter_low, bit 1 = k_exit_low
+    // (bit 1 in three-core contexts only: the four-core kernel keeps the register engine)
+    int low_sym() const { return (kLowSymEnter && low_sym_enter() ? 1 : 0) | (kLowSymExit && low_sym_exit() ? 2 : 0); }
     int low_map(int dir) const {
         if (trees_.size() > 5 && trees_[5].low32_A[dir]) return 32;
         if (trees_.size() > 4 && trees_[4].low16_A[dir]) return 16;
@@ -808,6 +811,9 @@ public:
     // better than 8 on M31 at 2^24 and equal below, profiles/r02/knob_sweep.txt)
     static constexpr unsigned kColStages = sizeof(E) == 4 ? ECFFT_COL_STAGES_4B : ECFFT_COL_STAGES;
     static constexpr bool kSymKernels = sizeof(E) == 32 && ECFFT_SYM_BFLY != 0;   // the SYM instantiations exist for 32-byte fields only
+    // ... and in the VALU sweeps of the 1024-element low-level ENTER kernel (-DECFFT_ENTER_LOW_SYM=0 keeps the general sweeps there)
+    static constexpr bool kLowSymEnter = kSymKernels && ECFFT_ENTER_LOW_SYM != 0;
+    // ... and of the three-core low-level EXIT kernel (-DECFFT_EXIT_LOW_SYM=0 keeps its register engine; kLowSymExit is defined next to kExitLowForm)
     static constexpr unsigned kLogColTileMax = (sizeof(E) == 32) ? ECFFT_LOG_COL_TILE_BYTES - 5 : ECFFT_LOG_COL_TILE_BYTES - 2;
     // Fusion of consecutive cores (EXIT): `next_ld` != nullptr says that another core of the same tree and size, opposite
     // direction, follows on `buf` with that load operator; if this core ends in a column pass, that pass and the next
@@ -1521,7 +1527,10 @@ public:
             // levels 1..ll: one launch, one HBM round trip (k_enter_low)
             E* dst = (l_end == ll && out != in) ? out : bufA;
             double bytes = 0; for (unsigned l = 1; l <= ll; ++l) bytes += enter_level_alg_bytes(nt, l);
-            if (ll == kLogLow)
+            if (ll == kLogLow && kLowSymEnter && low_sym_enter())       // symmetric context: one-multiply butterflies in the cores' VALU sweeps
+                ECFFT_LAUNCH(KC_FUSED_ENTER, bytes, (k_enter_low<F, (int)kLogLow, (int)kBlockLds, kLowSymEnter>), dim3((unsigned)(nt >> kLogLow)), dim3(kBlockLds),
+                             2 * (sizeof(E) << kLogLow), s, dst, src, (const Tree*)d_trees_);
+            else if (ll == kLogLow)
                 ECFFT_LAUNCH(KC_FUSED_ENTER, bytes, (k_enter_low<F, (int)kLogLow>), dim3((unsigned)(nt >> kLogLow)), dim3(kBlockLds),
                              2 * (sizeof(E) << kLogLow), s, dst, src, (const Tree*)d_trees_);
             else
@@ -1561,6 +1570,7 @@ public:
 #define ECFFT_EXIT_LOW_CORES 3  // EXTEND cores per level of k_exit_low's loop in a three-core context; 4 = the four-core kernel under a three-core driver (A/B)
 #endif
     static constexpr int kExitLowForm = (ECFFT_EXIT_CORES == 4 || ECFFT_EXIT_LOW_CORES == 4) ? 4 : 3;   // the second k_exit_low form a build holds
+    static constexpr bool kLowSymExit = kSymKernels && ECFFT_EXIT_LOW_SYM != 0 && kExitLowForm == 3;   // k_exit_low<10,512,3,SYM> exists and is used
     static constexpr unsigned kSplitMinLog = ECFFT_SPLIT_MIN_LOG;   // single transforms of at least 2^this run as concurrent halves
 #ifndef ECFFT_SPLIT_DEPTH
 #define ECFFT_SPLIT_DEPTH 1
@@ -1689,7 +1699,10 @@ public:
             // the kernel's level loop runs the context's form (the credit above models the reference's four cores all the same)
             const bool low3 = exit_low_cores() == 3;
             if (ll == kLogLow) {
-                if (low3) ECFFT_LAUNCH(KC_FUSED_EXIT, bytes, (k_exit_low<F, (int)kLogLow, (int)kBlockLds, kExitLowForm>), dim3((unsigned)(n >> kLogLow)), dim3(kBlockLds),
+                if (low3 && kLowSymExit && low_sym_exit())      // symmetric context: pair-per-thread one-multiply sweeps in the cores
+                    ECFFT_LAUNCH(KC_FUSED_EXIT, bytes, (k_exit_low<F, (int)kLogLow, (int)kBlockLds, kExitLowForm, kLowSymExit>), dim3((unsigned)(n >> kLogLow)), dim3(kBlockLds),
+                                 2 * (sizeof(E) << kLogLow), s, dst, cur, (const Tree*)d_trees_);
+                else if (low3) ECFFT_LAUNCH(KC_FUSED_EXIT, bytes, (k_exit_low<F, (int)kLogLow, (int)kBlockLds, kExitLowForm>), dim3((unsigned)(n >> kLogLow)), dim3(kBlockLds),
                                        2 * (sizeof(E) << kLogLow), s, dst, cur, (const Tree*)d_trees_);
                 else ECFFT_LAUNCH(KC_FUSED_EXIT, bytes, (k_exit_low<F, (int)kLogLow, (int)kBlockLds, 4>), dim3((unsigned)(n >> kLogLow)), dim3(kBlockLds),
                                   2 * (sizeof(E) << kLogLow), s, dst, cur, (const Tree*)d_trees_);
@@ -4713,6 +4726,10 @@ private:
     bool sym_off_ = ab_env("ECFFT_NO_SYM_BFLY") != nullptr;
     bool sym_general_kernels_ = ab_env("ECFFT_SYM_BFLY_GENERAL_KERNELS") != nullptr;
     bool sym_kernels() const { return sym_ && !sym_general_kernels_; }
+    bool low_general_kernels_ = ab_env("ECFFT_LOW_GENERAL_KERNELS") != nullptr;   // A/B switch: general low-level kernels under symmetric row and column passes
+    // (a context of the four-core A/B form, exit4_, keeps the general low-level kernels as well: it is the reference form throughout)
+    bool low_sym_enter() const { return sym_kernels() && !low_general_kernels_ && !exit4_; }
+    bool low_sym_exit() const { return low_sym_enter() && exit_low_cores() == 3; }
 };
 
 }  // namespace ecfft

@@ -681,7 +681,8 @@ __device__ __forceinline__ void lds_extend_fast(typename F::elem* a, const typen
 // (downwards for DEC, upwards otherwise), table entry e - 2h + (pair index mod h).  Ends with a barrier.
 // lh_after: pair-distance log of a one-pair-per-thread consumer that follows the last sweep (then the closing barrier is relaxed
 // like the ones between wave-local sweeps), or 99 = the consumer reads other waves' elements.
-template <class F, bool DEC, bool SYM = false>
+// PIPE = false (SYM only, an A/B form): every sweep requests its own constant after the barrier, as the low kernels' sweeps did.
+template <class F, bool DEC, bool SYM = false, bool PIPE = true>
 __device__ __forceinline__ void row_stages_pipe(typename F::elem* tile, const typename F::telem* __restrict__ ta, const typename F::telem* __restrict__ tb,
                                                 uint32_t e, int lh_from, int lh_to, uint32_t tid, int lh_after = 99) {
     using E = typename F::elem;
@@ -695,15 +696,17 @@ __device__ __forceinline__ void row_stages_pipe(typename F::elem* tile, const ty
     geom(lh_from, idx, ti);
     if constexpr (SYM) {      // symmetric butterflies (sym_bfly below): ONE constant per pair, dinv (DEC) or p0
         const TE* __restrict__ tk = DEC ? tb : ta;
-        TE nk = ldt(tk, ti);
+        TE nk;
+        if constexpr (PIPE) nk = ldt(tk, ti);
 #pragma unroll 1
         for (int lh = lh_from; DEC ? lh >= lh_to : lh <= lh_to; lh += DEC ? -1 : 1) {
+            if constexpr (!PIPE) nk = ldt(tk, ti);
             const TE t = nk;
             const uint32_t lo = idx, up = idx + (1u << lh);
             E a = tile[lo], b = tile[up];
             sym_bfly<F, DEC>(a, b, t);
             tile[lo] = a; tile[up] = b;
-            if (lh != lh_to) { geom(lh + (DEC ? -1 : 1), idx, ti); nk = ldt(tk, ti); }
+            if (lh != lh_to) { geom(lh + (DEC ? -1 : 1), idx, ti); if constexpr (PIPE) nk = ldt(tk, ti); }
             const int nxt = lh != lh_to ? lh + (DEC ? -1 : 1) : lh_after;
             if (wave_local_lh(lh) && wave_local_lh(nxt)) wave_local_sync(); else lds_barrier();
         }
@@ -1684,9 +1687,73 @@ __device__ __forceinline__ void reg_extend32(typename F::elem* a, uint32_t len, 
     __syncthreads();
 }
 
+// PAIR-PER-THREAD engine of a 512-element EXTEND core on symmetric tables (k_exit_low<10,512,3,SYM>).  On the
+// register engine above both lanes of a pair execute the multiply's instruction stream, so a one-multiply butterfly saves nothing
+// there.  Here the VALU stages (pair distance 2^(log_e-1) .. 16 down, then up) run as sym_bfly sweeps on `a` in LDS, one pair per
+// thread: 256 pairs on HALF of the workgroup (four waves, 64 consecutive pairs each, so sweeps at distance <= 64 stay inside the
+// wave's own 128-element span); the other half only takes part in the barriers.  The sweeping half requests the next sweep's
+// constant before the barrier, as row_stages_pipe does.  The matrix-core phase stays on all eight waves.  Same arithmetic on the
+// same residues as the general form: the same bytes.  `a` published by a barrier; ends with one.
+#ifndef ECFFT_EXIT_LOW_SYM
+#define ECFFT_EXIT_LOW_SYM 1          // 0: k_exit_low<10,512,3> keeps the register engine in symmetric contexts (A/B)
+#endif
+// which four waves sweep: 0 = waves 0..3 (one sweeping wave per SIMD: waves w and w + 4 share one), 1 = the even waves (two on each
+// of two SIMDs).  Measured (profiles/low_sym/low_sym_ab.txt): 0 gains 0.07 ms per step on the register engine, 1 nothing.
+#ifndef ECFFT_EXIT_LOW_SYM_WAVES
+#define ECFFT_EXIT_LOW_SYM_WAVES 0
+#endif
+template <class F, bool DEC, bool SWZ>
+__device__ __forceinline__ void half_stages_pipe(typename F::elem* a, const typename F::telem* __restrict__ tk, uint32_t e, int lh_from, int lh_to,
+                                                 uint32_t q, bool sw) {
+    using E = typename F::elem;
+    using TE = typename F::telem;
+    auto geom = [&](int lh, uint32_t& idx, uint32_t& ti) {
+        const uint32_t h = 1u << lh, i = q & (h - 1);
+        idx = ((q >> lh) << (lh + 1)) + i; ti = e - 2 * h + i;
+    };
+    uint32_t idx = 0, ti = 0;
+    TE nk;
+    if (sw) { geom(lh_from, idx, ti); nk = ldt(tk, ti); }
+#pragma unroll 1
+    for (int lh = lh_from; DEC ? lh >= lh_to : lh <= lh_to; lh += DEC ? -1 : 1) {
+        if (sw) {                                                           // wave-uniform
+            const TE t = nk;
+            const uint32_t lo = idx, up = idx + (1u << lh);
+            E x = lds_get<F, SWZ>(a, lo), y = lds_get<F, SWZ>(a, up);
+            sym_bfly<F, DEC>(x, y, t);
+            lds_put<F, SWZ>(a, lo, x); lds_put<F, SWZ>(a, up, y);
+            if (lh != lh_to) { geom(lh + (DEC ? -1 : 1), idx, ti); nk = ldt(tk, ti); }
+        }
+        const int nxt = lh != lh_to ? lh + (DEC ? -1 : 1) : 99;              // the phase / the caller reads other waves' elements
+        if (wave_local_lh(lh) && wave_local_lh(nxt)) wave_local_sync(); else lds_barrier();
+    }
+}
+template <class F, bool SWZ>
+__device__ __forceinline__ void pair_extend512(typename F::elem* a, uint32_t log_e, const typename F::telem* __restrict__ dinv, const typename F::telem* __restrict__ p0,
+                                               uint32_t tid, const uint8_t* __restrict__ blkA, const unsigned long long* __restrict__ blkK) {
+    using E = typename F::elem;
+    // log_e in 5 .. 9, 512 elements, 512 threads
+    const bool sw = ECFFT_EXIT_LOW_SYM_WAVES ? ((tid >> 6) & 1u) == 0 : tid < 256u;
+    const uint32_t q = ECFFT_EXIT_LOW_SYM_WAVES ? (((tid >> 7) << 6) | (tid & 63u)) : (tid & 255u);
+    const uint32_t e = 1u << log_e;
+    half_stages_pipe<F, true, SWZ>(a, dinv, e, (int)log_e - 1, 4, q, sw);
+    E x = lds_get<F, SWZ>(a, tid);
+    x = Blk16::phase512_regs(a, x, blkA, blkK, tid);                       // its first barrier: every read above is done
+    __syncthreads();                                                        // the phase's swizzled results are read
+    lds_put<F, SWZ>(a, tid, x);
+    __syncthreads();
+    half_stages_pipe<F, false, SWZ>(a, p0, e, 4, (int)log_e - 1, q, sw);
+}
+
 // every stage (decompose then recombine) of EXTEND on `len` LDS elements = len/e vectors of length e;
 // srcpar = parity of the source moiety.  Ends with a barrier.
-template <class F, int BLK = kBlockLds, bool SWZ = false>      // SWZ: `a` in the XOR-swizzled layout — only the register engine (len <= BLK) reads it that way
+// SYM (symmetric tables): the one-pair-per-thread VALU sweeps next to a matrix-core phase (len == 2 * BLK == 1024,
+// k_enter_low<10,512>'s cores) run the row kernel's engine: sym_bfly, ONE multiply and one constant per pair, the next sweep's
+// constant requested before the barrier.  Every other path keeps the general form.
+#ifndef ECFFT_ENTER_LOW_SYM
+#define ECFFT_ENTER_LOW_SYM 1   // 0: k_enter_low keeps the general sweeps in symmetric contexts; 2: symmetric sweeps without the constant pipelining (A/B)
+#endif
+template <class F, int BLK = kBlockLds, bool SWZ = false, bool SYM = false>      // SWZ: `a` in the XOR-swizzled layout — only the register engine (len <= BLK) reads it that way
 __device__ __forceinline__ void lds_extend_core(typename F::elem* a, uint32_t len, uint32_t log_e, const LevelTables<F>& T, int srcpar) {
     using E = typename F::elem;
     // The thread index is made opaque per call (32-byte fields): the callers run this core once per LEVEL in a loop, and with a
@@ -1708,6 +1775,10 @@ __device__ __forceinline__ void lds_extend_core(typename F::elem* a, uint32_t le
     }
     if constexpr (sizeof(E) == 32 && (BLK == 256 || BLK == 128)) {          // latency variants: one element per thread
         if (log_e >= 4 && len == (uint32_t)BLK) { bA = T.blk16_A[srcpar]; bK = T.blk16_K[srcpar]; }
+    }
+    if constexpr (SYM && sizeof(E) == 32 && BLK == 512 && ECFFT_EXIT_LOW_SYM != 0) {
+        // k_exit_low<10,512,3,SYM>'s half-tiles: symmetric pair-per-thread sweeps around the matrix-core phase
+        if (len == (uint32_t)BLK && bA && log_e >= 5) { pair_extend512<F, SWZ>(a, log_e, T.dinv[srcpar], T.p0[tgt], tid, bA, bK); return; }
     }
     if constexpr (sizeof(E) == 32 && ECFFT_REG_ENGINE) {
         if (len <= (uint32_t)BLK && (len & 63u) == 0) {
@@ -1767,6 +1838,13 @@ __device__ __forceinline__ void lds_extend_core(typename F::elem* a, uint32_t le
     // one-pair-per-thread sweeps (32-byte fields, at least one pair per thread): the sweeps at pair distance <= 64 stay inside the
     // wave's own span, and so does the merged innermost stage — no workgroup barrier between them (wave_local_sync)
     const bool wl = sizeof(E) == 32 && 2 * npairs > (uint32_t)BLK;
+    bool symp = false;                                  // symmetric pipelined sweeps at pair distance 2^(log_e-1) .. 16
+    if constexpr (SYM && sizeof(E) == 32 && BLK == 512) {
+        symp = mfma && npairs == (uint32_t)BLK;
+        // to_operand_form reads elements of other waves' spans: the last decompose sweep closes with a workgroup barrier (lh_after = 99)
+        if (symp) row_stages_pipe<F, true, true, ECFFT_ENTER_LOW_SYM != 2>(a, T.np0[srcpar], T.dinv[srcpar], (uint32_t)e, (int)log_e - 1, 4, tid);
+    }
+    if (!symp)
     for (uint32_t k = 0; k < k_dec_end; ++k) {
         const uint32_t lh = log_e - k - 1, h = 1u << lh;
         stage_sweep<F, true, BLK>(a, T.np0[srcpar] + (e - 2 * (size_t)h), T.dinv[srcpar] + (e - 2 * (size_t)h), lh, npairs, tid, T.c0t[srcpar] + (e - 2 * (size_t)h));
@@ -1795,6 +1873,10 @@ __device__ __forceinline__ void lds_extend_core(typename F::elem* a, uint32_t le
         }
         if (wl && ECFFT_WAVE_LOCAL && k_dec_end > 0) wave_local_sync(); else __syncthreads();
     }
+    if constexpr (SYM && sizeof(E) == 32 && BLK == 512) {
+        // from_swizzled ended with a workgroup barrier; the last recombine sweep ends the core with one
+        if (symp) { row_stages_pipe<F, false, true, ECFFT_ENTER_LOW_SYM != 2>(a, T.p0[tgt], T.p1[tgt], (uint32_t)e, 4, (int)log_e - 1, tid); return; }
+    }
     for (uint32_t k = k_dec_end; k-- > 0;) {
         const uint32_t lh = log_e - k - 1, h = 1u << lh;
         stage_sweep<F, false, BLK>(a, T.p0[tgt] + (e - 2 * (size_t)h), T.p1[tgt] + (e - 2 * (size_t)h), lh, npairs, tid);
@@ -1803,7 +1885,8 @@ __device__ __forceinline__ void lds_extend_core(typename F::elem* a, uint32_t le
 }
 
 // ENTER levels 1 .. log_tile (src/fftree.rs:143-161 for every block of size <= tile).  LDS: 2*tile elements.
-template <class F, int LOG_TILE, int BLK = kBlockLds>
+// SYM (symmetric contexts of a 32-byte field, 1024-element tiles): the VALU sweeps of the EXTEND cores run sym_bfly (lds_extend_core)
+template <class F, int LOG_TILE, int BLK = kBlockLds, bool SYM = false>
 __global__ __launch_bounds__(BLK, (BLK >= 512 ? ECFFT_MIN_WAVES : 2)) void k_enter_low(typename F::elem* __restrict__ dst, const typename F::elem* __restrict__ src,
                                                           const LevelTables<F>* __restrict__ trees) {
     using E = typename F::elem;
@@ -1913,7 +1996,7 @@ __global__ __launch_bounds__(BLK, (BLK >= 512 ? ECFFT_MIN_WAVES : 2)) void k_ent
         }
         for (uint32_t j = tid; j < T; j += BLK) work[j] = F::tmul(ldt(L.winv[0], j & (e - 1)), cur[j]);
         __syncthreads();
-        lds_extend_core<F, BLK>(work, T, le, L, 0);
+        lds_extend_core<F, BLK, false, SYM>(work, T, le, L, 0);
         // combine (:155-159): block [u0|v0] + extended [U1|V1] -> interleaved evaluations; results are held in
         // registers across the barrier because the interleaving store overwrites other threads' inputs
         if constexpr (kRoles) {
@@ -1966,7 +2049,8 @@ __global__ __launch_bounds__(BLK, (BLK >= 512 ? ECFFT_MIN_WAVES : 2)) void k_ent
 //   3  reduction over Z1 (the z* tables): G = zA1 cur[odd]; core S1->S0; G = H = zNB2 G + zB1 cur[even]; core S0->S1; G = zC1 G;
 //      core S1->S0; u0 = zNB3 G + zD1 H, v0 = xie (cur[even] - u0) — three cores, 7 multiplies per pair instead of 8
 // The matrix-core maps of the lowest levels (low16 / low32) are exact linear maps of the whole levels and serve both forms.
-template <class F, int LOG_TILE, int BLK = kBlockLds, int CORES = 4>
+// SYM (symmetric contexts of a 32-byte field, 1024-element tiles, CORES == 3): the cores' VALU stages run on pair_extend512
+template <class F, int LOG_TILE, int BLK = kBlockLds, int CORES = 4, bool SYM = false>
 __global__ __launch_bounds__(BLK, (BLK >= 512 ? ECFFT_MIN_WAVES : 1)) void k_exit_low(typename F::elem* __restrict__ dst, const typename F::elem* __restrict__ src,
                                                          const LevelTables<F>* __restrict__ trees) {
     using E = typename F::elem;
@@ -2104,24 +2188,24 @@ __global__ __launch_bounds__(BLK, (BLK >= 512 ? ECFFT_MIN_WAVES : 1)) void k_exi
         }
         for (uint32_t g = tid; g < nh; g += BLK) lds_put<F, kSwz>(G, g, F::tmul(ldt(k3 ? L.zA1 : L.A1, g & (e - 1)), lds_get<F, kSwz>(cur, 2 * g + par1)));
         __syncthreads();
-        lds_extend_core<F, BLK, kSwz>(G, nh, le, L, par1);
+        lds_extend_core<F, BLK, kSwz, SYM && k3>(G, nh, le, L, par1);
         for (uint32_t g = tid; g < nh; g += BLK) {
             uint32_t i = g & (e - 1);
             E r = F::tmul_add(ldt(k3 ? L.zNB2 : L.NB2, i), lds_get<F, kSwz>(G, g), F::tmul(ldt(k3 ? L.zB1 : L.B1, i), lds_get<F, kSwz>(cur, 2 * g + 1 - par1)));
             lds_put<F, kSwz>(G, g, r); lds_put<F, kSwz>(H, g, r);
         }
         __syncthreads();
-        lds_extend_core<F, BLK, kSwz>(G, nh, le, L, 1 - par1);
+        lds_extend_core<F, BLK, kSwz, SYM && k3>(G, nh, le, L, 1 - par1);
         for (uint32_t g = tid; g < nh; g += BLK) lds_put<F, kSwz>(G, g, F::tmul(ldt(k3 ? L.zC1 : L.C1, g & (e - 1)), lds_get<F, kSwz>(G, g)));
         __syncthreads();
-        lds_extend_core<F, BLK, kSwz>(G, nh, le, L, par1);
+        lds_extend_core<F, BLK, kSwz, SYM && k3>(G, nh, le, L, par1);
         if constexpr (!k3) {
             for (uint32_t g = tid; g < nh; g += BLK) {
                 uint32_t i = g & (e - 1);
                 lds_put<F, kSwz>(G, g, F::tmul_add(ldt(L.NB2, i), lds_get<F, kSwz>(G, g), F::tmul(ldt(L.D1, i), lds_get<F, kSwz>(H, g))));
             }
             __syncthreads();
-            lds_extend_core<F, BLK, kSwz>(G, nh, le, L, 1);
+            lds_extend_core<F, BLK, kSwz, SYM && k3>(G, nh, le, L, 1);
         }
         E u[PAIRS], v[PAIRS];
 #pragma unroll

@@ -6,7 +6,8 @@
  * the tests and the measurement tools load explicitly.  The same build also reads the A/B switches of the tuning experiments from
  * the environment (ECFFT_NO_MFMA, ECFFT_NO_LOW16, ECFFT_LOW32, ECFFT_NO_ROW256, ECFFT_NO_COL256, ECFFT_NO_SMALL_TILES,
  * ECFFT_SMALL_TILES_MAX, ECFFT_SMALL_LOW_MAX, ECFFT_SMALL_MIN_LOGC, ECFFT_NO_FULL_CYCLIC, ECFFT_SPLIT_GATHER_MAX_LOG,
- * ECFFT_SPLIT_Q2_SPLIT, ECFFT_EXIT_FOUR_CORES, ECFFT_EXIT_LOW_FOUR_CORES, ECFFT_NO_SYM_BFLY, ECFFT_SYM_BFLY_GENERAL_KERNELS); the shipped library reads no environment variable at all. */
+ * ECFFT_SPLIT_Q2_SPLIT, ECFFT_EXIT_FOUR_CORES, ECFFT_EXIT_LOW_FOUR_CORES, ECFFT_NO_SYM_BFLY, ECFFT_SYM_BFLY_GENERAL_KERNELS,
+ * ECFFT_LOW_GENERAL_KERNELS); the shipped library reads no environment variable at all. */
 #ifndef ECFFT_HIP_HOOKS_H
 #define ECFFT_HIP_HOOKS_H
 #include "ecfft_hip.h"
@@ -64,6 +65,12 @@ int ecfft_ctx_exit_low_cores(const ecfft_ctx* ctx);
  * butterfly in the full-size row and column passes (the library's own secp256k1 tree)   2 = symmetric basis under the general
  * kernels (A/B: ECFFT_SYM_BFLY_GENERAL_KERNELS)   -1 = no context */
 int ecfft_ctx_sym_bfly(const ecfft_ctx* ctx);
+/* ... and which of the 1024-element low-level kernels run symmetric butterflies in the VALU sweeps of their EXTEND cores: bit 0 =
+ * k_enter_low, bit 1 = k_exit_low (three-core form only: not under ECFFT_EXIT_LOW_FOUR_CORES).  0 in every context that reports
+ * sym_bfly != 1, in a four-core context (ECFFT_EXIT_FOUR_CORES) and under ECFFT_LOW_GENERAL_KERNELS (A/B: the general low-level
+ * kernels under symmetric row and column passes); builds with -DECFFT_ENTER_LOW_SYM=0 / -DECFFT_EXIT_LOW_SYM=0 never set bit 0 / 1
+ * -1 = no context */
+int ecfft_ctx_low_sym(const ecfft_ctx* ctx);
 /* measurement hook (tools/findcurve_time.py): the number of queue entries every stage of the curve search has read since the last
  * reset, summed over batches: [0] bb square, [1] discriminant, [2] point of order 4, [3 + r] halving round r; and the host seconds
  * spent around each stage's launch and the read of its queue length, which waits for it.  Copies up to `cap` entries into each
