@@ -146,6 +146,8 @@ public:
     // which 1024-element low-level kernels run symmetric butterflies in their VALU sweeps: bit 0 = k_enter_low, bit 1 = k_exit_low
     // (bit 1 in three-core contexts only: the four-core kernel keeps the register engine)
     int low_sym() const { return (kLowSymEnter && low_sym_enter() ? 1 : 0) | (kLowSymExit && low_sym_exit() ? 2 : 0); }
+    // 1: the EXTEND of ENTER level 11 (e = 1024) runs on the compile-time row engine in full-size launches, 0: on the run-time-tile row kernel
+    int enter_l11() const { return trees_.size() > kLogTileMax + 1 && enter_l11_tuned(trees_[kLogTileMax + 1], 0) ? 1 : 0; }
     int low_map(int dir) const {
         if (trees_.size() > 5 && trees_[5].low32_A[dir]) return 32;
         if (trees_.size() > 4 && trees_[4].low16_A[dir]) return 16;
@@ -793,6 +795,12 @@ public:
 #ifndef ECFFT_CT_ALL
 #define ECFFT_CT_ALL 0      // 1: compile-time tile sizes for every field (default: 4-byte fields only)
 #endif
+#ifndef ECFFT_ENTER_L11_TUNED
+#define ECFFT_ENTER_L11_TUNED 1      // 0: the EXTEND of an ENTER level with e = 1024 keeps the run-time-tile row kernel (A/B)
+#endif
+#ifndef ECFFT_ENTER_L11_THREADS
+#define ECFFT_ENTER_L11_THREADS 1024 // threads per workgroup of k_enter_l11: 512 (the block's halves in turn) or 1024 (side by side)
+#endif
     static constexpr unsigned kLogTileMax = (sizeof(E) == 32) ? ECFFT_LOG_TILE_BYTES - 5 : ECFFT_LOG_TILE_BYTES - 2;   // 32 KiB LDS tiles by default (A/B on MI355X: 512 threads x 32 KiB beat 64 KiB tiles by ~5%)
 #ifndef ECFFT_COL_STAGES
 #define ECFFT_COL_STAGES 9      // round 5: 9 (was 8) together with ECFFT_COL_MIN_LOGC 1 — the nine column stages of an EXTEND of 2^19 (every core of
@@ -813,6 +821,8 @@ public:
     static constexpr bool kSymKernels = sizeof(E) == 32 && ECFFT_SYM_BFLY != 0;   // the SYM instantiations exist for 32-byte fields only
     // ... and in the VALU sweeps of the 1024-element low-level ENTER kernel (-DECFFT_ENTER_LOW_SYM=0 keeps the general sweeps there)
     static constexpr bool kLowSymEnter = kSymKernels && ECFFT_ENTER_LOW_SYM != 0;
+    // the EXTEND of an ENTER level with e = 1024 on the compile-time engine (k_enter_l11: one [u0 | v0] block per workgroup)
+    static constexpr bool kEnterL11 = sizeof(E) == 32 && ECFFT_ENTER_L11_TUNED != 0 && kBlockRow == 512 && kLogTileMax == 10;
     // ... and of the three-core low-level EXIT kernel (-DECFFT_EXIT_LOW_SYM=0 keeps its register engine; kLowSymExit is defined next to kExitLowForm)
     static constexpr unsigned kLogColTileMax = (sizeof(E) == 32) ? ECFFT_LOG_COL_TILE_BYTES - 5 : ECFFT_LOG_COL_TILE_BYTES - 2;
     // Fusion of consecutive cores (EXIT): `next_ld` != nullptr says that another core of the same tree and size, opposite
@@ -838,7 +848,10 @@ public:
         if (small && log_tile > kLogLowSmall) log_tile = kLogLowSmall;
         unsigned k_first = le > log_tile ? le - log_tile : 0;                 // first stage with 2h <= tile
         if (k_first < k_begin) k_first = k_begin;
-        if (ef && k_first == 0 && le + 1 > log_tile) log_tile = le + 1;       // ST_ENTER wants whole [U | V] blocks in the tile (64 KiB at e = tile)
+        // ST_ENTER wants whole [U | V] blocks in the tile (64 KiB at e = tile).  At e = 1024 that is ENTER level 11: served by the compile-time
+        // engine on the block's two 1024-element halves (k_enter_l11, see enter_l11_tuned) where the tree has matrix-core tables,
+        // by the run-time-tile kernel k_stages_lds<F, 0> otherwise (M31, shard contexts, small tiles, no matrix cores) and at every smaller e
+        if (ef && k_first == 0 && le + 1 > log_tile) log_tile = le + 1;
         // pass list: (kind, ka, kb)
         struct Pass { int kind; unsigned ka, kb; };                           // kind 0 col-decompose, 1 row, 2 col-recombine
         Pass passes[2 * 8 + 1]; int np = 0;
@@ -935,6 +948,17 @@ public:
                     const bool mf = !mfma_off_ && T.blk16_A[srcpar] && le >= 4 && le - k_first >= 4;
                     ECFFT_LAUNCH(KC_ROW, bytes, (k_stages_row256<F>), dim3((unsigned)(total >> kLogLowSmall)), dim3(256), 0, s, d, T.dinv[srcpar], T.p0[tgt], T.p1[tgt], T.inner[srcpar],
                                  le, k_first, T.c0t[srcpar], mf ? T.blk16_A[srcpar] : (const uint8_t*)nullptr, mf ? T.blk16_K[srcpar] : (const unsigned long long*)nullptr);
+                } else
+                if (ef && k_first == 0 && le == kLogTileMax && log_tile == le + 1 && !small && enter_l11_tuned(T, srcpar)) {
+                    // ENTER level 11 (e = 1024): one [u0 | v0] block per workgroup, its halves through the 1024-element engine
+                    if constexpr (kEnterL11) {
+                    if (symk)
+                    ECFFT_LAUNCH(KC_ROW, bytes, (k_enter_l11<F, kSymKernels, ECFFT_ENTER_L11_THREADS>), dim3((unsigned)(total >> log_tile)), dim3(ECFFT_ENTER_L11_THREADS), ((size_t)sizeof(E)) << log_tile, s,
+                                 d, T.np0[srcpar], T.dinv[srcpar], T.p0[tgt], T.p1[tgt], T.blk16_A[srcpar], T.blk16_K[srcpar]);
+                    else
+                    ECFFT_LAUNCH(KC_ROW, bytes, (k_enter_l11<F, false, ECFFT_ENTER_L11_THREADS>), dim3((unsigned)(total >> log_tile)), dim3(ECFFT_ENTER_L11_THREADS), ((size_t)sizeof(E)) << log_tile, s,
+                                 d, T.np0[srcpar], T.dinv[srcpar], T.p0[tgt], T.p1[tgt], T.blk16_A[srcpar], T.blk16_K[srcpar]);
+                    }
                 } else
                 if (log_tile == kLogTileMax + 1 && ct_row) {
                     // (only instantiated for the fields that launch it: the 32-byte instantiation was dead code in the code object)
@@ -4730,6 +4754,9 @@ private:
     // (a context of the four-core A/B form, exit4_, keeps the general low-level kernels as well: it is the reference form throughout)
     bool low_sym_enter() const { return sym_kernels() && !low_general_kernels_ && !exit4_; }
     bool low_sym_exit() const { return low_sym_enter() && exit_low_cores() == 3; }
+    // ENTER level 11 on the compile-time row engine (extend_core): full contexts of a 32-byte field whose tree has matrix-core tables
+    bool enter_l11_generic_ = ab_env("ECFFT_ENTER_L11_GENERIC") != nullptr;   // A/B switch: that level on the run-time-tile row kernel
+    bool enter_l11_tuned(const Tree& T, int srcpar) const { return kEnterL11 && !enter_l11_generic_ && !mfma_off_ && !shard_mode() && T.blk16_A[srcpar] != nullptr; }
 };
 
 }  // namespace ecfft

@@ -1645,6 +1645,10 @@ int ecfft_ctx_low_sym(const ecfft_ctx* ctx) {
     if (!ctx) return -1;
     return ctx->secp ? ctx->secp->low_sym() : ctx->m31 ? ctx->m31->low_sym() : -1;
 }
+int ecfft_ctx_enter_l11(const ecfft_ctx* ctx) {
+    if (!ctx) return -1;
+    return ctx->secp ? ctx->secp->enter_l11() : ctx->m31 ? ctx->m31->enter_l11() : -1;
+}
 
 #endif  // ECFFT_TEST_HOOKS
 int ecfft_mul_ceiling(int field, int device, int waves_per_simd, double* mul_per_s) {

@@ -974,6 +974,81 @@ __global__ __launch_bounds__(kBlockRow, ECFFT_MIN_WAVES) void k_stages_lds(IoDes
 #endif
 }
 
+// ---------------------------------------------------------------------------------------------
+// Row kernel of ENTER level 11: the EXTEND of an ENTER level with e = 1024 and the level's combine (ST_ENTER), 32-byte fields with
+// matrix-core tables.  ST_ENTER combines U1~ and V1~ of one [u0 | v0] block, so the workgroup owns the whole block: 2048 elements,
+// 64 KiB of LDS.  The block's two 1024-element halves are independent EXTENDs on the same constants; each goes through the engine of
+// k_stages_lds<F, 10, SYM> on a 1024-element tile: pipelined sweeps at pair distance 512 .. 32, the fused sweep at distance 16 into
+// operand form, the matrix-core phase, the fused recombine at distance 16, pipelined sweeps back up to 512 — one pair per thread, so
+// the register footprint is that kernel's.  BLK = 512: one half after the other (two workgroups per CU); BLK = 1024: threads 0..511
+// take the first half and threads 512..1023 the second at the same time (one workgroup per CU, the same sixteen waves: a launch of
+// one block per CU — the half-streams of a single transform of 2^20 — then runs four waves per SIMD instead of two).
+// (k_stages_lds<F, 0> on a 2048-element tile, which served this level before, has neither the pipelined sweeps nor the matrix-core
+// phase.)  Same operators, canonical residues: the same bytes.
+// ---------------------------------------------------------------------------------------------
+template <class F, bool SYM, int BLK>
+__global__ __launch_bounds__(BLK, ECFFT_MIN_WAVES) void k_enter_l11(IoDesc<F> io,
+                                                                   const typename F::telem* __restrict__ np0,
+                                                                   const typename F::telem* __restrict__ dinv,
+                                                                   const typename F::telem* __restrict__ p0,
+                                                                   const typename F::telem* __restrict__ p1,
+                                                                   const uint8_t* __restrict__ blkA, const unsigned long long* __restrict__ blkK) {
+    using E = typename F::elem;
+    static_assert(sizeof(E) == 32 && Blk16::kSub == 1024 && (BLK == 512 || BLK == 1024), "32-byte field, 1024-element matrix-core phases");
+    extern __shared__ __attribute__((aligned(16))) unsigned char ecfft_smem[];
+    E* const blk = reinterpret_cast<E*>(ecfft_smem);
+    constexpr uint32_t e = 1024, log_e = 10;
+    const size_t base = (size_t)blockIdx.x << (log_e + 1);
+#pragma unroll
+    for (uint32_t j = threadIdx.x; j < 2 * e; j += BLK) blk[j] = io_load<F>(io, base + j, (size_t)e - 1);
+    __syncthreads();
+#pragma unroll 1
+    for (uint32_t sub = 0; sub < 1024u / BLK; ++sub) {
+        // the thread index taken anew in every iteration: nothing that depends on it (pair positions, table constants, the prefetched
+        // matrix rows) is carried in registers from one half to the other
+        uint32_t tid = threadIdx.x & 511u;
+        asm volatile("" : "+v"(tid));
+        E* const tile = blk + (BLK == 1024 ? threadIdx.x >> 9 : sub) * e;
+        row_stages_pipe<F, true, SYM>(tile, np0, dinv, e, (int)log_e - 1, 5, tid, 4);
+        Blk16::APre pre;
+        const uint32_t i = tid & 15u, idx = ((tid >> 4) << 5) + i;      // one pair per thread: (idx, idx + 16)
+        {
+            const E a = tile[idx], b = tile[idx + 16];
+            E q0, q1;
+            if constexpr (SYM) { q0 = a; q1 = b; sym_bfly<F, true>(q0, q1, ldt(dinv + (e - 32), i)); }
+            else { q1 = F::tmul(ldt(dinv + (e - 32), i), F::sub(b, a)); q0 = F::tmul_add(ldt(np0 + (e - 32), i), q1, a); }
+            __builtin_amdgcn_sched_barrier(0);
+            pre = Blk16::prefetch(blkA, tid);                            // after the multiplies (they need the registers), before the barriers
+            __builtin_amdgcn_sched_barrier(0);
+            // operand form permutes chunks inside 8-element groups (Blk16::phys), i.e. inside the wave's own span
+            if (ECFFT_WAVE_LOCAL) wave_local_sync(); else __syncthreads();
+            Blk16::store_operand(tile, idx, q0); Blk16::store_operand(tile, idx + 16, q1);
+            __syncthreads();
+        }
+        Blk16::phase(tile, blkA, blkK, tid, pre);
+        {                                                                // recombine sweep at distance 16, reading the swizzled results
+            const E a = Blk16::load_swizzled(tile, idx), b = Blk16::load_swizzled(tile, idx + 16);
+            E o0, o1;
+            if constexpr (SYM) { o0 = a; o1 = b; sym_bfly<F, false>(o0, o1, ldt(p0 + (e - 32), i)); }
+            else { o0 = F::tmul_add(ldt(p0 + (e - 32), i), b, a); o1 = F::tmul_add(ldt(p1 + (e - 32), i), b, a); }
+            // the swizzled positions read above and the plain ones written below lie in the wave's own span; so do the pairs of the
+            // recombine sweep at distance 32 that follows
+            if (ECFFT_WAVE_LOCAL) wave_local_sync(); else __syncthreads();
+            tile[idx] = o0; tile[idx + 16] = o1;
+            if (ECFFT_WAVE_LOCAL) wave_local_sync(); else __syncthreads();
+        }
+        row_stages_pipe<F, false, SYM>(tile, p0, p1, e, 5, (int)log_e - 1, tid);      // ends with a barrier
+    }
+    // the block holds [U1~ | V1~]: combine them with the level's input and store interleaved (ST_ENTER, as k_stages_lds)
+    for (uint32_t i = threadIdx.x; i < e; i += BLK) {
+        const E u0 = io.aux[base + i], v0 = io.aux[base + e + i];
+        const E ev = F::tmul_add(io.st_a[i], v0, u0);
+        const E od = F::tmul_add(io.st_b[i], blk[e + i], F::tmul(io.st_c[i], blk[i]));
+        io.dst[base + 2 * i] = F::canon(ev);
+        io.dst[base + 2 * i + 1] = F::canon(od);
+    }
+}
+
 // forward declaration (defined with the low-level kernels below)
 template <class F, int BLK, bool SWZ = false>
 __device__ __forceinline__ void reg_extend32(typename F::elem* a, uint32_t len, uint32_t log_e, uint32_t k_first,

@@ -58,7 +58,7 @@ SCHOOF_MAX_L = 199
 ORDER_BYTES = 40
 
 # include/ecfft_hip_hooks.h: only in a build with -DECFFT_TEST_HOOKS (tests/hooks/libecfft_hip_hooks.so), never in the shipped library
-HOOK_EXPORTS = ['ecfft_selftest_field', 'ecfft_selfcheck_pointwise_z', 'ecfft_test_fail_next_collective', 'ecfft_selftest_blk16', 'ecfft_selftest_blk16_small', 'ecfft_test_fail_build_rank', 'ecfft_comm_init_projection', 'ecfft_selftest_blk32', 'ecfft_ctx_low_map', 'ecfft_curve_search_stats', 'ecfft_test_ddf_iterate', 'ecfft_test_schoof_pi2', 'ecfft_ctx_exit_cores', 'ecfft_ctx_exit_low_cores', 'ecfft_ctx_sym_bfly', 'ecfft_ctx_low_sym']
+HOOK_EXPORTS = ['ecfft_selftest_field', 'ecfft_selfcheck_pointwise_z', 'ecfft_test_fail_next_collective', 'ecfft_selftest_blk16', 'ecfft_selftest_blk16_small', 'ecfft_test_fail_build_rank', 'ecfft_comm_init_projection', 'ecfft_selftest_blk32', 'ecfft_ctx_low_map', 'ecfft_curve_search_stats', 'ecfft_test_ddf_iterate', 'ecfft_test_schoof_pi2', 'ecfft_ctx_exit_cores', 'ecfft_ctx_exit_low_cores', 'ecfft_ctx_sym_bfly', 'ecfft_ctx_low_sym', 'ecfft_ctx_enter_l11']
 
 EXCHANGE_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_void_p),
                                ctypes.POINTER(ctypes.c_size_t), ctypes.c_int, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_void_p),
@@ -180,6 +180,8 @@ def _bind(L):
             L.ecfft_ctx_sym_bfly.restype, L.ecfft_ctx_sym_bfly.argtypes = ci, [vp]
         if hasattr(L, "ecfft_ctx_low_sym"):
             L.ecfft_ctx_low_sym.restype, L.ecfft_ctx_low_sym.argtypes = ci, [vp]
+        if hasattr(L, "ecfft_ctx_enter_l11"):
+            L.ecfft_ctx_enter_l11.restype, L.ecfft_ctx_enter_l11.argtypes = ci, [vp]
         L.ecfft_curve_search_stats.restype, L.ecfft_curve_search_stats.argtypes = ci, [ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_double), sz, ci]
         L.ecfft_test_ddf_iterate.restype, L.ecfft_test_ddf_iterate.argtypes = ci, [ci]
         L.ecfft_test_schoof_pi2.restype, L.ecfft_test_schoof_pi2.argtypes = ci, [ci]
@@ -1142,6 +1144,10 @@ class FFTree:
     def low_sym(self):
         """bit 0 / bit 1: the 1024-element low-level ENTER / EXIT kernel runs one-multiply butterflies in its VALU sweeps (hooks build)"""
         return self._L.ecfft_ctx_low_sym(self._h)
+
+    def enter_l11(self):
+        """1 / 0: the EXTEND of ENTER level 11 runs on the compile-time row engine / on the run-time-tile row kernel (hooks build)"""
+        return self._L.ecfft_ctx_enter_l11(self._h)
 
     def profile(self, on):
         _check(self._L.ecfft_profile_enable(self._h, int(on)))

@@ -7,7 +7,7 @@
  * the environment (ECFFT_NO_MFMA, ECFFT_NO_LOW16, ECFFT_LOW32, ECFFT_NO_ROW256, ECFFT_NO_COL256, ECFFT_NO_SMALL_TILES,
  * ECFFT_SMALL_TILES_MAX, ECFFT_SMALL_LOW_MAX, ECFFT_SMALL_MIN_LOGC, ECFFT_NO_FULL_CYCLIC, ECFFT_SPLIT_GATHER_MAX_LOG,
  * ECFFT_SPLIT_Q2_SPLIT, ECFFT_EXIT_FOUR_CORES, ECFFT_EXIT_LOW_FOUR_CORES, ECFFT_NO_SYM_BFLY, ECFFT_SYM_BFLY_GENERAL_KERNELS,
- * ECFFT_LOW_GENERAL_KERNELS); the shipped library reads no environment variable at all. */
+ * ECFFT_LOW_GENERAL_KERNELS, ECFFT_ENTER_L11_GENERIC); the shipped library reads no environment variable at all. */
 #ifndef ECFFT_HIP_HOOKS_H
 #define ECFFT_HIP_HOOKS_H
 #include "ecfft_hip.h"
@@ -71,6 +71,13 @@ int ecfft_ctx_sym_bfly(const ecfft_ctx* ctx);
  * kernels under symmetric row and column passes); builds with -DECFFT_ENTER_LOW_SYM=0 / -DECFFT_EXIT_LOW_SYM=0 never set bit 0 / 1
  * -1 = no context */
 int ecfft_ctx_low_sym(const ecfft_ctx* ctx);
+/* test / measurement hook: which row kernel runs the EXTEND of ENTER level 11 (e = 1024, the one ENTER level whose EXTEND is a single
+ * row pass with a 2048-element [u0 | v0] block per workgroup) in full-size launches.  1 = the compile-time engine of the 1024-element
+ * row tiles on the block's two halves (pipelined sweeps, matrix-core phase; one-multiply butterflies in a symmetric context): full
+ * secp256k1 contexts with matrix-core tables   0 = the run-time-tile row kernel (M31, shard contexts, ECFFT_NO_MFMA, A/B:
+ * ECFFT_ENTER_L11_GENERIC, -DECFFT_ENTER_L11_TUNED=0, trees below 2^11 leaves)   -1 = no context.  Launches under the small-tile rule
+ * take the 256-element kernels whatever this reads. */
+int ecfft_ctx_enter_l11(const ecfft_ctx* ctx);
 /* measurement hook (tools/findcurve_time.py): the number of queue entries every stage of the curve search has read since the last
  * reset, summed over batches: [0] bb square, [1] discriminant, [2] point of order 4, [3 + r] halving round r; and the host seconds
  * spent around each stage's launch and the read of its queue length, which waits for it.  Copies up to `cap` entries into each
