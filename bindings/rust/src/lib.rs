@@ -62,6 +62,8 @@ pub mod ffi {
         pub fn ecfft_poly_squarefree(ctx: *mut EcfftCtx, f: *const c_void, nf: usize, out: *mut c_void, degrees: *mut i64, count: usize, mem: i32, stream: *mut c_void) -> i32;
         pub fn ecfft_poly_distinct_degree(ctx: *mut EcfftCtx, f: *const c_void, nf: usize, factors: *mut c_void, degrees: *mut i64, count: usize, mem: i32, stream: *mut c_void) -> i32;
         pub fn ecfft_poly_equal_degree(ctx: *mut EcfftCtx, g: *const c_void, ng: usize, d: usize, factors: *mut c_void, n_factors: *mut i64, count: usize, mem: i32, stream: *mut c_void) -> i32;
+        pub fn ecfft_poly_squarefree_decompose(ctx: *mut EcfftCtx, f: *const c_void, nf: usize, parts: *mut c_void, degrees: *mut i64, lead: *mut c_void, count: usize, mem: i32, stream: *mut c_void) -> i32;
+        pub fn ecfft_poly_factor(ctx: *mut EcfftCtx, f: *const c_void, nf: usize, factors: *mut c_void, fdeg: *mut i64, fmult: *mut i64, n_factors: *mut i64, lead: *mut c_void, count: usize, mem: i32, stream: *mut c_void) -> i32;
         pub fn ecfft_division_polynomial(ctx: *mut EcfftCtx, a: *const c_void, b: *const c_void, n: usize, out: *mut c_void, count: usize, mem: i32, stream: *mut c_void) -> i32;
         pub fn ecfft_curve_cardinality(ctx: *mut EcfftCtx, a: *const c_void, b: *const c_void, order: *mut c_void, traces: *mut i64, count: usize, mem: i32, stream: *mut c_void) -> i32;
         pub fn ecfft_curve_trace_mod(ctx: *mut EcfftCtx, a: *const c_void, b: *const c_void, l: usize, t_out: *mut i64, count: usize, mem: i32, stream: *mut c_void) -> i32;
@@ -602,6 +604,61 @@ impl<F: HipField> HipFFTree<F> {
                 q
             })
             .collect()
+    }
+
+    /// Yun's squarefree decomposition `f = lead * prod_i a_i^i` (`ecfft_poly_squarefree_decompose`; the reference's
+    /// `square_free_factors`, src/utils.rs:46-50, returns `prod a_i` only): the leading coefficient and multiplicity `i` -> the monic
+    /// `a_i` of positive degree with its leading 1, the `a_i` squarefree and pairwise coprime.  `f` need not be trimmed; a non-zero
+    /// constant gives an empty map.  Panics on the zero polynomial.  Up to `ECFFT_FACTOR_SMALL_MAX` coefficients work on any tree;
+    /// tree rule: include/ecfft_hip.h.
+    pub fn square_free_decomposition(&self, f: &[F]) -> (F, std::collections::BTreeMap<usize, Vec<F>>) {
+        assert!(!f.is_empty());
+        let nd = core::cmp::max(f.len() - 1, 1);
+        let mut parts = Self::out_vec(nd);
+        let mut lead = Self::out_vec(1);
+        let mut deg = vec![0i64; nd];
+        check(unsafe { ffi::ecfft_poly_squarefree_decompose(self.ctx, f.as_ptr().cast(), f.len(), parts.as_mut_ptr().cast(), deg.as_mut_ptr(), lead.as_mut_ptr().cast(), 1, ffi::MEM_HOST, core::ptr::null_mut()) });
+        assert!(deg[0] >= 0, "square_free_decomposition: the zero polynomial");
+        unsafe { parts.set_len(nd); lead.set_len(1) };
+        let mut out = std::collections::BTreeMap::new();
+        let mut pos = 0usize;
+        for (i, &n) in deg.iter().enumerate() {
+            if n > 0 {
+                let mut a = parts[pos..pos + n as usize].to_vec();
+                a.push(F::one());
+                out.insert(i + 1, a);
+                pos += n as usize;
+            }
+        }
+        (lead[0], out)
+    }
+
+    /// The factorisation `f = lead * prod_j q_j^e_j` over the distinct monic irreducible `q_j` (`ecfft_poly_factor`: the reference's
+    /// `square_free_factors`, `distinct_degree_factors` and `equal_degree_factorization`, src/utils.rs:25-113, for every degree and
+    /// with the multiplicities): the leading coefficient and the `(q_j, e_j)`, `q_j` with its leading 1, in ascending
+    /// `(e_j, deg q_j, the order of equal_degree_factorization)`.  Deterministic.  `f` need not be trimmed; a non-zero constant gives
+    /// an empty vector.  Panics on the zero polynomial.  Up to `ECFFT_FACTOR_SMALL_MAX` coefficients work on any tree; tree rule:
+    /// include/ecfft_hip.h.
+    pub fn factor(&self, f: &[F]) -> (F, Vec<(Vec<F>, usize)>) {
+        assert!(!f.is_empty());
+        let nd = core::cmp::max(f.len() - 1, 1);
+        let mut fac = Self::out_vec(nd);
+        let mut lead = Self::out_vec(1);
+        let (mut fdeg, mut fmult) = (vec![0i64; nd], vec![0i64; nd]);
+        let mut n = 0i64;
+        check(unsafe { ffi::ecfft_poly_factor(self.ctx, f.as_ptr().cast(), f.len(), fac.as_mut_ptr().cast(), fdeg.as_mut_ptr(), fmult.as_mut_ptr(), &mut n, lead.as_mut_ptr().cast(), 1, ffi::MEM_HOST, core::ptr::null_mut()) });
+        assert!(n >= 0, "factor: the zero polynomial");
+        unsafe { fac.set_len(nd); lead.set_len(1) };
+        let mut out = Vec::with_capacity(n as usize);
+        let mut pos = 0usize;
+        for j in 0..n as usize {
+            let d = fdeg[j] as usize;
+            let mut q = fac[pos..pos + d].to_vec();
+            q.push(F::one());
+            out.push((q, fmult[j] as usize));
+            pos += d;
+        }
+        (lead[0], out)
     }
 
     /// `division_polynomial(n, &curve)` (examples/schoofs.rs:368-431) for y^2 = x^3 + a x + b: the L(n) coefficients of psi_n, low

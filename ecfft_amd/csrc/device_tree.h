@@ -3164,6 +3164,350 @@ public:
         return finish_flagged(ok, ec.flag, capped, s);
     }
 
+    // ---- ecfft_poly_squarefree_decompose / ecfft_poly_factor: f = lc prod_i a_i^i = lc prod_j q_j^e_j ----
+    // a polynomial of at most kFactorSmall + 1 coefficients is taken apart by the workgroup kernels, one workgroup per row or part
+    static constexpr size_t kFactorSmall = kRootsSmall;
+    // The leaves both calls need for rows of nf coefficients are ddf_leaves(nf), the rule of ecfft_poly_find_roots: Yun's gcds and
+    // divisions are pairs of at most nf coefficients, and every part goes to ddf_one_large and edf_one_large on fewer.
+private:
+    static_assert(kFactorSmall == kDdfSmall && kFactorSmall == kEdfSmall, "the parts of a small row go to k_ddf_small and k_edf_small as they are");
+    // A squarefree part a_e of row `row`: its low `deg` coefficients on the device (the leading 1 implied), and a group of r = len / d
+    // irreducible factors of degree d at multiplicity e, ranked, laid end to end at src.
+    struct FacPart { size_t row; long long e; size_t deg; const E* src; };
+    struct FacGroup { size_t row; long long e, d; size_t len; const E* src; };
+    struct FacSeg { const E* src; E* dst; size_t len; };
+    // one launch of k_yun_small over nblk rows: nin coefficients read, nw entries of parts and degrees written per row
+    void yun_small_launch(const E* in, size_t ldin, size_t nin, E* out, size_t ldout, size_t nw, long long* deg, size_t lddeg, E* lead, size_t nblk,
+                          hipStream_t s) {
+        const E r1 = crate_one();
+        for_chunks(nblk, [&](size_t b0, size_t nb) {
+            ECFFT_LAUNCH(KC_POINTWISE, sizeof(E) * (double)nb * (double)(nin + nw) + 32.0, (k_yun_small<F, (int)kFactorSmall>), dim3((unsigned)nb),
+                         dim3((unsigned)kFactorSmall), 0, s, in + b0 * ldin, ldin, (uint32_t)nin, out + b0 * ldout, ldout, (uint32_t)nw, deg + b0 * lddeg, lddeg,
+                         lead ? lead + b0 : (E*)nullptr, r1);
+        });
+    }
+    // The segments (uploaded once) laid into rows of ld entries of dst, row i = segment i: its len coefficients, then with `monic`
+    // the leading 1, then zeros.  With ld == 0 each segment goes to its own dst instead and nothing else is written (w: the longest).
+    bool factor_segments(const std::vector<FacSeg>& segs, E* dst, size_t ld, size_t w, hipStream_t s) {
+        const size_t n = segs.size();
+        if (!n) return true;
+        const E r1 = crate_one();
+        FacSeg* dsegs = temp_as<FacSeg>(n);
+        const bool ok = hipMemcpyAsync(dsegs, segs.data(), n * sizeof(FacSeg), hipMemcpyHostToDevice, s) == hipSuccess && hipStreamSynchronize(s) == hipSuccess;
+        if (ld) foreach_n(s, n * ld, [=] __device__(size_t k) {
+            const size_t i = k / ld, j = k - i * ld, len = dsegs[i].len;
+            E v = F::zero();
+            if (j < len) v = F::canon(dsegs[i].src[j]);
+            if (j == len) v = r1;
+            dst[k] = v;
+        });
+        else foreach_n(s, n * w, [=] __device__(size_t k) {
+            const size_t i = k / w, j = k - i * w;
+            if (j < dsegs[i].len) dsegs[i].dst[j] = F::canon(dsegs[i].src[j]);
+        });
+        return ok;
+    }
+    // Yun's loop on ONE polynomial of true length la > kFactorSmall + 1 (f: untrimmed, crate form), k_yun_small's steps on gcd_pair and
+    // the division body: b (monic, degree db) and a row d of db coefficients; u = gcd_pair(b, d) (d = 0: u = b); where deg u > 0,
+    // b <- b / u and c = d / u (divrem_body), else c = d; d <- c - b' (the plain integer j + 1 times a crate coefficient).  Step 0
+    // starts from b = f / lc(f), d = f' and yields nothing; step i >= 1 hands a_i = u of positive degree to emit(i, u with its leading
+    // 1, deg u), and a step with deg u = db is the last.  A squarefree f costs steps 0 and 1.  Synchronous (gcd_pair reads degrees back).
+    template <class Emit>
+    bool yun_one_large(const E* f, size_t la, Emit&& emit, hipStream_t s) {
+        const size_t n = la - 1;
+        E* bb[2] = {temp(la), temp(la)}; E* dd[2] = {temp(la), temp(la)}; E* u = temp(la);
+        monic_row(f, n, bb[0], s);
+        { const E* b0 = bb[0]; E* d0 = dd[0]; foreach_n(s, n, [=] __device__(size_t j) { d0[j] = F::canon(F::mul(F::from_u32((uint32_t)(j + 1)), b0[j + 1])); }); }
+        size_t db = n;
+        int bi = 0, di = 0;
+        bool ok = true;
+        for (size_t i = 0; ok && db > 0 && i <= n; ++i) {
+            const TempMark mark = temps_mark();
+            const E* b = bb[bi];
+            const E* c = dd[di];
+            long long dg = -1;
+            ok = gcd_pair(b, db + 1, c, db, nullptr, 1, nullptr, 1, u, la, &dg, false, s) && dg >= 0 && (size_t)dg <= db;
+            bool last = false;
+            if (ok && dg > 0) {
+                const size_t du = (size_t)dg;
+                if (i > 0) ok = emit(i, (const E*)u, du);
+                last = i > 0 && du == db;
+                if (ok && !last) {
+                    ok = du < db && divrem_body(b, db + 1, u, du + 1, bb[bi ^ 1], nullptr, 1, gcd_flag_, s)
+                                 && divrem_body(c, db, u, du + 1, dd[di ^ 1], nullptr, 1, gcd_flag_, s);
+                    bi ^= 1; di ^= 1; db -= du;
+                    c = dd[di];
+                }
+            }
+            if (ok && !last) {
+                const E* bn = bb[bi]; E* dn = dd[di ^ 1];
+                foreach_n(s, db, [=] __device__(size_t j) {
+                    dn[j] = F::canon(F::sub(F::canon(c[j]), F::canon(F::mul(F::from_u32((uint32_t)(j + 1)), bn[j + 1]))));
+                });
+                di ^= 1;
+            }
+            temps_release(mark);
+            if (last) break;
+        }
+        return ok && hipGetLastError() == hipSuccess;
+    }
+    // A part above kFactorSmall (u: deg + 1 coefficients with the leading 1) of row `row` at multiplicity e: ddf_one_large, then per
+    // non-empty d edf_one_large on g_d with its leading 1 appended (a g_d of one factor is copied).  The ranked factors go to dst
+    // (deg elements, zero on entry) in ascending d, one group each.
+    bool factor_large_part(const FactorCall& fc, const E* u, size_t deg, size_t row, long long e, E* dst, std::vector<FacGroup>& groups,
+                           hipStream_t s) {
+        const E r1 = crate_one();
+        const TempMark mark = temps_mark();
+        E* fac = temp(deg);
+        long long* ddeg = temp_as<long long>(deg);
+        std::vector<long long> hdeg(deg, 0);
+        bool ok = hipMemsetAsync(fac, 0, deg * sizeof(E), s) == hipSuccess;
+        ok = ok && ddf_one_large(fc, u, deg + 1, fac, ddeg, hdeg.data(), s);
+        size_t pos = 0;
+        for (size_t d = 1; d <= deg && ok; ++d) {
+            if (hdeg[d - 1] <= 0) continue;
+            const size_t m = (size_t)hdeg[d - 1];
+            if (m % d != 0 || pos + m > deg) { ok = false; break; }
+            if (m == d) {
+                ok = hipMemcpyAsync(dst + pos, fac + pos, m * sizeof(E), hipMemcpyDeviceToDevice, s) == hipSuccess;
+            } else {
+                const TempMark dm = temps_mark();
+                E* gd = temp(m + 1);
+                const E* src = fac + pos;
+                foreach_n(s, m + 1, [=] __device__(size_t j) { gd[j] = j < m ? src[j] : r1; });
+                long long nq = 0;
+                ok = edf_one_large(fc, gd, m + 1, d, dst + pos, &nq, s) && nq == (long long)(m / d);
+                temps_release(dm);
+            }
+            groups.push_back({row, e, (long long)d, m, dst + pos});
+            pos += m;
+        }
+        temps_release(mark);
+        return ok;
+    }
+    // The parts of the decomposition rows that k_yun_small wrote (rows x ld on the device, degrees read back to hdeg), appended to
+    // parts; rowid[r] (null: r0 + r) names the call's row.
+    static void factor_parts_of(const E* yparts, const long long* hdeg, size_t ld, size_t rows, const size_t* rowid, size_t r0, std::vector<FacPart>& parts) {
+        for (size_t r = 0; r < rows; ++r) {
+            size_t pos = 0;
+            for (size_t i = 1; i <= ld; ++i) {
+                const long long dg = hdeg[r * ld + i - 1];
+                if (dg <= 0) continue;
+                parts.push_back({rowid ? rowid[r] : r0 + r, (long long)i, (size_t)dg, yparts + r * ld + pos});
+                pos += (size_t)dg;
+            }
+        }
+    }
+    // The shared launches of the small regime over every part of degree <= kFactorSmall of the call, whichever row it came from:
+    //   ONE gather lays the parts with their leading 1 into rows of w + 1 (w: the highest degree among them), ONE k_ddf_small takes
+    //   them all and its degrees are read back ONCE; a g_d of degree d is a factor as it is; the others are gathered with their
+    //   leading 1, ordered by d, and split by ONE k_edf_small per distinct d present on descriptors (input offset, length, output
+    //   offset), then ranked (split_rank_launch).  Each (row, e, d) becomes one group.  The launches do not depend on the number of rows.
+    bool factor_small_parts(const FactorCall& fc, const std::vector<FacPart>& parts, std::vector<FacGroup>& groups, hipStream_t s) {
+        const size_t P = parts.size();
+        if (!P) return true;
+        size_t w = 1;
+        for (const FacPart& p : parts) if (p.deg > w) w = p.deg;
+        std::vector<FacSeg> segs(P);
+        for (size_t i = 0; i < P; ++i) segs[i] = {parts[i].src, nullptr, parts[i].deg};
+        E* G = temp(P * (w + 1)); E* DD = temp(P * w);
+        long long* ddeg = temp_as<long long>(P * w);
+        std::vector<long long> hd(P * w);
+        bool ok = factor_segments(segs, G, w + 1, w, s);
+        ddf_small_launch(fc, G, w + 1, w + 1, DD, w, w, ddeg, w, false, P, s);
+        ok = hipMemcpyAsync(hd.data(), ddeg, P * w * sizeof(long long), hipMemcpyDeviceToHost, s) == hipSuccess && hipStreamSynchronize(s) == hipSuccess && ok;
+        if (!ok) return false;
+        struct Split { size_t part, d, len; const E* src; };
+        std::vector<Split> sp;
+        size_t w2 = 0;
+        for (size_t i = 0; i < P; ++i) {
+            size_t pos = 0;
+            for (size_t d = 1; d <= w; ++d) {
+                const long long m = hd[i * w + d - 1];
+                if (m <= 0) continue;
+                if ((size_t)m % d != 0 || pos + (size_t)m > parts[i].deg) return false;
+                if ((size_t)m == d) groups.push_back({parts[i].row, parts[i].e, (long long)d, d, DD + i * w + pos});
+                else { sp.push_back({i, d, (size_t)m, DD + i * w + pos}); if ((size_t)m > w2) w2 = (size_t)m; }
+                pos += (size_t)m;
+            }
+        }
+        const size_t Q = sp.size();
+        if (!Q) return true;
+        std::stable_sort(sp.begin(), sp.end(), [](const Split& a, const Split& b) { return a.d < b.d; });
+        if (Q * (w2 + 1) > 0xFFFFFFFFull) return false;               // the descriptors are 32-bit offsets; the callers bound the rows of a pass
+        segs.resize(Q);
+        std::vector<uint32_t> desc(3 * Q);
+        for (size_t q = 0; q < Q; ++q) {
+            segs[q] = {sp[q].src, nullptr, sp[q].len};
+            desc[3 * q] = (uint32_t)(q * (w2 + 1)); desc[3 * q + 1] = (uint32_t)(sp[q].len + 1); desc[3 * q + 2] = (uint32_t)(q * w2);
+        }
+        E* H = temp(Q * (w2 + 1)); E* U = temp(Q * w2); E* V = temp(Q * w2);
+        long long* dn = temp_as<long long>(Q);
+        uint32_t* ddesc = temp_as<uint32_t>(3 * Q);
+        ok = factor_segments(segs, H, w2 + 1, w2, s);
+        ok = hipMemcpyAsync(ddesc, desc.data(), 3 * Q * sizeof(uint32_t), hipMemcpyHostToDevice, s) == hipSuccess && hipStreamSynchronize(s) == hipSuccess && ok;
+        ok = hipMemsetAsync(U, 0, Q * w2 * sizeof(E), s) == hipSuccess && ok;
+        for (size_t q0 = 0; q0 < Q && ok;) {
+            size_t q1 = q0, coeffs = 0;
+            while (q1 < Q && sp[q1].d == sp[q0].d) coeffs += 2 * sp[q1++].len + 1;
+            const size_t d = sp[q0].d;
+            const TempMark dm = temps_mark();
+            split_small_launch(fc, H, 0, 0, d, U, 0, ddesc + 3 * q0, dn + q0, false, 1u, q1 - q0, (double)coeffs, s);
+            split_rank_launch(V + q0 * w2, w2, U + q0 * w2, w2, d, dn + q0, 0, q1 - q0, s);
+            temps_release(dm);
+            q0 = q1;
+        }
+        for (size_t q = 0; q < Q; ++q) groups.push_back({parts[sp[q].part].row, parts[sp[q].part].e, (long long)sp[q].d, sp[q].len, V + q * w2});
+        return ok && hipGetLastError() == hipSuccess;
+    }
+    // The end of ecfft_poly_factor: the groups in ascending (row, e, d) are the canonical order, since each is ranked inside; the host
+    // arrays are filled from them and ONE scatter writes the factors (count x nd, zero on entry).
+    bool factor_finish(std::vector<FacGroup>& groups, size_t nd, E* factors, long long* fdeg, long long* fmult, long long* n_factors, hipStream_t s) {
+        std::sort(groups.begin(), groups.end(), [](const FacGroup& a, const FacGroup& b) {
+            return a.row != b.row ? a.row < b.row : a.e != b.e ? a.e < b.e : a.d < b.d;
+        });
+        std::vector<FacSeg> segs;
+        size_t w = 0, row = ~(size_t)0, off = 0, j = 0;
+        for (const FacGroup& g : groups) {
+            if (g.row != row) { row = g.row; off = 0; j = 0; }
+            const size_t r = g.len / (size_t)g.d;
+            if (off + g.len > nd || j + r > nd) return false;
+            segs.push_back({g.src, factors + row * nd + off, g.len});
+            for (size_t k = 0; k < r; ++k) { fdeg[row * nd + j + k] = g.d; fmult[row * nd + j + k] = g.e; }
+            n_factors[row] += (long long)r;
+            off += g.len; j += r;
+            if (g.len > w) w = g.len;
+        }
+        return factor_segments(segs, nullptr, 0, w, s);
+    }
+public:
+    // ecfft_poly_squarefree_decompose: with nd = max(nf - 1, 1), degrees (host, count x nd): degrees[b][i-1] = deg a_i of f_b = lead_b
+    // prod a_i^i (zero polynomial: -1, 0, 0, ...); parts (count x nd, crate form): the a_i of positive degree in ascending i, each as
+    // its low deg a_i coefficients, then zeros; lead (device, may be null): the leading coefficients, 0 for the zero polynomial.
+    // nf <= kFactorSmall + 1: ONE launch of k_yun_small for all rows and one read-back.  Otherwise the rows run one after another: a
+    // short polynomial in a long row goes to the same kernel on its true length, the others to yun_one_large.  Synchronous.  Caller
+    // holds lock() and checks the tree rule (ddf_leaves).
+    bool poly_squarefree_decompose(const E* f, size_t nf, E* parts, long long* degrees, E* lead, size_t count, hipStream_t s) {
+        const size_t K = kFactorSmall, nd = nf > 1 ? nf - 1 : 1;
+        long long* ddeg = temp_as<long long>(count * nd);
+        if (nf <= K + 1) {
+            yun_small_launch(f, nf, nf, parts, nd, nd, ddeg, nd, lead, count, s);
+            const bool ok = hipMemcpyAsync(degrees, ddeg, count * nd * sizeof(long long), hipMemcpyDeviceToHost, s) == hipSuccess;
+            return finish_api(s) && ok;
+        }
+        gcd_flag_ = new_flag(s);
+        bool ok = hipMemsetAsync(parts, 0, count * nd * sizeof(E), s) == hipSuccess;
+        for (size_t i = 0; i < count * nd; ++i) degrees[i] = 0;
+        for (size_t p = 0; p < count && ok; ++p) {
+            const TempMark mark = temps_mark();
+            const E* fp = f + p * nf;
+            E* op = parts + p * nd;
+            long long* hp = degrees + p * nd;
+            size_t la = 0;
+            ok = gcd_row_lens(fp, nf, nf, 1, &la, s);
+            if (ok && la <= K + 1) {
+                const size_t nw = la > 1 ? la - 1 : 1;
+                yun_small_launch(fp, nf, la ? la : 1, op, nd, nw, ddeg + p * nd, nd, lead ? lead + p : (E*)nullptr, 1, s);
+                ok = hipMemcpyAsync(hp, ddeg + p * nd, nw * sizeof(long long), hipMemcpyDeviceToHost, s) == hipSuccess && hipStreamSynchronize(s) == hipSuccess;
+            } else if (ok) {
+                if (lead) { E* lp = lead + p; foreach_n(s, 1, [=] __device__(size_t) { lp[0] = F::canon(fp[la - 1]); }); }
+                size_t pos = 0;
+                ok = yun_one_large(fp, la, [&](size_t i, const E* u, size_t du) {
+                    if (pos + du > nd || i > nd) return false;
+                    hp[i - 1] = (long long)du;
+                    const bool c = hipMemcpyAsync(op + pos, u, du * sizeof(E), hipMemcpyDeviceToDevice, s) == hipSuccess;
+                    pos += du;
+                    return c;
+                }, s);
+            }
+            temps_release(mark);
+        }
+        return finish_api(s) && ok;
+    }
+    // ecfft_poly_factor: f_b = lead_b prod_j q_j^e_j over the distinct monic irreducible q_j.  With nd = max(nf - 1, 1): n_factors (host)
+    // their number (-1: the zero polynomial), fdeg / fmult (host, count x nd) deg q_j and e_j, factors (count x nd, crate form) the
+    // q_j laid end to end, each as its low deg q_j coefficients, in ascending (e_j, deg q_j, the order of ecfft_poly_equal_degree),
+    // then zeros; lead as above.
+    //   nf <= kFactorSmall + 1: k_yun_small over all rows (passes of at most 2^16 rows), one read-back, then factor_small_parts and
+    //   factor_finish: the launches and read-backs do not depend on count.
+    //   Otherwise the rows run one after another: a row of true length <= kFactorSmall + 1 is set aside for one k_yun_small at the end;
+    //   the others run yun_one_large, whose parts of degree <= kFactorSmall are queued (copied into the row's store) and whose longer
+    //   parts go to factor_large_part.  The queued parts of ALL rows then share the launches of factor_small_parts.
+    // *capped = a factor exhausted the attempt cap.  Synchronous.  Caller holds lock() and checks the tree rule (ddf_leaves).
+    bool poly_factor(const E* f, size_t nf, E* factors, long long* fdeg, long long* fmult, long long* n_factors, E* lead, size_t count,
+                     bool* capped, hipStream_t s) {
+        const size_t K = kFactorSmall, nd = nf > 1 ? nf - 1 : 1;
+        FactorCall fc;
+        bool ok = factor_call_init(&fc, true, s);
+        ok = hipMemsetAsync(factors, 0, count * nd * sizeof(E), s) == hipSuccess && ok;
+        for (size_t i = 0; i < count * nd; ++i) fdeg[i] = fmult[i] = 0;
+        for (size_t b = 0; b < count; ++b) n_factors[b] = 0;
+        std::vector<FacGroup> groups;
+        std::vector<FacPart> parts;
+        if (nf <= K + 1) {
+            const size_t pass = (size_t)1 << 16;
+            for (size_t r0 = 0; r0 < count && ok; r0 += pass) {
+                const size_t rows = count - r0 < pass ? count - r0 : pass;
+                const TempMark mark = temps_mark();
+                E* yp = temp(rows * nd);
+                long long* ddeg = temp_as<long long>(rows * nd);
+                std::vector<long long> hdeg(rows * nd);
+                yun_small_launch(f + r0 * nf, nf, nf, yp, nd, nd, ddeg, nd, lead ? lead + r0 : (E*)nullptr, rows, s);
+                ok = hipMemcpyAsync(hdeg.data(), ddeg, rows * nd * sizeof(long long), hipMemcpyDeviceToHost, s) == hipSuccess && hipStreamSynchronize(s) == hipSuccess;
+                parts.clear(); groups.clear();
+                if (ok) {
+                    for (size_t r = 0; r < rows; ++r) if (hdeg[r * nd] < 0) n_factors[r0 + r] = -1;
+                    factor_parts_of(yp, hdeg.data(), nd, rows, nullptr, r0, parts);
+                }
+                ok = ok && factor_small_parts(fc, parts, groups, s) && factor_finish(groups, nd, factors, fdeg, fmult, n_factors, s);
+                temps_release(mark);
+            }
+            return finish_flagged(ok, fc.flag, capped, s);
+        }
+        gcd_flag_ = new_flag(s);
+        E* store = temp(count * nd);                         // per row: the queued parts from the front, the factors of the long parts from the back
+        ok = hipMemsetAsync(store, 0, count * nd * sizeof(E), s) == hipSuccess && ok;
+        std::vector<size_t> shortrows;
+        for (size_t p = 0; p < count && ok; ++p) {
+            const TempMark mark = temps_mark();
+            const E* fp = f + p * nf;
+            size_t la = 0;
+            ok = gcd_row_lens(fp, nf, nf, 1, &la, s);
+            if (ok && lead) { E* lp = lead + p; foreach_n(s, 1, [=] __device__(size_t) { lp[0] = la ? F::canon(fp[la - 1]) : F::zero(); }); }
+            if (ok && la == 0) n_factors[p] = -1;
+            else if (ok && la <= K + 1) shortrows.push_back(p);
+            else if (ok) {
+                E* sp = store + p * nd;
+                size_t front = 0, back = nd;
+                ok = yun_one_large(fp, la, [&](size_t i, const E* u, size_t du) {
+                    if (front + du > back) return false;
+                    if (du <= K) {
+                        parts.push_back({p, (long long)i, du, sp + front});
+                        front += du;
+                        return hipMemcpyAsync(sp + front - du, u, du * sizeof(E), hipMemcpyDeviceToDevice, s) == hipSuccess;
+                    }
+                    back -= du;
+                    return factor_large_part(fc, u, du, p, (long long)i, sp + back, groups, s);
+                }, s);
+            }
+            temps_release(mark);
+        }
+        if (ok && !shortrows.empty()) {
+            const size_t ns = shortrows.size();
+            E* sr = temp(ns * (K + 1)); E* yp = temp(ns * K);
+            long long* ddeg = temp_as<long long>(ns * K);
+            std::vector<long long> hdeg(ns * K);
+            std::vector<FacSeg> segs(ns);
+            for (size_t r = 0; r < ns; ++r) segs[r] = {f + shortrows[r] * nf, sr + r * (K + 1), K + 1};
+            ok = factor_segments(segs, nullptr, 0, K + 1, s);
+            yun_small_launch(sr, K + 1, K + 1, yp, K, K, ddeg, K, nullptr, ns, s);
+            ok = hipMemcpyAsync(hdeg.data(), ddeg, ns * K * sizeof(long long), hipMemcpyDeviceToHost, s) == hipSuccess && hipStreamSynchronize(s) == hipSuccess && ok;
+            if (ok) factor_parts_of(yp, hdeg.data(), K, ns, shortrows.data(), 0, parts);
+        }
+        ok = ok && factor_small_parts(fc, parts, groups, s) && factor_finish(groups, nd, factors, fdeg, fmult, n_factors, s);
+        return finish_flagged(ok, fc.flag, capped, s);
+    }
+
     // ---- ecfft_division_polynomial (division_polynomial, examples/schoofs.rs:368-431) ----
     static constexpr size_t kDivpolyMaxN = 199;
     // L(n): the coefficients of psi_n with the factor 2y of an even index removed

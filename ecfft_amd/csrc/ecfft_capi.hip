@@ -610,6 +610,38 @@ int run_poly_equal_degree(ecfft_ctx* c, DeviceChain<F>& ch, const void* g, size_
     });
 }
 
+// ecfft_poly_squarefree_decompose / ecfft_poly_factor: synchronous (degrees are read back between the steps, and the int64 arrays are
+// host arrays whatever `mem` is).  Both share ddf_check: the tree rule of ecfft_poly_find_roots and the byte counts.  Nothing fails
+// on the data; ECFFT_ERR_HIP also reports a factor that exhausted the attempt cap.
+template <class F>
+int run_poly_squarefree_decompose(ecfft_ctx* c, DeviceChain<F>& ch, const void* f, size_t nf, void* parts, int64_t* degrees, void* lead,
+                                  size_t count, int mem, void* stream) {
+    using E = typename F::elem;
+    if (!f || !parts || !degrees) return ECFFT_ERR_BAD_ARG;
+    static_assert(DeviceChain<F>::kFactorSmall + 1 == ECFFT_FACTOR_SMALL_MAX, "the header states the small regime's bound");
+    if (const int rc = ddf_check(ch, nf, count); rc != ECFFT_OK) return rc;
+    const size_t eb = count * sizeof(E), nd = nf > 1 ? nf - 1 : 1;
+    return staged(c, ch, mem, stream, {{f, nf * eb}}, {{parts, nd * eb}, {lead, eb}}, [&](auto d, auto o) -> int {
+        return ch.poly_squarefree_decompose((const E*)d[0], nf, (E*)o[0], (long long*)degrees, (E*)o[1], count, (hipStream_t)stream) ? ECFFT_OK
+                                                                                                                                      : ECFFT_ERR_HIP;
+    });
+}
+template <class F>
+int run_poly_factor(ecfft_ctx* c, DeviceChain<F>& ch, const void* f, size_t nf, void* factors, int64_t* fdeg, int64_t* fmult, int64_t* n_factors,
+                    void* lead, size_t count, int mem, void* stream) {
+    using E = typename F::elem;
+    if (!f || !factors || !fdeg || !fmult || !n_factors) return ECFFT_ERR_BAD_ARG;
+    if (const int rc = ddf_check(ch, nf, count); rc != ECFFT_OK) return rc;
+    const size_t eb = count * sizeof(E), nd = nf > 1 ? nf - 1 : 1;
+    return staged(c, ch, mem, stream, {{f, nf * eb}}, {{factors, nd * eb}, {lead, eb}}, [&](auto d, auto o) -> int {
+        bool capped = false;
+        if (!ch.poly_factor((const E*)d[0], nf, (E*)o[0], (long long*)fdeg, (long long*)fmult, (long long*)n_factors, (E*)o[1], count, &capped,
+                            (hipStream_t)stream))
+            return ECFFT_ERR_HIP;
+        return capped ? ECFFT_ERR_HIP : ECFFT_OK;
+    });
+}
+
 // ecfft_division_polynomial: inputs of one element per curve and an output of L(n) elements per curve; asynchronous like ecfft_poly_mul
 template <class F>
 int run_division_polynomial(ecfft_ctx* c, DeviceChain<F>& ch, const void* A, const void* B, size_t n, void* out, size_t count, int mem,
@@ -1351,6 +1383,16 @@ int ecfft_poly_equal_degree(ecfft_ctx* ctx, const void* g, size_t ng, size_t d, 
                             void* stream) {
     if (ng == 0 || d == 0 || count == 0) return ECFFT_ERR_BAD_ARG;
     return on_chain(ctx, [&](auto& ch) { return run_poly_equal_degree(ctx, ch, g, ng, d, factors, n_factors, count, mem, stream); });
+}
+int ecfft_poly_squarefree_decompose(ecfft_ctx* ctx, const void* f, size_t nf, void* parts, int64_t* degrees, void* lead, size_t count, int mem,
+                                    void* stream) {
+    if (nf == 0 || count == 0) return ECFFT_ERR_BAD_ARG;
+    return on_chain(ctx, [&](auto& ch) { return run_poly_squarefree_decompose(ctx, ch, f, nf, parts, degrees, lead, count, mem, stream); });
+}
+int ecfft_poly_factor(ecfft_ctx* ctx, const void* f, size_t nf, void* factors, int64_t* fdeg, int64_t* fmult, int64_t* n_factors, void* lead,
+                      size_t count, int mem, void* stream) {
+    if (nf == 0 || count == 0) return ECFFT_ERR_BAD_ARG;
+    return on_chain(ctx, [&](auto& ch) { return run_poly_factor(ctx, ch, f, nf, factors, fdeg, fmult, n_factors, lead, count, mem, stream); });
 }
 int ecfft_division_polynomial(ecfft_ctx* ctx, const void* A, const void* B, size_t n, void* out, size_t count, int mem, void* stream) {
     if (count == 0) return ECFFT_ERR_BAD_ARG;

@@ -3558,6 +3558,103 @@ __global__ __launch_bounds__(K) void k_ddf_small(const typename F::elem* __restr
     __syncthreads();
     if (t < nw) { ob[t] = sout[t]; db[t] = sdegs[t]; }
 }
+// Yun's squarefree decomposition f = lc prod_i a_i^i (a_i monic, squarefree, pairwise coprime) of one polynomial of degree <= K in
+// one workgroup of K threads, everything in LDS (ecfft_poly_squarefree_decompose; the first step of ecfft_poly_factor).  Block b
+// reads nin <= K + 1 coefficients (crate form, untrimmed, any non-zero leading coefficient) at in + b*ldin.
+//   The state is the monic b (sb, plain residues without the leading 1, degree db) and a row sd of degree < db.  One step takes
+//   u = gcd(b, sd) (roots_gcd_rows; sd = 0 leaves u = b), made monic by the one inversion of the step, and where deg u > 0 divides
+//   it out of both: b <- b / u and c = sd / u.  sd is not monic, but b + sd is, of degree db, and u divides both, so
+//   (b + sd) / u = b / u + sd / u: two runs of ddf_div_monic and a subtraction.  Then sd <- c - b', with b'_j = (j + 1) b_(j+1) on the
+//   plain integer j + 1 as in k_ddf_small (p > K: derivatives vanish for constants only, there is no p-th-power case).
+//   Step 0 starts from b = f, sd = f': u = a_0 = gcd(f, f') is not an output, and leaves b = f / a_0, sd = f' / a_0 - b'.  Step
+//   i >= 1 yields a_i = u; a step that meets sd = 0 yields a_i = b and ends the loop.  A squarefree f has a_0 = 1, so sd = f' - f' =
+//   0 and step 1 is its last.  i never exceeds deg f.
+//   out + b*ldout receives nw <= K entries: the a_i of positive degree in ascending i, each as its low deg a_i coefficients (crate
+//   form; the layout of k_ddf_small's g_d), then zeros; deg_out[b*lddeg + i - 1] = deg a_i for i <= nw (the zero polynomial: -1, 0,
+//   0, ...; a non-zero constant: zeros); lead[b] (lead may be null) = the leading coefficient, 0 for the zero polynomial.
+// Loop bounds are fixed at launch: at most K + 1 steps on degrees <= K.  Every thread takes every barrier: degrees come from LDS
+// behind a barrier (gcd_remainder_loop), and pos + db <= deg f holds throughout, so nothing is written past sout.  r1 = R.
+template <class F, int K>
+__global__ __launch_bounds__(K) void k_yun_small(const typename F::elem* __restrict__ in, size_t ldin, uint32_t nin,
+                                                 typename F::elem* __restrict__ out, size_t ldout, uint32_t nw,
+                                                 long long* __restrict__ deg_out, size_t lddeg, typename F::elem* __restrict__ lead,
+                                                 typename F::elem r1) {
+    using E = typename F::elem;
+    __shared__ E sb[K], sd[K], sx[K], squo[K + 1], scq[K + 1], sout[K], swork[K + 1], rows[2 * (K + 1)];
+    __shared__ E snorm;
+    __shared__ int sdeg[2], sdegs[K];
+    const uint32_t t = threadIdx.x;
+    const size_t b = blockIdx.x;
+    const E* fb = in + b * ldin;
+    E* ob = out + b * ldout;
+    long long* dgb = deg_out + b * lddeg;
+    sout[t] = F::zero();
+    sdegs[t] = 0;
+    // ---- the true degree, and the row made monic (plain residues f_t / f_n) ----
+    const int n = small_row_monic<F, K>(fb, nin, sb, &snorm, sdeg, t);
+    if (t == 0 && lead) lead[b] = n >= 0 ? F::canon(fb[n]) : F::zero();
+    int db = n < 0 ? 0 : n;                                  // deg b
+    uint32_t pos = 0;                                        // coefficients appended so far
+    if (n >= 1) {
+        __syncthreads();
+        {
+            E v = F::zero();                                 // sd = f'
+            if ((int)t < n) {
+                v = F::from_u32(t + 1);
+                if ((int)t + 1 < n) v = F::canon(F::mul(v, sb[t + 1]));
+            }
+            sd[t] = v;
+        }
+        __syncthreads();
+        for (int i = 0; i <= K && db > 0; ++i) {
+            E* R0 = rows;
+            E* R1 = rows + K + 1;
+            if ((int)t < db) { R0[t] = sb[t]; R1[t] = sd[t]; }
+            if (t == 0) R0[db] = F::one();
+            const int du = roots_gcd_rows<F, K>(R0, R1, db, sdeg, t);
+            E c = sd[t];                                     // deg u = 0: c = sd
+            if (du > 0) {
+                if (i > 0 && du == db) {                     // sd = 0: a_i = b, the last one
+                    if ((int)t < db) sout[pos + t] = F::canon(F::mul(sb[t], r1));
+                    if (t == 0) sdegs[i - 1] = db;
+                    break;
+                }
+                if (t == 0) snorm = F::canon(F::inv(R0[du]));
+                __syncthreads();
+                if ((int)t < du) {
+                    const E v = F::canon(F::mul(R0[t], snorm));
+                    sx[t] = v;
+                    if (i > 0) sout[pos + t] = F::canon(F::mul(v, r1));
+                }
+                if (t == 0 && i > 0) sdegs[i - 1] = du;
+                if ((int)t < db) sd[t] = F::canon(F::add(sd[t], sb[t]));
+                __syncthreads();
+                ddf_div_monic<F>(squo, swork, sb, db, sx, du, t);
+                ddf_div_monic<F>(scq, swork, sd, db, sx, du, t);
+                if (i > 0) pos += (uint32_t)du;
+                db -= du;
+                E bq = F::zero();
+                c = F::zero();
+                if ((int)t < db) { bq = squo[t]; c = F::canon(F::sub(scq[t], bq)); }
+                sb[t] = bq;
+                __syncthreads();
+            }
+            {
+                E v = F::zero();                             // sd <- c - b'
+                if ((int)t < db) {
+                    E m = F::from_u32(t + 1);
+                    if ((int)t + 1 < db) m = F::canon(F::mul(m, sb[t + 1]));
+                    v = F::canon(F::sub(c, m));
+                }
+                sd[t] = v;
+            }
+            __syncthreads();
+        }
+    }
+    if (t == 0 && n < 0) sdegs[0] = -1;
+    __syncthreads();
+    if (t < nw) { ob[t] = sout[t]; dgb[t] = sdegs[t]; }
+}
 
 // ---------------------------------------------------------------------------------------------
 // ecfft_poly_equal_degree (utils::equal_degree_factorization, src/utils.rs:82-113, with the splitting element taken through the

@@ -34,7 +34,7 @@ EXPORTS = ["ecfft_elem_size", "ecfft_build_fftree", "ecfft_fftree_new", "ecfft_c
            "ecfft_fftree_serialize", "ecfft_fftree_deserialize", "ecfft_tree_rational_maps", "ecfft_ctx_trim", "ecfft_comm_abort", "ecfft_comm_set_rccl_library", "ecfft_comm_set_link_striping",
            "ecfft_poly_mul", "ecfft_poly_inv_series", "ecfft_poly_divrem", "ecfft_poly_eval_points", "ecfft_poly_interpolate",
            "ecfft_poly_pow_mod", "ecfft_poly_mul_mod", "ecfft_poly_gcd", "ecfft_poly_xgcd", "ecfft_poly_xgcd_partial", "ecfft_rs_decode", "ecfft_poly_find_roots",
-           "ecfft_poly_compose_mod", "ecfft_poly_squarefree", "ecfft_poly_distinct_degree", "ecfft_poly_equal_degree", "ecfft_division_polynomial", "ecfft_curve_trace_mod", "ecfft_curve_cardinality",
+           "ecfft_poly_compose_mod", "ecfft_poly_squarefree", "ecfft_poly_distinct_degree", "ecfft_poly_equal_degree", "ecfft_poly_squarefree_decompose", "ecfft_poly_factor", "ecfft_division_polynomial", "ecfft_curve_trace_mod", "ecfft_curve_cardinality",
            "ecfft_find_curve_candidate", "ecfft_curve_two_sylow", "ecfft_find_curve", "ecfft_build_fftree_on_curve",
            "ecfft_curve_point_mul", "ecfft_curve_point_two_adicity", "ecfft_curve_find_generator", "ecfft_build_ec_fftree"]
 # include/ecfft_hip.h ECFFT_GCD_SMALL_MAX: max(na, nb) up to which a gcd runs in one workgroup per pair, on any tree
@@ -51,6 +51,8 @@ COMPOSE_SMALL_MAX = 65
 DDF_SMALL_MAX = 65
 # include/ecfft_hip.h ECFFT_EDF_SMALL_MAX: ng up to which poly_equal_degree finishes a polynomial in one workgroup, on any tree
 EDF_SMALL_MAX = 65
+# include/ecfft_hip.h ECFFT_FACTOR_SMALL_MAX: nf up to which poly_squarefree_decompose / poly_factor run on workgroup kernels alone, on any tree
+FACTOR_SMALL_MAX = 65
 # include/ecfft_hip.h ECFFT_SCHOOF_SMALL_MAX / ECFFT_SCHOOF_MAX_L / ECFFT_ORDER_BYTES: coefficients of a modulus that one workgroup of
 # curve_trace_mod finishes; the largest prime l and the largest index of division_polynomial; bytes of an order
 SCHOOF_SMALL_MAX = 65
@@ -105,6 +107,8 @@ def _bind(L):
     L.ecfft_poly_squarefree.restype, L.ecfft_poly_squarefree.argtypes = ci, [vp, vp, sz, vp, vp, sz, ci, vp]
     L.ecfft_poly_distinct_degree.restype, L.ecfft_poly_distinct_degree.argtypes = ci, [vp, vp, sz, vp, vp, sz, ci, vp]
     L.ecfft_poly_equal_degree.restype, L.ecfft_poly_equal_degree.argtypes = ci, [vp, vp, sz, sz, vp, vp, sz, ci, vp]
+    L.ecfft_poly_squarefree_decompose.restype, L.ecfft_poly_squarefree_decompose.argtypes = ci, [vp, vp, sz, vp, vp, vp, sz, ci, vp]
+    L.ecfft_poly_factor.restype, L.ecfft_poly_factor.argtypes = ci, [vp, vp, sz, vp, vp, vp, vp, vp, sz, ci, vp]
     L.ecfft_division_polynomial.restype, L.ecfft_division_polynomial.argtypes = ci, [vp, vp, vp, sz, vp, sz, ci, vp]
     L.ecfft_curve_cardinality.restype, L.ecfft_curve_cardinality.argtypes = ci, [vp, vp, vp, vp, vp, sz, ci, vp]
     L.ecfft_curve_trace_mod.restype, L.ecfft_curve_trace_mod.argtypes = ci, [vp, vp, vp, sz, vp, sz, ci, vp]
@@ -964,6 +968,65 @@ class FFTree:
         for d, gd in self.ddf_unpack(fac, deg[0]).items():
             row, n = self.poly_equal_degree(np.ascontiguousarray(gd), d)
             out[d] = self.edf_unpack(row, n[0], d)
+        return out
+
+    def poly_squarefree_decompose(self, f, count=1):
+        """(parts, degrees, lead): Yun's squarefree decomposition f_b = lead_b prod_i a_i^i (ecfft_poly_squarefree_decompose; the a_i
+        monic, squarefree and pairwise coprime) of `count` polynomials laid end to end, f of count * nf coefficients; rows need not be
+        trimmed.  With nd = max(nf - 1, 1), degrees is a numpy int64 array of shape (count, nd): degrees[b, i-1] = deg a_i (the zero
+        polynomial: -1, 0, 0, ...; a non-zero constant: zeros).  parts has count * nd elements: row b holds the a_i of positive degree
+        in ascending i, each as its low deg a_i coefficients (the leading 1 is implied), then zeros: the layout of
+        poly_distinct_degree, so ddf_unpack(row, degrees[b]) makes the dict {i: a_i}.  lead has count elements: the leading
+        coefficients, 0 for the zero polynomial.  nf <= FACTOR_SMALL_MAX works on any tree (one launch for all rows); otherwise a tree
+        of next_pow2(2 nf - 1) leaves.  numpy arrays (host) or contiguous CUDA tensors (device, on the current stream).  Synchronous."""
+        (f,), (pf,), new, mem, stream = self._poly_io([f])
+        assert count > 0 and f.shape[0] % count == 0
+        nf = f.shape[0] // count
+        nd = max(nf - 1, 1)
+        parts = new(count * nd if nf else 0)
+        lead = new(count)
+        degrees = np.empty((count, nd), np.int64)
+        rc = self._L.ecfft_poly_squarefree_decompose(self._h, pf, nf, self._ptr(parts) if nf else None, degrees.ctypes.data, self._ptr(lead), count, mem, stream)
+        if rc == ERR_BAD_ARG:
+            raise ValueError("poly_squarefree_decompose: empty operand, count = 0 or a context that holds no full tree")
+        _check(rc)
+        return parts, degrees, lead
+
+    def poly_factor(self, f, count=1):
+        """(factors, fdeg, fmult, n_factors, lead): the factorisation f_b = lead_b prod_j q_j^e_j over the distinct monic irreducible
+        q_j (ecfft_poly_factor) of `count` polynomials laid end to end, f of count * nf coefficients; rows need not be trimmed.  With
+        nd = max(nf - 1, 1): n_factors is a numpy int64 array, -1 for the zero polynomial and 0 for a non-zero constant; fdeg and fmult
+        are int64 arrays of shape (count, nd) whose entries j < n_factors[b] hold deg q_j and e_j, the rest 0; factors has count * nd
+        elements: row b holds the q_j laid end to end, each as its low deg q_j coefficients (the leading 1 is implied), in ascending
+        (e_j, deg q_j, then the order of poly_equal_degree), then zeros; factor_unpack(row, fdeg[b], fmult[b], n_factors[b]) makes a
+        list of them.  lead as in poly_squarefree_decompose.  Deterministic and byte-exact: nothing depends on the splitting shifts.
+        nf <= FACTOR_SMALL_MAX works on any tree, with a number of launches that does not depend on count; otherwise a tree of
+        next_pow2(2 nf - 1) leaves.  numpy arrays (host) or contiguous CUDA tensors (device, on the current stream).  Synchronous."""
+        (f,), (pf,), new, mem, stream = self._poly_io([f])
+        assert count > 0 and f.shape[0] % count == 0
+        nf = f.shape[0] // count
+        nd = max(nf - 1, 1)
+        factors = new(count * nd if nf else 0)
+        lead = new(count)
+        fdeg, fmult = np.empty((count, nd), np.int64), np.empty((count, nd), np.int64)
+        n_factors = np.empty(count, np.int64)
+        rc = self._L.ecfft_poly_factor(self._h, pf, nf, self._ptr(factors) if nf else None, fdeg.ctypes.data, fmult.ctypes.data, n_factors.ctypes.data,
+                                       self._ptr(lead), count, mem, stream)
+        if rc == ERR_BAD_ARG:
+            raise ValueError("poly_factor: empty operand, count = 0 or a context that holds no full tree")
+        _check(rc)
+        return factors, fdeg, fmult, n_factors, lead
+
+    def factor_unpack(self, row, fdeg_row, fmult_row, n):
+        """One row of poly_factor as [(q, e), ...]: q the deg q + 1 coefficients of the factor with its leading 1 (in the crate's form),
+        e its multiplicity, in the call's order.  Host arrays."""
+        row = np.ascontiguousarray(row, self.field.dtype)
+        one = self._crate_one()
+        out, pos = [], 0
+        for j in range(max(int(n), 0)):
+            d = int(fdeg_row[j])
+            out.append((np.concatenate([row[pos:pos + d], one]), int(fmult_row[j])))
+            pos += d
         return out
 
     @staticmethod

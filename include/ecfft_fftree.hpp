@@ -12,6 +12,7 @@
 #include <optional>
 #include <stdexcept>
 #include <string>
+#include <utility>
 #include <vector>
 #include "ecfft_hip.h"
 
@@ -422,6 +423,58 @@ public:
             std::vector<Elem> q(fac.data() + i * d, fac.data() + (i + 1) * d);
             q.push_back(one);
             out.push_back(std::move(q));
+        }
+        return out;
+    }
+    // multiplicity i -> the monic a_i of positive degree, with its leading 1, of Yun's decomposition f = lead prod_i a_i^i: the a_i
+    // squarefree and pairwise coprime (ecfft_poly_squarefree_decompose; the reference's square_free_factors, src/utils.rs:46-50,
+    // returns prod a_i only).  lead (may be null) receives the leading coefficient.  A non-zero constant gives an empty map; the zero
+    // polynomial throws.  Up to ECFFT_FACTOR_SMALL_MAX coefficients work on any tree; tree rule as square_free.  Synchronous.
+    std::map<size_t, std::vector<Elem>> square_free_decomposition(const std::vector<Elem>& f, Elem* lead = nullptr) const {
+        require(!f.empty(), "square_free_decomposition: the polynomial must not be empty");
+        const size_t nd = f.size() > 1 ? f.size() - 1 : 1;
+        std::vector<Elem> parts(nd);
+        std::vector<int64_t> deg(nd);
+        check(ecfft_poly_squarefree_decompose(ctx_, f.data(), f.size(), parts.data(), deg.data(), lead, 1, ECFFT_MEM_HOST, nullptr));
+        require(deg[0] >= 0, "square_free_decomposition: the zero polynomial");
+        Elem std_one{}, one{};
+        const uint32_t u = 1;
+        std::memcpy(&std_one, &u, sizeof u);                    // standard form is little-endian
+        check(ecfft_elems_from_standard(F::id, &std_one, &one, 1));
+        std::map<size_t, std::vector<Elem>> out;
+        size_t pos = 0;
+        for (size_t i = 1; i <= nd; ++i) {
+            if (deg[i - 1] <= 0) continue;
+            std::vector<Elem> a(parts.data() + pos, parts.data() + pos + (size_t)deg[i - 1]);
+            a.push_back(one);
+            out.emplace(i, std::move(a));
+            pos += (size_t)deg[i - 1];
+        }
+        return out;
+    }
+    // (q, e) for every distinct monic irreducible factor q of f = lead prod q^e, q with its leading 1, in ascending (e, deg q, then the
+    // order of equal_degree_factors) (ecfft_poly_factor: the reference's three steps, src/utils.rs:25-113, for every degree and with
+    // the multiplicities).  lead (may be null) receives the leading coefficient.  A non-zero constant gives an empty vector; the zero
+    // polynomial throws.  Deterministic.  Up to ECFFT_FACTOR_SMALL_MAX coefficients work on any tree; tree rule as square_free.
+    std::vector<std::pair<std::vector<Elem>, size_t>> factor(const std::vector<Elem>& f, Elem* lead = nullptr) const {
+        require(!f.empty(), "factor: the polynomial must not be empty");
+        const size_t nd = f.size() > 1 ? f.size() - 1 : 1;
+        std::vector<Elem> fac(nd);
+        std::vector<int64_t> fdeg(nd), fmult(nd);
+        int64_t n = 0;
+        check(ecfft_poly_factor(ctx_, f.data(), f.size(), fac.data(), fdeg.data(), fmult.data(), &n, lead, 1, ECFFT_MEM_HOST, nullptr));
+        require(n >= 0, "factor: the zero polynomial");
+        Elem std_one{}, one{};
+        const uint32_t u = 1;
+        std::memcpy(&std_one, &u, sizeof u);                    // standard form is little-endian
+        check(ecfft_elems_from_standard(F::id, &std_one, &one, 1));
+        std::vector<std::pair<std::vector<Elem>, size_t>> out;
+        size_t pos = 0;
+        for (size_t j = 0; j < (size_t)n; ++j) {
+            std::vector<Elem> q(fac.data() + pos, fac.data() + pos + (size_t)fdeg[j]);
+            q.push_back(one);
+            out.emplace_back(std::move(q), (size_t)fmult[j]);
+            pos += (size_t)fdeg[j];
         }
         return out;
     }

@@ -395,6 +395,48 @@ int ecfft_poly_distinct_degree(ecfft_ctx* ctx, const void* f, size_t nf, void* f
 int ecfft_poly_equal_degree(ecfft_ctx* ctx, const void* g, size_t ng, size_t d, void* factors, int64_t* n_factors, size_t count, int mem,
                             void* stream);
 
+/* Factorisation over the field in one call: f = lead prod_i a_i^i (squarefree decomposition) and f = lead prod_j q_j^e_j.
+ *   ecfft_poly_squarefree_decompose <-> no reference item: ecfft::utils::square_free_factors (src/utils.rs:46-50) returns
+ *                                       f / gcd(f, f') only; this is Yun's decomposition, which keeps the multiplicities
+ *   ecfft_poly_factor               <-> square_free_factors, distinct_degree_factors and equal_degree_factorization strung
+ *                                       together as find_roots strings them (src/utils.rs:25-113), for every degree and with the
+ *                                       multiplicities the reference drops
+ * Layout: f is count x nf coefficients in the crate's form; the rows NEED NOT BE TRIMMED and any non-zero leading coefficient is
+ * accepted.  nd = max(nf - 1, 1).  `lead` may be NULL; otherwise it is `count` elements in the memory `mem` names: the leading
+ * coefficient of f_b, 0 for the zero polynomial.  Element outputs are fully reduced, in the crate's form, zero-padded, and must not
+ * overlap f.  The int64 outputs are HOST pointers whatever `mem` is.
+ * ecfft_poly_squarefree_decompose: f_b = lead prod_i a_i^i with the a_i monic, squarefree and pairwise coprime.  degrees is
+ *   count x nd and degrees[b][i-1] = deg a_i (i never exceeds deg f <= nd); the zero polynomial gives -1, 0, 0, ..., a non-zero
+ *   constant all zeros.  parts is count x nd elements: row b holds the a_i of positive degree in ascending i, each as its LOW
+ *   deg a_i coefficients (the leading 1 is implied: the layout of ecfft_poly_distinct_degree's g_d); sum i deg a_i = deg f_b.
+ * ecfft_poly_factor: f_b = lead prod_j q_j^e_j over the distinct monic irreducible q_j.  n_factors[b] is their number: -1 for the
+ *   zero polynomial, 0 for a non-zero constant.  fdeg and fmult are count x nd: entry j < n_factors[b] holds deg q_j and e_j, the
+ *   rest are 0.  factors is count x nd elements: the q_j laid end to end, each as its low deg q_j coefficients.
+ *   Order: ascending (e_j, deg q_j, then the lexicographic order of ecfft_poly_equal_degree).  Every group (multiplicity, degree)
+ *   is one contiguous, ranked output of the equal-degree step.  Nothing in the result depends on the shifts, so it is deterministic
+ *   and bit-exact.
+ * Method: with f made monic, a_0 = gcd(f, f'), b = f / a_0, c = f' / a_0, d = c - b'; for i = 1, 2, ... while deg b > 0:
+ *   a_i = gcd(b, d) (gcd(b, 0) = b), b <- b / a_i, c <- d / a_i, d <- c - b' (Yun).  Both fields have p larger than any degree a
+ *   tree holds, so derivatives vanish for constants only and there is no p-th-power case; a squarefree f costs one iteration.
+ *   ecfft_poly_factor then takes every a_i through the steps of ecfft_poly_distinct_degree and ecfft_poly_equal_degree.
+ * ECFFT_FACTOR_SMALL_MAX: nf up to which everything is done by workgroup kernels, one workgroup per row or part, everything in
+ *   LDS: one launch for Yun's loop over all rows, one for the distinct-degree step over all parts of all rows, one equal-degree
+ *   launch per distinct degree that needs splitting (and its ordering), and one scatter; the number of launches and of read-backs
+ *   does not depend on `count`.  Above it the rows run one after another on the bodies of ecfft_poly_gcd and ecfft_poly_divrem; a
+ *   row whose true length fits goes to the workgroup kernels, parts of degree above 64 run the large regimes of the two calls
+ *   above, and the parts of degree at most 64 of ALL rows share the launches of the small regime at the end of the call.
+ * A factor that fails 64 shifts in a row (chance below 2^-63; the bound keeps a defect from spinning) ends ecfft_poly_factor with
+ * ECFFT_ERR_HIP; the context keeps working.
+ * Tree: nf <= ECFFT_FACTOR_SMALL_MAX needs no transform (any tree).  Otherwise the rule of ecfft_poly_find_roots, next_pow2(2 nf - 1)
+ * leaves, checked on the row length before anything runs.  Else ECFFT_ERR_TREE_TOO_SMALL.
+ * ECFFT_ERR_BAD_ARG: NULL f, parts / factors or host array, nf or count 0, a context that holds no full tree, a byte count that
+ * would wrap.  Both calls are SYNCHRONOUS.  Memory, stream, threading and pooled temporaries as for ecfft_poly_gcd. */
+#define ECFFT_FACTOR_SMALL_MAX 65   /* coefficients per row finished by workgroup kernels on any tree */
+int ecfft_poly_squarefree_decompose(ecfft_ctx* ctx, const void* f, size_t nf, void* parts, int64_t* degrees, void* lead, size_t count,
+                                    int mem, void* stream);
+int ecfft_poly_factor(ecfft_ctx* ctx, const void* f, size_t nf, void* factors, int64_t* fdeg, int64_t* fmult, int64_t* n_factors,
+                      void* lead, size_t count, int mem, void* stream);
+
 /* Division polynomials of short Weierstrass curves y^2 = x^3 + A x + B on the GPU.
  *   ecfft_division_polynomial <-> division_polynomial(n, &curve)                          examples/schoofs.rs:368-431
  * A and B are `count` elements each in the crate's form (host or device memory per `mem`); out is count x L(n) coefficients,
