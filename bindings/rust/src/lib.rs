@@ -27,6 +27,8 @@ pub mod ffi {
     pub const ERR_HIP: i32 = 4;
     pub const ERR_BAD_ARG: i32 = 5;
     pub const MEM_HOST: i32 = 0;
+    pub const RS_OUT_COEFFS: i32 = 0;
+    pub const RS_OUT_CODEWORD: i32 = 1;
     pub const MEM_DEVICE: i32 = 1;
     // ECFFT_TBL_*
     pub const TBL_F: i32 = 0;
@@ -72,6 +74,8 @@ pub mod ffi {
         pub fn ecfft_poly_xgcd(ctx: *mut EcfftCtx, a: *const c_void, na: usize, b: *const c_void, nb: usize, s: *mut c_void, t: *mut c_void, g: *mut c_void, degrees: *mut i64, count: usize, mem: i32, stream: *mut c_void) -> i32;
         pub fn ecfft_poly_xgcd_partial(ctx: *mut EcfftCtx, a: *const c_void, na: usize, b: *const c_void, nb: usize, stop: usize, r: *mut c_void, s: *mut c_void, t: *mut c_void, degrees: *mut i64, count: usize, mem: i32, stream: *mut c_void) -> i32;
         pub fn ecfft_rs_decode(ctx: *mut EcfftCtx, points: *const c_void, m: usize, values: *const c_void, k: usize, message: *mut c_void, n_errors: *mut i64, count: usize, mem: i32, stream: *mut c_void) -> i32;
+        pub fn ecfft_rs_encode(ctx: *mut EcfftCtx, points: *const c_void, m: usize, data: *const c_void, k: usize, codeword: *mut c_void, count: usize, mem: i32, stream: *mut c_void) -> i32;
+        pub fn ecfft_rs_decode_erasures(ctx: *mut EcfftCtx, points: *const c_void, m: usize, values: *const c_void, erased: *const u8, k: usize, out: *mut c_void, out_form: i32, n_errors: *mut i64, count: usize, mem: i32, stream: *mut c_void) -> i32;
         pub fn ecfft_mextend(ctx: *mut EcfftCtx, inp: *const c_void, out: *mut c_void, e: usize, moiety: i32, count: usize, mem: i32, stream: *mut c_void) -> i32;
         pub fn ecfft_redc(ctx: *mut EcfftCtx, evals: *const c_void, a: *const c_void, out: *mut c_void, n: usize, moiety: i32, mem: i32, stream: *mut c_void) -> i32;
         pub fn ecfft_modular_reduce(ctx: *mut EcfftCtx, evals: *const c_void, a: *const c_void, c: *const c_void, out: *mut c_void, n: usize, mem: i32, stream: *mut c_void) -> i32;
@@ -537,6 +541,39 @@ impl<F: HipField> HipFFTree<F> {
             None
         } else {
             Some((message, n_errors as usize))
+        }
+    }
+
+    /// `ecfft_rs_encode` (no reference counterpart): the systematic Reed-Solomon encoder.  `points`: `m` pairwise distinct elements;
+    /// `data`: `1 <= k <= m` symbols.  Returns the `m` symbols of the `f` of degree `< k` with `f(points[i]) = data[i]` for `i < k`
+    /// at all points: the data, then `m - k` parity symbols.  Up to `ECFFT_RS_SMALL_MAX` points work on any tree; tree rule:
+    /// include/ecfft_hip.h.  Panics on two equal points.
+    pub fn rs_encode(&self, points: &[F], data: &[F]) -> Vec<F> {
+        assert!(!data.is_empty() && data.len() <= points.len());
+        let mut codeword = Self::out_vec(points.len());
+        check(unsafe { ffi::ecfft_rs_encode(self.ctx, points.as_ptr().cast(), points.len(), data.as_ptr().cast(), data.len(), codeword.as_mut_ptr().cast(), 1, ffi::MEM_HOST, core::ptr::null_mut()) });
+        unsafe { codeword.set_len(points.len()) };
+        codeword
+    }
+
+    /// `ecfft_rs_decode_erasures`: Reed-Solomon decoding with erasures and errors.  `erased[i] != 0` marks a lost symbol, whose value
+    /// is never read (`None`: no erasure).  The result is `rs_decode` on the kept points and values: with `m'` of them, the `f` of
+    /// degree `< k` within `(m' - k) / 2` errors, `None` when there is none or `m' < k`.  `Some((out, n_errors))`: the `k`
+    /// coefficients of `f`, or with `codeword` its `m` symbols at all points — the erased positions filled in, the first `k` the
+    /// corrected data of `rs_encode`'s code.  Tree rule and panics as `rs_decode`.
+    pub fn rs_decode_erasures(&self, points: &[F], values: &[F], erased: Option<&[u8]>, k: usize, codeword: bool) -> Option<(Vec<F>, usize)> {
+        assert!(!points.is_empty() && points.len() == values.len() && k >= 1 && k <= points.len());
+        assert!(erased.map_or(true, |e| e.len() == points.len()));
+        let n = if codeword { points.len() } else { k };
+        let mut out = Self::out_vec(n);
+        let mut n_errors: i64 = -1;
+        let mask = erased.map_or(core::ptr::null(), |e| e.as_ptr());
+        check(unsafe { ffi::ecfft_rs_decode_erasures(self.ctx, points.as_ptr().cast(), points.len(), values.as_ptr().cast(), mask, k, out.as_mut_ptr().cast(), if codeword { ffi::RS_OUT_CODEWORD } else { ffi::RS_OUT_COEFFS }, &mut n_errors, 1, ffi::MEM_HOST, core::ptr::null_mut()) });
+        unsafe { out.set_len(n) };
+        if n_errors < 0 {
+            None
+        } else {
+            Some((out, n_errors as usize))
         }
     }
 

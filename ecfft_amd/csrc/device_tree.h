@@ -4082,6 +4082,12 @@ public:
     // at the leaves (k_eval_leaves).  G == B: no tree, f itself is every block's remainder.  Device pointers; asynchronous on `s`
     // (every node is monic, so nothing can fail on the data).  Caller holds lock() and checks the tree rule (G <= size() if G > B).
     bool poly_eval_points(const E* f, size_t nf, const E* points, size_t m, E* out, size_t count, hipStream_t s) {
+        const bool ok = eval_points_body(f, nf, points, m, out, count, s);
+        temps_done();
+        return ok && hipGetLastError() == hipSuccess;
+    }
+    // poly_eval_points without its end of call: the temporaries stay the caller's
+    bool eval_points_body(const E* f, size_t nf, const E* points, size_t m, E* out, size_t count, hipStream_t s) {
         const size_t B = kEvalLeaf, G = eval_group(nf), P = (m + G - 1) / G * G;
         bool ok = true;
         const E* rem = f;
@@ -4097,8 +4103,7 @@ public:
         ECFFT_LAUNCH(KC_POINTWISE, sizeof(E) * ((double)rows * nc + (double)count * m + (double)m), (k_eval_leaves<F, (int)kEvalLeaf>),
                      dim3(nblocks(rows * B)), dim3(kBlock), 0, s, out, rem, ld_poly, ld_row, (uint32_t)nc, points, m, P / B, rows,
                      rinv_table());
-        temps_done();
-        return ok && hipGetLastError() == hipSuccess;
+        return ok;
     }
     // leaf size B of the remainder tree: a node of B points is evaluated by Horner (B multiplies per point) instead of descending
     static constexpr size_t kEvalLeaf = 64;
@@ -4329,6 +4334,179 @@ public:
             }
         }
         ok = finish_flagged(ok, flag, repeated, s);
+        for (size_t p = 0; p < count; ++p) n_errors[p] = herr[p];
+        return ok;
+    }
+    // ---- ecfft_rs_encode / ecfft_rs_decode_erasures: the systematic codec ----
+    // Above kRsSmall the encoder interpolates at the first k points and evaluates k coefficients at the other m - k
+    static size_t rs_encode_leaves(size_t m, size_t k) { return m <= kRsSmall || k <= kEvalLeaf ? 1 : eval_group(k); }
+    // *repeated = two of the m points are equal: fully reduced copies sorted on the host (the large regime's check over ALL points,
+    // which no single interpolation of that regime covers).  Drains s.
+    bool rs_points_repeat(const E* points, size_t m, bool* repeated, hipStream_t s) {
+        E* c = temp(m);
+        foreach_n(s, m, [=] __device__(size_t i) { c[i] = F::canon(points[i]); });
+        std::vector<E> h(m);
+        if (hipMemcpyAsync(h.data(), c, m * sizeof(E), hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) return false;
+        auto less = [](const E& a, const E& b) { return std::memcmp(&a, &b, sizeof(E)) < 0; };
+        std::sort(h.begin(), h.end(), less);
+        *repeated = false;
+        for (size_t i = 1; i < m; ++i) if (std::memcmp(&h[i - 1], &h[i], sizeof(E)) == 0) *repeated = true;
+        return true;
+    }
+    // codeword (count x m) = data (count x k, fully reduced) followed by the m - k values at points[k..m) of the f_b of degree < k
+    // with f_b(points[i]) = data[b][i], i < k.
+    //   m <= kRsSmall: k_rs_encode_prepare (the (m - k) x k matrix of the Lagrange basis at the parity points, shared by the rows),
+    //     then k_rs_encode_small, G / (m - k) rows per workgroup.
+    //   otherwise interpolate_body at the first k points and eval_points_body at the others, for all rows at once.
+    // Synchronous; *repeated = two equal points among all m.  Caller holds lock() and checks the tree rule (rs_encode_leaves).
+    bool rs_encode(const E* points, size_t m, const E* data, size_t k, E* codeword, size_t count, bool* repeated, hipStream_t s) {
+        const size_t npar = m - k;
+        int* flag = new_flag(s);
+        bool ok = true, rep = false;
+        if (m <= kRsSmall) {
+            constexpr int G = (int)kGcdSmall;
+            E* gt = temp(npar ? npar * k : 1);
+            ECFFT_LAUNCH(KC_POINTWISE, sizeof(E) * ((double)m + (double)npar * (double)k), (k_rs_encode_prepare<F, G>), dim3((unsigned)(npar ? npar : 1)),
+                         dim3(G), 0, s, points, (uint32_t)m, (uint32_t)k, gt, flag);
+            const size_t rpb = npar ? (size_t)G / npar : (size_t)G, blocks = (count + rpb - 1) / rpb;
+            for_chunks(blocks, [&](size_t c0, size_t c) {
+                const size_t b0 = c0 * rpb;
+                ECFFT_LAUNCH(KC_POINTWISE, sizeof(E) * ((double)(count - b0) * (double)(m + k) + (double)npar * (double)k), (k_rs_encode_small<F, G>),
+                             dim3((unsigned)c), dim3(G), 0, s, data + b0 * k, (uint32_t)m, (uint32_t)k, (const E*)gt, codeword + b0 * m, count - b0,
+                             (uint32_t)rpb);
+            });
+        } else {
+            ok = rs_points_repeat(points, m, &rep, s);
+            if (ok && !rep) {
+                E* coef = temp(count * k); E* par = temp(npar ? count * npar : 1);
+                if (npar) {
+                    ok = interpolate_body(points, k, data, coef, count, flag, nullptr, s);
+                    ok = eval_points_body(coef, k, points + k, npar, par, count, s) && ok;
+                }
+                foreach_n(s, count * m, [=] __device__(size_t idx) {
+                    const size_t b = idx / m, i = idx - b * m;
+                    codeword[idx] = i < k ? F::canon(data[b * k + i]) : par[b * npar + (i - k)];
+                });
+            }
+        }
+        ok = finish_flagged(ok, flag, repeated, s);
+        *repeated = *repeated || rep;
+        return ok;
+    }
+    // One row of the large regime after its interpolation: g0 (mm + 1 coefficients), g1 (mm), the partial row with `stop`, the exact
+    // division; msg (k coefficients, zeroed by the caller) and *verdict are written on success only.  rs_decode's loop body.
+    bool rs_decode_row(const E* g0, size_t mm, const E* g1, size_t k, size_t stop, E* r, E* t, E* msg, long long* verdict, hipStream_t s) {
+        const TempMark mark = temps_mark();
+        long long deg[3] = {-1, -1, -1};
+        bool ok = gcd_partial_pair(g0, mm + 1, g1, mm, stop, r, mm + 1, nullptr, mm, t, mm + 1, deg, s);
+        const long long dq = deg[0] - deg[2];
+        if (ok && deg[0] < 0) {
+            *verdict = deg[2];                                   // r = 0: f = 0
+        } else if (ok && deg[2] >= 0 && dq >= 0 && dq < (long long)k) {
+            const size_t lr = (size_t)deg[0] + 1, lt = (size_t)deg[2] + 1, lrem = lt - 1;
+            E* q = temp((size_t)dq + 1); E* rem = temp(lrem ? lrem : 1);
+            size_t nz = 0;
+            ok = divrem_body(r, lr, t, lt, q, lrem ? rem : nullptr, 1, gcd_flag_, s) && gcd_row_lens(rem, lrem, lrem, 1, &nz, s);
+            if (ok && nz == 0) {
+                *verdict = deg[2];
+                ok = hipMemcpyAsync(msg, q, ((size_t)dq + 1) * sizeof(E), hipMemcpyDeviceToDevice, s) == hipSuccess;
+            }
+        }
+        temps_release(mark);
+        return ok;
+    }
+    // out (count x k coefficients, or count x m symbols of the re-encoded codeword for form != 0) and n_errors (host) of Gao's
+    // decoder on the kept positions of every row: erased (count x m bytes, may be null) marks the lost symbols, whose values are
+    // never read.  A row with fewer than k kept symbols, or without a codeword in its radius floor((m' - k) / 2), is zero and -1.
+    //   m <= kRsSmall: rs_decode's k_rs_prepare over all m points, then ONE launch of k_rs_decode_ee_small for all rows.
+    //   otherwise the rows without erasure go through rs_decode's path together (one interpolate_body); a row with erasures is
+    //     compacted on the device to its kept points and values and decoded as a code of length m': through k_rs_prepare and
+    //     k_rs_decode_small when m' <= kRsSmall, else interpolate_body (g0' from its weights pass) and rs_decode_row.  The re-encoded
+    //     codeword is eval_points_body of all decoded rows at all m points.
+    // Synchronous; *repeated = two equal points among all m.  Caller holds lock() and checks the tree rule (rs_leaves).
+    bool rs_decode_erasures(const E* points, size_t m, const E* values, const uint8_t* erased, size_t k, E* out, bool codeword,
+                            long long* n_errors, size_t count, bool* repeated, hipStream_t s) {
+        const E r1 = crate_one();
+        int* flag = new_flag(s);
+        bool ok = true, rep = false;
+        std::vector<long long> herr(count, -1);
+        std::vector<std::vector<uint32_t>> kept;                 // host sources of asynchronous uploads: alive to the end of the call
+        constexpr int G = (int)kGcdSmall;
+        if (m <= kRsSmall) {
+            E* g0 = temp(m + 1); E* np = temp(m * m); E* invd = temp(m * m);
+            long long* derr = temp_as<long long>(count);
+            const size_t no = codeword ? m : k;
+            ECFFT_LAUNCH(KC_POINTWISE, sizeof(E) * (2.0 * (double)m * (double)m + 2.0 * (double)m), (k_rs_prepare<F, G>), dim3((unsigned)m), dim3(G), 0, s,
+                         points, (uint32_t)m, np, g0, invd, rinv_, r1, flag);
+            for_chunks(count, [&](size_t c0, size_t c) {
+                ECFFT_LAUNCH(KC_POINTWISE, sizeof(E) * ((double)c * (double)(m + no) + 2.0 * (double)m * (double)m), (k_rs_decode_ee_small<F, G>),
+                             dim3((unsigned)c), dim3(G), 0, s, values + c0 * m, erased ? erased + c0 * m : (const uint8_t*)nullptr, points, (uint32_t)m,
+                             (uint32_t)k, (const E*)np, (const E*)g0, (const E*)invd, out + c0 * no, codeword ? 1u : 0u, derr + c0, rinv_, r1);
+            });
+            ok = hipMemcpyAsync(herr.data(), derr, count * sizeof(long long), hipMemcpyDeviceToHost, s) == hipSuccess;
+        } else {
+            std::vector<uint8_t> mask;
+            if (erased) {
+                mask.resize(count * m);
+                ok = hipMemcpyAsync(mask.data(), erased, count * m, hipMemcpyDeviceToHost, s) == hipSuccess;
+            }
+            ok = rs_points_repeat(points, m, &rep, s) && ok;     // drains s: the masks are here
+            E* coef = codeword ? temp(count * k) : out;
+            ok = ok && hipMemsetAsync(coef, 0, count * k * sizeof(E), s) == hipSuccess;
+            if (ok && !rep) {
+                std::vector<size_t> clean;
+                kept.resize(count);
+                for (size_t p = 0; p < count; ++p) {
+                    for (size_t i = 0; erased && i < m; ++i) if (!mask[p * m + i]) kept[p].push_back((uint32_t)i);
+                    if (!erased || kept[p].size() == m) clean.push_back(p);
+                }
+                gcd_flag_ = new_flag(s);
+                E* g0 = temp(m + 1); E* r = temp(m + 1); E* t = temp(m + 1);
+                long long* derr = temp_as<long long>(1);
+                if (!clean.empty()) {
+                    const size_t nc = clean.size();
+                    const E* cv = values;
+                    if (nc < count) {
+                        E* g = temp(nc * m);
+                        for (size_t i = 0; i < nc && ok; ++i)
+                            ok = hipMemcpyAsync(g + i * m, values + clean[i] * m, m * sizeof(E), hipMemcpyDeviceToDevice, s) == hipSuccess;
+                        cv = g;
+                    }
+                    E* g1 = temp(nc * m);
+                    ok = ok && interpolate_body(points, m, cv, g1, nc, flag, g0, s);
+                    for (size_t i = 0; i < nc && ok; ++i)
+                        ok = rs_decode_row(g0, m, g1 + i * m, k, (m + k + 1) / 2, r, t, coef + clean[i] * k, &herr[clean[i]], s);
+                }
+                E* cp = temp(m); E* cy = temp(m); E* g1 = temp(m);
+                uint32_t* didx = temp_as<uint32_t>(m);
+                for (size_t p = 0; p < count && ok && erased; ++p) {
+                    const size_t mk = kept[p].size();
+                    if (mk == m || mk < k) continue;
+                    const TempMark mark = temps_mark();
+                    const size_t stop = (mk + k + 1) / 2;
+                    const E* row = values + p * m;
+                    ok = hipMemcpyAsync(didx, kept[p].data(), mk * sizeof(uint32_t), hipMemcpyHostToDevice, s) == hipSuccess;
+                    foreach_n(s, mk, [=] __device__(size_t i) { const uint32_t j = didx[i]; cp[i] = points[j]; cy[i] = row[j]; });
+                    if (mk <= kRsSmall) {
+                        E* np = temp(mk * mk); E* invd = temp(mk * mk);
+                        ECFFT_LAUNCH(KC_POINTWISE, sizeof(E) * (2.0 * (double)mk * (double)mk + 2.0 * (double)mk), (k_rs_prepare<F, G>), dim3((unsigned)mk),
+                                     dim3(G), 0, s, (const E*)cp, (uint32_t)mk, np, g0, invd, rinv_, r1, flag);
+                        ECFFT_LAUNCH(KC_POINTWISE, sizeof(E) * ((double)(mk + k) + 2.0 * (double)mk * (double)mk), (k_rs_decode_small<F, G>), dim3(1), dim3(G),
+                                     0, s, (const E*)cy, (uint32_t)mk, (uint32_t)k, (int32_t)stop, (const E*)np, (const E*)g0, (const E*)invd,
+                                     coef + p * k, derr, r1);
+                        ok = ok && hipMemcpyAsync(&herr[p], derr, sizeof(long long), hipMemcpyDeviceToHost, s) == hipSuccess
+                                && hipStreamSynchronize(s) == hipSuccess;
+                    } else {
+                        ok = ok && interpolate_body(cp, mk, cy, g1, 1, flag, g0, s);
+                        ok = ok && rs_decode_row(g0, mk, g1, k, stop, r, t, coef + p * k, &herr[p], s);
+                    }
+                    temps_release(mark);
+                }
+                if (codeword && ok) ok = eval_points_body(coef, k, points, m, out, count, s);
+            }
+        }
+        ok = finish_flagged(ok, flag, repeated, s);
+        *repeated = *repeated || rep;
         for (size_t p = 0; p < count; ++p) n_errors[p] = herr[p];
         return ok;
     }

@@ -212,9 +212,9 @@ int staged(ecfft_ctx* c, Chain& ch, int mem, void* stream, const In (&in)[NI], c
         size_t off[NI + NO], total = 0;
         auto same = [&](size_t i) { for (size_t j = 0; j < i; ++j) if (in[j].ptr == in[i].ptr && in[j].bytes == in[i].bytes) return j; return i; };
         for (size_t i = 0; i < NI; ++i)
-            if (in[i].ptr && same(i) == i) { off[i] = total; total += in[i].bytes; }
+            if (in[i].ptr && same(i) == i) { off[i] = total; total += (in[i].bytes + 31) & ~(size_t)31; }   // a byte mask keeps the next slot aligned
         for (size_t o = 0; o < NO; ++o)
-            if (out[o].ptr && !out[o].in_place) { off[NI + o] = total; total += out[o].bytes; }
+            if (out[o].ptr && !out[o].in_place) { off[NI + o] = total; total += (out[o].bytes + 31) & ~(size_t)31; }
         if (!ensure_stage(c, total)) return ECFFT_ERR_HIP;
         char* st = (char*)c->stage;
         for (size_t i = 0; i < NI; ++i) {
@@ -520,6 +520,50 @@ int run_rs_decode(ecfft_ctx* c, DeviceChain<F>& ch, const void* points, size_t m
         if (!ch.rs_decode((const E*)d[0], m, (const E*)d[1], k, (E*)o[0], (long long*)n_errors, count, &repeated, (hipStream_t)stream))
             return ECFFT_ERR_HIP;
         return repeated ? ECFFT_ERR_BAD_ARG : ECFFT_OK;                      // two equal points: no code
+    });
+}
+
+// ecfft_rs_encode: synchronous like ecfft_rs_decode (two equal points among all m are reported as ECFFT_ERR_BAD_ARG)
+template <class F>
+int run_rs_encode(ecfft_ctx* c, DeviceChain<F>& ch, const void* points, size_t m, const void* data, size_t k, void* codeword, size_t count,
+                  int mem, void* stream) {
+    using E = typename F::elem;
+    if (!points || !data || !codeword || k > m) return ECFFT_ERR_BAD_ARG;
+    if (m > SIZE_MAX / (64 * sizeof(E)) / 4) return ECFFT_ERR_BAD_ARG;
+    const size_t N = DeviceChain<F>::rs_encode_leaves(m, k);                 // the interpolation at k points, the evaluation of k coefficients
+    if (N > 1 && N > ch.size()) return ECFFT_ERR_TREE_TOO_SMALL;
+    const size_t per = N > 4 * (m + 1) ? N : 4 * (m + 1);
+    if (N > SIZE_MAX / (8 * 64 * sizeof(E))) return ECFFT_ERR_BAD_ARG;       // node data of the two bodies
+    if (count > SIZE_MAX / (16 * per * sizeof(E))) return ECFFT_ERR_BAD_ARG;  // byte counts of the rows and temporaries must not wrap
+    const size_t eb = count * sizeof(E);
+    return staged(c, ch, mem, stream, {{points, m * sizeof(E)}, {data, k * eb}}, {{codeword, m * eb}}, [&](auto d, auto o) -> int {
+        bool repeated = false;
+        if (!ch.rs_encode((const E*)d[0], m, (const E*)d[1], k, (E*)o[0], count, &repeated, (hipStream_t)stream)) return ECFFT_ERR_HIP;
+        return repeated ? ECFFT_ERR_BAD_ARG : ECFFT_OK;
+    });
+}
+
+// ecfft_rs_decode_erasures: ecfft_rs_decode's checks and tree rule; the mask travels with the values
+template <class F>
+int run_rs_decode_erasures(ecfft_ctx* c, DeviceChain<F>& ch, const void* points, size_t m, const void* values, const uint8_t* erased, size_t k,
+                           void* out, int out_form, int64_t* n_errors, size_t count, int mem, void* stream) {
+    using E = typename F::elem;
+    if (!points || !values || !out || !n_errors || k > m) return ECFFT_ERR_BAD_ARG;
+    if (out_form != ECFFT_RS_OUT_COEFFS && out_form != ECFFT_RS_OUT_CODEWORD) return ECFFT_ERR_BAD_ARG;
+    if (m > SIZE_MAX / (64 * sizeof(E)) / 4) return ECFFT_ERR_BAD_ARG;
+    const size_t N = DeviceChain<F>::rs_leaves(m);
+    if (N > 1 && N > ch.size()) return ECFFT_ERR_TREE_TOO_SMALL;
+    const size_t per = N > 4 * (m + 1) ? N : 4 * (m + 1);
+    if (N > SIZE_MAX / (8 * 64 * sizeof(E))) return ECFFT_ERR_BAD_ARG;       // node data of the interpolation
+    if (count > SIZE_MAX / (16 * per * sizeof(E))) return ECFFT_ERR_BAD_ARG;  // byte counts of the rows and temporaries must not wrap
+    const size_t eb = count * sizeof(E), no = out_form == ECFFT_RS_OUT_CODEWORD ? m : k;
+    return staged(c, ch, mem, stream, {{points, m * sizeof(E)}, {values, m * eb}, {erased, erased ? m * count : 0}}, {{out, no * eb}},
+                  [&](auto d, auto o) -> int {
+        bool repeated = false;
+        if (!ch.rs_decode_erasures((const E*)d[0], m, (const E*)d[1], (const uint8_t*)d[2], k, (E*)o[0], out_form == ECFFT_RS_OUT_CODEWORD,
+                                   (long long*)n_errors, count, &repeated, (hipStream_t)stream))
+            return ECFFT_ERR_HIP;
+        return repeated ? ECFFT_ERR_BAD_ARG : ECFFT_OK;                      // two equal points, erased or not: no code
     });
 }
 
@@ -1366,6 +1410,18 @@ int ecfft_rs_decode(ecfft_ctx* ctx, const void* points, size_t m, const void* va
                     size_t count, int mem, void* stream) {
     if (m == 0 || k == 0 || count == 0) return ECFFT_ERR_BAD_ARG;
     return on_chain(ctx, [&](auto& ch) { return run_rs_decode(ctx, ch, points, m, values, k, message, n_errors, count, mem, stream); });
+}
+int ecfft_rs_encode(ecfft_ctx* ctx, const void* points, size_t m, const void* data, size_t k, void* codeword, size_t count, int mem,
+                    void* stream) {
+    if (m == 0 || k == 0 || count == 0) return ECFFT_ERR_BAD_ARG;
+    return on_chain(ctx, [&](auto& ch) { return run_rs_encode(ctx, ch, points, m, data, k, codeword, count, mem, stream); });
+}
+int ecfft_rs_decode_erasures(ecfft_ctx* ctx, const void* points, size_t m, const void* values, const uint8_t* erased, size_t k, void* out,
+                             int out_form, int64_t* n_errors, size_t count, int mem, void* stream) {
+    if (m == 0 || k == 0 || count == 0) return ECFFT_ERR_BAD_ARG;
+    return on_chain(ctx, [&](auto& ch) {
+        return run_rs_decode_erasures(ctx, ch, points, m, values, erased, k, out, out_form, n_errors, count, mem, stream);
+    });
 }
 int ecfft_poly_find_roots(ecfft_ctx* ctx, const void* f, size_t nf, void* roots, int64_t* n_roots, size_t count, int mem, void* stream) {
     if (nf == 0 || count == 0) return ECFFT_ERR_BAD_ARG;

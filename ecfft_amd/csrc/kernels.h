@@ -3082,6 +3082,194 @@ __global__ __launch_bounds__(G) void k_rs_decode_small(const typename F::elem* _
     }
     if (t == 0) n_err[p] = good ? dt : -1;
 }
+// ecfft_rs_decode_erasures, small regime: k_rs_decode_small with a mask per row (erased + p m, may be null: no erasure; a non-zero
+// byte marks a lost symbol, whose stored value is never read) behind the same k_rs_prepare over ALL m points.
+// With K the kept positions, m' = |K| and g0' = prod_{i in K} (x - x_i): the interpolant over all m points of the row with its
+// erased symbols read as 0 is congruent mod g0' to the interpolant over K, and the remainder sequence of (g0', g1) is the swap row,
+// g1 mod g0' with cofactor 1, then the rows of the punctured code's own pair.  So steps 1 and 2 of k_rs_decode_small stay, and
+// only the loop's first operand and its bound change: R0 = g0' (deg m'), stop' = ceil((m' + k) / 2).
+//   g0': a row without erasure takes the shared g0.  Otherwise the product over the kept points, the loop of k_rs_prepare's block 0
+//     with the erased points skipped (m' steps on PLAIN coefficients, then R for crate form; the mask is in LDS, so every thread
+//     skips the same steps; the plain points are staged once in a free LDS row and the coefficient row alternates between two
+//     rows: one multiply and one barrier a step).
+//   m' < k: the row fails before any work.
+//   form == 0: out row p = the k coefficients of f, as k_rs_decode_small's message.  form != 0: out row p = the m symbols f(x_i),
+//     thread i by Horner on the plain x_i = x_i R^-1 (k steps, no barrier); a failed row is zero in both forms.
+template <class F, int G>
+__global__ __launch_bounds__(G) void k_rs_decode_ee_small(const typename F::elem* __restrict__ values, const uint8_t* __restrict__ erased,
+                                                          const typename F::elem* __restrict__ points, uint32_t m, uint32_t k,
+                                                          const typename F::elem* __restrict__ np, const typename F::elem* __restrict__ g0,
+                                                          const typename F::elem* __restrict__ invd, typename F::elem* __restrict__ out,
+                                                          uint32_t form, long long* __restrict__ n_err, typename F::elem rinv,
+                                                          typename F::elem r1) {
+    using E = typename F::elem;
+    __shared__ E buf[4 * G];
+    __shared__ E snorm;
+    __shared__ int sdeg[2];
+    __shared__ uint8_t smask[G];
+    const uint32_t t = threadIdx.x;
+    const size_t p = blockIdx.x;
+    const uint32_t no = form ? m : k;                        // symbols of an output row
+    E *R0 = buf, *R1 = buf + G, *T0 = buf + 2 * G, *T1 = buf + 3 * G;
+    const bool lost = erased && t < m && erased[p * m + t] != 0;
+    smask[t] = lost ? 1 : 0;
+    const uint32_t mk = (uint32_t)__syncthreads_count(t < m && !lost);          // m', and smask is visible
+    if (mk < k) {
+        if (t < no) out[p * no + t] = F::zero();
+        if (t == 0) n_err[p] = -1;
+        return;
+    }
+    const int32_t stop = (int32_t)((mk + k + 1) / 2);
+    E mine = F::zero();
+    if (t < m && !lost) mine = F::canon(values[p * m + t]);
+    {
+        E *A = T0, *B = T1;
+        for (uint32_t j = 1; j < m; ++j) {
+            A[t] = mine;
+            __syncthreads();
+            if (t >= j && t < m) mine = F::canon(F::mul(F::canon(F::sub(mine, A[t - 1])), invd[(size_t)j * m + t]));
+            E* x = A; A = B; B = x;
+        }
+    }
+    __syncthreads();
+    R0[t] = mine;                                            // the divided differences
+    if (t < 2) sdeg[t] = -1;
+    __syncthreads();
+    E acc = F::zero();
+    if (t < m)
+        for (uint32_t i = t; i < m; ++i) acc = F::canon(F::mul_add(np[(size_t)i * m + t], R0[i], acc));
+    __syncthreads();
+    E va = F::zero();
+    if (mk == m) {
+        if (t <= m) va = g0[t];
+    } else {
+        E cur = F::zero(), x = F::zero();
+        if (t == 0) cur = F::one();
+        if (t < m) x = F::canon(F::mul(F::canon(points[t]), rinv));
+        T0[t] = x;                                           // the plain points; read behind the first step's barrier
+        E *A = R0, *B = R1;                                  // two alternating rows, one barrier a step, as the divided differences
+        for (uint32_t i = 0; i < m; ++i) {
+            if (smask[i]) continue;
+            A[t] = cur;
+            __syncthreads();
+            E lo = F::zero();
+            if (t) lo = A[t - 1];
+            cur = F::canon(F::sub(lo, F::canon(F::mul(T0[i], cur))));
+            E* y = A; A = B; B = y;
+        }
+        __syncthreads();
+        if (t <= mk) va = F::canon(F::mul(cur, r1));
+    }
+    {
+        E one = F::zero();
+        if (t == 0) one = r1;
+        R0[t] = va; R1[t] = acc;
+        if (!F::is_zero(acc)) atomicMax(&sdeg[1], (int)t);
+        T0[t] = F::zero(); T1[t] = one;
+    }
+    __syncthreads();
+    int d0 = (int)mk, d1 = sdeg[1], c0 = 1, c1 = 1;
+    __syncthreads();
+    if (t < 2) sdeg[t] = -1;
+    __syncthreads();
+    E *S0 = T0, *S1 = T1;
+    gcd_remainder_loop<F>(R0, R1, d0, d1, S0, S1, T0, T1, c0, c1, 1u, stop, sdeg, t);
+    __syncthreads();
+    if (t < 2) sdeg[t] = -1;
+    __syncthreads();
+    if (!F::is_zero(T1[t])) atomicMax(&sdeg[0], (int)t);     // written whole at the start and zero above its length
+    __syncthreads();
+    const int dt = sdeg[0], dq = d1 - dt;
+    bool good = dt >= 0 && (d1 < 0 || (dq >= 0 && dq < (int)k));
+    if (good && d1 >= 0) {
+        if (t == 0) snorm = F::canon(F::inv(T1[dt]));
+        __syncthreads();
+        if ((int)t < dt) T1[t] = F::canon(F::mul(T1[t], snorm));
+        __syncthreads();
+        for (int i = dq; i >= 0; --i) {
+            const E qi = R1[i + dt];
+            if ((int)t < dt) R1[i + (int)t] = F::canon(F::sub(R1[i + (int)t], F::canon(F::mul(qi, T1[t]))));
+            __syncthreads();
+        }
+        if ((int)t < dt && !F::is_zero(R1[t])) atomicMax(&sdeg[1], (int)t);
+        __syncthreads();
+        good = sdeg[1] < 0;
+    }
+    E v = F::zero();
+    if (t < k && good && d1 >= 0 && (int)t <= dq) v = F::canon(F::mul(R1[dt + (int)t], F::canon(F::mul(snorm, r1))));
+    if (t == 0) n_err[p] = good ? dt : -1;
+    if (!form) {
+        if (t < k) out[p * k + t] = v;
+        return;
+    }
+    T0[t] = v;                                               // f in crate form, zero from k up; the cofactor rows are done
+    __syncthreads();
+    if (t < m) {
+        const E x = F::canon(F::mul(F::canon(points[t]), rinv));
+        E y = T0[k - 1];
+        for (uint32_t i = k - 1; i-- > 0;) y = F::canon(F::mul_add(y, x, T0[i]));
+        out[p * m + t] = y;
+    }
+}
+// ecfft_rs_encode, small regime: with shared points a systematic encoder is ONE linear map, parity = G data, with
+// G[j][i] = L_i(x_{k+j}) for the Lagrange basis L_i of the first k points.  Block j < max(m - k, 1), thread i < k:
+//   den_i = prod_{l < k, l != i} (x_i - x_l), num_i = prod_{l < k, l != i} (x_{k+j} - x_l): both carry R^(k-1), so num_i / den_i is
+//   the PLAIN number G[j][i], and plain x crate stays crate.  Stored transposed, gt[i (m - k) + j]: the encode kernel's threads run
+//   along j.  Every pair of points meets in a zero test: two of the first k in den_i (every block), x_{k+j} and any other point in
+//   block j's comparison of thread t < m, t != k + j.  Equal points raise *flag.  k == m: one block, the zero tests only.
+template <class F, int G>
+__global__ __launch_bounds__(G) void k_rs_encode_prepare(const typename F::elem* __restrict__ points, uint32_t m, uint32_t k,
+                                                         typename F::elem* __restrict__ gt, int* __restrict__ flag) {
+    using E = typename F::elem;
+    __shared__ E sx[G];
+    const uint32_t t = threadIdx.x, j = blockIdx.x, npar = m - k;
+    E x = F::zero();
+    if (t < m) x = F::canon(points[t]);
+    sx[t] = x;
+    __syncthreads();
+    if (t >= m) return;
+    const bool par = k + j < m;
+    E y = F::zero();
+    if (par) {
+        y = sx[k + j];
+        if (t != k + j && F::is_zero(F::canon(F::sub(y, x)))) *flag = 1;
+    }
+    if (t >= k) return;
+    E den = F::one(), num = F::one();
+    for (uint32_t l = 0; l < k; ++l) {
+        if (l == t) continue;
+        const E xl = sx[l];
+        den = F::canon(F::mul(den, F::canon(F::sub(x, xl))));
+        num = F::canon(F::mul(num, F::canon(F::sub(y, xl))));
+    }
+    if (F::is_zero(den)) { *flag = 1; return; }
+    if (par) gt[(size_t)t * npar + j] = F::canon(F::mul(num, F::inv(den)));
+}
+// codeword row b (m symbols) = data row b (k symbols, fully reduced), then parity[j] = sum_i G[j][i] data[b][i], j < npar = m - k.
+// A workgroup takes rpb = max(1, G / npar) rows: thread t is parity j = t mod npar of row t / npar, so a wave's loads of gt are
+// contiguous and a row's data symbol is one address for all its threads.  gt: k_rs_encode_prepare's, i-major.
+template <class F, int G>
+__global__ __launch_bounds__(G) void k_rs_encode_small(const typename F::elem* __restrict__ data, uint32_t m, uint32_t k,
+                                                       const typename F::elem* __restrict__ gt, typename F::elem* __restrict__ codeword,
+                                                       size_t count, uint32_t rpb) {
+    using E = typename F::elem;
+    const uint32_t t = threadIdx.x, npar = m - k;
+    const size_t b0 = (size_t)blockIdx.x * rpb;
+    const size_t rows = count - b0 < (size_t)rpb ? count - b0 : (size_t)rpb;
+    if (npar) {
+        const uint32_t r = t / npar, j = t - r * npar;
+        if (r < rows) {
+            const E* d = data + (b0 + r) * k;
+            E acc = F::zero();
+            for (uint32_t i = 0; i < k; ++i) acc = F::canon(F::mul_add(gt[(size_t)i * npar + j], F::canon(d[i]), acc));
+            codeword[(b0 + r) * m + k + j] = acc;
+        }
+    }
+    for (size_t idx = t; idx < rows * k; idx += G) {
+        const size_t r = idx / k, i = idx - r * k;
+        codeword[(b0 + r) * m + i] = F::canon(data[(b0 + r) * k + i]);
+    }
+}
 // Rows of different lengths gathered into one zero-padded block: dst row r (blockIdx.y) of n coefficients = rows.p[r] below
 // rows.len[r].  The operands of the batched products of the half-GCD (matrix entries, remainders) live in separate buffers.
 template <class F>

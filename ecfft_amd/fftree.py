@@ -33,7 +33,7 @@ EXPORTS = ["ecfft_elem_size", "ecfft_build_fftree", "ecfft_fftree_new", "ecfft_c
            "ecfft_comm_stats_enable", "ecfft_comm_stats_read", "ecfft_extend_sharded", "ecfft_enter_sharded", "ecfft_exit_sharded", "ecfft_device_copy", "ecfft_shader_clock", "ecfft_device_alloc", "ecfft_device_free", "ecfft_device_sync", "ecfft_build_extend_shard", "ecfft_ctx_device_bytes", "ecfft_extend_sharded_layout", "ecfft_build_enter_shard", "ecfft_build_exit_shard", "ecfft_build_exit_shard_opts",
            "ecfft_fftree_serialize", "ecfft_fftree_deserialize", "ecfft_tree_rational_maps", "ecfft_ctx_trim", "ecfft_comm_abort", "ecfft_comm_set_rccl_library", "ecfft_comm_set_link_striping",
            "ecfft_poly_mul", "ecfft_poly_inv_series", "ecfft_poly_divrem", "ecfft_poly_eval_points", "ecfft_poly_interpolate",
-           "ecfft_poly_pow_mod", "ecfft_poly_mul_mod", "ecfft_poly_gcd", "ecfft_poly_xgcd", "ecfft_poly_xgcd_partial", "ecfft_rs_decode", "ecfft_poly_find_roots",
+           "ecfft_poly_pow_mod", "ecfft_poly_mul_mod", "ecfft_poly_gcd", "ecfft_poly_xgcd", "ecfft_poly_xgcd_partial", "ecfft_rs_decode", "ecfft_rs_encode", "ecfft_rs_decode_erasures", "ecfft_poly_find_roots",
            "ecfft_poly_compose_mod", "ecfft_poly_squarefree", "ecfft_poly_distinct_degree", "ecfft_poly_equal_degree", "ecfft_poly_squarefree_decompose", "ecfft_poly_factor", "ecfft_division_polynomial", "ecfft_curve_trace_mod", "ecfft_curve_cardinality",
            "ecfft_find_curve_candidate", "ecfft_curve_two_sylow", "ecfft_find_curve", "ecfft_build_fftree_on_curve",
            "ecfft_curve_point_mul", "ecfft_curve_point_two_adicity", "ecfft_curve_find_generator", "ecfft_build_ec_fftree"]
@@ -43,6 +43,8 @@ GCD_SMALL_MAX = 256
 XGCD_PARTIAL_SMALL_MAX = 256
 # include/ecfft_hip.h ECFFT_RS_SMALL_MAX: code length m up to which rs_decode decodes a row in one workgroup, on any tree
 RS_SMALL_MAX = 255
+# include/ecfft_hip.h ECFFT_RS_OUT_*: what rs_decode_erasures writes, the k coefficients of f or its m re-encoded symbols
+RS_OUT_COEFFS, RS_OUT_CODEWORD = 0, 1
 # include/ecfft_hip.h ECFFT_ROOTS_SMALL_MAX: nf up to which poly_find_roots finishes a polynomial in one workgroup, on any tree
 ROOTS_SMALL_MAX = 65
 # include/ecfft_hip.h ECFFT_COMPOSE_SMALL_MAX: nm up to which poly_compose_mod runs Horner for a triple in one workgroup, on any tree
@@ -103,6 +105,8 @@ def _bind(L):
     L.ecfft_poly_xgcd.restype, L.ecfft_poly_xgcd.argtypes = ci, [vp, vp, sz, vp, sz, vp, vp, vp, vp, sz, ci, vp]
     L.ecfft_poly_xgcd_partial.restype, L.ecfft_poly_xgcd_partial.argtypes = ci, [vp, vp, sz, vp, sz, sz, vp, vp, vp, vp, sz, ci, vp]
     L.ecfft_rs_decode.restype, L.ecfft_rs_decode.argtypes = ci, [vp, vp, sz, vp, sz, vp, vp, sz, ci, vp]
+    L.ecfft_rs_encode.restype, L.ecfft_rs_encode.argtypes = ci, [vp, vp, sz, vp, sz, vp, sz, ci, vp]
+    L.ecfft_rs_decode_erasures.restype, L.ecfft_rs_decode_erasures.argtypes = ci, [vp, vp, sz, vp, vp, sz, vp, ci, vp, sz, ci, vp]
     L.ecfft_poly_find_roots.restype, L.ecfft_poly_find_roots.argtypes = ci, [vp, vp, sz, vp, vp, sz, ci, vp]
     L.ecfft_poly_squarefree.restype, L.ecfft_poly_squarefree.argtypes = ci, [vp, vp, sz, vp, vp, sz, ci, vp]
     L.ecfft_poly_distinct_degree.restype, L.ecfft_poly_distinct_degree.argtypes = ci, [vp, vp, sz, vp, vp, sz, ci, vp]
@@ -849,6 +853,56 @@ class FFTree:
             raise ValueError("rs_decode: two equal points, k = 0, k > m, count = 0 or a context that holds no full tree")
         _check(rc)
         return message, n_errors
+
+    def rs_encode(self, points, data, k, count=1):
+        """codeword: the systematic Reed-Solomon encoder (ecfft_rs_encode).  points: m pairwise distinct elements shared by all rows;
+        data: count * k symbols; 1 <= k <= m.  Returns count * m symbols: row b is f_b at all m points for the f_b of degree < k
+        with f_b(points[i]) = data[b][i], i < k, so its first k symbols are the data (fully reduced) and the other m - k the parity.
+        m <= RS_SMALL_MAX works on any tree (one fixed (m - k) x k matrix applied to every row); otherwise, for k > 64, a tree of
+        next_pow2(k) leaves.  Two equal points, k = 0 or k > m raise ValueError.  numpy arrays (host) or contiguous CUDA tensors
+        (device, on the current stream), both of the same kind.  Synchronous."""
+        (points, data), (pp, pd), new, mem, stream = self._poly_io([points, data])
+        m = points.shape[0]
+        assert count > 0 and m > 0 and data.shape[0] == count * max(int(k), 0)
+        codeword = new(count * m)
+        rc = self._L.ecfft_rs_encode(self._h, pp, m, pd if data.shape[0] else None, int(k), self._ptr(codeword), count, mem, stream)
+        if rc == ERR_BAD_ARG:
+            raise ValueError("rs_encode: two equal points, k = 0, k > m, count = 0 or a context that holds no full tree")
+        _check(rc)
+        return codeword
+
+    def rs_decode_erasures(self, points, values, erased, k, count=1, codeword=False):
+        """(out, n_errors): Reed-Solomon decoding with erasures and errors (ecfft_rs_decode_erasures).  points, values, k as rs_decode;
+        erased: count * m uint8 or bool entries of the same kind as values (numpy array or CUDA tensor), non-zero where the symbol is
+        lost (its value is never read), or None for no erasure.  With m' kept symbols a row decodes to the unique f of degree < k
+        that differs from the kept symbols in at most (m' - k) // 2 positions; n_errors is a numpy int64 array of their number, -1
+        (and a zero row) where there is no such f or m' < k: exactly rs_decode on the kept points and values, beyond the radius
+        too.  out has count * k coefficients of f, or with codeword=True count * m symbols, f at all m points: the erased positions
+        filled in, the first k the corrected data of a code made by rs_encode.  Tree rule, argument errors, memory kinds and
+        synchronisation as rs_decode."""
+        (points, values), (pp, pv), new, mem, stream = self._poly_io([points, values])
+        m = points.shape[0]
+        assert count > 0 and m > 0 and values.shape[0] == count * m
+        pe = None
+        if erased is not None:
+            if _is_torch(erased):
+                import torch
+                assert mem == MEM_DEVICE and erased.is_cuda and erased.is_contiguous() and erased.dtype in (torch.uint8, torch.bool)
+                assert erased.numel() == count * m
+                pe = erased.data_ptr()
+            else:
+                assert mem == MEM_HOST, "the mask is of the same kind as the values"
+                erased = np.ascontiguousarray(erased)
+                assert erased.dtype in (np.uint8, np.bool_) and erased.size == count * m
+                pe = erased.ctypes.data
+        out = new(count * (m if codeword else max(int(k), 0)))
+        n_errors = np.empty(count, np.int64)
+        rc = self._L.ecfft_rs_decode_erasures(self._h, pp, m, pv, pe, int(k), self._ptr(out) if out.shape[0] else None,
+                                              RS_OUT_CODEWORD if codeword else RS_OUT_COEFFS, n_errors.ctypes.data, count, mem, stream)
+        if rc == ERR_BAD_ARG:
+            raise ValueError("rs_decode_erasures: two equal points, k = 0, k > m, count = 0 or a context that holds no full tree")
+        _check(rc)
+        return out, n_errors
 
     def poly_find_roots(self, f, count=1):
         """(roots, n_roots): the distinct roots in the field (ecfft_poly_find_roots <-> utils::find_roots, src/utils.rs:25-44) of

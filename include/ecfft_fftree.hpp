@@ -351,6 +351,31 @@ public:
         if (n_errors) *n_errors = n;
         return message;
     }
+    // The systematic Reed-Solomon encoder (ecfft_rs_encode; no reference counterpart): the m symbols f(x_0), ..., f(x_{m-1}) of the f
+    // of degree < k with f(x_i) = data[i], i < k = data.size(): the data, then m - k parity symbols.  Up to ECFFT_RS_SMALL_MAX
+    // points on any tree; tree rule in ecfft_hip.h.  Two equal points throw.  Synchronous.
+    std::vector<Elem> rs_encode(const std::vector<Elem>& points, const std::vector<Elem>& data) const {
+        require(!data.empty() && data.size() <= points.size(), "rs_encode: m points and 1 <= k <= m data symbols");
+        std::vector<Elem> codeword(points.size());
+        check(ecfft_rs_encode(ctx_, points.data(), points.size(), data.data(), data.size(), codeword.data(), 1, ECFFT_MEM_HOST, nullptr));
+        return codeword;
+    }
+    // Reed-Solomon decoding with erasures and errors (ecfft_rs_decode_erasures): erased[i] != 0 marks a lost symbol, whose value is
+    // never read (an empty vector: no erasure).  rs_decode on the kept points and values: with m' of them, the f of degree < k
+    // within floor((m' - k) / 2) errors; n_errors (may be null) receives their number, or -1 when there is no such f or m' < k
+    // (the result is then zero).  Returns the k coefficients of f, or with codeword = true its m symbols at all points: the erased
+    // positions filled in, the first k the corrected data of rs_encode's code.  Tree rule and errors as rs_decode.  Synchronous.
+    std::vector<Elem> rs_decode_erasures(const std::vector<Elem>& points, const std::vector<Elem>& values, const std::vector<uint8_t>& erased,
+                                         size_t k, bool codeword = false, int64_t* n_errors = nullptr) const {
+        require(!points.empty() && points.size() == values.size() && (erased.empty() || erased.size() == points.size()) && k >= 1 && k <= points.size(),
+                "rs_decode_erasures: m points, m values, no or m mask bytes and 1 <= k <= m");
+        std::vector<Elem> out(codeword ? points.size() : k);
+        int64_t n = -1;
+        check(ecfft_rs_decode_erasures(ctx_, points.data(), points.size(), values.data(), erased.empty() ? nullptr : erased.data(), k, out.data(),
+                                       codeword ? ECFFT_RS_OUT_CODEWORD : ECFFT_RS_OUT_COEFFS, &n, 1, ECFFT_MEM_HOST, nullptr));
+        if (n_errors) *n_errors = n;
+        return out;
+    }
     // the distinct roots of f in the field in ascending order of their standard form (ecfft_poly_find_roots <-> utils::find_roots,
     // src/utils.rs:25-44, whose result is sorted the same way).  f need not be trimmed; multiplicities do not matter; a non-zero
     // constant has none.  The zero polynomial, on which the reference panics, throws.  Up to ECFFT_ROOTS_SMALL_MAX coefficients on
@@ -554,6 +579,16 @@ public:
     // count received words of m symbols at m shared points -> message count x k; n_errors: count HOST entries (-1: not decodable).  Synchronous.
     void rs_decode_device(const Elem* points, size_t m, const Elem* values, size_t k, Elem* message, int64_t* n_errors, size_t count, void* stream) const {
         check(ecfft_rs_decode(ctx_, points, m, values, k, message, n_errors, count, ECFFT_MEM_DEVICE, stream));
+    }
+    // count data rows of k symbols -> codeword count x m, the data then the parity (ecfft_rs_encode).  Synchronous.
+    void rs_encode_device(const Elem* points, size_t m, const Elem* data, size_t k, Elem* codeword, size_t count, void* stream) const {
+        check(ecfft_rs_encode(ctx_, points, m, data, k, codeword, count, ECFFT_MEM_DEVICE, stream));
+    }
+    // count received words with their masks (count x m device bytes, or null) -> out count x k coefficients, or count x m symbols
+    // for out_form = ECFFT_RS_OUT_CODEWORD; n_errors: count HOST entries (-1: not decodable).  Synchronous.
+    void rs_decode_erasures_device(const Elem* points, size_t m, const Elem* values, const uint8_t* erased, size_t k, Elem* out, int out_form,
+                                   int64_t* n_errors, size_t count, void* stream) const {
+        check(ecfft_rs_decode_erasures(ctx_, points, m, values, erased, k, out, out_form, n_errors, count, ECFFT_MEM_DEVICE, stream));
     }
     // count polynomials f count x nf (untrimmed), roots count x (nf - 1) sorted and zero-padded; n_roots: count HOST entries (-1: the
     // zero polynomial).  Synchronous.

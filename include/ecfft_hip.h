@@ -294,6 +294,40 @@ int ecfft_poly_xgcd_partial(ecfft_ctx* ctx, const void* a, size_t na, const void
 int ecfft_rs_decode(ecfft_ctx* ctx, const void* points, size_t m, const void* values, size_t k, void* message, int64_t* n_errors,
                     size_t count, int mem, void* stream);
 
+/* The Reed-Solomon codec: a SYSTEMATIC encoder and a decoder for erasures mixed with errors.  The reference has no counterpart.
+ * ecfft_rs_encode: points as in ecfft_rs_decode; data: count x k symbols; codeword: count x m symbols, row b =
+ * (f_b(x_0), ..., f_b(x_{m-1})) for the unique f_b of degree < k with f_b(x_i) = data[b][i], i < k: the first k symbols are the
+ * data, fully reduced, the other m - k the parity.  1 <= k <= m; k = m copies the data.  For m <= ECFFT_RS_SMALL_MAX the parity
+ * is one fixed (m - k) x k matrix (the Lagrange basis of the first k points at the others, one shared launch) applied to every
+ * row in one launch; above it the body of ecfft_poly_interpolate at the first k points and the body of ecfft_poly_eval_points at
+ * the other m - k, for all rows at once.
+ * Tree of the encoder: m <= ECFFT_RS_SMALL_MAX, or k <= 64, needs no transform (any tree); otherwise next_pow2(k) leaves, which
+ * is what the interpolation at k points and the evaluation of k coefficients need; else ECFFT_ERR_TREE_TOO_SMALL, checked before
+ * anything runs.
+ * ecfft_rs_decode_erasures: `erased` is count x m bytes in the same memory kind as `values`, a non-zero byte marks a LOST symbol,
+ * whose stored value is never read; NULL means no erasure anywhere.  With K the kept positions of a row and m' their number,
+ * the row decodes to the unique f of degree < k whose codeword differs from `values` on K in at most floor((m' - k) / 2)
+ * positions, and n_errors[b] (HOST pointer, required) is the number of those positions; where there is no such f, or m' < k,
+ * n_errors[b] = -1 and the output row is zero.  The result is DEFINED, beyond the radius too, as that of ecfft_rs_decode on the
+ * punctured code (the points and values of K): a row without erasures is byte for byte what ecfft_rs_decode returns.
+ * out_form: ECFFT_RS_OUT_COEFFS: out is count x k coefficients of f, as ecfft_rs_decode's message.  ECFFT_RS_OUT_CODEWORD: out is
+ * count x m symbols, f at all m points: the erased positions are filled in and the first k symbols are the corrected data of a
+ * code made by ecfft_rs_encode.
+ * Method: for m <= ECFFT_RS_SMALL_MAX the shared launch of ecfft_rs_decode over ALL m points and one launch for all rows, a
+ * workgroup per row: the interpolant over all points with the erased symbols read as 0 is congruent to the interpolant over K
+ * modulo g0' = prod_{i in K} (x - x_i), so only the first operand of the remainder loop is the row's own.  Above it the rows
+ * without erasure take the path of ecfft_rs_decode together and a row with erasures is compacted on the device and decoded as a
+ * code of length m'.  Tree of the decoder: that of ecfft_rs_decode.
+ * ECFFT_ERR_BAD_ARG: as ecfft_rs_decode; an unknown out_form; two equal points among ALL m, erased or not, for both calls.  Both
+ * calls are SYNCHRONOUS; the context keeps working after an error.  Outputs must not overlap the inputs.  Memory, stream,
+ * threading and pooled temporaries as for ecfft_rs_decode. */
+#define ECFFT_RS_OUT_COEFFS   0   /* out: count x k coefficients of f, as ecfft_rs_decode's message */
+#define ECFFT_RS_OUT_CODEWORD 1   /* out: count x m symbols f(x_0..x_{m-1}); the first k are the data of a systematic code */
+int ecfft_rs_encode(ecfft_ctx* ctx, const void* points, size_t m, const void* data, size_t k, void* codeword, size_t count, int mem,
+                    void* stream);
+int ecfft_rs_decode_erasures(ecfft_ctx* ctx, const void* points, size_t m, const void* values, const uint8_t* erased, size_t k, void* out,
+                             int out_form, int64_t* n_errors, size_t count, int mem, void* stream);
+
 /* Roots of polynomials in the field.
  *   ecfft_poly_find_roots <-> ecfft::utils::find_roots(poly)                        src/utils.rs:25-44
  * Layout: f is count x nf coefficients in the crate's form; as in ecfft_poly_gcd the rows NEED NOT BE TRIMMED.  roots is
