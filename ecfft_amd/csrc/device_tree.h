@@ -4281,61 +4281,22 @@ public:
     // the m pairwise distinct points, n_errors[b] (host) the number of those positions; a zero row and -1 where there is none.
     // g0 = prod (x - x_i), g1 = the interpolant of the row, (r, ., t) = the partial row of (g0, g1) with stop = ceil((m + k) / 2),
     // f = r / t: the word decodes iff the division is exact and deg f < k, and then n_errors = deg t.
-    //   m <= kRsSmall: k_rs_prepare (g0, the Newton basis and the inverse denominators, shared by the rows), then ONE launch of
-    //     k_rs_decode_small for all rows.
-    //   otherwise interpolate_body for all rows at once (g0 from its weights pass), then per row gcd_partial_pair and divrem_body.
-    // Synchronous; *repeated = two equal points.  Caller holds lock() and checks the tree rule (rs_leaves).
+    // rs_decode_erasures without a mask, in coefficient form: one driver serves both.
     bool rs_decode(const E* points, size_t m, const E* values, size_t k, E* message, long long* n_errors, size_t count, bool* repeated,
                    hipStream_t s) {
-        const size_t stop = (m + k + 1) / 2;
-        const E r1 = crate_one();
-        int* flag = new_flag(s);
-        bool ok = true;
-        std::vector<long long> herr(count, -1);
-        E* g0 = temp(m + 1);
-        if (m <= kRsSmall) {
-            constexpr int G = (int)kGcdSmall;
-            E* np = temp(m * m); E* invd = temp(m * m);
-            long long* derr = temp_as<long long>(count);
-            ECFFT_LAUNCH(KC_POINTWISE, sizeof(E) * (2.0 * (double)m * (double)m + 2.0 * (double)m), (k_rs_prepare<F, G>), dim3((unsigned)m), dim3(G), 0, s,
-                         points, (uint32_t)m, np, g0, invd, rinv_, r1, flag);
-            for_chunks(count, [&](size_t c0, size_t c) {
-                ECFFT_LAUNCH(KC_POINTWISE, sizeof(E) * ((double)c * (double)(m + k) + 2.0 * (double)m * (double)m), (k_rs_decode_small<F, G>),
-                             dim3((unsigned)c), dim3(G), 0, s, values + c0 * m, (uint32_t)m, (uint32_t)k, (int32_t)stop, (const E*)np, (const E*)g0,
-                             (const E*)invd, message + c0 * k, derr + c0, r1);
-            });
-            ok = hipMemcpyAsync(herr.data(), derr, count * sizeof(long long), hipMemcpyDeviceToHost, s) == hipSuccess;
-        } else {
-            E* g1 = temp(count * m);
-            ok = interpolate_body(points, m, values, g1, count, flag, g0, s);
-            int h = 0;
-            ok = ok && hipMemcpyAsync(&h, flag, sizeof(int), hipMemcpyDeviceToHost, s) == hipSuccess && hipStreamSynchronize(s) == hipSuccess;
-            ok = ok && hipMemsetAsync(message, 0, count * k * sizeof(E), s) == hipSuccess;
-            gcd_flag_ = new_flag(s);
-            E* r = temp(m + 1); E* t = temp(m + 1);
-            for (size_t p = 0; p < count && ok && !h; ++p) {
-                const TempMark mark = temps_mark();
-                long long deg[3] = {-1, -1, -1};
-                ok = gcd_partial_pair(g0, m + 1, g1 + p * m, m, stop, r, m + 1, nullptr, m, t, m + 1, deg, s);
-                const long long dq = deg[0] - deg[2];
-                if (ok && deg[0] < 0) {
-                    herr[p] = deg[2];                            // r = 0: f = 0
-                } else if (ok && deg[2] >= 0 && dq >= 0 && dq < (long long)k) {
-                    const size_t lr = (size_t)deg[0] + 1, lt = (size_t)deg[2] + 1, lrem = lt - 1;
-                    E* q = temp((size_t)dq + 1); E* rem = temp(lrem ? lrem : 1);
-                    size_t nz = 0;
-                    ok = divrem_body(r, lr, t, lt, q, lrem ? rem : nullptr, 1, gcd_flag_, s) && gcd_row_lens(rem, lrem, lrem, 1, &nz, s);
-                    if (ok && nz == 0) {
-                        herr[p] = deg[2];
-                        ok = hipMemcpyAsync(message + p * k, q, ((size_t)dq + 1) * sizeof(E), hipMemcpyDeviceToDevice, s) == hipSuccess;
-                    }
-                }
-                temps_release(mark);
-            }
-        }
-        ok = finish_flagged(ok, flag, repeated, s);
-        for (size_t p = 0; p < count; ++p) n_errors[p] = herr[p];
-        return ok;
+        return rs_decode_erasures(points, m, values, nullptr, k, message, false, n_errors, count, repeated, s);
+    }
+    // What the small-regime rows over m <= kRsSmall points share (k_rs_prepare): g0 (m + 1), np and invd (m x m each)
+    void rs_prepare_launch(const E* points, size_t m, E* np, E* g0, E* invd, int* flag, hipStream_t s) {
+        ECFFT_LAUNCH(KC_POINTWISE, sizeof(E) * (2.0 * (double)m * (double)m + 2.0 * (double)m), (k_rs_prepare<F, (int)kGcdSmall>), dim3((unsigned)m),
+                     dim3((unsigned)kGcdSmall), 0, s, points, (uint32_t)m, np, g0, invd, rinv_, crate_one(), flag);
+    }
+    // k_rs_decode_small over c <= 2^16 rows behind rs_prepare_launch: msg (c x k), derr (c verdicts, device)
+    void rs_small_launch(const E* values, size_t m, size_t k, const E* np, const E* g0, const E* invd, E* msg, long long* derr, size_t c,
+                         hipStream_t s) {
+        ECFFT_LAUNCH(KC_POINTWISE, sizeof(E) * ((double)c * (double)(m + k) + 2.0 * (double)m * (double)m), (k_rs_decode_small<F, (int)kGcdSmall>),
+                     dim3((unsigned)c), dim3((unsigned)kGcdSmall), 0, s, values, (uint32_t)m, (uint32_t)k, (int32_t)((m + k + 1) / 2), np, g0, invd, msg,
+                     derr, crate_one());
     }
     // ---- ecfft_rs_encode / ecfft_rs_decode_erasures: the systematic codec ----
     // Above kRsSmall the encoder interpolates at the first k points and evaluates k coefficients at the other m - k
@@ -4394,7 +4355,7 @@ public:
         return ok;
     }
     // One row of the large regime after its interpolation: g0 (mm + 1 coefficients), g1 (mm), the partial row with `stop`, the exact
-    // division; msg (k coefficients, zeroed by the caller) and *verdict are written on success only.  rs_decode's loop body.
+    // division; msg (k coefficients, zeroed by the caller) and *verdict are written on success only.
     bool rs_decode_row(const E* g0, size_t mm, const E* g1, size_t k, size_t stop, E* r, E* t, E* msg, long long* verdict, hipStream_t s) {
         const TempMark mark = temps_mark();
         long long deg[3] = {-1, -1, -1};
@@ -4415,33 +4376,37 @@ public:
         temps_release(mark);
         return ok;
     }
-    // out (count x k coefficients, or count x m symbols of the re-encoded codeword for form != 0) and n_errors (host) of Gao's
-    // decoder on the kept positions of every row: erased (count x m bytes, may be null) marks the lost symbols, whose values are
-    // never read.  A row with fewer than k kept symbols, or without a codeword in its radius floor((m' - k) / 2), is zero and -1.
-    //   m <= kRsSmall: rs_decode's k_rs_prepare over all m points, then ONE launch of k_rs_decode_ee_small for all rows.
-    //   otherwise the rows without erasure go through rs_decode's path together (one interpolate_body); a row with erasures is
-    //     compacted on the device to its kept points and values and decoded as a code of length m': through k_rs_prepare and
-    //     k_rs_decode_small when m' <= kRsSmall, else interpolate_body (g0' from its weights pass) and rs_decode_row.  The re-encoded
-    //     codeword is eval_points_body of all decoded rows at all m points.
+    // The driver of ecfft_rs_decode and ecfft_rs_decode_erasures.  out (count x k coefficients, or count x m symbols of the
+    // re-encoded codeword for codeword == true) and n_errors (host) of Gao's decoder on the kept positions of every row: erased
+    // (count x m bytes, may be null) marks the lost symbols, whose values are never read.  A row with fewer than k kept symbols,
+    // or without a codeword in its radius floor((m' - k) / 2), is zero and -1.
+    //   m <= kRsSmall: rs_prepare_launch over all m points, then ONE launch for all rows: k_rs_decode_small for coefficients without
+    //     a mask, else k_rs_decode_ee_small (byte-equal where both apply).
+    //   otherwise the rows without erasure go together through one interpolate_body (g0 from its weights pass), then rs_decode_row
+    //     each; a row with erasures is compacted on the device to its kept points and values and decoded as a code of length m':
+    //     through rs_prepare_launch and rs_small_launch when m' <= kRsSmall, else interpolate_body and rs_decode_row.  The re-encoded
+    //     codeword is eval_points_body of all decoded rows at all m points.  Two equal points: with a mask no single interpolation
+    //     sees all m points, so rs_points_repeat sorts them first; without one the interpolation of the clean rows raises the flag,
+    //     which is read back before the row loop.  No row is decoded once a repeat is known.
     // Synchronous; *repeated = two equal points among all m.  Caller holds lock() and checks the tree rule (rs_leaves).
     bool rs_decode_erasures(const E* points, size_t m, const E* values, const uint8_t* erased, size_t k, E* out, bool codeword,
                             long long* n_errors, size_t count, bool* repeated, hipStream_t s) {
-        const E r1 = crate_one();
         int* flag = new_flag(s);
         bool ok = true, rep = false;
         std::vector<long long> herr(count, -1);
         std::vector<std::vector<uint32_t>> kept;                 // host sources of asynchronous uploads: alive to the end of the call
-        constexpr int G = (int)kGcdSmall;
+        E* g0 = temp(m + 1);
         if (m <= kRsSmall) {
-            E* g0 = temp(m + 1); E* np = temp(m * m); E* invd = temp(m * m);
+            E* np = temp(m * m); E* invd = temp(m * m);
             long long* derr = temp_as<long long>(count);
             const size_t no = codeword ? m : k;
-            ECFFT_LAUNCH(KC_POINTWISE, sizeof(E) * (2.0 * (double)m * (double)m + 2.0 * (double)m), (k_rs_prepare<F, G>), dim3((unsigned)m), dim3(G), 0, s,
-                         points, (uint32_t)m, np, g0, invd, rinv_, r1, flag);
+            rs_prepare_launch(points, m, np, g0, invd, flag, s);
             for_chunks(count, [&](size_t c0, size_t c) {
-                ECFFT_LAUNCH(KC_POINTWISE, sizeof(E) * ((double)c * (double)(m + no) + 2.0 * (double)m * (double)m), (k_rs_decode_ee_small<F, G>),
-                             dim3((unsigned)c), dim3(G), 0, s, values + c0 * m, erased ? erased + c0 * m : (const uint8_t*)nullptr, points, (uint32_t)m,
-                             (uint32_t)k, (const E*)np, (const E*)g0, (const E*)invd, out + c0 * no, codeword ? 1u : 0u, derr + c0, rinv_, r1);
+                if (!erased && !codeword) rs_small_launch(values + c0 * m, m, k, np, g0, invd, out + c0 * k, derr + c0, c, s);
+                else ECFFT_LAUNCH(KC_POINTWISE, sizeof(E) * ((double)c * (double)(m + no) + 2.0 * (double)m * (double)m),
+                             (k_rs_decode_ee_small<F, (int)kGcdSmall>), dim3((unsigned)c), dim3((unsigned)kGcdSmall), 0, s, values + c0 * m,
+                             erased ? erased + c0 * m : (const uint8_t*)nullptr, points, (uint32_t)m, (uint32_t)k, (const E*)np, (const E*)g0,
+                             (const E*)invd, out + c0 * no, codeword ? 1u : 0u, derr + c0, rinv_, crate_one());
             });
             ok = hipMemcpyAsync(herr.data(), derr, count * sizeof(long long), hipMemcpyDeviceToHost, s) == hipSuccess;
         } else {
@@ -4449,61 +4414,62 @@ public:
             if (erased) {
                 mask.resize(count * m);
                 ok = hipMemcpyAsync(mask.data(), erased, count * m, hipMemcpyDeviceToHost, s) == hipSuccess;
+                ok = rs_points_repeat(points, m, &rep, s) && ok; // drains s: the masks are here
             }
-            ok = rs_points_repeat(points, m, &rep, s) && ok;     // drains s: the masks are here
             E* coef = codeword ? temp(count * k) : out;
             ok = ok && hipMemsetAsync(coef, 0, count * k * sizeof(E), s) == hipSuccess;
-            if (ok && !rep) {
-                std::vector<size_t> clean;
-                kept.resize(count);
-                for (size_t p = 0; p < count; ++p) {
-                    for (size_t i = 0; erased && i < m; ++i) if (!mask[p * m + i]) kept[p].push_back((uint32_t)i);
-                    if (!erased || kept[p].size() == m) clean.push_back(p);
-                }
-                gcd_flag_ = new_flag(s);
-                E* g0 = temp(m + 1); E* r = temp(m + 1); E* t = temp(m + 1);
-                long long* derr = temp_as<long long>(1);
-                if (!clean.empty()) {
-                    const size_t nc = clean.size();
-                    const E* cv = values;
-                    if (nc < count) {
-                        E* g = temp(nc * m);
-                        for (size_t i = 0; i < nc && ok; ++i)
-                            ok = hipMemcpyAsync(g + i * m, values + clean[i] * m, m * sizeof(E), hipMemcpyDeviceToDevice, s) == hipSuccess;
-                        cv = g;
-                    }
-                    E* g1 = temp(nc * m);
-                    ok = ok && interpolate_body(points, m, cv, g1, nc, flag, g0, s);
+            std::vector<size_t> clean;
+            kept.resize(count);
+            for (size_t p = 0; p < count; ++p) {
+                for (size_t i = 0; erased && i < m; ++i) if (!mask[p * m + i]) kept[p].push_back((uint32_t)i);
+                if (!erased || kept[p].size() == m) clean.push_back(p);
+            }
+            gcd_flag_ = new_flag(s);
+            E* r = temp(m + 1); E* t = temp(m + 1);
+            if (ok && !rep && !clean.empty()) {
+                const size_t nc = clean.size();
+                const E* cv = values;
+                if (nc < count) {
+                    E* g = temp(nc * m);
                     for (size_t i = 0; i < nc && ok; ++i)
-                        ok = rs_decode_row(g0, m, g1 + i * m, k, (m + k + 1) / 2, r, t, coef + clean[i] * k, &herr[clean[i]], s);
+                        ok = hipMemcpyAsync(g + i * m, values + clean[i] * m, m * sizeof(E), hipMemcpyDeviceToDevice, s) == hipSuccess;
+                    cv = g;
                 }
+                E* g1 = temp(nc * m);
+                ok = ok && interpolate_body(points, m, cv, g1, nc, flag, g0, s);
+                if (!erased) {                                   // no sort ran: this interpolation met all m points
+                    int h = 0;
+                    ok = ok && hipMemcpyAsync(&h, flag, sizeof(int), hipMemcpyDeviceToHost, s) == hipSuccess && hipStreamSynchronize(s) == hipSuccess;
+                    rep = h != 0;
+                }
+                for (size_t i = 0; i < nc && ok && !rep; ++i)
+                    ok = rs_decode_row(g0, m, g1 + i * m, k, (m + k + 1) / 2, r, t, coef + clean[i] * k, &herr[clean[i]], s);
+            }
+            if (ok && !rep && clean.size() < count) {
                 E* cp = temp(m); E* cy = temp(m); E* g1 = temp(m);
                 uint32_t* didx = temp_as<uint32_t>(m);
-                for (size_t p = 0; p < count && ok && erased; ++p) {
+                long long* derr = temp_as<long long>(1);
+                for (size_t p = 0; p < count && ok; ++p) {
                     const size_t mk = kept[p].size();
                     if (mk == m || mk < k) continue;
                     const TempMark mark = temps_mark();
-                    const size_t stop = (mk + k + 1) / 2;
                     const E* row = values + p * m;
                     ok = hipMemcpyAsync(didx, kept[p].data(), mk * sizeof(uint32_t), hipMemcpyHostToDevice, s) == hipSuccess;
                     foreach_n(s, mk, [=] __device__(size_t i) { const uint32_t j = didx[i]; cp[i] = points[j]; cy[i] = row[j]; });
                     if (mk <= kRsSmall) {
                         E* np = temp(mk * mk); E* invd = temp(mk * mk);
-                        ECFFT_LAUNCH(KC_POINTWISE, sizeof(E) * (2.0 * (double)mk * (double)mk + 2.0 * (double)mk), (k_rs_prepare<F, G>), dim3((unsigned)mk),
-                                     dim3(G), 0, s, (const E*)cp, (uint32_t)mk, np, g0, invd, rinv_, r1, flag);
-                        ECFFT_LAUNCH(KC_POINTWISE, sizeof(E) * ((double)(mk + k) + 2.0 * (double)mk * (double)mk), (k_rs_decode_small<F, G>), dim3(1), dim3(G),
-                                     0, s, (const E*)cy, (uint32_t)mk, (uint32_t)k, (int32_t)stop, (const E*)np, (const E*)g0, (const E*)invd,
-                                     coef + p * k, derr, r1);
+                        rs_prepare_launch(cp, mk, np, g0, invd, flag, s);
+                        rs_small_launch(cy, mk, k, np, g0, invd, coef + p * k, derr, 1, s);
                         ok = ok && hipMemcpyAsync(&herr[p], derr, sizeof(long long), hipMemcpyDeviceToHost, s) == hipSuccess
                                 && hipStreamSynchronize(s) == hipSuccess;
                     } else {
                         ok = ok && interpolate_body(cp, mk, cy, g1, 1, flag, g0, s);
-                        ok = ok && rs_decode_row(g0, mk, g1, k, stop, r, t, coef + p * k, &herr[p], s);
+                        ok = ok && rs_decode_row(g0, mk, g1, k, (mk + k + 1) / 2, r, t, coef + p * k, &herr[p], s);
                     }
                     temps_release(mark);
                 }
-                if (codeword && ok) ok = eval_points_body(coef, k, points, m, out, count, s);
             }
+            if (codeword && ok && !rep) ok = eval_points_body(coef, k, points, m, out, count, s);
         }
         ok = finish_flagged(ok, flag, repeated, s);
         *repeated = *repeated || rep;
@@ -4522,25 +4488,14 @@ public:
         bool ok = exit(st.lv.back().Mh, Mc, P, 2, s);
         ok = poly_mul_body(Mc, h, P, Mc + P, h, P, AB, 1, s) && ok;              // P - 1 coefficients
         const E r1 = crate_one();
-        foreach_n(s, m, [=] __device__(size_t j) {
-            const size_t c = k + j + 1;                                          // coefficient of Mp
-            E v = r1;
-            if (c < P) {
-                v = c < P - 1 ? AB[c] : F::zero();
-                if (c >= h) v = F::add(v, F::add(F::canon(Mc[c - h]), F::canon(Mc[P + c - h])));
-            }
-            dM[j] = F::canon(F::mul(v, F::from_u32((uint32_t)(j + 1))));
-        });
-        if (m0)
-            foreach_n(s, m + 1, [=] __device__(size_t j) {
-                const size_t c = k + j;
-                E v = r1;
-                if (c < P) {
-                    v = c < P - 1 ? AB[c] : F::zero();
-                    if (c >= h) v = F::add(v, F::add(F::canon(Mc[c - h]), F::canon(Mc[P + c - h])));
-                }
-                m0[j] = F::canon(v);
-            });
+        auto mp = [=] __device__(size_t c) {                                     // coefficient c <= P of Mp, not reduced
+            if (c == P) return r1;
+            E v = c < P - 1 ? AB[c] : F::zero();
+            if (c >= h) v = F::add(v, F::add(F::canon(Mc[c - h]), F::canon(Mc[P + c - h])));
+            return v;
+        };
+        foreach_n(s, m, [=] __device__(size_t j) { dM[j] = F::canon(F::mul(mp(k + j + 1), F::from_u32((uint32_t)(j + 1)))); });
+        if (m0) foreach_n(s, m + 1, [=] __device__(size_t j) { m0[j] = F::canon(mp(k + j)); });
         ok = remainder_descent(dM, m, st, 1, rem, s) && ok;
         ECFFT_LAUNCH(KC_POINTWISE, sizeof(E) * ((double)P + 2.0 * (double)m), (k_eval_leaves<F, (int)kEvalLeaf>), dim3(nblocks(P)),
                      dim3(kBlock), 0, s, w, (const E*)rem, P, B, (uint32_t)B, points, m, P / B, P / B, rinv_table());

@@ -499,21 +499,29 @@ int run_poly_xgcd_partial(ecfft_ctx* c, DeviceChain<F>& ch, const void* a, size_
     });
 }
 
+// What the three Reed-Solomon calls check alike, after their own pointers: the first failing code or ECFFT_OK.  N: the call's
+// tree rule (rs_leaves, rs_encode_leaves), which covers its interpolations, evaluations and the partial xgcd of (m + 1, m).
+template <class F>
+int rs_call_checks(const DeviceChain<F>& ch, size_t m, size_t k, size_t N, size_t count) {
+    using E = typename F::elem;
+    if (k > m || m > SIZE_MAX / (64 * sizeof(E)) / 4) return ECFFT_ERR_BAD_ARG;
+    if (N > 1 && N > ch.size()) return ECFFT_ERR_TREE_TOO_SMALL;
+    const size_t per = N > 4 * (m + 1) ? N : 4 * (m + 1);
+    if (N > SIZE_MAX / (8 * 64 * sizeof(E))) return ECFFT_ERR_BAD_ARG;       // node data of the interpolations
+    if (count > SIZE_MAX / (16 * per * sizeof(E))) return ECFFT_ERR_BAD_ARG;  // byte counts of the rows and temporaries must not wrap
+    return ECFFT_OK;
+}
+
 // ecfft_rs_decode: synchronous (the verdicts are returned to the host, and two equal points raise a device flag, reported as
 // ECFFT_ERR_BAD_ARG)
 template <class F>
 int run_rs_decode(ecfft_ctx* c, DeviceChain<F>& ch, const void* points, size_t m, const void* values, size_t k, void* message,
                   int64_t* n_errors, size_t count, int mem, void* stream) {
     using E = typename F::elem;
-    if (!points || !values || !message || !n_errors || k > m) return ECFFT_ERR_BAD_ARG;
-    if (m > SIZE_MAX / (64 * sizeof(E)) / 4) return ECFFT_ERR_BAD_ARG;
+    if (!points || !values || !message || !n_errors) return ECFFT_ERR_BAD_ARG;
     static_assert(DeviceChain<F>::kRsSmall == ECFFT_RS_SMALL_MAX, "the header states the small regime's bound");
     static_assert(sizeof(long long) == sizeof(int64_t), "verdicts are read back as long long");
-    const size_t N = DeviceChain<F>::rs_leaves(m);                           // covers the interpolation and the partial xgcd of (m + 1, m)
-    if (N > 1 && N > ch.size()) return ECFFT_ERR_TREE_TOO_SMALL;
-    const size_t per = N > 4 * (m + 1) ? N : 4 * (m + 1);
-    if (N > SIZE_MAX / (8 * 64 * sizeof(E))) return ECFFT_ERR_BAD_ARG;       // node data of the interpolation
-    if (count > SIZE_MAX / (16 * per * sizeof(E))) return ECFFT_ERR_BAD_ARG;  // byte counts of the rows and temporaries must not wrap
+    if (const int rc = rs_call_checks(ch, m, k, DeviceChain<F>::rs_leaves(m), count)) return rc;
     const size_t eb = count * sizeof(E);
     return staged(c, ch, mem, stream, {{points, m * sizeof(E)}, {values, m * eb}}, {{message, k * eb}}, [&](auto d, auto o) -> int {
         bool repeated = false;
@@ -528,13 +536,8 @@ template <class F>
 int run_rs_encode(ecfft_ctx* c, DeviceChain<F>& ch, const void* points, size_t m, const void* data, size_t k, void* codeword, size_t count,
                   int mem, void* stream) {
     using E = typename F::elem;
-    if (!points || !data || !codeword || k > m) return ECFFT_ERR_BAD_ARG;
-    if (m > SIZE_MAX / (64 * sizeof(E)) / 4) return ECFFT_ERR_BAD_ARG;
-    const size_t N = DeviceChain<F>::rs_encode_leaves(m, k);                 // the interpolation at k points, the evaluation of k coefficients
-    if (N > 1 && N > ch.size()) return ECFFT_ERR_TREE_TOO_SMALL;
-    const size_t per = N > 4 * (m + 1) ? N : 4 * (m + 1);
-    if (N > SIZE_MAX / (8 * 64 * sizeof(E))) return ECFFT_ERR_BAD_ARG;       // node data of the two bodies
-    if (count > SIZE_MAX / (16 * per * sizeof(E))) return ECFFT_ERR_BAD_ARG;  // byte counts of the rows and temporaries must not wrap
+    if (!points || !data || !codeword) return ECFFT_ERR_BAD_ARG;
+    if (const int rc = rs_call_checks(ch, m, k, DeviceChain<F>::rs_encode_leaves(m, k), count)) return rc;
     const size_t eb = count * sizeof(E);
     return staged(c, ch, mem, stream, {{points, m * sizeof(E)}, {data, k * eb}}, {{codeword, m * eb}}, [&](auto d, auto o) -> int {
         bool repeated = false;
@@ -548,14 +551,9 @@ template <class F>
 int run_rs_decode_erasures(ecfft_ctx* c, DeviceChain<F>& ch, const void* points, size_t m, const void* values, const uint8_t* erased, size_t k,
                            void* out, int out_form, int64_t* n_errors, size_t count, int mem, void* stream) {
     using E = typename F::elem;
-    if (!points || !values || !out || !n_errors || k > m) return ECFFT_ERR_BAD_ARG;
+    if (!points || !values || !out || !n_errors) return ECFFT_ERR_BAD_ARG;
     if (out_form != ECFFT_RS_OUT_COEFFS && out_form != ECFFT_RS_OUT_CODEWORD) return ECFFT_ERR_BAD_ARG;
-    if (m > SIZE_MAX / (64 * sizeof(E)) / 4) return ECFFT_ERR_BAD_ARG;
-    const size_t N = DeviceChain<F>::rs_leaves(m);
-    if (N > 1 && N > ch.size()) return ECFFT_ERR_TREE_TOO_SMALL;
-    const size_t per = N > 4 * (m + 1) ? N : 4 * (m + 1);
-    if (N > SIZE_MAX / (8 * 64 * sizeof(E))) return ECFFT_ERR_BAD_ARG;       // node data of the interpolation
-    if (count > SIZE_MAX / (16 * per * sizeof(E))) return ECFFT_ERR_BAD_ARG;  // byte counts of the rows and temporaries must not wrap
+    if (const int rc = rs_call_checks(ch, m, k, DeviceChain<F>::rs_leaves(m), count)) return rc;
     const size_t eb = count * sizeof(E), no = out_form == ECFFT_RS_OUT_CODEWORD ? m : k;
     return staged(c, ch, mem, stream, {{points, m * sizeof(E)}, {values, m * eb}, {erased, erased ? m * count : 0}}, {{out, no * eb}},
                   [&](auto d, auto o) -> int {

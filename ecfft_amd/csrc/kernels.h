@@ -2999,7 +2999,9 @@ __global__ __launch_bounds__(G) void k_rs_prepare(const typename F::elem* __rest
     }
     if (t <= m) g0[t] = F::canon(F::mul(cur, r1));
 }
-// One received word of m <= G - 1 symbols per workgroup, everything in LDS, thread t owning coefficient t of every row:
+// The two decoders below are one body between a prologue and an epilogue of their own: rs_interpolant (step 1), then rs_gao_finish
+// (steps 2 and 3).  One received word of m <= G - 1 symbols per workgroup, everything in LDS, thread t owning coefficient t of
+// every row:
 //   1. the interpolant g1: Newton's divided differences (m - 1 steps of one multiply by k_rs_prepare's inverse denominators; a
 //      thread keeps its own entry in a register and reads its neighbour's through two alternating rows, one barrier a step),
 //      then coefficient t of sum_i dd_i N_i as a sum over the basis rows in global memory — no sequential Horner;
@@ -3007,7 +3009,83 @@ __global__ __launch_bounds__(G) void k_rs_prepare(const typename F::elem* __rest
 //      of g1 is needed): R1 = c r and T1 = c t for the wanted row (r, s, t) of the sequence and some scalar c;
 //   3. f = R1 / T1 by long division with T1 made monic as PLAIN numbers (one inversion, u = 1 / lc(T1)): the quotient of the
 //      stored numbers is lc(T1) times the plain f, so u R brings its coefficients to crate form.  The word decodes iff the
-//      remainder is zero and deg f < k.  message row p (k coefficients) = f, zero-padded, n_err[p] = deg t; else a zero row and -1.
+//      remainder is zero and deg f < k, and then its verdict is deg t; else -1.
+// Step 1: mine = the thread's symbol (zero from m up, and for a lost one); returns coefficient t of g1.  A, B: the two alternating
+// rows, dd: the row that holds the divided differences for the sum.  All three are free behind the closing barrier, and sdeg is
+// -1, -1 there.
+template <class F>
+__device__ __forceinline__ typename F::elem rs_interpolant(typename F::elem mine, uint32_t m, const typename F::elem* __restrict__ np,
+                                                           const typename F::elem* __restrict__ invd, typename F::elem* dd,
+                                                           typename F::elem* A, typename F::elem* B, int* sdeg, uint32_t t) {
+    using E = typename F::elem;
+    for (uint32_t j = 1; j < m; ++j) {
+        A[t] = mine;
+        __syncthreads();
+        if (t >= j && t < m) mine = F::canon(F::mul(F::canon(F::sub(mine, A[t - 1])), invd[(size_t)j * m + t]));
+        E* x = A; A = B; B = x;
+    }
+    __syncthreads();
+    dd[t] = mine;
+    if (t < 2) sdeg[t] = -1;
+    __syncthreads();
+    E acc = F::zero();
+    if (t < m)
+        for (uint32_t i = t; i < m; ++i) acc = F::canon(F::mul_add(np[(size_t)i * m + t], dd[i], acc));
+    __syncthreads();
+    return acc;
+}
+// Steps 2 and 3 on the thread's coefficients va of R0 (deg R0 = d0) and acc of R1 = g1, behind rs_interpolant's closing barrier:
+// sets up the four rows, and owns sdeg and *snorm from there on.  Returns the thread's coefficient of f in crate form — zero from
+// deg f + 1 up, and everywhere for a word that does not decode — and the word's verdict.  No barrier closes it: other threads may
+// still read the R rows, the two T rows are free.
+template <class F>
+__device__ __forceinline__ typename F::elem rs_gao_finish(typename F::elem va, typename F::elem acc, int d0, int stop, uint32_t k,
+                                                          typename F::elem r1, typename F::elem* R0, typename F::elem* R1,
+                                                          typename F::elem* T0, typename F::elem* T1, typename F::elem* snorm, int* sdeg,
+                                                          uint32_t t, long long& verdict) {
+    using E = typename F::elem;
+    {
+        E one = F::zero();
+        if (t == 0) one = r1;
+        R0[t] = va; R1[t] = acc;
+        if (!F::is_zero(acc)) atomicMax(&sdeg[1], (int)t);
+        T0[t] = F::zero(); T1[t] = one;
+    }
+    __syncthreads();
+    int d1 = sdeg[1], c0 = 1, c1 = 1;
+    __syncthreads();
+    if (t < 2) sdeg[t] = -1;
+    __syncthreads();
+    E *S0 = T0, *S1 = T1;
+    gcd_remainder_loop<F>(R0, R1, d0, d1, S0, S1, T0, T1, c0, c1, 1u, stop, sdeg, t);
+    __syncthreads();
+    if (t < 2) sdeg[t] = -1;
+    __syncthreads();
+    if (!F::is_zero(T1[t])) atomicMax(&sdeg[0], (int)t);     // written whole at the start and zero above its length
+    __syncthreads();
+    const int dt = sdeg[0], dq = d1 - dt;
+    bool good = dt >= 0 && (d1 < 0 || (dq >= 0 && dq < (int)k));
+    if (good && d1 >= 0) {
+        if (t == 0) *snorm = F::canon(F::inv(T1[dt]));
+        __syncthreads();
+        if ((int)t < dt) T1[t] = F::canon(F::mul(T1[t], *snorm));
+        __syncthreads();
+        for (int i = dq; i >= 0; --i) {
+            const E qi = R1[i + dt];
+            if ((int)t < dt) R1[i + (int)t] = F::canon(F::sub(R1[i + (int)t], F::canon(F::mul(qi, T1[t]))));
+            __syncthreads();
+        }
+        if ((int)t < dt && !F::is_zero(R1[t])) atomicMax(&sdeg[1], (int)t);
+        __syncthreads();
+        good = sdeg[1] < 0;
+    }
+    E v = F::zero();
+    if (good && d1 >= 0 && (int)t <= dq) v = F::canon(F::mul(R1[dt + (int)t], F::canon(F::mul(*snorm, r1))));
+    verdict = good ? dt : -1;
+    return v;
+}
+// ecfft_rs_decode's kernel: the shared body on k_rs_prepare's g0.  message row p (k coefficients) = f, zero-padded, n_err[p] = the
+// verdict; a word that does not decode leaves a zero row.
 template <class F, int G>
 __global__ __launch_bounds__(G) void k_rs_decode_small(const typename F::elem* __restrict__ values, uint32_t m, uint32_t k, int32_t stop,
                                                        const typename F::elem* __restrict__ np, const typename F::elem* __restrict__ g0,
@@ -3022,76 +3100,25 @@ __global__ __launch_bounds__(G) void k_rs_decode_small(const typename F::elem* _
     E *R0 = buf, *R1 = buf + G, *T0 = buf + 2 * G, *T1 = buf + 3 * G;
     E mine = F::zero();
     if (t < m) mine = F::canon(values[p * m + t]);
-    {
-        E *A = T0, *B = T1;
-        for (uint32_t j = 1; j < m; ++j) {
-            A[t] = mine;
-            __syncthreads();
-            if (t >= j && t < m) mine = F::canon(F::mul(F::canon(F::sub(mine, A[t - 1])), invd[(size_t)j * m + t]));
-            E* x = A; A = B; B = x;
-        }
-    }
-    __syncthreads();
-    R0[t] = mine;                                            // the divided differences
-    if (t < 2) sdeg[t] = -1;
-    __syncthreads();
-    E acc = F::zero();
-    if (t < m)
-        for (uint32_t i = t; i < m; ++i) acc = F::canon(F::mul_add(np[(size_t)i * m + t], R0[i], acc));
-    __syncthreads();
-    {
-        E va = F::zero(), one = F::zero();
-        if (t <= m) va = g0[t];
-        if (t == 0) one = r1;
-        R0[t] = va; R1[t] = acc;
-        if (!F::is_zero(acc)) atomicMax(&sdeg[1], (int)t);
-        T0[t] = F::zero(); T1[t] = one;
-    }
-    __syncthreads();
-    int d0 = (int)m, d1 = sdeg[1], c0 = 1, c1 = 1;
-    __syncthreads();
-    if (t < 2) sdeg[t] = -1;
-    __syncthreads();
-    E *S0 = T0, *S1 = T1;
-    gcd_remainder_loop<F>(R0, R1, d0, d1, S0, S1, T0, T1, c0, c1, 1u, stop, sdeg, t);
-    __syncthreads();
-    if (t < 2) sdeg[t] = -1;
-    __syncthreads();
-    if (!F::is_zero(T1[t])) atomicMax(&sdeg[0], (int)t);     // written whole at the start and zero above its length
-    __syncthreads();
-    const int dt = sdeg[0], dq = d1 - dt;
-    bool good = dt >= 0 && (d1 < 0 || (dq >= 0 && dq < (int)k));
-    if (good && d1 >= 0) {
-        if (t == 0) snorm = F::canon(F::inv(T1[dt]));
-        __syncthreads();
-        if ((int)t < dt) T1[t] = F::canon(F::mul(T1[t], snorm));
-        __syncthreads();
-        for (int i = dq; i >= 0; --i) {
-            const E qi = R1[i + dt];
-            if ((int)t < dt) R1[i + (int)t] = F::canon(F::sub(R1[i + (int)t], F::canon(F::mul(qi, T1[t]))));
-            __syncthreads();
-        }
-        if ((int)t < dt && !F::is_zero(R1[t])) atomicMax(&sdeg[1], (int)t);
-        __syncthreads();
-        good = sdeg[1] < 0;
-    }
-    if (t < k) {
-        E v = F::zero();
-        if (good && d1 >= 0 && (int)t <= dq) v = F::canon(F::mul(R1[dt + (int)t], F::canon(F::mul(snorm, r1))));
-        message[p * k + t] = v;
-    }
-    if (t == 0) n_err[p] = good ? dt : -1;
+    const E acc = rs_interpolant<F>(mine, m, np, invd, R0, T0, T1, sdeg, t);
+    E va = F::zero();
+    if (t <= m) va = g0[t];
+    long long verdict;
+    const E v = rs_gao_finish<F>(va, acc, (int)m, stop, k, r1, R0, R1, T0, T1, &snorm, sdeg, t, verdict);
+    if (t < k) message[p * k + t] = v;
+    if (t == 0) n_err[p] = verdict;
 }
-// ecfft_rs_decode_erasures, small regime: k_rs_decode_small with a mask per row (erased + p m, may be null: no erasure; a non-zero
+// ecfft_rs_decode_erasures, small regime: the shared body with a mask per row (erased + p m, may be null: no erasure; a non-zero
 // byte marks a lost symbol, whose stored value is never read) behind the same k_rs_prepare over ALL m points.
 // With K the kept positions, m' = |K| and g0' = prod_{i in K} (x - x_i): the interpolant over all m points of the row with its
 // erased symbols read as 0 is congruent mod g0' to the interpolant over K, and the remainder sequence of (g0', g1) is the swap row,
-// g1 mod g0' with cofactor 1, then the rows of the punctured code's own pair.  So steps 1 and 2 of k_rs_decode_small stay, and
-// only the loop's first operand and its bound change: R0 = g0' (deg m'), stop' = ceil((m' + k) / 2).
-//   g0': a row without erasure takes the shared g0.  Otherwise the product over the kept points, the loop of k_rs_prepare's block 0
-//     with the erased points skipped (m' steps on PLAIN coefficients, then R for crate form; the mask is in LDS, so every thread
-//     skips the same steps; the plain points are staged once in a free LDS row and the coefficient row alternates between two
-//     rows: one multiply and one barrier a step).
+// g1 mod g0' with cofactor 1, then the rows of the punctured code's own pair.  So rs_interpolant stays as it is, and rs_gao_finish
+// takes another first operand and bound: R0 = g0' (deg m'), stop' = ceil((m' + k) / 2).
+//   g0': a row without erasure takes the shared g0.  Otherwise the product over the kept points, the recurrence of k_rs_prepare's
+//     block 0 with the erased points skipped (m' steps on PLAIN coefficients, then R for crate form; the mask is in LDS, so every
+//     thread skips the same steps; the plain points are staged once in a free LDS row and the coefficient row alternates between
+//     two rows: one multiply and one barrier a step).  The two loops stay apart: block 0 keeps one row and pays a second barrier a
+//     step, which this kernel has the rows to avoid.
 //   m' < k: the row fails before any work.
 //   form == 0: out row p = the k coefficients of f, as k_rs_decode_small's message.  form != 0: out row p = the m symbols f(x_i),
 //     thread i by Horner on the plain x_i = x_i R^-1 (k steps, no barrier); a failed row is zero in both forms.
@@ -3119,26 +3146,9 @@ __global__ __launch_bounds__(G) void k_rs_decode_ee_small(const typename F::elem
         if (t == 0) n_err[p] = -1;
         return;
     }
-    const int32_t stop = (int32_t)((mk + k + 1) / 2);
     E mine = F::zero();
     if (t < m && !lost) mine = F::canon(values[p * m + t]);
-    {
-        E *A = T0, *B = T1;
-        for (uint32_t j = 1; j < m; ++j) {
-            A[t] = mine;
-            __syncthreads();
-            if (t >= j && t < m) mine = F::canon(F::mul(F::canon(F::sub(mine, A[t - 1])), invd[(size_t)j * m + t]));
-            E* x = A; A = B; B = x;
-        }
-    }
-    __syncthreads();
-    R0[t] = mine;                                            // the divided differences
-    if (t < 2) sdeg[t] = -1;
-    __syncthreads();
-    E acc = F::zero();
-    if (t < m)
-        for (uint32_t i = t; i < m; ++i) acc = F::canon(F::mul_add(np[(size_t)i * m + t], R0[i], acc));
-    __syncthreads();
+    const E acc = rs_interpolant<F>(mine, m, np, invd, R0, T0, T1, sdeg, t);
     E va = F::zero();
     if (mk == m) {
         if (t <= m) va = g0[t];
@@ -3160,44 +3170,9 @@ __global__ __launch_bounds__(G) void k_rs_decode_ee_small(const typename F::elem
         __syncthreads();
         if (t <= mk) va = F::canon(F::mul(cur, r1));
     }
-    {
-        E one = F::zero();
-        if (t == 0) one = r1;
-        R0[t] = va; R1[t] = acc;
-        if (!F::is_zero(acc)) atomicMax(&sdeg[1], (int)t);
-        T0[t] = F::zero(); T1[t] = one;
-    }
-    __syncthreads();
-    int d0 = (int)mk, d1 = sdeg[1], c0 = 1, c1 = 1;
-    __syncthreads();
-    if (t < 2) sdeg[t] = -1;
-    __syncthreads();
-    E *S0 = T0, *S1 = T1;
-    gcd_remainder_loop<F>(R0, R1, d0, d1, S0, S1, T0, T1, c0, c1, 1u, stop, sdeg, t);
-    __syncthreads();
-    if (t < 2) sdeg[t] = -1;
-    __syncthreads();
-    if (!F::is_zero(T1[t])) atomicMax(&sdeg[0], (int)t);     // written whole at the start and zero above its length
-    __syncthreads();
-    const int dt = sdeg[0], dq = d1 - dt;
-    bool good = dt >= 0 && (d1 < 0 || (dq >= 0 && dq < (int)k));
-    if (good && d1 >= 0) {
-        if (t == 0) snorm = F::canon(F::inv(T1[dt]));
-        __syncthreads();
-        if ((int)t < dt) T1[t] = F::canon(F::mul(T1[t], snorm));
-        __syncthreads();
-        for (int i = dq; i >= 0; --i) {
-            const E qi = R1[i + dt];
-            if ((int)t < dt) R1[i + (int)t] = F::canon(F::sub(R1[i + (int)t], F::canon(F::mul(qi, T1[t]))));
-            __syncthreads();
-        }
-        if ((int)t < dt && !F::is_zero(R1[t])) atomicMax(&sdeg[1], (int)t);
-        __syncthreads();
-        good = sdeg[1] < 0;
-    }
-    E v = F::zero();
-    if (t < k && good && d1 >= 0 && (int)t <= dq) v = F::canon(F::mul(R1[dt + (int)t], F::canon(F::mul(snorm, r1))));
-    if (t == 0) n_err[p] = good ? dt : -1;
+    long long verdict;
+    const E v = rs_gao_finish<F>(va, acc, (int)mk, (int)((mk + k + 1) / 2), k, r1, R0, R1, T0, T1, &snorm, sdeg, t, verdict);
+    if (t == 0) n_err[p] = verdict;
     if (!form) {
         if (t < k) out[p * k + t] = v;
         return;

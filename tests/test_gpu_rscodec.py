@@ -157,10 +157,11 @@ def test_shortest_codes(oracle_mod, field):
 
 
 @pytest.mark.parametrize("field", FIELDS)
-@pytest.mark.parametrize("m,k", [(15, 7), (64, 32), (255, 223)])
+@pytest.mark.parametrize("m,k", [(15, 7), (64, 32), (255, 223), (300, 200)])
 def test_without_erasures_it_is_rs_decode(oracle_mod, field, m, k):
-    """erased = None and an all-zero mask: the bytes of rs_decode, message and verdict, at 0, 1, the radius and one error beyond it"""
-    F, t = oracle_mod.field(field), tree(field, 4)
+    """erased = None and an all-zero mask: the bytes of rs_decode, message and verdict, at 0, 1, the radius and one error beyond it;
+    (300, 200) is the large regime, on the smallest tree its rule allows"""
+    F, t = oracle_mod.field(field), tree(field, 1024 if m > 255 else 4)
     rad = (m - k) // 2
     xs = make_points(field, m, 100 * m + k)
     clean, words, masks = make_rows(field, xs, k, [(0, 0), (0, 1), (0, rad), (0, rad + 1)], m + k)
@@ -190,6 +191,19 @@ def test_large_regime(oracle_mod, field):
         assert verdicts[:4] == [40, 0, 10, 50]
     want = model(("large", field), field, xs, words, masks, k)
     assert [w[2] for w in want[:4]] == clean[:4]
+
+
+@pytest.mark.parametrize("field", FIELDS)
+def test_large_regime_compaction_boundaries(oracle_mod, field):
+    """m = 300, k = 200, erasures only, one call: m' = 300 (a clean row), 256 (the first length that is interpolated on the tree),
+    255 (the last one for the compacted small kernels), 200 (m' = k) and 199 (m' < k: skipped)"""
+    m, k = 300, 200
+    F, t = oracle_mod.field(field), tree(field, 1024)
+    xs = make_points(field, m, 300256)
+    clean, words, masks = make_rows(field, xs, k, [(0, 0), (44, 0), (45, 0), (100, 0), (101, 0)], 256)
+    for codeword in (False, True):
+        assert check(F, field, t, ("bounds", field), xs, words, masks, k, codeword) == [0, 0, 0, 0, -1]
+    assert [w[2] for w in model(("bounds", field), field, xs, words, masks, k)[:4]] == clean[:4]
 
 
 ENC = [(15, 7), (255, 223), (7, 7), (5, 1), (300, 200)]
