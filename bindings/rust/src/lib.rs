@@ -76,6 +76,8 @@ pub mod ffi {
         pub fn ecfft_rs_decode(ctx: *mut EcfftCtx, points: *const c_void, m: usize, values: *const c_void, k: usize, message: *mut c_void, n_errors: *mut i64, count: usize, mem: i32, stream: *mut c_void) -> i32;
         pub fn ecfft_rs_encode(ctx: *mut EcfftCtx, points: *const c_void, m: usize, data: *const c_void, k: usize, codeword: *mut c_void, count: usize, mem: i32, stream: *mut c_void) -> i32;
         pub fn ecfft_rs_decode_erasures(ctx: *mut EcfftCtx, points: *const c_void, m: usize, values: *const c_void, erased: *const u8, k: usize, out: *mut c_void, out_form: i32, n_errors: *mut i64, count: usize, mem: i32, stream: *mut c_void) -> i32;
+        pub fn ecfft_seq_min_poly(ctx: *mut EcfftCtx, seq: *const c_void, n_terms: usize, min_poly: *mut c_void, orders: *mut i64, count: usize, mem: i32, stream: *mut c_void) -> i32;
+        pub fn ecfft_seq_nth_term(ctx: *mut EcfftCtx, char_poly: *const c_void, nc: usize, init: *const c_void, index: *const c_void, index_bytes: usize, out: *mut c_void, nout: usize, count: usize, mem: i32, stream: *mut c_void) -> i32;
         pub fn ecfft_mextend(ctx: *mut EcfftCtx, inp: *const c_void, out: *mut c_void, e: usize, moiety: i32, count: usize, mem: i32, stream: *mut c_void) -> i32;
         pub fn ecfft_redc(ctx: *mut EcfftCtx, evals: *const c_void, a: *const c_void, out: *mut c_void, n: usize, moiety: i32, mem: i32, stream: *mut c_void) -> i32;
         pub fn ecfft_modular_reduce(ctx: *mut EcfftCtx, evals: *const c_void, a: *const c_void, c: *const c_void, out: *mut c_void, n: usize, mem: i32, stream: *mut c_void) -> i32;
@@ -575,6 +577,39 @@ impl<F: HipField> HipFFTree<F> {
         } else {
             Some((out, n_errors as usize))
         }
+    }
+
+    /// `ecfft_seq_min_poly` (no reference counterpart): the minimal polynomial of the sequence `seq` of `N` terms, what
+    /// Berlekamp-Massey computes.  `Some(C)`: the monic `C = x^L + sum c_j x^j` of least degree with
+    /// `s[i+L] + sum_j c_j s[i+j] = 0` for all `0 <= i < N - L`, as `L + 1` coefficients (`[1]` for a zero sequence), where
+    /// `2 L <= N` makes it unique; `None` where the sequence is too short to determine it.  Up to `ECFFT_SEQ_SMALL_MAX` terms work
+    /// on any tree; tree rule: include/ecfft_hip.h.
+    pub fn seq_min_poly(&self, seq: &[F]) -> Option<Vec<F>> {
+        assert!(!seq.is_empty());
+        let n = seq.len() / 2 + 1;
+        let mut c = Self::out_vec(n);
+        let mut order: i64 = -1;
+        check(unsafe { ffi::ecfft_seq_min_poly(self.ctx, seq.as_ptr().cast(), seq.len(), c.as_mut_ptr().cast(), &mut order, 1, ffi::MEM_HOST, core::ptr::null_mut()) });
+        if order < 0 {
+            None
+        } else {
+            unsafe { c.set_len(order as usize + 1) };
+            Some(c)
+        }
+    }
+
+    /// `ecfft_seq_nth_term` (no reference counterpart): the terms `s_K .. s_(K + nout - 1)` of the linear recurrence with the
+    /// characteristic polynomial `char_poly` (`L + 1 >= 2` coefficients, a non-zero leading one; monic not required:
+    /// `sum_{j<=L} c_j s[i+j] = 0`) and the `L` initial terms `init`; `index` is `K` in little-endian bytes of any length.  One power
+    /// `x^K mod C` and `nout L` multiply-adds.  Up to `ECFFT_SEQ_TERM_SMALL_MAX` coefficients work on any tree; tree rule:
+    /// include/ecfft_hip.h.  Panics on a zero leading coefficient.
+    pub fn seq_nth_term(&self, char_poly: &[F], init: &[F], index: &[u8], nout: usize) -> Vec<F> {
+        assert!(char_poly.len() >= 2 && init.len() == char_poly.len() - 1 && nout >= 1);
+        let mut out = Self::out_vec(nout);
+        let idx = if index.is_empty() { core::ptr::null() } else { index.as_ptr().cast() };
+        check(unsafe { ffi::ecfft_seq_nth_term(self.ctx, char_poly.as_ptr().cast(), char_poly.len(), init.as_ptr().cast(), idx, index.len(), out.as_mut_ptr().cast(), nout, 1, ffi::MEM_HOST, core::ptr::null_mut()) });
+        unsafe { out.set_len(nout) };
+        out
     }
 
     /// `ecfft::utils::find_roots` (src/utils.rs:25-44): the distinct roots of `f` in the field, in ascending order of their

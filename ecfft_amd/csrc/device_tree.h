@@ -1819,6 +1819,13 @@ public:
     bool poly_pow_mod(const E* a, size_t na, const uint8_t* exp, size_t nbits, const E* f, size_t nm, E* out, size_t count, bool* singular,
                       hipStream_t s) {
         int* flag = new_flag(s);
+        const bool ok = pow_mod_body(a, na, exp, nbits, f, nm, out, count, flag, s);
+        return finish_flagged(ok, flag, singular, s);
+    }
+    // poly_pow_mod without the read-back of the flag and the release of the temporaries, which stay with the caller (seq_nth_term
+    // takes the power of x with it)
+    bool pow_mod_body(const E* a, size_t na, const uint8_t* exp, size_t nbits, const E* f, size_t nm, E* out, size_t count, int* flag,
+                      hipStream_t s) {
         const size_t d = nm - 1;
         bool ok = true;
         const RowsRef base = reduced_below(a, na, f, nm, count, flag, &ok, s);           // the base below nm coefficients
@@ -1835,7 +1842,7 @@ public:
                              (k_powmod_small<F, (int)kPowSmall>), dim3((unsigned)c), dim3((unsigned)kPowSmall), 0, s, out + c0 * d,
                              ar + c0 * lda, lda, (uint32_t)la, f + c0 * nm, (uint32_t)d, (const uint8_t*)dexp, (uint32_t)nbits, rinv, r1, flag);
             });
-            return finish_flagged(ok, flag, singular, s);
+            return ok;
         }
         E* kept = temp(3 * count * powmod_leaves(nm));
         KeptModulus km;
@@ -1846,7 +1853,7 @@ public:
             ok = powmod_step(out, nullptr, km, count, rinv, s) && ok;
             if ((exp[i >> 3] >> (i & 7)) & 1) ok = powmod_step(out, km.base, km, count, rinv, s) && ok;
         }
-        return finish_flagged(ok, flag, singular, s);
+        return ok;
     }
 
     // residues of at most this many coefficients are composed by k_compose_small (one workgroup per triple, no transform)
@@ -2164,6 +2171,89 @@ public:
         ok = finish_api(s) && ok;
         if (degrees) for (size_t p = 0; p < 3 * count; ++p) degrees[p] = hdeg[p];
         return ok;
+    }
+    // ---- ecfft_seq_min_poly / ecfft_seq_nth_term: linear recurrences ----
+    // rows of at most this many terms find their minimal polynomial in one workgroup (k_seq_minpoly_small), on any tree: x^n has
+    // n + 1 <= kGcdSmall coefficients
+    static constexpr size_t kSeqSmall = kGcdSmall - 1;
+    static size_t seq_leaves(size_t n) { return n <= kSeqSmall ? 1 : gcd_leaves(n + 1); }
+    // min_poly (count x (n / 2 + 1)) and orders (host) of `count` rows of n terms (seq: count x n): per row the order L and the
+    // monic minimal polynomial C (leading 1 at index L, zero above) where 2 L <= n, else -1 and a zero row.  (r, ., t) = the partial
+    // row of (x^n, the row) with stop = n / 2, d = max(1 + deg r, deg t); determined iff t(0) != 0 and 2 d <= n, and then L = d,
+    // C = x^d t(1/x) / t(0).
+    //   n <= kSeqSmall: one launch of k_seq_minpoly_small for all rows; x^n is built in LDS.
+    //   otherwise x^n is written once and the rows run one after another through gcd_partial_pair (no s cofactor), each finished
+    //     by k_seq_minpoly_finish on the device.
+    // The verdicts are read back once.  Synchronous.  Caller holds lock() and checks the tree rule (seq_leaves).
+    bool seq_min_poly(const E* seq, size_t n, E* min_poly, long long* orders, size_t count, hipStream_t s) {
+        const size_t nh = n / 2 + 1;
+        const E r1 = crate_one();
+        bool ok = true;
+        std::vector<long long> hord(count, -1);
+        long long* dord = temp_as<long long>(count);
+        if (n <= kSeqSmall) {
+            for_chunks(count, [&](size_t c0, size_t c) {
+                ECFFT_LAUNCH(KC_POINTWISE, sizeof(E) * (double)c * (double)(n + nh), (k_seq_minpoly_small<F, (int)kGcdSmall>), dim3((unsigned)c),
+                             dim3((unsigned)kGcdSmall), 0, s, seq + c0 * n, (uint32_t)n, min_poly + c0 * nh, dord + c0, r1);
+            });
+        } else {
+            E* xn = temp(n + 1); E* r = temp(n + 1); E* t = temp(n + 1);
+            foreach_n(s, n + 1, [=] __device__(size_t j) { E v = F::zero(); if (j == n) v = r1; xn[j] = v; });
+            gcd_flag_ = new_flag(s);
+            for (size_t p = 0; p < count && ok; ++p) {
+                const TempMark mark = temps_mark();
+                long long deg[3] = {-1, -1, -1};
+                ok = gcd_partial_pair(xn, n + 1, seq + p * n, n, n / 2, r, n + 1, nullptr, n, t, n + 1, deg, s);
+                if (ok) {
+                    ECFFT_LAUNCH(KC_POINTWISE, sizeof(E) * (double)(2 * (n + 1) + nh), k_seq_minpoly_finish<F>, dim3(1u), dim3(kBlock), 0, s,
+                                 (const E*)r, (const E*)t, (uint32_t)n, min_poly + p * nh, dord + p, r1);
+                }
+                temps_release(mark);
+            }
+        }
+        ok = ok && hipMemcpyAsync(hord.data(), dord, count * sizeof(long long), hipMemcpyDeviceToHost, s) == hipSuccess;
+        ok = finish_api(s) && ok;
+        for (size_t p = 0; p < count; ++p) orders[p] = hord[p];
+        return ok;
+    }
+    // recurrences of at most this order take their terms in one workgroup (k_seq_terms_small), on any tree
+    static constexpr size_t kSeqTermSmall = kPowSmall;
+    // out (count x nout) = the terms s_K .. s_(K + nout - 1) of the `count` sequences with characteristic polynomials char_poly
+    // (count x nc, any non-zero leading coefficient) and initial terms init (count x L, L = nc - 1): u = x^K mod C, then per term
+    // the sum of u_j s_j and the shift u <- x u mod C.  index: K as `nbits` bits in little-endian HOST bytes, bit nbits - 1 set
+    // (nbits == 0: K = 0), shared by all rows.
+    //   L <= kSeqTermSmall: one launch of k_seq_terms_small for all rows.
+    //   otherwise pow_mod_body on the base x for all rows at once (the kept-modulus scan of poly_pow_mod), then one launch of
+    //     k_seq_terms; the shifted residue alternates between the power's row and a second one taken only for nout > 1.
+    // Synchronous; *singular = some char_poly_b[nc-1] == 0.  Caller holds lock() and checks the tree rule (powmod_leaves(nc)).
+    bool seq_nth_term(const E* char_poly, size_t nc, const E* init, const uint8_t* index, size_t nbits, E* out, size_t nout, size_t count,
+                      bool* singular, hipStream_t s) {
+        int* flag = new_flag(s);
+        const size_t L = nc - 1;
+        const E r1 = crate_one();
+        const TE rinv = rinv_table();
+        bool ok = true;
+        if (L <= kSeqTermSmall) {
+            const size_t nbytes = (nbits + 7) / 8;
+            uint8_t* didx = temp_as<uint8_t>(nbytes);
+            if (nbytes) ok = hipMemcpyAsync(didx, index, nbytes, hipMemcpyHostToDevice, s) == hipSuccess;
+            for_chunks(count, [&](size_t c0, size_t c) {
+                ECFFT_LAUNCH(KC_POINTWISE, sizeof(E) * (double)c * (double)(nc + L + nout) + (double)nbytes, (k_seq_terms_small<F, (int)kPowSmall>),
+                             dim3((unsigned)c), dim3((unsigned)kPowSmall), 0, s, out + c0 * nout, (uint32_t)nout, char_poly + c0 * nc, (uint32_t)L,
+                             init + c0 * L, (const uint8_t*)didx, (uint32_t)nbits, rinv, r1, flag);
+            });
+            return finish_flagged(ok, flag, singular, s);
+        }
+        E* x = temp(2 * count); E* u = temp(count * L);
+        E* alt = nout > 1 ? temp(count * L) : nullptr;
+        foreach_n(s, 2 * count, [=] __device__(size_t i) { E v = F::zero(); if (i & 1) v = r1; x[i] = v; });
+        ok = pow_mod_body(x, 2, index, nbits, char_poly, nc, u, count, flag, s);
+        for_chunks(count, [&](size_t c0, size_t c) {
+            ECFFT_LAUNCH(KC_POINTWISE, sizeof(E) * (double)c * (double)(nc + L + nout + (nout > 1 ? 2 * (nout - 1) * L : L)), k_seq_terms<F>,
+                         dim3((unsigned)c), dim3(kBlock), 0, s, out + c0 * nout, (uint32_t)nout, u + c0 * L, alt ? alt + c0 * L : (E*)nullptr,
+                         char_poly + c0 * nc, (uint32_t)L, init + c0 * L, rinv);
+        });
+        return finish_flagged(ok, flag, singular, s);
     }
 
 private:

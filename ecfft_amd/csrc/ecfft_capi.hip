@@ -5,6 +5,7 @@
 #include <new>
 #include "device_tree.h"
 #include "wire_parse.h"
+#include "seq_host.h"
 #include "../../include/ecfft_hip.h"
 #ifdef ECFFT_TEST_HOOKS
 #include "../../include/ecfft_hip_hooks.h"    // test / measurement entry points: never in the shipped library
@@ -562,6 +563,47 @@ int run_rs_decode_erasures(ecfft_ctx* c, DeviceChain<F>& ch, const void* points,
                                    (long long*)n_errors, count, &repeated, (hipStream_t)stream))
             return ECFFT_ERR_HIP;
         return repeated ? ECFFT_ERR_BAD_ARG : ECFFT_OK;                      // two equal points, erased or not: no code
+    });
+}
+
+// ecfft_seq_min_poly: synchronous (the verdicts are returned to the host).  Nothing fails on the data.
+template <class F>
+int run_seq_min_poly(ecfft_ctx* c, DeviceChain<F>& ch, const void* seq, size_t n, void* min_poly, int64_t* orders, size_t count, int mem,
+                     void* stream) {
+    using E = typename F::elem;
+    if (!seq || !min_poly || !orders) return ECFFT_ERR_BAD_ARG;
+    static_assert(DeviceChain<F>::kSeqSmall == ECFFT_SEQ_SMALL_MAX, "the header states the small regime's bound");
+    static_assert(sizeof(long long) == sizeof(int64_t), "orders are read back as long long");
+    if (n > SIZE_MAX / (64 * sizeof(E)) / 4) return ECFFT_ERR_BAD_ARG;
+    const size_t N = DeviceChain<F>::seq_leaves(n);
+    if (N > 1 && N > ch.size()) return ECFFT_ERR_TREE_TOO_SMALL;
+    if (!seq_min_poly_fits(n, count, N, sizeof(E))) return ECFFT_ERR_BAD_ARG;    // byte counts of the rows and temporaries must not wrap
+    const size_t eb = count * sizeof(E);
+    return staged(c, ch, mem, stream, {{seq, n * eb}}, {{min_poly, (n / 2 + 1) * eb}}, [&](auto d, auto o) -> int {
+        return ch.seq_min_poly((const E*)d[0], n, (E*)o[0], (long long*)orders, count, (hipStream_t)stream) ? ECFFT_OK : ECFFT_ERR_HIP;
+    });
+}
+
+// ecfft_seq_nth_term: synchronous like ecfft_poly_pow_mod, whose tree rule and device check of the leading coefficient it shares
+template <class F>
+int run_seq_nth_term(ecfft_ctx* c, DeviceChain<F>& ch, const void* char_poly, size_t nc, const void* init, const void* index,
+                     size_t index_bytes, void* out, size_t nout, size_t count, int mem, void* stream) {
+    using E = typename F::elem;
+    if (!char_poly || !init || !out || (!index && index_bytes)) return ECFFT_ERR_BAD_ARG;
+    static_assert(DeviceChain<F>::kSeqTermSmall + 1 == ECFFT_SEQ_TERM_SMALL_MAX, "the header states the small regime's bound");
+    if (nc > SIZE_MAX / (64 * sizeof(E))) return ECFFT_ERR_BAD_ARG;
+    const size_t N = DeviceChain<F>::powmod_leaves(nc), L = nc - 1;            // 1 for L <= kSeqTermSmall
+    if (N > 1 && N > ch.size()) return ECFFT_ERR_TREE_TOO_SMALL;
+    if (!seq_nth_term_fits(nc, nout, count, N, sizeof(E))) return ECFFT_ERR_BAD_ARG;
+    size_t nbits = 0;
+    if (!seq_index_bits((const uint8_t*)index, index_bytes, &nbits)) return ECFFT_ERR_BAD_ARG;
+    const size_t eb = count * sizeof(E);
+    return staged(c, ch, mem, stream, {{char_poly, nc * eb}, {init, L * eb}}, {{out, nout * eb}}, [&](auto dv, auto o) -> int {
+        bool singular = false;
+        if (!ch.seq_nth_term((const E*)dv[0], nc, (const E*)dv[1], (const uint8_t*)index, nbits, (E*)o[0], nout, count, &singular,
+                             (hipStream_t)stream))
+            return ECFFT_ERR_HIP;
+        return singular ? ECFFT_ERR_BAD_ARG : ECFFT_OK;                          // a zero leading coefficient of some C_b
     });
 }
 
@@ -1419,6 +1461,18 @@ int ecfft_rs_decode_erasures(ecfft_ctx* ctx, const void* points, size_t m, const
     if (m == 0 || k == 0 || count == 0) return ECFFT_ERR_BAD_ARG;
     return on_chain(ctx, [&](auto& ch) {
         return run_rs_decode_erasures(ctx, ch, points, m, values, erased, k, out, out_form, n_errors, count, mem, stream);
+    });
+}
+int ecfft_seq_min_poly(ecfft_ctx* ctx, const void* seq, size_t n_terms, void* min_poly, int64_t* orders, size_t count, int mem,
+                       void* stream) {
+    if (n_terms == 0 || count == 0) return ECFFT_ERR_BAD_ARG;
+    return on_chain(ctx, [&](auto& ch) { return run_seq_min_poly(ctx, ch, seq, n_terms, min_poly, orders, count, mem, stream); });
+}
+int ecfft_seq_nth_term(ecfft_ctx* ctx, const void* char_poly, size_t nc, const void* init, const void* index, size_t index_bytes,
+                       void* out, size_t nout, size_t count, int mem, void* stream) {
+    if (nc < 2 || nout == 0 || count == 0) return ECFFT_ERR_BAD_ARG;
+    return on_chain(ctx, [&](auto& ch) {
+        return run_seq_nth_term(ctx, ch, char_poly, nc, init, index, index_bytes, out, nout, count, mem, stream);
     });
 }
 int ecfft_poly_find_roots(ecfft_ctx* ctx, const void* f, size_t nf, void* roots, int64_t* n_roots, size_t count, int mem, void* stream) {

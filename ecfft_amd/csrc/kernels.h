@@ -4542,6 +4542,221 @@ __global__ __launch_bounds__(kPointBlock) void k_find_generator(const typename F
 }
 
 // ---------------------------------------------------------------------------------------------
+// ecfft_seq_min_poly / ecfft_seq_nth_term (no reference counterpart): linear recurrences.  The minimal polynomial
+// of a row of N terms is read off the row (r, ., t) of the remainder sequence of (x^N, h), h = sum s_i x^i, that is the first
+// below degree floor(N / 2) (MCA Alg. 12.9); the terms at an index K are x^K mod C against the initial terms (Fiduccia).
+// ---------------------------------------------------------------------------------------------
+// The verdict and the minimal polynomial from a row of the sequence, T = c t for some scalar c != 0, deg T = dt >= 0, and dr =
+// deg r: d = max(dr + 1, dt); the row is determined iff T[0] != 0 and 2 d <= n.  Then C = x^d t(1/x) / t(0): coefficient j is
+// T[d - j] / T[0], which takes the scale c out, and the one inversion of the row is R / T[0] (r1 = R), so that plain products of
+// stored numbers stay in crate form.  Returns the order d, or -1 for an undetermined row.
+__device__ __forceinline__ int seq_minpoly_order(bool t0_nonzero, int dr, int dt, uint32_t n) {
+    const int d = dr + 1 > dt ? dr + 1 : dt;
+    return t0_nonzero && 2 * (uint32_t)d <= n ? d : -1;
+}
+// ecfft_seq_min_poly, small regime (n <= G - 1 terms): one row per workgroup of G threads, everything in LDS, thread t owning
+// coefficient t of every row.  R0 = x^n is built here (the crate's 1 at index n: any non-zero scalar would do), R1 = the row, and
+// gcd_remainder_loop runs with bound = floor(n / 2) and its S rows aliased to the T rows, as in rs_gao_finish: the cofactor of x^n
+// is never needed, and both get the same values.  When the loop ends R1 = c r and T1 = c t for the wanted row.  seq: row p at
+// seq + p n; min_poly: row p of n / 2 + 1 coefficients, C with its leading 1 at index L and zero above, a zero row where the row is
+// undetermined; orders[p] = L or -1.  Every thread takes the same path: the verdict comes from LDS behind a barrier.
+template <class F, int G>
+__global__ __launch_bounds__(G) void k_seq_minpoly_small(const typename F::elem* __restrict__ seq, uint32_t n,
+                                                         typename F::elem* __restrict__ min_poly, long long* __restrict__ orders,
+                                                         typename F::elem r1) {
+    using E = typename F::elem;
+    __shared__ E buf[4 * G];
+    __shared__ E snorm;
+    __shared__ int sdeg[2];
+    const uint32_t t = threadIdx.x;
+    const size_t p = blockIdx.x;
+    E *R0 = buf, *R1 = buf + G, *T0 = buf + 2 * G, *T1 = buf + 3 * G;
+    if (t < 2) sdeg[t] = -1;
+    __syncthreads();
+    {
+        E va = F::zero(), vb = F::zero(), one = F::zero();
+        if (t == n) va = r1;
+        if (t < n) vb = F::canon(seq[p * n + t]);
+        if (t == 0) one = r1;
+        R0[t] = va; R1[t] = vb;
+        if (!F::is_zero(vb)) atomicMax(&sdeg[1], (int)t);
+        T0[t] = F::zero(); T1[t] = one;
+    }
+    __syncthreads();
+    int d0 = (int)n, d1 = sdeg[1], c0 = 1, c1 = 1;
+    __syncthreads();
+    if (t < 2) sdeg[t] = -1;
+    __syncthreads();
+    E *S0 = T0, *S1 = T1;
+    gcd_remainder_loop<F>(R0, R1, d0, d1, S0, S1, T0, T1, c0, c1, 1u, (int)(n / 2), sdeg, t);
+    __syncthreads();
+    if (t < 2) sdeg[t] = -1;
+    __syncthreads();
+    if (!F::is_zero(T1[t])) atomicMax(&sdeg[0], (int)t);     // written whole at the start and zero above its length
+    __syncthreads();
+    const int order = seq_minpoly_order(!F::is_zero(T1[0]), d1, sdeg[0], n);
+    if (t == 0) {
+        E c = F::zero();
+        if (order >= 0) c = F::canon(F::mul(F::inv(T1[0]), r1));
+        snorm = c;
+        orders[p] = order;
+    }
+    __syncthreads();
+    const uint32_t nh = n / 2 + 1;
+    if (t < nh) {
+        E v = F::zero();
+        if ((int)t <= order) v = F::canon(F::mul(T1[order - (int)t], snorm));
+        min_poly[p * nh + t] = v;
+    }
+}
+// ecfft_seq_min_poly, large regime: k_seq_minpoly_small's epilogue in global memory, after gcd_partial_pair has left the row's r
+// and t (n + 1 coefficients each, zero-padded, fully reduced).  One workgroup: the two degrees by a strided scan, the verdict, the
+// one inversion, the reversed write of min_poly (n / 2 + 1 coefficients) and *order.
+template <class F>
+__global__ __launch_bounds__(kBlock) void k_seq_minpoly_finish(const typename F::elem* __restrict__ r, const typename F::elem* __restrict__ tt,
+                                                               uint32_t n, typename F::elem* __restrict__ min_poly,
+                                                               long long* __restrict__ order_out, typename F::elem r1) {
+    using E = typename F::elem;
+    __shared__ E snorm;
+    __shared__ int sdeg[2];
+    const uint32_t t = threadIdx.x;
+    if (t < 2) sdeg[t] = -1;
+    __syncthreads();
+    int dr = -1, dt = -1;
+    for (uint32_t j = t; j <= n; j += kBlock) {
+        if (!F::is_zero(F::canon(r[j]))) dr = (int)j;
+        if (!F::is_zero(F::canon(tt[j]))) dt = (int)j;
+    }
+    if (dr >= 0) atomicMax(&sdeg[0], dr);
+    if (dt >= 0) atomicMax(&sdeg[1], dt);
+    __syncthreads();
+    const E t0 = F::canon(tt[0]);
+    const int order = seq_minpoly_order(!F::is_zero(t0), sdeg[0], sdeg[1], n);
+    if (t == 0) {
+        E c = F::zero();
+        if (order >= 0) c = F::canon(F::mul(F::inv(t0), r1));
+        snorm = c;
+        *order_out = order;
+    }
+    __syncthreads();
+    const uint32_t nh = n / 2 + 1;
+    for (uint32_t j = t; j < nh; j += kBlock) {
+        E v = F::zero();
+        if ((int)j <= order) v = F::canon(F::mul(tt[order - (int)j], snorm));
+        min_poly[j] = v;
+    }
+}
+// sres <- x sres mod (x^e + smod) for a residue of e >= 1 crate-form coefficients and the PLAIN low coefficients smod of the monic
+// modulus: a shift and one elimination step, as roots_pow_scan multiplies by its base.  Two barriers.
+template <class F>
+__device__ __forceinline__ void seq_shift(typename F::elem* sres, const typename F::elem* smod, uint32_t e, uint32_t t) {
+    using E = typename F::elem;
+    E v = F::zero();
+    if (t < e) {
+        const E top = sres[e - 1];
+        if (t) v = sres[t - 1];
+        v = F::canon(F::sub(v, F::canon(F::mul(top, smod[t]))));
+    }
+    __syncthreads();
+    if (t < e) sres[t] = v;
+    __syncthreads();
+}
+// ecfft_seq_nth_term, small regime (L = nc - 1 <= K): one row per workgroup of K threads.  u = x^index mod C by k_powmod_small's
+// scan on the product modmul_* with the base x (a set bit is seq_shift; the scan starts from 1, so L = 1 and index = 0 need no case
+// of their own), C made monic as k_powmod_small makes its modulus (a zero leading coefficient raises *flag).  Then nout rounds of
+// {out = sum_j u_j init_j by a tree reduction in LDS, u <- x u mod C}.  u and init are both crate form, so the plain sum carries
+// R^2 and one table multiply by R^-1 per term restores crate form (M31: R = 1).  char_poly: row b at char_poly + b (L + 1); init:
+// row b at init + b L; index: nbits bits, little-endian bytes, bit nbits - 1 set (nbits == 0: index 0); out: count x nout.
+template <class F, int K>
+__global__ __launch_bounds__(K) void k_seq_terms_small(typename F::elem* __restrict__ out, uint32_t nout,
+                                                       const typename F::elem* __restrict__ char_poly, uint32_t L,
+                                                       const typename F::elem* __restrict__ init, const uint8_t* __restrict__ index,
+                                                       uint32_t nbits, typename F::telem rinv, typename F::elem r1, int* __restrict__ flag) {
+    using E = typename F::elem;
+    __shared__ E sres[K], sinit[K], smod[K], sx[K], sprod[2 * K];
+    const uint32_t t = threadIdx.x;
+    const size_t b = blockIdx.x;
+    modmul_monic<F>(smod, sx, char_poly + b * ((size_t)L + 1), L, flag, t);
+    {
+        E v = F::zero(), one = F::zero();
+        if (t < L) v = F::canon(init[b * L + t]);
+        if (t == 0) one = r1;
+        sinit[t] = v;
+        sres[t] = one;
+    }
+    __syncthreads();
+    for (uint32_t i = nbits; i-- > 0;) {
+        if (i + 1 < nbits) {                                 // the top bit meets the residue 1: no squaring
+            modmul_plain<F>(sx, sres, rinv, t);
+            modmul_reduce<F>(sprod, sx, sres, smod, L, t);
+            if (t < L) sres[t] = sprod[t];
+            __syncthreads();
+        }
+        if ((index[i >> 3] >> (i & 7)) & 1) seq_shift<F>(sres, smod, L, t);
+    }
+    for (uint32_t o = 0; o < nout; ++o) {
+        E v = F::zero();
+        if (t < L) v = F::canon(F::mul(sres[t], sinit[t]));
+        sprod[t] = v;
+        __syncthreads();
+        for (uint32_t h = K / 2; h > 0; h >>= 1) {
+            if (t < h) sprod[t] = F::canon(F::add(sprod[t], sprod[t + h]));
+            __syncthreads();
+        }
+        if (t == 0) {
+            E sum = sprod[0];
+            if constexpr (sizeof(E) == 32) sum = F::tmul(rinv, sum);
+            out[b * nout + o] = F::canon(sum);
+        }
+        if (o + 1 < nout) seq_shift<F>(sres, smod, L, t);
+    }
+}
+// ecfft_seq_nth_term, large regime, behind the power u = x^index mod C of every row (u: count x L, crate form): a workgroup per
+// row, each thread striding over L, one block reduction per term, and between two terms the shift u' = x u mod C,
+// u'_j = u_{j-1} - (u_{L-1} / c_L) c_j, from one global row into the other (u and alt, each count x L; alt is not touched for
+// nout == 1).  The quotient u_{L-1} / c_L is a PLAIN number (the stored inverse of c_L times the stored u_{L-1}), so its products
+// with the crate-form c_j stay crate.  A zero c_L was flagged by the power; its row computes on inv(0) = 0 and is not used.
+template <class F>
+__global__ __launch_bounds__(kBlock) void k_seq_terms(typename F::elem* __restrict__ out, uint32_t nout, typename F::elem* __restrict__ u,
+                                                      typename F::elem* __restrict__ alt, const typename F::elem* __restrict__ char_poly,
+                                                      uint32_t L, const typename F::elem* __restrict__ init, typename F::telem rinv) {
+    using E = typename F::elem;
+    __shared__ E sred[kBlock];
+    __shared__ E slinv;
+    const uint32_t t = threadIdx.x;
+    const size_t b = blockIdx.x;
+    const E* c = char_poly + b * ((size_t)L + 1);
+    const E* s0 = init + b * (size_t)L;
+    E* cur = u + b * (size_t)L;
+    E* nxt = alt ? alt + b * (size_t)L : nullptr;
+    if (t == 0) slinv = F::canon(F::inv(F::canon(c[L])));
+    for (uint32_t o = 0; o < nout; ++o) {
+        E acc = F::zero();
+        for (uint32_t j = t; j < L; j += kBlock) acc = F::canon(F::mul_add(cur[j], F::canon(s0[j]), acc));
+        sred[t] = acc;
+        __syncthreads();
+        for (uint32_t h = kBlock / 2; h > 0; h >>= 1) {
+            if (t < h) sred[t] = F::canon(F::add(sred[t], sred[t + h]));
+            __syncthreads();
+        }
+        if (t == 0) {
+            E sum = sred[0];
+            if constexpr (sizeof(E) == 32) sum = F::tmul(rinv, sum);
+            out[b * nout + o] = F::canon(sum);
+        }
+        if (o + 1 == nout) break;
+        const E w = F::canon(F::mul(F::canon(cur[L - 1]), slinv));
+        for (uint32_t j = t; j < L; j += kBlock) {
+            E v = F::zero();
+            if (j) v = F::canon(cur[j - 1]);
+            nxt[j] = F::canon(F::sub(v, F::canon(F::mul(w, F::canon(c[j])))));
+        }
+        __syncthreads();                                     // the row just written is the next term's operand
+        { E* x = cur; cur = nxt; nxt = x; }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
 // generic element-wise helper for tree construction: functor(i) for i < n
 // ---------------------------------------------------------------------------------------------
 template <class Fn>

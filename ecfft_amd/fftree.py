@@ -33,7 +33,7 @@ EXPORTS = ["ecfft_elem_size", "ecfft_build_fftree", "ecfft_fftree_new", "ecfft_c
            "ecfft_comm_stats_enable", "ecfft_comm_stats_read", "ecfft_extend_sharded", "ecfft_enter_sharded", "ecfft_exit_sharded", "ecfft_device_copy", "ecfft_shader_clock", "ecfft_device_alloc", "ecfft_device_free", "ecfft_device_sync", "ecfft_build_extend_shard", "ecfft_ctx_device_bytes", "ecfft_extend_sharded_layout", "ecfft_build_enter_shard", "ecfft_build_exit_shard", "ecfft_build_exit_shard_opts",
            "ecfft_fftree_serialize", "ecfft_fftree_deserialize", "ecfft_tree_rational_maps", "ecfft_ctx_trim", "ecfft_comm_abort", "ecfft_comm_set_rccl_library", "ecfft_comm_set_link_striping",
            "ecfft_poly_mul", "ecfft_poly_inv_series", "ecfft_poly_divrem", "ecfft_poly_eval_points", "ecfft_poly_interpolate",
-           "ecfft_poly_pow_mod", "ecfft_poly_mul_mod", "ecfft_poly_gcd", "ecfft_poly_xgcd", "ecfft_poly_xgcd_partial", "ecfft_rs_decode", "ecfft_rs_encode", "ecfft_rs_decode_erasures", "ecfft_poly_find_roots",
+           "ecfft_poly_pow_mod", "ecfft_poly_mul_mod", "ecfft_poly_gcd", "ecfft_poly_xgcd", "ecfft_poly_xgcd_partial", "ecfft_rs_decode", "ecfft_rs_encode", "ecfft_rs_decode_erasures", "ecfft_seq_min_poly", "ecfft_seq_nth_term", "ecfft_poly_find_roots",
            "ecfft_poly_compose_mod", "ecfft_poly_squarefree", "ecfft_poly_distinct_degree", "ecfft_poly_equal_degree", "ecfft_poly_squarefree_decompose", "ecfft_poly_factor", "ecfft_division_polynomial", "ecfft_curve_trace_mod", "ecfft_curve_cardinality",
            "ecfft_find_curve_candidate", "ecfft_curve_two_sylow", "ecfft_find_curve", "ecfft_build_fftree_on_curve",
            "ecfft_curve_point_mul", "ecfft_curve_point_two_adicity", "ecfft_curve_find_generator", "ecfft_build_ec_fftree"]
@@ -45,6 +45,10 @@ XGCD_PARTIAL_SMALL_MAX = 256
 RS_SMALL_MAX = 255
 # include/ecfft_hip.h ECFFT_RS_OUT_*: what rs_decode_erasures writes, the k coefficients of f or its m re-encoded symbols
 RS_OUT_COEFFS, RS_OUT_CODEWORD = 0, 1
+# include/ecfft_hip.h ECFFT_SEQ_SMALL_MAX: terms N up to which seq_min_poly finds a row's minimal polynomial in one workgroup, on any tree
+SEQ_SMALL_MAX = 255
+# include/ecfft_hip.h ECFFT_SEQ_TERM_SMALL_MAX: nc up to which seq_nth_term takes the terms of a row in one workgroup, on any tree
+SEQ_TERM_SMALL_MAX = 65
 # include/ecfft_hip.h ECFFT_ROOTS_SMALL_MAX: nf up to which poly_find_roots finishes a polynomial in one workgroup, on any tree
 ROOTS_SMALL_MAX = 65
 # include/ecfft_hip.h ECFFT_COMPOSE_SMALL_MAX: nm up to which poly_compose_mod runs Horner for a triple in one workgroup, on any tree
@@ -105,6 +109,8 @@ def _bind(L):
     L.ecfft_poly_xgcd.restype, L.ecfft_poly_xgcd.argtypes = ci, [vp, vp, sz, vp, sz, vp, vp, vp, vp, sz, ci, vp]
     L.ecfft_poly_xgcd_partial.restype, L.ecfft_poly_xgcd_partial.argtypes = ci, [vp, vp, sz, vp, sz, sz, vp, vp, vp, vp, sz, ci, vp]
     L.ecfft_rs_decode.restype, L.ecfft_rs_decode.argtypes = ci, [vp, vp, sz, vp, sz, vp, vp, sz, ci, vp]
+    L.ecfft_seq_min_poly.restype, L.ecfft_seq_min_poly.argtypes = ci, [vp, vp, sz, vp, vp, sz, ci, vp]
+    L.ecfft_seq_nth_term.restype, L.ecfft_seq_nth_term.argtypes = ci, [vp, vp, sz, vp, vp, sz, vp, sz, sz, ci, vp]
     L.ecfft_rs_encode.restype, L.ecfft_rs_encode.argtypes = ci, [vp, vp, sz, vp, sz, vp, sz, ci, vp]
     L.ecfft_rs_decode_erasures.restype, L.ecfft_rs_decode_erasures.argtypes = ci, [vp, vp, sz, vp, vp, sz, vp, ci, vp, sz, ci, vp]
     L.ecfft_poly_find_roots.restype, L.ecfft_poly_find_roots.argtypes = ci, [vp, vp, sz, vp, vp, sz, ci, vp]
@@ -903,6 +909,49 @@ class FFTree:
             raise ValueError("rs_decode_erasures: two equal points, k = 0, k > m, count = 0 or a context that holds no full tree")
         _check(rc)
         return out, n_errors
+
+    def seq_min_poly(self, seq, count=1):
+        """(min_poly, orders): the minimal polynomials of `count` rows of N terms laid end to end (ecfft_seq_min_poly; what
+        Berlekamp-Massey computes, here by the partial remainder row of (x^N, the row)).  A row's order L is the smallest L with
+        s[i+L] + sum_{j<L} c_j s[i+j] = 0 for all 0 <= i < N - L; where 2 L <= N the monic C = x^L + sum c_j x^j is unique.
+        min_poly has count * (N // 2 + 1) coefficients, row b holding C_b with its leading 1 at index L_b and zero above; orders is
+        a numpy int64 array of the L_b, -1 where 2 L > N: the row is undetermined and its min_poly row zero.  N <= SEQ_SMALL_MAX
+        works on any tree (one workgroup per row, one launch for all rows); otherwise a tree of next_pow2(2 N + 1) leaves.  numpy
+        array (host) or contiguous CUDA tensor (device, on the current stream).  Synchronous."""
+        (seq,), (ps,), new, mem, stream = self._poly_io([seq])
+        assert count > 0 and seq.shape[0] % count == 0
+        n = seq.shape[0] // count
+        min_poly = new(count * (n // 2 + 1)) if n else new(0)
+        orders = np.empty(count, np.int64)
+        rc = self._L.ecfft_seq_min_poly(self._h, ps, n, self._ptr(min_poly) if min_poly.shape[0] else None, orders.ctypes.data, count, mem, stream)
+        if rc == ERR_BAD_ARG:
+            raise ValueError("seq_min_poly: an empty row, count = 0 or a context that holds no full tree")
+        _check(rc)
+        return min_poly, orders
+
+    def seq_nth_term(self, char_poly, init, index, nout=1, count=1):
+        """The terms s_index .. s_(index + nout - 1) of `count` linear recurrences laid end to end (ecfft_seq_nth_term, Fiduccia:
+        x^index mod C against the initial terms).  char_poly: count * nc coefficients of the C_b, nc >= 2, leading coefficient
+        non-zero (monic not required); init: count * (nc - 1) initial terms of the sequences with sum_{j<=L} c_j s[i+j] = 0;
+        `index` is one non-negative Python int shared by all rows.  Returns count * nout terms.  nc <= SEQ_TERM_SMALL_MAX works on
+        any tree (one workgroup per row); a longer recurrence needs a tree of next_pow2(2 (nc - 1) - 1) leaves.  numpy arrays
+        (host) or contiguous CUDA tensors (device, on the current stream), both of the same kind.  Synchronous."""
+        index = int(index)
+        if index < 0:
+            raise ValueError("seq_nth_term: the index must be non-negative")
+        (char_poly, init), (pc, pi), new, mem, stream = self._poly_io([char_poly, init])
+        assert count > 0 and char_poly.shape[0] % count == 0
+        nc = char_poly.shape[0] // count
+        assert init.shape[0] == count * max(nc - 1, 0)
+        ib = index.to_bytes((index.bit_length() + 7) // 8, "little")
+        out = new(count * max(int(nout), 0))
+        rc = self._L.ecfft_seq_nth_term(self._h, pc, nc, pi if init.shape[0] else None, ctypes.c_char_p(ib) if ib else None, len(ib),
+                                        self._ptr(out) if out.shape[0] else None, int(nout), count, mem, stream)
+        if rc == ERR_BAD_ARG:
+            raise ValueError("seq_nth_term: a characteristic polynomial of fewer than 2 coefficients, a zero leading coefficient, "
+                             "nout = 0, count = 0 or a context that holds no full tree")
+        _check(rc)
+        return out
 
     def poly_find_roots(self, f, count=1):
         """(roots, n_roots): the distinct roots in the field (ecfft_poly_find_roots <-> utils::find_roots, src/utils.rs:25-44) of

@@ -376,6 +376,39 @@ public:
         if (n_errors) *n_errors = n;
         return out;
     }
+    // The minimal polynomial of a sequence of N terms (ecfft_seq_min_poly, what Berlekamp-Massey computes; no reference
+    // counterpart): the monic C = x^L + sum c_j x^j of least degree with s[i+L] + sum_j c_j s[i+j] = 0 for all 0 <= i < N - L, as
+    // L + 1 coefficients ({1} for a zero sequence), where 2 L <= N makes it unique; an EMPTY vector where the sequence is too short
+    // to determine it.  order (may be null) receives L or -1.  Up to ECFFT_SEQ_SMALL_MAX terms on any tree; tree rule in
+    // ecfft_hip.h.  Synchronous.
+    std::vector<Elem> min_poly(const std::vector<Elem>& seq, int64_t* order = nullptr) const {
+        require(!seq.empty(), "min_poly: the sequence must not be empty");
+        std::vector<Elem> c(seq.size() / 2 + 1);
+        int64_t n = -1;
+        check(ecfft_seq_min_poly(ctx_, seq.data(), seq.size(), c.data(), &n, 1, ECFFT_MEM_HOST, nullptr));
+        if (order) *order = n;
+        c.resize((size_t)(n + 1));
+        return c;
+    }
+    // The terms s_K .. s_(K + nout - 1) of the linear recurrence with the characteristic polynomial char_poly (L + 1 >= 2
+    // coefficients, a non-zero leading one, monic not required: sum_{j<=L} c_j s[i+j] = 0) and the L initial terms init
+    // (ecfft_seq_nth_term; no reference counterpart); index is K in little-endian bytes of any length (empty: K = 0).  One power
+    // x^K mod C and nout L multiply-adds.  Up to ECFFT_SEQ_TERM_SMALL_MAX coefficients on any tree; tree rule in ecfft_hip.h.  A
+    // zero leading coefficient throws.  Synchronous.
+    std::vector<Elem> nth_term(const std::vector<Elem>& char_poly, const std::vector<Elem>& init, const std::vector<uint8_t>& index,
+                               size_t nout = 1) const {
+        require(char_poly.size() >= 2 && init.size() + 1 == char_poly.size() && nout >= 1, "nth_term: L + 1 >= 2 coefficients, L initial terms, nout >= 1");
+        std::vector<Elem> out(nout);
+        check(ecfft_seq_nth_term(ctx_, char_poly.data(), char_poly.size(), init.data(), index.empty() ? nullptr : index.data(), index.size(),
+                                 out.data(), nout, 1, ECFFT_MEM_HOST, nullptr));
+        return out;
+    }
+    // ... with a 64-bit index
+    std::vector<Elem> nth_term(const std::vector<Elem>& char_poly, const std::vector<Elem>& init, uint64_t index, size_t nout = 1) const {
+        std::vector<uint8_t> bytes(8);
+        for (int i = 0; i < 8; ++i) bytes[(size_t)i] = (uint8_t)(index >> (8 * i));
+        return nth_term(char_poly, init, bytes, nout);
+    }
     // the distinct roots of f in the field in ascending order of their standard form (ecfft_poly_find_roots <-> utils::find_roots,
     // src/utils.rs:25-44, whose result is sorted the same way).  f need not be trimmed; multiplicities do not matter; a non-zero
     // constant has none.  The zero polynomial, on which the reference panics, throws.  Up to ECFFT_ROOTS_SMALL_MAX coefficients on
@@ -589,6 +622,16 @@ public:
     void rs_decode_erasures_device(const Elem* points, size_t m, const Elem* values, const uint8_t* erased, size_t k, Elem* out, int out_form,
                                    int64_t* n_errors, size_t count, void* stream) const {
         check(ecfft_rs_decode_erasures(ctx_, points, m, values, erased, k, out, out_form, n_errors, count, ECFFT_MEM_DEVICE, stream));
+    }
+    // count rows of n_terms -> min_poly count x (n_terms / 2 + 1); orders: count HOST entries (-1: undetermined, a zero row).  Synchronous.
+    void min_poly_device(const Elem* seq, size_t n_terms, Elem* min_poly, int64_t* orders, size_t count, void* stream) const {
+        check(ecfft_seq_min_poly(ctx_, seq, n_terms, min_poly, orders, count, ECFFT_MEM_DEVICE, stream));
+    }
+    // count recurrences: char_poly count x nc, init count x (nc - 1), index: index_bytes little-endian HOST bytes shared by all rows,
+    // out count x nout.  Synchronous.
+    void nth_term_device(const Elem* char_poly, size_t nc, const Elem* init, const void* index, size_t index_bytes, Elem* out, size_t nout,
+                         size_t count, void* stream) const {
+        check(ecfft_seq_nth_term(ctx_, char_poly, nc, init, index, index_bytes, out, nout, count, ECFFT_MEM_DEVICE, stream));
     }
     // count polynomials f count x nf (untrimmed), roots count x (nf - 1) sorted and zero-padded; n_roots: count HOST entries (-1: the
     // zero polynomial).  Synchronous.

@@ -328,6 +328,45 @@ int ecfft_rs_encode(ecfft_ctx* ctx, const void* points, size_t m, const void* da
 int ecfft_rs_decode_erasures(ecfft_ctx* ctx, const void* points, size_t m, const void* values, const uint8_t* erased, size_t k, void* out,
                              int out_form, int64_t* n_errors, size_t count, int mem, void* stream);
 
+/* Linear recurrences: the minimal polynomial of a sequence (what Berlekamp-Massey computes) and its terms at a huge index.  The
+ * reference has no counterpart.
+ * A row is N elements s_0 .. s_{N-1}.  Its linear complexity L is the smallest L >= 0 with c_0 .. c_{L-1} such that
+ * s_{i+L} + sum_{j<L} c_j s_{i+j} = 0 for all 0 <= i < N - L; L = 0 iff the row is zero.  Where 2 L <= N the monic
+ * C(x) = x^L + sum c_j x^j is unique, the MINIMAL POLYNOMIAL; where 2 L > N it is not, and the row is reported UNDETERMINED.
+ * ecfft_seq_min_poly: seq is count x N elements in the crate's form, any values.  min_poly is count x (N / 2 + 1) coefficients:
+ * row b holds C_b with its leading 1 at index L_b and zero above, fully reduced; an undetermined row is zero.  `orders` is a HOST
+ * pointer whatever `mem` is, `count` entries, required: L_b, or -1 for an undetermined row.  N >= 1 (N = 1: 0 for a zero term, -1
+ * otherwise).  Nothing fails on the data, and the output is unique and bit-exact.
+ * Method (MCA Alg. 12.9): with h = sum s_i x^i (the row as it stands) and (r, ., t) the row of ecfft_poly_xgcd_partial(x^N, h)
+ * with stop = N / 2, d = max(1 + deg r, deg t): the row is determined iff t(0) != 0 and 2 d <= N, and then L = d and
+ * C = x^d t(1/x) / t(0).  Only the t cofactor is computed, x^N is never staged per row, and verdict, inversion and reversal
+ * happen on the device.
+ * ECFFT_SEQ_SMALL_MAX: N up to which a row is ONE workgroup, everything in LDS, all rows in one launch, on any tree.  Above it
+ * the rows run one after another through the large regime of ecfft_poly_xgcd_partial against one shared x^N, each finished by a
+ * small kernel; the verdicts are read back once.
+ * Tree: N <= ECFFT_SEQ_SMALL_MAX needs no transform (any tree).  Otherwise the rule of ecfft_poly_xgcd_partial for (N + 1, N)
+ * coefficients, next_pow2(2 N + 1) leaves; else ECFFT_ERR_TREE_TOO_SMALL, checked before anything runs.
+ * ecfft_seq_nth_term: char_poly is count x nc coefficients, nc >= 2, of polynomials C_b of degree L = nc - 1 whose leading
+ * coefficient is non-zero (monic not required); init is count x L initial terms s_0 .. s_{L-1} of the sequences with
+ * sum_{j<=L} c_j s_{i+j} = 0.  `index` is `index_bytes` little-endian HOST bytes, one K >= 0 shared by all rows (high zero bytes
+ * are ignored; index may be NULL when index_bytes is 0: K = 0).  out is count x nout, nout >= 1: s_K .. s_{K+nout-1} of every row,
+ * fully reduced; K < L returns initial terms themselves.
+ * Method (Fiduccia): u = x^K mod C, s_K = sum_{j<L} u_j s_j, and the next term takes x u mod C: one power and nout L
+ * multiply-adds per row.  ECFFT_SEQ_TERM_SMALL_MAX: nc up to which a row is ONE workgroup, all rows in one launch, on any tree.
+ * Above it the kept-modulus power of ecfft_poly_pow_mod runs on the base x for all rows at once, then one launch takes the terms.
+ * Tree: nc <= ECFFT_SEQ_TERM_SMALL_MAX any tree; otherwise the rule of ecfft_poly_pow_mod with nm = nc, next_pow2(2 (nc - 1) - 1)
+ * leaves; else ECFFT_ERR_TREE_TOO_SMALL, checked before anything runs.
+ * ECFFT_ERR_BAD_ARG, both calls: a NULL pointer (index with index_bytes > 0), N, nout or count 0, nc < 2, a context that holds no
+ * full tree, a byte count that would wrap — and for ecfft_seq_nth_term a zero leading coefficient of some C_b, which is checked on
+ * the device.  Both calls are SYNCHRONOUS; the context keeps working after an error.  Outputs must not overlap the inputs.
+ * Memory, stream, threading and pooled temporaries as for ecfft_poly_gcd. */
+#define ECFFT_SEQ_SMALL_MAX      255  /* terms N up to which a row is one workgroup, on any tree (x^N has ECFFT_GCD_SMALL_MAX coefficients) */
+#define ECFFT_SEQ_TERM_SMALL_MAX  65  /* nc up to which the terms of a row are one workgroup, on any tree (= ECFFT_COMPOSE_SMALL_MAX) */
+int ecfft_seq_min_poly(ecfft_ctx* ctx, const void* seq, size_t n_terms, void* min_poly, int64_t* orders, size_t count, int mem,
+                       void* stream);
+int ecfft_seq_nth_term(ecfft_ctx* ctx, const void* char_poly, size_t nc, const void* init, const void* index, size_t index_bytes,
+                       void* out, size_t nout, size_t count, int mem, void* stream);
+
 /* Roots of polynomials in the field.
  *   ecfft_poly_find_roots <-> ecfft::utils::find_roots(poly)                        src/utils.rs:25-44
  * Layout: f is count x nf coefficients in the crate's form; as in ecfft_poly_gcd the rows NEED NOT BE TRIMMED.  roots is
